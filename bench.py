@@ -17,7 +17,14 @@ queries' own embeddings as the device computes them on the first image), so that
 FAILS if it does not.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--images B] [--size S] [--vocab coco133|ade150|ade847] [--semantic-only]
-                    [--stage full|unet] [--no-cpu-baseline] [--no-inclusive]
+                    [--stage full|unet] [--full [--no-cpu-baseline] [--no-inclusive]] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the line: `metric` / `value` / `ms_per_step` and the in-step figures recorded
+during those K steps (`roofline` from the launch probe and the stage marks, `exchange` from the records the steps wrote).  `--full` adds
+the legs that take runs of their own after the timed region: the dominant kernel and the UNet stage alone on the idle chip
+(`roofline.isolated`, `roofline.unet_isolated`), the host-fed and JPEG-fed rates (`inclusive`, `value_host_fed`; `--no-inclusive` skips
+them) and the CPU oracle (`cpu_baseline`; `--no-cpu-baseline` skips it).  `--dump-outputs DIR` writes what the last timed step computed
+as DIR/<name>.npy (float32 / float64, at most 64 MB; larger outputs as a fixed seeded sample, see `_whole_or_sample`).
 
 `--stage unet` runs BASELINE configs[1] (SD-UNet single-step feature extraction, `--images` = crops of 512x512).
 `--vocab ade150` = configs[3] shape (K=150 / 403 strings), `--vocab ade847 --size 1280 --semantic-only` = configs[4] (K=847 / 1342
@@ -83,9 +90,15 @@ def parse():
                    "4096 = never the 8-phase kernels, 8192 = the 8-phase kernels on 32x32x16 MFMAs), process-wide")
     p.add_argument("--picture-rank", type=int, default=None, help="rehearsal: use the pictures (and the vocabulary calibration) rank R of a multi-GPU run would "
                    "use, on one GPU - checks that every rank's decisions are non-degenerate without eight GPUs")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-inclusive", action="store_true", help="skip the PCIe- / JPEG-inclusive legs")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true", help="after the timed region also measure the isolated dominant kernel and UNet stage, the "
+                   "PCIe- / JPEG-inclusive legs and the CPU baseline (a plain run prints the headline and the in-step figures only)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-inclusive", action="store_true", help="with --full: skip the PCIe- / JPEG-inclusive legs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _threads():
@@ -102,6 +115,36 @@ def _threads():
 def _peak_rss_gb():
     import resource
     return resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / (1 << 20)   # Linux: kilobytes
+
+
+def _rank_line(msg):
+    """One line on stderr in ONE write: the ranks of --gpus N share that pipe, and their stderr is unbuffered under the launcher, where
+    print() writes the newline separately - two ranks' lines then run together into one."""
+    sys.stderr.write(msg + "\n")
+    sys.stderr.flush()
+
+
+def synthetic_weights(prefixes=None, strip=""):
+    """odise_amd.synthetic.synthetic_state drawn on this rank's host threads: 1.28 G normal draws take most of a single-GPU set-up on one
+    core.  Every tensor has a seed of its own, derived from its name, so each group below (exact names, balanced by size) draws the same
+    values as the serial loop; numpy releases the interpreter lock while it fills and scales an array.  Same keys, same order, same bits."""
+    from concurrent.futures import ThreadPoolExecutor
+    from odise_amd.synthetic import load_spec, synthetic_state
+    spec = load_spec()
+    pre = tuple(prefixes) if prefixes is not None else None
+    names = [n for n in spec if pre is None or n.startswith(pre)]
+    n_groups = max(1, min(_threads(), len(names)))
+    groups, load = [[] for _ in range(n_groups)], [0] * n_groups
+    for n in sorted(names, key=lambda n: -int(np.prod(spec[n][0]))):
+        k = load.index(min(load))
+        groups[k].append(n)
+        load[k] += int(np.prod(spec[n][0]))
+    with ThreadPoolExecutor(n_groups) as ex:
+        parts = list(ex.map(lambda g: synthetic_state(g) if g else {}, groups))
+    drawn = {}
+    for part in parts:
+        drawn.update(part)
+    return {(n[len(strip):] if strip and n.startswith(strip) else n): drawn[n] for n in names}
 
 
 def image_u8(size, seed):
@@ -323,7 +366,7 @@ def calibrated_model(ctx, first_image_u8, S, K, K_TOT, things, anchored, positiv
         state, shared = syn.synthetic_state_shared()
         state = dict(state)
     else:
-        state = syn.synthetic_state()
+        state = synthetic_weights()
     syn.apply_branch_gain(state)
     hip = HipCategoryODISE(ctx, state, overlap_threshold=0.8)
     state = {k: np.array(v) for k, v in state.items() if k.startswith(("sem_seg_head.", "category_head."))}   # the frozen towers are on the device now
@@ -385,6 +428,90 @@ def calibrated_model(ctx, first_image_u8, S, K, K_TOT, things, anchored, positiv
     return hip, float((pm > 0).mean())
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: all files together
+DUMP_WHOLE = 24 << 20      # an output of at most this many float32 bytes is written whole ...
+DUMP_SAMPLE = 1 << 20      # ... a larger one as this many values (split evenly over its pictures / crops) at seeded positions
+
+
+def _whole_or_sample(parts, seed):
+    """parts: one (shape, loader) per picture (loader() -> host array) -> one float32 array: the parts stacked (flattened and concatenated
+    when their shapes differ) if that takes at most DUMP_WHOLE bytes; else DUMP_SAMPLE // len(parts) values of each part at the flat
+    positions numpy.random.default_rng([seed, part]).choice(size, n, replace=False) (sorted), concatenated.  The positions depend only on the
+    seed and the shape, so two runs with the same arguments sample the same elements."""
+    sizes = [int(np.prod(s, dtype=np.int64)) for s, _ in parts]
+    load = lambda shape, fn: fn() if int(np.prod(shape, dtype=np.int64)) else np.empty(shape, np.float32)
+    if sum(sizes) * 4 <= DUMP_WHOLE:
+        arrays = [load(s, fn) for s, fn in parts]
+        if len({a.shape for a in arrays}) == 1:
+            return np.stack(arrays).astype(np.float32)
+        return np.concatenate([a.reshape(-1) for a in arrays]).astype(np.float32)
+    n, out = DUMP_SAMPLE // len(parts), []
+    for k, ((shape, fn), size) in enumerate(zip(parts, sizes)):
+        flat = load(shape, fn).reshape(-1)
+        if size > n:
+            flat = flat[np.sort(np.random.default_rng([seed, k]).choice(size, n, replace=False))]
+        out.append(flat.astype(np.float32))
+    return np.concatenate(out)
+
+
+def outputs_full(hip, sl, S):
+    """What a caller of the timed step receives from its LAST step (slot `sl`): per picture the semantic scores [K,S,S] (or the fused arg-max
+    [S,S] with --semantic-only) and the instances (scores, classes, query index, masks [n,S,S]) from the model call, and the panoptic map
+    [S,S] + segment table of every picture from the records the exchange step gathered.  Ragged tables are concatenated over the pictures
+    (`instances_count` / the picture column of `panoptic_segments` split them)."""
+    import torch
+    from odise_amd import distributed as D
+    res, out = sl["res"], {}
+    if hip.semantic_on and not hip.semantic_argmax:
+        out["sem_seg"] = _whole_or_sample([(r["sem_seg"].shape, r["sem_seg"].numpy) for r in res], seed=1)
+    if hip.semantic_on and hip.semantic_argmax:
+        out["sem_seg_argmax"] = _whole_or_sample([(r["sem_seg_argmax"].shape, r["sem_seg_argmax"].numpy) for r in res], seed=2)
+    if hip.panoptic_on:
+        segs, table = [], []
+        for i, row in enumerate(sl["allrec"].numpy()):
+            seg, info = D.unpack_record(torch.from_numpy(row), S, S)
+            segs.append(seg)
+            table += [[i, s["id"], int(s["isthing"]), s["category_id"]] for s in info]
+        out["panoptic_seg"] = _whole_or_sample([(s.shape, lambda s=s: s) for s in segs], seed=3)
+        out["panoptic_segments"] = np.asarray(table, np.float64).reshape(-1, 4)   # picture, segment id, isthing, category
+    if hip.instance_on:
+        inst = [r["instances"] for r in res]
+        out["instances_count"] = np.asarray([len(x["scores"]) for x in inst], np.float64)
+        out["instances_scores"] = np.concatenate([np.asarray(x["scores"], np.float32).reshape(-1) for x in inst])
+        out["instances_pred_classes"] = np.concatenate([np.asarray(x["pred_classes"], np.float64).reshape(-1) for x in inst])
+        out["instances_query_index"] = np.concatenate([np.asarray(x["query_index"], np.float64).reshape(-1) for x in inst])
+        out["instances_pred_masks"] = _whole_or_sample([(x["pred_masks"].shape, x["pred_masks"].numpy) for x in inst], seed=4)
+    return out
+
+
+def outputs_unet(ctx, hip, taps, B):
+    """The four fp16 NHWC taps [B, h/d, w/d, C] the last timed `run_nhwc` left in the library's arena, as float32."""
+    import ctypes as C
+    from odise_amd._lib import check
+    out = {}
+    for i, ((b, c, h, w), ptr) in enumerate(zip(hip.tap_shapes(B, 64, 64), taps)):
+        if not ptr:
+            raise RuntimeError(f"--dump-outputs: the library returned no pointer for UNet tap {i}")
+
+        def load(shape=(b, h, w, c), ptr=ptr):
+            a = np.empty(shape, np.float16)
+            check(ctx.lib.odise_hip_memcpy_d2h(ctx.h, a.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), C.c_size_t(a.nbytes)), "memcpy_d2h")
+            return a
+        out[f"unet_tap{i}"] = _whole_or_sample([((b, h, w, c), load)], seed=5 + i)
+    return out
+
+
+def dump_outputs(directory, outputs):
+    """{name: float32 / float64 array} -> directory/<name>.npy; -> bytes written (at most DUMP_BYTES)."""
+    total = sum(a.nbytes for a in outputs.values())
+    assert total <= DUMP_BYTES, f"--dump-outputs: {total} bytes > {DUMP_BYTES}"
+    os.makedirs(directory, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return total
+
+
 def main():
     args = parse()
     from odise_amd import launch
@@ -416,22 +543,22 @@ def main():
         ctx.set_option(ctx.OPT_VAE_CHUNK_BYTES, int(args.vae_chunk_mb * (1 << 20)))
     B = args.images if args.images is not None else (4 if args.stage == "full" else 1)
 
-    # Weights: random tensors of the real architecture's shapes (odise_amd/synthetic.py; no checkpoints, no network).  The oracle is
-    # imported only by the cpu_baseline leg below.
-    from odise_amd.synthetic import synthetic_state
+    # Weights: random tensors of the real architecture's shapes (odise_amd/synthetic.py via synthetic_weights; no checkpoints, no network).
+    # The oracle is imported only by the cpu_baseline leg of --full.
     check_exchange = None
     rccl_ranks, positive_fraction = None, None
     if args.stage == "unet":
         from odise_amd.unet import HipUNet
-        hip = HipUNet(ctx, synthetic_state(["model.diffusion_model."], strip="model.diffusion_model."), use_graph=True)
+        hip = HipUNet(ctx, synthetic_weights(["model.diffusion_model."], strip="model.diffusion_model."), use_graph=True)
         r = np.random.default_rng(1)
         x = r.standard_normal((B, 4, 64, 64), dtype=np.float32)                                   # x_t
         context = (r.standard_normal((1, 77, 768), dtype=np.float32) + 0.1 * r.standard_normal((B, 77, 768), dtype=np.float32))
         cond_emb = 0.02 * r.standard_normal((B, 1280), dtype=np.float32)                          # implicit-captioner time-embedding term
         dx, dc, de = ctx.to_device(x), ctx.to_device(context.astype(np.float32)), ctx.to_device(cond_emb.astype(np.float32))
+        unet_taps = {}
 
         def step():
-            hip.run_nhwc(dx, dc, de, 0)
+            unet_taps["ptrs"] = hip.run_nhwc(dx, dc, de, 0)     # fp16 NHWC taps in the library's arena, valid until its next call
             ctx.sync()
         flops_per_unit, unit, metric = UNET_FLOPS_LIVE, "crops/s", "SD-UNet single-step feature extraction crops/sec (stage of panoptic-inference images/sec @1024x1024; UNet MFMA %peak)"
         workload = (f"BASELINE configs[1]: SD-UNet single-step feature extraction, bs={B} x 512x512 crop (64x64 latent) per GPU, t=0, "
@@ -548,7 +675,7 @@ def main():
             if headline and S == 1024 and args.vocab == "coco133" and B >= 4:   # the headline configuration: the decision kernels are timed on real tables
                 assert min(counts) >= 2 and sum(counts) >= 5 * B, f"near-degenerate segment tables: {counts}"
             if not headline:
-                print(f"[bench] rank {rank} (pictures of rank {prank}): segments per image {counts}, instances {report.get('instances_per_image')}", file=sys.stderr, flush=True)
+                _rank_line(f"[bench] rank {rank} (pictures of rank {prank}): segments per image {counts}, instances {report.get('instances_per_image')}")
             report.update({"segments_per_image": counts, "segments_image0": counts[0], "records_bytes_per_rank": int(B * rec * 4)})
             return report
         ncrops = (-(-S // 512)) ** 2                                       # slide windows of 512 (feature_extractor.py:197-222): 4 at 1024, 9 at 1280
@@ -575,8 +702,7 @@ def main():
 
     # set-up is over (weights generated, packed, uploaded and calibrated on every rank): one line per rank, so that a multi-GPU run that dies or crawls
     # in set-up leaves its cause behind (never exercised at 8 concurrent ranks on one host)
-    print(f"[bench rank {rank}/{world}] set-up {time.perf_counter() - t_setup0:.1f} s, peak host RSS {_peak_rss_gb():.1f} GB, {_threads()} host threads",
-          file=sys.stderr, flush=True)
+    _rank_line(f"[bench rank {rank}/{world}] set-up {time.perf_counter() - t_setup0:.1f} s, peak host RSS {_peak_rss_gb():.1f} GB, {_threads()} host threads")
     n_fly = len(slots) if args.stage == "full" else 1
     single_ms = None
     probe = None
@@ -668,11 +794,15 @@ def main():
         wall, ev_ms = float(tt[0]), float(tt[1])
 
     exch = check_exchange() if check_exchange is not None else None
+    if rank == 0 and args.dump_outputs:   # before anything else runs: the last step's outputs live in the library's arena
+        outputs = outputs_full(hip, slots[0], S) if args.stage == "full" else outputs_unet(ctx, hip, unet_taps["ptrs"], B)
+        nbytes = dump_outputs(args.dump_outputs, outputs)
+        print(f"[bench] --dump-outputs: {len(outputs)} arrays, {nbytes / 2**20:.1f} MB -> {args.dump_outputs}", file=sys.stderr, flush=True)
 
-    # Boundary variants, reported beside `value` (never as it): the same step fed from host memory over PCIe, and from JPEG bytes
+    # --full only.  Boundary variants, reported beside `value` (never as it): the same step fed from host memory over PCIe, and from JPEG bytes
     # (host Huffman decoding in loader threads + device IDCT / resize).  Outputs stay on the device as in the reference.
     inclusive = None
-    if rank == 0 and world == 1 and args.stage == "full" and not args.no_inclusive:
+    if args.full and rank == 0 and world == 1 and args.stage == "full" and not args.no_inclusive:
         try:
             inclusive = inclusive_rates(ctx, hip, u8, S, B, hw, max(2, min(args.steps, 3)))
         except Exception as exc:  # side legs must never take the headline measurement down with them
@@ -680,11 +810,11 @@ def main():
 
     # every rank: one diagnostic line on stderr (which device, how many ranks the RCCL communicator spans, this rank's own step time), so that a
     # multi-GPU run that goes wrong leaves more than one number behind
-    print(f"[bench rank {rank}/{world}] device {local_rank} ({ctx.device_info()[0]}), rccl_ranks {rccl_ranks}, {args.steps} steps, "
-          f"{wall * 1e3 / args.steps:.2f} ms/step (max over ranks), in-step dominant-kernel launches recorded "
-          f"{0 if probe is None or 'us' not in probe else len(probe['us'])}", file=sys.stderr, flush=True)
+    _rank_line(f"[bench rank {rank}/{world}] device {local_rank} ({ctx.device_info()[0]}), rccl_ranks {rccl_ranks}, {args.steps} steps, "
+               f"{wall * 1e3 / args.steps:.2f} ms/step (max over ranks), in-step dominant-kernel launches recorded "
+               f"{0 if probe is None or 'us' not in probe else len(probe['us'])}")
     dom = None
-    if rank == 0 and args.stage == "full" and probe is not None:
+    if args.full and rank == 0 and args.stage == "full" and probe is not None:
         try:
             dom = dominant_kernel_isolated(ctx, probe["crops"])
         except Exception as exc:  # the whole-step roofline below still goes out
@@ -740,19 +870,20 @@ def main():
                                            "algorithmic_flops_per_crop": UNET_FLOPS_LIVE, "achieved": total_crops * UNET_FLOPS_LIVE / (ms_u * 1e-3) / 1e12,
                                            "frac": total_crops * UNET_FLOPS_LIVE / (ms_u * 1e-3) / MFMA_F16_PEAK,
                                            "where": "in the timed step, stage marks (HIP events on the CLIP -> UNet lane; the VAE decoder runs beside it)"}
-            try:
-                iso = unet_isolated(ctx, total_crops)
-                out["roofline"]["unet_isolated"] = dict(iso, crops=total_crops, achieved=total_crops * UNET_FLOPS_LIVE / (iso["ms"] * 1e-3) / 1e12,
-                                                        frac=total_crops * UNET_FLOPS_LIVE / (iso["ms"] * 1e-3) / MFMA_F16_PEAK)
-            except Exception as exc:
-                print(f"[bench] isolated UNet measurement failed: {type(exc).__name__}: {exc}", file=sys.stderr, flush=True)
+            if args.full:
+                try:
+                    iso = unet_isolated(ctx, total_crops)
+                    out["roofline"]["unet_isolated"] = dict(iso, crops=total_crops, achieved=total_crops * UNET_FLOPS_LIVE / (iso["ms"] * 1e-3) / 1e12,
+                                                            frac=total_crops * UNET_FLOPS_LIVE / (iso["ms"] * 1e-3) / MFMA_F16_PEAK)
+                except Exception as exc:
+                    print(f"[bench] isolated UNet measurement failed: {type(exc).__name__}: {exc}", file=sys.stderr, flush=True)
         if exch is not None:
             out["exchange"] = exch
         if inclusive is not None:
             out["inclusive"] = inclusive
             if "host_u8" in inclusive:   # the evaluator-faithful figure (pictures arrive from host memory every step), next to `value` - never as it
                 out["value_host_fed"] = inclusive["host_u8"]["value"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = baseline()
             except Exception as exc:

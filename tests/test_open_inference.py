@@ -8,6 +8,15 @@ import pytest
 
 from odise_amd.pipeline import HipCategoryODISE, HipOpenPanopticInference
 
+LABELS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "openseg_labels")
+
+
+@pytest.fixture(autouse=True)
+def _training_vocabulary(monkeypatch):
+    """`attach_text` without `train_labels` falls back to the reference's COCO label file (checkpoint.default_train_labels): the copy
+    stored with the golden vectors."""
+    monkeypatch.setenv("ODISE_OPENSEG_LABELS", LABELS)
+
 
 class _Tok:
     def __call__(self, texts, context_length=77):

@@ -150,7 +150,7 @@ def test_checkpoint_uri_resolution_matches_reference_handlers(tmp_path, monkeypa
 
 def test_label_file_parser(tmp_path):
     """`get_openseg_labels` (odise/data/build.py:17-51) -> odise_amd.checkpoint.read_openseg_labels: the format on a hand-written file,
-    and - where the reference checkout exists - every label file of the reference against the digests its own function produced."""
+    and every label file of the reference (stored under tests/golden/openseg_labels) against the digests its own function produced."""
     import hashlib
     import json
     from odise_amd.checkpoint import read_openseg_labels
@@ -159,9 +159,8 @@ def test_label_file_parser(tmp_path):
     assert read_openseg_labels(str(f)) == [["person", "child"], ["traffic light"], ["sky"]]
     summary = json.load(open(os.path.join(GOLD, "openseg_labels.json")))
     assert summary["coco_panoptic_with_prompt_eng"]["categories"] == 133 and summary["coco_panoptic_with_prompt_eng"]["strings"] == 254
-    root = "/root/reference/odise/data/datasets/openseg_labels"
-    if os.path.isdir(root):
-        for name, want in summary.items():
-            ls = read_openseg_labels(os.path.join(root, name + ".txt"))
-            assert (len(ls), sum(len(l) for l in ls)) == (want["categories"], want["strings"])
-            assert hashlib.sha256(json.dumps(ls).encode()).hexdigest() == want["sha256"], name
+    root = os.path.join(GOLD, "openseg_labels")
+    for name, want in summary.items():
+        ls = read_openseg_labels(os.path.join(root, name + ".txt"))
+        assert (len(ls), sum(len(l) for l in ls)) == (want["categories"], want["strings"])
+        assert hashlib.sha256(json.dumps(ls).encode()).hexdigest() == want["sha256"], name
