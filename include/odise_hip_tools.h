@@ -37,7 +37,8 @@ int odise_hip_gemm_ln(odise_hip_ctx* ctx, const odise_gemm_desc* d, const float*
  * *stats_blocks = row blocks per image (0: this kernel declined the fusion, the stand-alone GroupNorm ran) */
 int odise_hip_conv2d_gn_forced(odise_hip_ctx* ctx, const odise_conv_desc* d, int tile, int splitk, const float* gamma, const float* beta,
                                int groups, float eps, int act, void* y_norm, float* stats_scratch, int* stats_blocks);
-/* process-wide kernel-selection switches for A/B measurements (bits: gemm.hip launch_gemm) */
+/* process-wide kernel-selection switches for A/B measurements (bits 0-3: timing ablations of the tools build; bits 4-23: gemm.hip g_conv_flags << 4).
+ * Bits of retired kernel generations and switches (1, 4, 8, 4096, 8192, 16384 << 4; 1 << 24 and up) are accepted and ignored. */
 int odise_hip_gemm_debug(int flags);
 
 /* 1: the post-processing kernels never take their exact-x4-upsampling specialisations (tests assert both forms are bit-identical);

@@ -6,13 +6,14 @@
 // These are the dense conv / im2col and Linear GEMMs of the SD-v1 UNet ResBlock / SpatialTransformer
 // (ldm.py:469-491 -> ldm UNetModel), the VAE, CLIP and Mask2Former heads.
 //
-// CDNA4 mapping (v_mfma_f32_32x32x16_f16, fp32 accumulate, block tile BM x BN x 64):
+// CDNA4 mapping (v_mfma_f32_16x16x32_f16, fp32 accumulate, block tile BM x BN x 64):
 //   * gemm_kernel      - 4- or 8-wave tiles 64x64 .. 256x320; A and W tiles go global -> LDS by LDS-DMA (global_load_lds_dwordx4),
 //                        double-buffered, one barrier per K-tile; small / ragged problems, split-K over grid.z.
 //   * gemm_pp_kernel   - 256x256 / 256x320 / 512x128 tiles, 8 waves in two groups staggered by a barrier (one multiplies while the
 //                        other feeds), DMA in flight across barriers with counted vmcnt.
 //   * gemm_pp2_kernel  - same, with the next phase's fragment reads issued under the MFMAs.
 //   * conv3_halo_kernel- 3x3 convs: A fragments come from an LDS-resident 18x18 input patch fetched once per 64-channel chunk.
+//   * conv3_halo4_kernel - the same patch reuse with four waves, two blocks per CU.
 //   LDS rows are 128 B (64 halves); 16-byte slots are XOR-swizzled (applied to the DMA source address, the LDS image of a DMA
 //   instruction being lane-linear) so that the 16-lane groups of ds_read_b128 hit 16 distinct slots of the 256-B bank row.
 //   The epilogue goes through LDS (fp32) so that bias / time-embedding broadcast / activation / GEGLU / residual run on 8 consecutive
@@ -20,7 +21,6 @@
 //   cost model.  Every variant keeps the same fp32 summation order: results are bit-identical across kernels for a given K order.
 #include "common.h"
 #include <stdlib.h>
-#include <type_traits>
 
 // Timing-only ablation switches (GemmArgs::dbg: drop the operand DMA / fragment reads / epilogue, freeze the K walk) and the
 // ODISE_GEMM_FLAGS / ODISE_GEMM_FREEZE_K environment switches exist only in the measurement build of the library
@@ -172,7 +172,7 @@ __device__ __forceinline__ void epi_store8(const GemmEpi& e, float (&v)[8], int 
 }
 
 // Block tile BM x BN x 64 computed by WAVES_M x WAVES_N wavefronts (each a (BM/WAVES_M) x (BN/WAVES_N) sub-tile of
-// 32x32x16 MFMAs).  Instantiated as 4-wave tiles (128x128, 64x128, 64x64: small problems, with split-K) and 8-wave
+// 32x32 blocks of 16x16x32 MFMAs).  Instantiated as 4-wave tiles (128x128, 64x128, 64x64: small problems, with split-K) and 8-wave
 // tiles (256x320 for the 320*k channel counts of the SD UNet, 256x256, 256x128): at 256 rows one K-tile carries
 // 2048-2560 MFMA cycles per SIMD, which covers an L2-miss round trip with a single tile of LDS-DMA prefetch in flight,
 // and halves the operand bytes per flop (29 B/clk/CU at peak vs the 64 B/clk/CU L1 limit).
@@ -287,7 +287,7 @@ constexpr int epi16_wave_rows(int BM, int BN, int WAVES_M, int lds_bytes) {
     while (WAVES_M % ew) --ew;
     return ew;
 }
-// Where the math-first form runs (0 = keep the fp32-staged epilogue).  Measured on MI355X (tools/epi16_ab.py, profiles/r03_epilogue_f16_ab.txt):
+// Where the math-first form runs (0 = keep the fp32-staged epilogue).  Measured on MI355X (profiles/r03_epilogue_f16_ab.txt):
 // both forms are bound by the write burst of a round - every CU stores its tile at the same time, ~2.5 TB/s across the chip - so the
 // shorter LDS / VALU path only pays where the tile is staged in ONE pass: +4 % on the 3x3 convolutions (halo tiles), +6..15 % on the
 // GEGLU GEMMs (256x256), +15..35 % on 256x128; the two-pass 256x320 tile loses 15-30 % (half of the waves idle per pass and all stores at
@@ -313,60 +313,42 @@ constexpr int epi_wave_rows(int BM, int BN, int WAVES_M, int lds_bytes) {
 constexpr int epi_lds_bytes(int BM, int BN, int WAVES_M, int WG) { return WG * (BM / WAVES_M) * (BN + 4) * 4; }
 
 // ---- how a wave's sub-tile sits in its accumulator registers -------------------------------------------------------------------------
-// Per 32x32 block (p, j) of the sub-tile a lane owns NR rows x NC column quads; quad (rr, cc) = registers 4 (rr NC + cc) .. + 3 of the
-// block's 16 = four consecutive columns of one row (the kernels multiply with the MFMA operands swapped, see gemm_epilogue).
-//   L16 = false: one v_mfma_f32_32x32x16_f16 tile - row l & 31, quads 8 cc + 4 (l >> 5)                     (f32x16 acc[TM][TN])
-//   L16 = true : 2 x 2 v_mfma_f32_16x16x32_f16 tiles - rows 16 rr + (l & 15), quads 16 cc + 4 (l >> 4)      (f32x4 acc[TM][TN][4], [2 rr + cc])
+// A 32x32 block (p, j) of the sub-tile is 2 x 2 v_mfma_f32_16x16x32_f16 tiles (AccBlock: f32x4 [2 rr + cc]).  Per block a lane owns NR rows x
+// NC column quads: rows 16 rr + (l & 15), quads 16 cc + 4 (l >> 4); quad (rr, cc) = registers 4 (rr NC + cc) .. + 3 of the block's 16 = four
+// consecutive columns of one row (the kernels multiply with the MFMA operands swapped, see gemm_epilogue).
 // Round 5: on operands that toggle like real data the matrix pipes are power-bound, and the 16x16x32 instruction sustains 1.95 PFLOP/s
 // (1.84 GHz) where 32x32x16 sustains 1.62 (1.52 GHz) - tools/mfma_rate.py, profiles/r05_mfma_rate_by_shape.txt; same FLOPs, fragment
 // bytes and LDS reads per 32x32 block either way.
-template <bool L16>
-struct FragLayout;
-template <>
-struct FragLayout<false> {
-    static constexpr int NR = 1, NC = 4;
-    static __device__ __forceinline__ int row(int lane, int) { return lane & 31; }
-    static __device__ __forceinline__ int col(int lane, int cc) { return 8 * cc + 4 * (lane >> 5); }
-    static __device__ __forceinline__ bool leader(int lane) { return lane < 32; }                    // one lane per row
-    static __device__ __forceinline__ float row_sum(float v) { return v + __shfl_xor(v, 32); }       // over the lanes that share a row
-};
-template <>
-struct FragLayout<true> {
+struct FragLayout {
     static constexpr int NR = 2, NC = 2;
     static __device__ __forceinline__ int row(int lane, int rr) { return 16 * rr + (lane & 15); }
     static __device__ __forceinline__ int col(int lane, int cc) { return 16 * cc + 4 * (lane >> 4); }
-    static __device__ __forceinline__ bool leader(int lane) { return lane < 16; }
-    static __device__ __forceinline__ float row_sum(float v) { v += __shfl_xor(v, 16); return v + __shfl_xor(v, 32); }
+    static __device__ __forceinline__ bool leader(int lane) { return lane < 16; }                                        // one lane per row
+    static __device__ __forceinline__ float row_sum(float v) { v += __shfl_xor(v, 16); return v + __shfl_xor(v, 32); }   // over the lanes that share a row
 };
-template <class ACC>
-struct AccTraits;
-template <int TM_, int TN_>
-struct AccTraits<f32x16[TM_][TN_]> { static constexpr bool L16 = false; static constexpr int TM = TM_, TN = TN_; };
-template <int TM_, int TN_>
-struct AccTraits<f32x4[TM_][TN_][4]> { static constexpr bool L16 = true; static constexpr int TM = TM_, TN = TN_; };
+typedef f32x4 AccBlock[4];
+// the accumulators of a wave's (BM / WAVES_M) x (BN / WAVES_N) sub-tile
+template <int BM, int BN, int WAVES_M, int WAVES_N>
+using WaveAcc = AccBlock[BM / WAVES_M / 32][BN / WAVES_N / 32];
 template <int TM, int TN>
-__device__ __forceinline__ float acc_get(const f32x16 (&a)[TM][TN], int p, int j, int r) { return a[p][j][r]; }
-template <int TM, int TN>
-__device__ __forceinline__ float acc_get(const f32x4 (&a)[TM][TN][4], int p, int j, int r) { return a[p][j][r >> 2][r & 3]; }
+__device__ __forceinline__ float acc_get(const AccBlock (&a)[TM][TN], int p, int j, int r) { return a[p][j][r >> 2][r & 3]; }
 
 // ---- math-first epilogue for fp16 outputs ----------------------------------------------------------------------------------------------
 // The fp32-staged epilogue below costs a 256x256 tile ~12 us, a third of a K = 1024 GEMM: the accumulators go through LDS as fp32 in up to
 // four passes in which only the waves of one or two wave-rows write while the others wait, and every thread then walks 16 dependent rounds of
 // {LDS read, bias / activation / residual arithmetic, convert, store}.  Here every wave applies the epilogue to its OWN accumulators in
-// registers (lane l of a 32x32 tile owns row l & 31 and, per register quad, four consecutive columns: bias and residual come in as 16- and
-// 8-byte loads of exactly those columns), rounds to fp16 and stages 8 bytes per quad; the tile then sits in LDS in its final form at half the
+// registers (per register quad a lane owns four consecutive columns of one row, FragLayout: bias and residual come in as 16- and 8-byte
+// loads of exactly those columns), rounds to fp16 and stages 8 bytes per quad; the tile then sits in LDS in its final form at half the
 // size - one pass for every tile but 256x320 - and the second phase is a pure copy: all of a thread's 16-byte LDS reads are issued back to
-// back, then its global stores.  Element for element the arithmetic is that of epi_fast8 in the same order: results are bit-identical
-// (tools/epi_ab.py compares the two forms; ODISE_EPI_OLD=1 in the tools build keeps the fp32-staged form).
+// back, then its global stores.  Element for element the arithmetic is that of epi_fast8 in the same order: results are bit-identical.
 // Staging rows are (BN + 8) halves: 16-byte aligned for the copy's ds_read_b128; the quad writes of 16 consecutive rows land 2-way on the
 // banks (row pitch = 4 banks mod 32), which stays below the write instruction's own issue cost.
-template <int BM, int BN, int WAVES_M, int WAVES_N, int EW, bool HALO, bool STATS, bool GEGLU, class ACC>
-__device__ __forceinline__ void gemm_epilogue_f16(const GemmArgs& g, ACC& acc, char* smem, int m0, int n0, int zb) {
+template <int BM, int BN, int WAVES_M, int WAVES_N, int EW, bool HALO, bool STATS, bool GEGLU>
+__device__ __forceinline__ void gemm_epilogue_f16(const GemmArgs& g, WaveAcc<BM, BN, WAVES_M, WAVES_N>& acc, char* smem, int m0, int n0, int zb) {
     constexpr int NT = 64 * WAVES_M * WAVES_N;
     constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
     constexpr int TM = WTM / 32, TN = WTN / 32;
-    static_assert(AccTraits<ACC>::TM == TM && AccTraits<ACC>::TN == TN, "accumulator array does not match the wave tile");
-    using FL = FragLayout<AccTraits<ACC>::L16>;
+    using FL = FragLayout;
     constexpr int NR = FL::NR, NC = FL::NC, TR = TM * NR;   // rows per lane: TR
     constexpr int ROWS = EW * WTM;                 // tile rows per pass
     constexpr int BNO = GEGLU ? BN / 2 : BN;       // output columns of the tile
@@ -595,7 +577,7 @@ __device__ __forceinline__ void gemm_epilogue_f16(const GemmArgs& g, ACC& acc, c
 }
 
 // ---- wave-private epilogue (round 5) -------------------------------------------------------------------------------------------------
-// Measured (tools/g8_ablate.py, profiles/r05_epilogue_share.txt): the two block-wide epilogues below cost a 256x256 tile 18-23 us per residency
+// Measured (profiles/r05_epilogue_share.txt): the two block-wide epilogues below cost a 256x256 tile 18-23 us per residency
 // round - 40 of 110 us on the CLIP c_fc GEMM (K = 1024), 16-20 of 115 us at 4096^3 - where the yardstick kernel of csrc/gemm8p.hip spends
 // 3-4 us: they stage the whole tile behind block barriers (every wave waits for the slowest), the math-first form reads the residual and
 // writes LDS in fragment layout (8-byte pieces of 16 rows per instruction), and with one block per CU nothing else runs meanwhile.
@@ -612,20 +594,19 @@ constexpr int wave_epi_rows(int WTM, int WTN, int waves, int lds_bytes, int rmin
         if (WTM % r == 0 && (r * chw) % 64 == 0 && r * (WTN + 4) * 4 <= lds_bytes / waves) best = r;
     return best;
 }
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool HALO, bool STATS, bool GEGLU_OK, int LDSB, class ACC>
-__device__ __forceinline__ void gemm_epilogue_wave(const GemmArgs& g, ACC& acc, char* smem, int m0, int n0, int zb) {
-    constexpr bool L16 = AccTraits<ACC>::L16;
-    using FL = FragLayout<L16>;
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool HALO, bool STATS, bool GEGLU_OK, int LDSB>
+__device__ __forceinline__ void gemm_epilogue_wave(const GemmArgs& g, WaveAcc<BM, BN, WAVES_M, WAVES_N>& acc, char* smem, int m0, int n0, int zb) {
+    using FL = FragLayout;
     constexpr int NWAVES = WAVES_M * WAVES_N;
     constexpr int WTM = BM / WAVES_M, WTN = BN / WAVES_N;
     constexpr int TN = WTN / 32;
-    constexpr int R = wave_epi_rows(WTM, WTN, NWAVES, LDSB, L16 ? 16 : 32);
+    constexpr int RSUB = 16;                   // rows a lane group covers per fragment row index
+    constexpr int R = wave_epi_rows(WTM, WTN, NWAVES, LDSB, RSUB);
     static_assert(R > 0, "no wave-private staging fits");
     constexpr int PITCH = WTN + 4;             // floats
     constexpr int CHW = WTN / 8;               // 8-column chunks per row of the wave tile
     constexpr int ITEMS = R * CHW / 64;        // (row, chunk) items per lane and pass
     constexpr bool FIXED = (64 % CHW) == 0;    // a lane keeps ONE column chunk over all its items: per-column terms are loaded once
-    constexpr int RSUB = L16 ? 16 : 32;        // rows a lane group covers per fragment row index
     const GemmEpi& e = g.epi;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -719,7 +700,7 @@ __device__ __forceinline__ void gemm_epilogue_wave(const GemmArgs& g, ACC& acc, 
             for (int rr = 0; rr < FL::NR; ++rr) {
                 const int rbase = p * 32 + rr * RSUB;          // first tile row of this fragment row group (compile-time after unrolling)
                 if (rbase < ps * R || rbase >= (ps + 1) * R) continue;
-                const int row = rbase - ps * R + (L16 ? (lane & 15) : (lane & 31));
+                const int row = rbase - ps * R + (lane & 15);
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -944,25 +925,24 @@ __device__ __forceinline__ void gemm_epilogue_wave(const GemmArgs& g, ACC& acc, 
     }
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, int WG, bool HALO = false, bool STATS = false, bool PAIRS = true, int EW16 = 0, bool GEGLU_OK = false, int LDSB = 0,
-          class ACC>
-__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, char* smem, int m0, int n0, int z, int zb, bool split) {
-    using FL = FragLayout<AccTraits<ACC>::L16>;
-    // LDSB = the kernel's LDS request: the wave-private form wherever it applies (tools: ODISE_EPI_OLD=1 keeps the block-wide forms).  8-wave kernels
-    // only: in the 4-wave kernels (64x64 .. 128x128 tiles, several blocks per CU) it returned rare wrong elements on the hardware - one dword of a
-    // staged row read as zero in lanes 48-63, not cured by a barrier or a full LDS wait between staging and read-back, never seen with 8 waves
-    // (tools/epi_debug.py; unexplained, so those kernels keep the block-wide forms)
-    // Where it measured faster (tools/g8_shapes.py, profiles/r05_epilogue_forms.txt): wave tiles whose 8-column chunks divide the wavefront (a lane keeps one
+template <int BM, int BN, int WAVES_M, int WAVES_N, int WG, bool HALO = false, bool STATS = false, bool PAIRS = true, int EW16 = 0, bool GEGLU_OK = false, int LDSB = 0>
+__device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, WaveAcc<BM, BN, WAVES_M, WAVES_N>& acc, char* smem, int m0, int n0, int z, int zb, bool split) {
+    using FL = FragLayout;
+    // LDSB = the kernel's LDS request: the wave-private form wherever it applies.  8-wave kernels only: in the 4-wave kernels (64x64 .. 128x128
+    // tiles, several blocks per CU) it returned rare wrong elements on the hardware - one dword of a staged row read as zero in lanes 48-63, not
+    // cured by a barrier or a full LDS wait between staging and read-back, never seen with 8 waves (unexplained, so those kernels keep the
+    // block-wide forms)
+    // Where it measured faster (profiles/r05_epilogue_forms.txt): wave tiles whose 8-column chunks divide the wavefront (a lane keeps one
     // chunk: everything but the 256x320 tile), without GEGLU (its half-width rows leave the lean loop; the block-wide form is ~15 % ahead there).
     // ODISE_GEMM_FLAGS 32768 keeps the block-wide forms everywhere (A/B of whole steps: bench.py --gemm-flags).
     if constexpr (LDSB > 0 && WAVES_M * WAVES_N == 8 && (64 % ((BN / WAVES_N) / 8)) == 0) {
-        if (g.epi.fast && !split && !g.epi.geglu && !g.epi_block && !ODISE_ABLATE(g, 8 | 32)) {
+        if (g.epi.fast && !split && !g.epi.geglu && !g.epi_block && !ODISE_ABLATE(g, 8)) {
             gemm_epilogue_wave<BM, BN, WAVES_M, WAVES_N, HALO, STATS, GEGLU_OK, LDSB>(g, acc, smem, m0, n0, zb);
             return;
         }
     }
     if constexpr (EW16 > 0) {
-        if (g.epi.f16path && !split && !ODISE_ABLATE(g, 8 | 32)) {   // tools: ODISE_EPI_OLD=1 (bit 32) keeps the fp32-staged form for A/B runs
+        if (g.epi.f16path && !split && !ODISE_ABLATE(g, 8)) {
             if constexpr (GEGLU_OK) {
                 if (g.epi.geglu) { gemm_epilogue_f16<BM, BN, WAVES_M, WAVES_N, EW16, HALO, false, true>(g, acc, smem, m0, n0, zb); return; }
             }
@@ -1024,9 +1004,9 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, char*
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     // The kernels multiply with the operands swapped - acc = mfma(b_frag, a_frag, acc), same products and k order, i.e. the same
-                    // bits - so the 32x32 tile sits TRANSPOSED in the registers: lane l owns row l & 31 and, per register quad q, the four
-                    // consecutive columns 8q + 4(l >> 5) + (0..3).  A quad is one 16-byte staging write (32 ds_write_b128 per wave and tile
-                    // instead of 128 ds_write_b32); eight consecutive rows of the padded staging image hit all 32 banks once ((BN + 4) % 32 == 4).
+                    // bits - so the tile sits TRANSPOSED in the registers: per register quad a lane owns four consecutive columns of one row
+                    // (FragLayout).  A quad is one 16-byte staging write (32 ds_write_b128 per wave and tile instead of 128 ds_write_b32); eight
+                    // consecutive rows of the padded staging image hit all 32 banks once ((BN + 4) % 32 == 4).
 #pragma unroll
                     for (int rr = 0; rr < FL::NR; ++rr) {
                         const int row = (wm % WG) * WTM + p * 32 + FL::row(lane, rr);
@@ -1051,7 +1031,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, char*
         // loaded once per kernel.  The runtime-flag-per-element form below serialised a global-load round trip per row (8-16 per tile).
         // Same operations in the same order per element as epi_fast8: results are bit-identical.
         if constexpr ((NT % CH == 0) && ((ROWS * CH) % NT == 0)) {
-            if (g.epi.fast && !split && n0 + BN <= g.N && !ODISE_ABLATE(g, 8 | 32)) {   // tools: ODISE_EPI_OLD=1 (bit 32) keeps the previous form for A/B runs
+            if (g.epi.fast && !split && n0 + BN <= g.N && !ODISE_ABLATE(g, 8)) {
                 constexpr int IT = (ROWS * CH) / NT, RSTEP = NT / CH;
                 // rows in pairs where the registers allow it: kernels that also carry the GroupNorm statistics (16 accumulators) or the plain
                 // kernel's wider address state would spill to scratch (measured as +144 MB of HBM writes per launch on the dominant conv)
@@ -1251,49 +1231,30 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, ACC& acc, char*
 }
 
 // ---- MFMA shape of the main loops --------------------------------------------------------------------------------------------------
-// Every kernel below walks a 64-deep K-tile of a 32x32 output block in Frag::NSTEP steps; a step consumes Frag::PER fragments (16 bytes
-// per lane each) of the block's A rows and of its B rows:
-//   32x32x16: 4 steps of one MFMA; fragment = rows l & 31, 16-byte k-slot 2 st + (l >> 5)
-//   16x16x32: 2 steps of 2 x 2 MFMAs; fragment u = rows 16 u + (l & 15), k-slot 4 st + (l >> 4)
-// Same fragment bytes, LDS reads and FLOPs per block either way.  kL16 selects the shape for all of them (round 5: the 16x16x32
-// instruction sustains 1.95 PFLOP/s on operands that toggle like real data, 32x32x16 is power-bound at 1.62 - FragLayout above); the
-// k order inside a K-tile (steps ascending) is the same in every kernel, so kernels still agree bit for bit on a given K walk.
-#ifdef ODISE_MFMA32   // A/B build only (python -m odise_amd.build --m32): the MFMA shape of rounds 1-4
-constexpr bool kL16 = false;
-#else
-constexpr bool kL16 = true;
-#endif
-template <bool L16>
+// Every kernel below walks a 64-deep K-tile of a 32x32 output block in Frag::NSTEP = 2 steps of 2 x 2 v_mfma_f32_16x16x32_f16; a step
+// consumes Frag::PER = 2 fragments (16 bytes per lane each) of the block's A rows and of its B rows: fragment u = rows 16 u + (l & 15),
+// 16-byte k-slot 4 st + (l >> 4).  The k order inside a K-tile (steps ascending) is the same in every kernel, so kernels agree bit for bit
+// on a given K walk.
 struct Frag {
-    static constexpr int NSTEP = L16 ? 2 : 4;
-    static constexpr int PER = L16 ? 2 : 1;
-    static __device__ __forceinline__ int lrow(int lane) { return L16 ? (lane & 15) : (lane & 31); }
-    static __device__ __forceinline__ int lk(int lane) { return L16 ? (lane >> 4) : (lane >> 5); }
-    static __device__ __forceinline__ int kslot(int st, int lk) { return L16 ? st * 4 + lk : st * 2 + lk; }
+    static constexpr int NSTEP = 2;
+    static constexpr int PER = 2;
+    static __device__ __forceinline__ int lrow(int lane) { return lane & 15; }
+    static __device__ __forceinline__ int lk(int lane) { return lane >> 4; }
+    static __device__ __forceinline__ int kslot(int st, int lk) { return st * 4 + lk; }
 };
-template <bool L16> struct AccBlockT { typedef f32x16 type; };
-template <> struct AccBlockT<true> { typedef f32x4 type[4]; };
-template <bool L16> using AccBlock = typename AccBlockT<L16>::type;
-__device__ __forceinline__ void acc_zero(f32x16& a) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.f;
-}
-__device__ __forceinline__ void acc_zero(f32x4 (&a)[4]) {
+__device__ __forceinline__ void acc_zero(AccBlock& a) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) a[t] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 // one step of a 32x32 block; operands swapped (transposed tile in the registers, see gemm_epilogue)
-__device__ __forceinline__ void mma_step(f32x16& acc, const f16x8 (&b)[1], const f16x8 (&a)[1]) {
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(b[0], a[0], acc, 0, 0, 0);
-}
-__device__ __forceinline__ void mma_step(f32x4 (&acc)[4], const f16x8 (&b)[2], const f16x8 (&a)[2]) {
+__device__ __forceinline__ void mma_step(AccBlock& acc, const f16x8 (&b)[2], const f16x8 (&a)[2]) {
 #pragma unroll
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) acc[rt * 2 + ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[ct], a[rt], acc[rt * 2 + ct], 0, 0, 0);
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool CONV, bool INTERLEAVE>
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool CONV>
 __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) gemm_kernel(GemmArgs g) {
     constexpr int BK = 64;
     constexpr int NT = 64 * WAVES_M * WAVES_N;
@@ -1446,7 +1407,7 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) gemm_kernel(GemmArgs g
         for (int l = 0; l < NL; ++l) issue_load(l, stage);
     };
 
-    AccBlock<kL16> acc[TM][TN];
+    AccBlock acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -1454,11 +1415,10 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) gemm_kernel(GemmArgs g
 
     // The swizzle key (r>>1)&7 of a fragment row r = wave_base + 32*tile + (lane&31) only depends on the lane (bases are
     // multiples of 32), so the four k-step slot offsets are shared by every A and B fragment of this lane.
-    using FR = Frag<kL16>;
-    const int lrow = FR::lrow(lane), lkq = FR::lk(lane);
-    int koff[FR::NSTEP];   // 16-byte slot of step st, swizzled with the lane's row key (tile bases are multiples of 16 rows); fragment u: + u * 16 rows
+    const int lrow = Frag::lrow(lane), lkq = Frag::lk(lane);
+    int koff[Frag::NSTEP];   // 16-byte slot of step st, swizzled with the lane's row key (tile bases are multiples of 16 rows); fragment u: + u * 16 rows
 #pragma unroll
-    for (int s = 0; s < FR::NSTEP; ++s) koff[s] = (FR::kslot(s, lkq) ^ ((lrow >> 1) & 7)) << 4;
+    for (int s = 0; s < Frag::NSTEP; ++s) koff[s] = (Frag::kslot(s, lkq) ^ ((lrow >> 1) & 7)) << 4;
     const int a_lane_off = (wm * WTM + lrow) * 128;
     const int b_lane_off = (wn * WTN + lrow) * 128;
 
@@ -1472,40 +1432,35 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N) gemm_kernel(GemmArgs g
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         const bool dma = more && !(ODISE_ABLATE(g, 1));
-        if (dma) {
-            if (INTERLEAVE) prep_tile(kt + 1);
-            else issue_tile(kt + 1, cur ^ 1);
-        }
+        if (dma) prep_tile(kt + 1);
         // fragment reads: per-lane base + per-k-step swizzled slot offset (loop invariant) + compile-time tile offset
         const char* fa = smem + cur * STAGE_BYTES + a_lane_off;
         const char* fb = smem + cur * STAGE_BYTES + BM * BK * 2 + b_lane_off;
-        f16x8 af[TM][FR::PER], bf[TN][FR::PER];
+        f16x8 af[TM][Frag::PER], bf[TN][Frag::PER];
 #pragma unroll
-        for (int s = 0; s < FR::NSTEP; ++s) {
+        for (int s = 0; s < Frag::NSTEP; ++s) {
             if (!(ODISE_ABLATE(g, 2)) || (kt == kt_begin && s == 0)) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i)
 #pragma unroll
-                    for (int u = 0; u < FR::PER; ++u) af[i][u] = *reinterpret_cast<const f16x8*>(fa + koff[s] + i * 4096 + u * 2048);
+                    for (int u = 0; u < Frag::PER; ++u) af[i][u] = *reinterpret_cast<const f16x8*>(fa + koff[s] + i * 4096 + u * 2048);
 #pragma unroll
                 for (int j = 0; j < TN; ++j)
 #pragma unroll
-                    for (int u = 0; u < FR::PER; ++u) bf[j][u] = *reinterpret_cast<const f16x8*>(fb + koff[s] + j * 4096 + u * 2048);
+                    for (int u = 0; u < Frag::PER; ++u) bf[j][u] = *reinterpret_cast<const f16x8*>(fb + koff[s] + j * 4096 + u * 2048);
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
                 for (int j = 0; j < TN; ++j) mma_step(acc[i][j], bf[j], af[i]);  // operands swapped: transposed tile (see gemm_epilogue)
-            if (INTERLEAVE) {
-                // next tile's LDS-DMA loads are issued in the shadow of this k-step's MFMAs (the matrix pipe keeps
-                // draining the queued MFMAs while the wave issues address math + global_load_lds)
-                if (dma) {
+            // next tile's LDS-DMA loads are issued in the shadow of this k-step's MFMAs (the matrix pipe keeps
+            // draining the queued MFMAs while the wave issues address math + global_load_lds)
+            if (dma) {
 #pragma unroll
-                    for (int l = 0; l < NL; ++l)
-                        if ((l * FR::NSTEP) / NL == s) issue_load(l, cur ^ 1);
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                for (int l = 0; l < NL; ++l)
+                    if ((l * Frag::NSTEP) / NL == s) issue_load(l, cur ^ 1);
             }
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
     __syncthreads();  // every wave is done with the operand tiles before the staging buffer is reused
@@ -1697,17 +1652,16 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(GemmArgs g) {
         glds16(src, smem + stage * STAGE_BYTES + A_BYTES + b_lds0 + j * RB * 128);
     };
 
-    AccBlock<kL16> acc[TM][TN];
+    AccBlock acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc_zero(acc[i][j]);
 
-    using FR = Frag<kL16>;
-    const int lrow = FR::lrow(lane), lkq = FR::lk(lane);
-    int koff[FR::NSTEP];   // 16-byte slot of step st, swizzled with the lane's row key (tile bases are multiples of 16 rows); fragment u: + u * 16 rows
+    const int lrow = Frag::lrow(lane), lkq = Frag::lk(lane);
+    int koff[Frag::NSTEP];   // 16-byte slot of step st, swizzled with the lane's row key (tile bases are multiples of 16 rows); fragment u: + u * 16 rows
 #pragma unroll
-    for (int s = 0; s < FR::NSTEP; ++s) koff[s] = (FR::kslot(s, lkq) ^ ((lrow >> 1) & 7)) << 4;
+    for (int s = 0; s < Frag::NSTEP; ++s) koff[s] = (Frag::kslot(s, lkq) ^ ((lrow >> 1) & 7)) << 4;
     const int a_lane_off = (wm * 64 + lrow) * 128;
     const int b_lane_off = A_BYTES + (wn * WTN + lrow) * 128;
 
@@ -1739,7 +1693,7 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(GemmArgs g) {
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();  // stagger: group 1 runs one barrier interval behind group 0
 
-    f16x8 af[TM][FR::NSTEP][FR::PER], bf[PT][FR::NSTEP][FR::PER];
+    f16x8 af[TM][Frag::NSTEP][Frag::PER], bf[PT][Frag::NSTEP][Frag::PER];
     for (int kt = kt_begin; kt < kt_end; ++kt) {
         const int cur = (kt - kt_begin) & 1;
         const bool has1 = (kt + 1) < kt_end && !(ODISE_ABLATE(g, 1)), has2 = (kt + 2) < kt_end && !(ODISE_ABLATE(g, 1));  // dbg 1: ablate the DMA
@@ -1756,17 +1710,17 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(GemmArgs g) {
 #pragma unroll
                     for (int i = 0; i < TM; ++i)
 #pragma unroll
-                        for (int s = 0; s < FR::NSTEP; ++s)
+                        for (int s = 0; s < Frag::NSTEP; ++s)
 #pragma unroll
-                            for (int u = 0; u < FR::PER; ++u) af[i][s][u] = *reinterpret_cast<const f16x8*>(fa + koff[s] + i * 4096 + u * 2048);
+                            for (int u = 0; u < Frag::PER; ++u) af[i][s][u] = *reinterpret_cast<const f16x8*>(fa + koff[s] + i * 4096 + u * 2048);
                 }
 #pragma unroll
                 for (int jj = 0; jj < PT; ++jj)
                     if (jj < nj && rd) {
 #pragma unroll
-                        for (int s = 0; s < FR::NSTEP; ++s)
+                        for (int s = 0; s < Frag::NSTEP; ++s)
 #pragma unroll
-                            for (int u = 0; u < FR::PER; ++u) bf[jj][s][u] = *reinterpret_cast<const f16x8*>(fb + koff[s] + (j0 + jj) * 4096 + u * 2048);
+                            for (int u = 0; u < Frag::PER; ++u) bf[jj][s][u] = *reinterpret_cast<const f16x8*>(fb + koff[s] + (j0 + jj) * 4096 + u * 2048);
                     }
             };
             read_frags();
@@ -1825,7 +1779,7 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(GemmArgs g) {
             // -------- MFMA segment
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int s = 0; s < FR::NSTEP; ++s)
+            for (int s = 0; s < Frag::NSTEP; ++s)
 #pragma unroll
                 for (int jj = 0; jj < PT; ++jj)
                     if (jj < nj) {
@@ -2051,17 +2005,16 @@ __global__ void __launch_bounds__(512) gemm_pp2_kernel(GemmArgs g) {
         glds16(src, smem + stage * STAGE_BYTES + A_BYTES + b_lds0 + j * RB * 128);
     };
 
-    AccBlock<kL16> acc[TM][TN];
+    AccBlock acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc_zero(acc[i][j]);
 
-    using FR = Frag<kL16>;
-    const int lrow = FR::lrow(lane), lkq = FR::lk(lane);
-    int koff[FR::NSTEP];   // 16-byte slot of step st, swizzled with the lane's row key (tile bases are multiples of 16 rows); fragment u: + u * 16 rows
+    const int lrow = Frag::lrow(lane), lkq = Frag::lk(lane);
+    int koff[Frag::NSTEP];   // 16-byte slot of step st, swizzled with the lane's row key (tile bases are multiples of 16 rows); fragment u: + u * 16 rows
 #pragma unroll
-    for (int s = 0; s < FR::NSTEP; ++s) koff[s] = (FR::kslot(s, lkq) ^ ((lrow >> 1) & 7)) << 4;
+    for (int s = 0; s < Frag::NSTEP; ++s) koff[s] = (Frag::kslot(s, lkq) ^ ((lrow >> 1) & 7)) << 4;
     const int a_lane_off = (wm * 64 + lrow) * 128;
     const int b_lane_off = A_BYTES + (wn * WTN + lrow) * 128;
 
@@ -2093,15 +2046,15 @@ __global__ void __launch_bounds__(512) gemm_pp2_kernel(GemmArgs g) {
     t2 = t1;
     advance(t2);
     __builtin_amdgcn_s_barrier();
-    f16x8 af[TM][FR::NSTEP][FR::PER], bf[PT][FR::NSTEP][FR::PER];
+    f16x8 af[TM][Frag::NSTEP][Frag::PER], bf[PT][Frag::NSTEP][Frag::PER];
     // fragments of phase (0,0)
     {
         const char* fa = smem + a_lane_off;
         const char* fb = smem + b_lane_off;
 #pragma unroll
-        for (int s = 0; s < FR::NSTEP; ++s)
+        for (int s = 0; s < Frag::NSTEP; ++s)
 #pragma unroll
-            for (int u = 0; u < FR::PER; ++u) {
+            for (int u = 0; u < Frag::PER; ++u) {
 #pragma unroll
                 for (int i = 0; i < TM; ++i) af[i][s][u] = *reinterpret_cast<const f16x8*>(fa + koff[s] + i * 4096 + u * 2048);
 #pragma unroll
@@ -2136,14 +2089,14 @@ __global__ void __launch_bounds__(512) gemm_pp2_kernel(GemmArgs g) {
             const char* nfb = smem + (next_in_tile ? cur : (cur ^ 1)) * STAGE_BYTES + b_lane_off + (next_in_tile ? (j0 + PT) * 4096 : 0);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int s = 0; s < FR::NSTEP; ++s) {
+            for (int s = 0; s < Frag::NSTEP; ++s) {
 #pragma unroll
                 for (int jj = 0; jj < PT; ++jj)
 #pragma unroll
                     for (int i = 0; i < TM; ++i) mma_step(acc[i][j0 + jj], bf[jj][s], af[i][s]);  // transposed tile (see gemm_epilogue)
                 if (have_next) {
 #pragma unroll
-                    for (int u = 0; u < FR::PER; ++u) {
+                    for (int u = 0; u < Frag::PER; ++u) {
                         if (!next_in_tile) {
 #pragma unroll
                             for (int i = 0; i < TM; ++i) af[i][s][u] = *reinterpret_cast<const f16x8*>(nfa + koff[s] + i * 4096 + u * 2048);
@@ -2167,321 +2120,6 @@ __global__ void __launch_bounds__(512) gemm_pp2_kernel(GemmArgs g) {
     if (ODISE_ABLATE(g, 4)) return;
     gemm_epilogue<BM, BN, WAVES_M, WAVES_N, epi_wave_rows(BM, BN, WAVES_M, pp_lds_bytes(BM, BN, WAVES_M)), false, CONV, true,
                   epi16_rows_if_enabled(BM, BN, WAVES_M, pp_lds_bytes(BM, BN, WAVES_M)), !CONV, pp_lds_bytes(BM, BN, WAVES_M)>(g, acc, smem, m0, n0, z, zb, split);
-}
-
-// ---- 8-phase pipelined 256x256 tile (round 5) ---------------------------------------------------------------------------------------
-// The schedule of /opt/skills/guides/cdna_hip_programming.md section 5 ("The 256^2 8-phase template"), first built as a yardstick
-// (csrc/gemm8p.hip, tools/gemm8p_bench.py: 1320-1360 TFLOP/s on uniform random operands at 4096^3 / 8192^3 / 65536x1024x4096 against
-// 1030-1110 for the two ping-pong kernels above on the same box, same process, same data: profiles/r05_8phase_vs_pp2.txt) and then moved
-// onto the product's operands, MFMA shape and epilogue:
-//   * 8 waves as 2(M) x 4(N), 128x64 per wave = 4 x 2 tiles of v_mfma_f32_32x32x16_f16 (the shape every kernel of this file uses: with the
-//     k-steps of a K-tile taken in the same order the fp32 sums are the same bits as the other kernels');
-//   * LDS: 2 K-tile buffers x {A0, A1, B0, B1} half-tiles (128 rows x 128 B each; half X0 / X1 = the first / second 64 rows (32 columns) of
-//     every wave row (wave column)), each two global_load_lds_dwordx4 per thread;
-//   * a K-tile is four phases, each one 64x32 quadrant of the wave tile over the whole K-tile (8 MFMAs = 512 matrix-pipe cycles):
-//       phase 1: read B0, A0; stage A1(t+1) -> C[0][0]     phase 3: read A1; stage A0(t+2)  -> C[1][1]
-//       phase 2: read B1;     stage B0(t+2) -> C[0][1]     phase 4: stage B1(t+2); vmcnt(6) -> C[1][0]
-//     {reads, 2 DMA, [wait]} s_barrier lgkmcnt(0) {MFMA} s_barrier; wave row 1 runs one barrier behind wave row 0 (one wave of each per
-//     SIMD), so one group multiplies while the other reads and stages;
-//   * three half-tiles of DMA stay in flight across every barrier; the one vector-memory wait per K-tile (phase 4) retires K-tile t+1,
-//     which is read from the next phase on; a buffer is restaged two phases after its last read (B0: one phase, its reads are retired by
-//     lgkmcnt(8) before phase 1's first barrier).
-// Rows beyond M / N and padded convolution taps read a zero line (no predication of the DMA, uniform vmcnt accounting).
-template <int BM, int BN, bool CONV, bool L16>
-__global__ void __launch_bounds__(512) gemm8_kernel(GemmArgs g) {
-    constexpr int BK = 64, WAVES_M = BM / 128, WAVES_N = BN / 64;
-    static_assert(WAVES_M * WAVES_N == 8 && BM % 128 == 0 && BN % 128 == 0, "8 waves of 128x64");
-    constexpr int JA = BM / 128, JB = BN / 128;                 // 64-row DMA pieces (one 16-byte load per thread) per A / B half-tile
-    constexpr int HALF_A = (BM / 2) * BK * 2, HALF_B = (BN / 2) * BK * 2, STAGE = 2 * HALF_A + 2 * HALF_B;
-    constexpr int OFF_A0 = 0, OFF_A1 = HALF_A, OFF_B0 = 2 * HALF_A, OFF_B1 = 2 * HALF_A + HALF_B;
-    constexpr int INFLIGHT = JA + 2 * JB;                       // loads issued after A1(t+1): B0, A0, B1 of K-tile t+2
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / WAVES_N, wn = wave % WAVES_N;
-    const int grp = wave >> 2;   // waves w and w + 4 share a SIMD: the two groups run one barrier apart
-    int bx, by;
-    {
-        const int nbx = gridDim.x, nb = gridDim.x * gridDim.y;
-        const int bid = blockIdx.y * nbx + blockIdx.x;
-        const int q = nb >> 3, r = nb & 7;
-        const int xcd = bid & 7, idx = bid >> 3;
-        const int logical = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        by = logical / nbx;
-        bx = logical - by * nbx;
-    }
-    const int m0 = by * BM;
-    const int n0 = bx * BN;
-    const int z = blockIdx.z;
-    const bool split = g.splitk > 1;
-    const int zb = split ? 0 : z;
-    const int nk_total = g.K / BK;
-    int kt_begin = 0, kt_end = nk_total;
-    if (split) {
-        kt_begin = z * g.ktiles_per_split;
-        kt_end = kt_begin + g.ktiles_per_split;
-        if (kt_end > nk_total) kt_end = nk_total;
-    }
-    const int nk = kt_end - kt_begin;
-    const f16* Ab = g.A + (int64_t)zb * g.strideA;
-    const f16* Wb = g.W + (int64_t)zb * g.strideW;
-
-    // ---- staging descriptors: the thread fills physical 16-byte slot (lane & 7) of half-tile row i*64 + srow (piece i) and fetches
-    // logical slot ls (XOR swizzle on the source: the LDS image of a DMA instruction is lane-linear)
-    const int srow = wave * 8 + (lane >> 3);
-    const int ls = (lane & 7) ^ ((srow >> 1) & 7);
-    // A half h, piece i: tile row i*128 + h*64 + srow.  Dense: one base pointer, row validity by compare.  Conv: per row the window's
-    // top-left input coordinate (packed y << 16 | x & 0xffff; rows >= M get y far out of range) and a 32-bit element offset.
-    int a_yx[2][JA], a_eoff[2][JA];
-    bool a_ok[2][JA];
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < JA; ++i) {
-            const int m = m0 + i * 128 + h * 64 + srow;
-            const bool ok = m < g.M;
-            a_ok[h][i] = ok;
-            a_yx[h][i] = 0;
-            a_eoff[h][i] = 0;
-            if (CONV) {
-                const int ohw = g.cg.OH * g.cg.OW;
-                const int mm = ok ? m : 0;
-                const int img = mm / ohw;
-                const int rem = mm - img * ohw;
-                const int oy = rem / g.cg.OW;
-                const int ox = rem - oy * g.cg.OW;
-                const int iy0 = ok ? oy * g.cg.stride - g.cg.pad_t : -30000;
-                const int ix0 = ox * g.cg.stride - g.cg.pad_l;
-                a_yx[h][i] = (int)(((unsigned)iy0 << 16) | ((unsigned)ix0 & 0xffffu));
-                a_eoff[h][i] = ok ? (int)((((int64_t)img * g.cg.H + iy0) * g.cg.W + ix0) * g.cg.Cin) + ls * 8 : 0;
-            }
-        }
-    const f16* const a_src = Ab + (int64_t)(m0 + srow) * g.lda + ls * 8;   // dense only
-    // B half h, piece i: tile row (i*2 + wave/4)*64 + h*32 + (wave%4)*8 + lane/8
-    const int b_row = (wave >> 2) * 64 + (wave & 3) * 8 + (lane >> 3);
-    const f16* const b_src = Wb + (int64_t)(n0 + b_row) * g.ldw + ls * 8;
-    bool b_ok[2][JB];
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int i = 0; i < JB; ++i) b_ok[h][i] = (n0 + b_row + i * 128 + h * 32) < g.N;
-    char* const lds_w = smem + wave * 1024;   // this wave's 8 rows inside a 64-row piece
-
-    // K-tile position (wave-uniform, advanced incrementally; conv taps are whole 64-channel chunks walked chunk-major or tap-major: see gemm_kernel::prep_tile)
-    struct TileK {
-        int ky, kx, c0;
-        int64_t a_delta;  // element offset added to the A row offset
-        int kw;           // element offset inside a weight row
-    };
-    auto finish = [&](TileK& t) {
-        if (CONV) {
-            t.a_delta = ((int64_t)t.ky * g.cg.W + t.kx) * g.cg.Cin + t.c0;
-            t.kw = (t.ky * g.cg.KW + t.kx) * g.cg.Cin + t.c0;
-        } else {
-            t.a_delta = t.c0;
-            t.kw = t.c0;
-        }
-    };
-    auto decode = [&](int kt) {
-        TileK t;
-        t.ky = t.kx = 0;
-        t.c0 = kt * BK;
-        if (CONV) {
-            int tap;
-            if (g.cg.chunk_major) {
-                const int taps = g.cg.KH * g.cg.KW;
-                const int chunk = kt / taps;
-                tap = kt - chunk * taps;
-                t.c0 = chunk * BK;
-            } else {
-                tap = (kt * BK) / g.cg.Cin;
-                t.c0 = kt * BK - tap * g.cg.Cin;
-            }
-            t.ky = tap / g.cg.KW;
-            t.kx = tap - t.ky * g.cg.KW;
-        }
-        finish(t);
-        return t;
-    };
-    auto advance = [&](TileK& t) {
-        if (CONV) {
-            if (g.cg.chunk_major) {
-                if (++t.kx == g.cg.KW) {
-                    t.kx = 0;
-                    if (++t.ky == g.cg.KH) { t.ky = 0; t.c0 += BK; }
-                }
-            } else {
-                t.c0 += BK;
-                if (t.c0 == g.cg.Cin) {
-                    t.c0 = 0;
-                    if (++t.kx == g.cg.KW) { t.kx = 0; ++t.ky; }
-                }
-            }
-        } else {
-            t.c0 += BK;
-        }
-        finish(t);
-    };
-    auto stage_A = [&](int h, int buf, const TileK& t) {
-        char* d = lds_w + buf * STAGE + (h ? OFF_A1 : OFF_A0);
-#pragma unroll
-        for (int i = 0; i < JA; ++i) {
-            const f16* src;
-            if (CONV) {
-                const int iy = (a_yx[h][i] >> 16) + t.ky, ix = (int)(short)(a_yx[h][i] & 0xffff) + t.kx;
-                const bool ok = (unsigned)iy < (unsigned)g.cg.H && (unsigned)ix < (unsigned)g.cg.W;
-                src = ok ? Ab + ((int64_t)a_eoff[h][i] + t.a_delta) : g.zeros;
-            } else {
-                src = a_ok[h][i] ? a_src + (int64_t)(i * 128 + h * 64) * g.lda + t.a_delta : g.zeros;
-            }
-            glds16(src, d + i * 8192);
-        }
-    };
-    auto stage_B = [&](int h, int buf, const TileK& t) {
-        char* d = lds_w + buf * STAGE + (h ? OFF_B1 : OFF_B0);
-#pragma unroll
-        for (int i = 0; i < JB; ++i) {
-            const f16* src = b_ok[h][i] ? b_src + (int64_t)(i * 128 + h * 32) * g.ldw + t.kw : g.zeros;
-            glds16(src, d + i * 8192);
-        }
-    };
-
-    // ---- accumulators and fragments of the wave's 128x64 tile (FragLayout).  L16: 16-row tiles i = 0..3 of the 64-row sub-tile (block
-    // p = 2 ih + i / 2, row half i % 2), 16-column tiles jj = 0, 1 of the 32-column sub-tile, k-steps of 32; L32: 32-row tiles i = 0, 1, k-steps of 16
-    typedef typename std::conditional<L16, f32x4[4][2][4], f32x16[4][2]>::type AccT;
-    AccT acc;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            if constexpr (L16) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) acc[i][j][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-            } else {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-            }
-        }
-    // lane reads row lrow of a tile, 16-byte slot kslot(s) of k-step s -> physical slot ^ ((row >> 1) & 7) (tile bases are multiples of 16 rows)
-    const int lrow = L16 ? (lane & 15) : (lane & 31);
-    const int lk = L16 ? (lane >> 4) : (lane >> 5);
-    constexpr int KS = L16 ? 2 : 4, KSLOTS = L16 ? 4 : 2;       // k-steps per K-tile, 16-byte slots per lane group and k-step
-    constexpr int MT = L16 ? 4 : 2, NT_ = L16 ? 2 : 1;          // row / column tiles per sub-tile
-    constexpr int TROWS = L16 ? 16 : 32;
-    int koff[KS];
-#pragma unroll
-    for (int s = 0; s < KS; ++s) koff[s] = ((s * KSLOTS + lk) ^ ((lrow >> 1) & 7)) << 4;
-    const int a_lane = (wm * 64 + lrow) * 128;
-    const int b_lane = (wn * 32 + lrow) * 128;
-    f16x8 af[MT][KS], b0f[NT_][KS], b1f[NT_][KS];
-    auto read_A = [&](int h, int buf) {
-        const char* p = smem + buf * STAGE + (h ? OFF_A1 : OFF_A0) + a_lane;
-#pragma unroll
-        for (int i = 0; i < MT; ++i)
-#pragma unroll
-            for (int s = 0; s < KS; ++s) af[i][s] = *reinterpret_cast<const f16x8*>(p + i * TROWS * 128 + koff[s]);
-    };
-    auto read_B = [&](f16x8 (&bf)[NT_][KS], int h, int buf) {
-        const char* p = smem + buf * STAGE + (h ? OFF_B1 : OFF_B0) + b_lane;
-#pragma unroll
-        for (int j = 0; j < NT_; ++j)
-#pragma unroll
-            for (int s = 0; s < KS; ++s) bf[j][s] = *reinterpret_cast<const f16x8*>(p + j * TROWS * 128 + koff[s]);
-    };
-#define G8_BAR()                               \
-    do {                                       \
-        __builtin_amdgcn_sched_barrier(0);     \
-        __builtin_amdgcn_s_barrier();          \
-        __builtin_amdgcn_sched_barrier(0);     \
-    } while (0)
-    // the MFMAs of quadrant (ih, jh): 64 rows x 32 columns x the whole K-tile; operands swapped (transposed tile in the registers, see gemm_epilogue)
-#define G8_MMA(ih, bfr, jh)                                                                                                               \
-    do {                                                                                                                                  \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                                                \
-        __builtin_amdgcn_sched_barrier(0);                                                                                                \
-        __builtin_amdgcn_s_setprio(1);                                                                                                    \
-        if constexpr (L16) {                                                                                                              \
-            _Pragma("unroll") for (int s = 0; s < 2; ++s)                                                                                 \
-                _Pragma("unroll") for (int i = 0; i < 4; ++i)                                                                             \
-                    _Pragma("unroll") for (int jj = 0; jj < 2; ++jj)                                                                      \
-                        acc[(ih) * 2 + i / 2][jh][(i % 2) * 2 + jj] =                                                                     \
-                            __builtin_amdgcn_mfma_f32_16x16x32_f16(bfr[jj][s], af[i][s], acc[(ih) * 2 + i / 2][jh][(i % 2) * 2 + jj], 0, 0, 0); \
-        } else {                                                                                                                          \
-            _Pragma("unroll") for (int s = 0; s < 4; ++s)                                                                                 \
-                _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                                             \
-                    acc[(ih) * 2 + i][jh] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bfr[0][s], af[i][s], acc[(ih) * 2 + i][jh], 0, 0, 0);  \
-        }                                                                                                                                 \
-        __builtin_amdgcn_s_setprio(0);                                                                                                    \
-        G8_BAR();                                                                                                                         \
-    } while (0)
-
-    TileK t1 = decode(kt_begin), t2;   // t1 / t2: K-tiles t+1 / t+2 of the tile being multiplied
-    // one K-tile (4 phases) on buffer `buf`; has1 / has2: K-tiles t+1 / t+2 exist (compile-time constants in the steady loop, block-uniform
-    // run-time flags in the tail of at most three K-tiles)
-    auto ktile = [&](const int buf, const bool has1, const bool has2) __attribute__((always_inline)) {
-        // phase 1
-        read_B(b0f, 0, buf);
-        __builtin_amdgcn_sched_barrier(0);
-        read_A(0, buf);
-        if (has1) stage_A(1, buf ^ 1, t1);
-        __builtin_amdgcn_sched_barrier(0);
-        asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");   // retires the four B0 reads (issued first): B0 may be restaged in the next phase
-        G8_BAR();
-        G8_MMA(0, b0f, 0);
-        // phase 2
-        read_B(b1f, 1, buf);
-        if (has2) stage_B(0, buf, t2);
-        G8_BAR();
-        G8_MMA(0, b1f, 1);
-        // phase 3
-        read_A(1, buf);
-        if (has2) stage_A(0, buf, t2);
-        G8_BAR();
-        G8_MMA(1, b1f, 1);
-        // phase 4
-        if (has2) { stage_B(1, buf, t2); wait_vmcnt<INFLIGHT>(); }
-        else if (has1) wait_vmcnt<0>();
-        G8_BAR();
-        G8_MMA(1, b0f, 0);
-        t1 = t2;
-        advance(t2);
-    };
-
-    // ---- prologue: K-tile 0 (B0, A0, B1, A1) and B0, A0, B1 of K-tile 1
-    if (nk > 0) {
-        const TileK t0 = t1;
-        advance(t1);
-        stage_B(0, 0, t0); stage_A(0, 0, t0); stage_B(1, 0, t0); stage_A(1, 0, t0);
-        if (nk > 1) {
-            stage_B(0, 1, t1); stage_A(0, 1, t1); stage_B(1, 1, t1);
-            wait_vmcnt<INFLIGHT>();
-        } else {
-            wait_vmcnt<0>();
-        }
-    }
-    t2 = t1;
-    advance(t2);
-    G8_BAR();
-    if (grp == 1) G8_BAR();   // stagger: the second wave group runs one barrier behind the first
-
-    int kt = 0;
-    for (; kt + 3 < nk; kt += 2) {   // steady state: two K-tiles per iteration, buffers and flags compile-time constants
-        ktile(0, true, true);
-        ktile(1, true, true);
-    }
-    for (; kt < nk; ++kt) ktile(kt & 1, kt + 1 < nk, kt + 2 < nk);   // the last one to three K-tiles (kt is even here)
-    if (grp == 0) G8_BAR();   // re-align the two groups
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-#undef G8_MMA
-#undef G8_BAR
-    if (ODISE_ABLATE(g, 4)) return;   // tools: main loop only
-    constexpr int LDS = pp_lds_bytes(BM, BN, WAVES_M);
-    static_assert(LDS >= 2 * STAGE, "operand stages exceed the LDS request");
-    gemm_epilogue<BM, BN, WAVES_M, WAVES_N, epi_wave_rows(BM, BN, WAVES_M, LDS), false, CONV, true, epi16_rows_if_enabled(BM, BN, WAVES_M, LDS), !CONV, LDS>(
-        g, acc, smem, m0, n0, z, zb, split);
 }
 
 // (A third structure - every wave free-running through the four k-steps with register double-buffered fragments and ONE barrier per
@@ -2604,30 +2242,29 @@ __global__ void __launch_bounds__(512) conv3_halo_kernel(GemmArgs g) {
         finish(t);
     };
 
-    AccBlock<kL16> acc[TM][TN];
+    AccBlock acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc_zero(acc[i][j]);
 
-    using FR = Frag<kL16>;
-    const int lrow = FR::lrow(lane), lkq = FR::lk(lane);
-    int koff[FR::NSTEP];   // 16-byte slot of step st, swizzled with the lane's row key (tile bases are multiples of 16 rows); fragment u: + u * 16 rows
+    const int lrow = Frag::lrow(lane), lkq = Frag::lk(lane);
+    int koff[Frag::NSTEP];   // 16-byte slot of step st, swizzled with the lane's row key (tile bases are multiples of 16 rows); fragment u: + u * 16 rows
 #pragma unroll
-    for (int s = 0; s < FR::NSTEP; ++s) koff[s] = (FR::kslot(s, lkq) ^ ((lrow >> 1) & 7)) << 4;
+    for (int s = 0; s < Frag::NSTEP; ++s) koff[s] = (Frag::kslot(s, lkq) ^ ((lrow >> 1) & 7)) << 4;
     const int b_lane_off = (wn * WTN + lrow) * 128;
     const int a_pix0 = (wm * 4 + (lrow >> 4)) * HW_ + (lrow & 15);  // halo pixel of this lane's row of A tile i = 0, fragment 0 at tap (0,0); tile 1: +2 rows, fragment u: + u rows
 
     // A fragments of the K-tile at position t (chunk, tap) for k-step s, from the chunk's halo buffer
-    auto read_a = [&](const TileK& t, int s, f16x8 (&dst)[TM][FR::NSTEP][FR::PER]) {
+    auto read_a = [&](const TileK& t, int s, f16x8 (&dst)[TM][Frag::NSTEP][Frag::PER]) {
         const char* ha = smem + HALO0 + (t.chunk & 1) * HALO_BYTES;
         const int pix = a_pix0 + t.ky * HW_ + t.kx;
         const int key = (((lrow & 15) + t.kx) >> 1) & 7;  // swizzle key = halo COLUMN / 2 (see the header)
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int u = 0; u < FR::PER; ++u)
-                dst[i][s][u] = *reinterpret_cast<const f16x8*>(ha + (pix + (i * 2 + u) * HW_) * 128 + ((FR::kslot(s, lkq) ^ key) << 4));
+            for (int u = 0; u < Frag::PER; ++u)
+                dst[i][s][u] = *reinterpret_cast<const f16x8*>(ha + (pix + (i * 2 + u) * HW_) * 128 + ((Frag::kslot(s, lkq) ^ key) << 4));
     };
     // ---- prologue: halo of the first chunk, B of tile 0, first half of B of tile 1; everything of tile 0 lands before the first reads
     TileK t0;
@@ -2652,16 +2289,16 @@ __global__ void __launch_bounds__(512) conv3_halo_kernel(GemmArgs g) {
     advance(t2);
     __builtin_amdgcn_s_barrier();
     TileK tc = t0;  // position of the K-tile being multiplied
-    f16x8 af[TM][FR::NSTEP][FR::PER], bf[PT][FR::NSTEP][FR::PER];
+    f16x8 af[TM][Frag::NSTEP][Frag::PER], bf[PT][Frag::NSTEP][Frag::PER];
     {   // fragments of phase (0,0)
         const char* fb = smem + b_lane_off;
 #pragma unroll
-        for (int s = 0; s < FR::NSTEP; ++s) {
+        for (int s = 0; s < Frag::NSTEP; ++s) {
             read_a(tc, s, af);
 #pragma unroll
             for (int jj = 0; jj < PT; ++jj)
 #pragma unroll
-                for (int u = 0; u < FR::PER; ++u) bf[jj][s][u] = *reinterpret_cast<const f16x8*>(fb + koff[s] + jj * 4096 + u * 2048);
+                for (int u = 0; u < Frag::PER; ++u) bf[jj][s][u] = *reinterpret_cast<const f16x8*>(fb + koff[s] + jj * 4096 + u * 2048);
         }
     }
     if (grp == 1) __builtin_amdgcn_s_barrier();  // stagger: group 1 runs one barrier interval behind group 0
@@ -2706,7 +2343,7 @@ __global__ void __launch_bounds__(512) conv3_halo_kernel(GemmArgs g) {
             const char* nfb = smem + (next_in_tile ? cur : (cur ^ 1)) * B_BYTES + b_lane_off + (next_in_tile ? (j0 + PT) * 4096 : 0);
             __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-            for (int s = 0; s < FR::NSTEP; ++s) {
+            for (int s = 0; s < Frag::NSTEP; ++s) {
 #pragma unroll
                 for (int jj = 0; jj < PT; ++jj)
 #pragma unroll
@@ -2716,7 +2353,7 @@ __global__ void __launch_bounds__(512) conv3_halo_kernel(GemmArgs g) {
 #pragma unroll
                     for (int jj = 0; jj < PT; ++jj)
 #pragma unroll
-                        for (int u = 0; u < FR::PER; ++u) bf[jj][s][u] = *reinterpret_cast<const f16x8*>(nfb + koff[s] + jj * 4096 + u * 2048);
+                        for (int u = 0; u < Frag::PER; ++u) bf[jj][s][u] = *reinterpret_cast<const f16x8*>(nfb + koff[s] + jj * 4096 + u * 2048);
                 }
             }
             __builtin_amdgcn_s_setprio(0);
@@ -2828,17 +2465,16 @@ __global__ void __launch_bounds__(256, 2) conv3_halo4_kernel(GemmArgs g) {
         }
     };
 
-    AccBlock<kL16> acc[TM][TN];
+    AccBlock acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc_zero(acc[i][j]);
 
-    using FR = Frag<kL16>;
-    const int lrow = FR::lrow(lane), lkq = FR::lk(lane);
-    int koff[FR::NSTEP];   // 16-byte slot of step st, swizzled with the lane's row key (tile bases are multiples of 16 rows); fragment u: + u * 16 rows
+    const int lrow = Frag::lrow(lane), lkq = Frag::lk(lane);
+    int koff[Frag::NSTEP];   // 16-byte slot of step st, swizzled with the lane's row key (tile bases are multiples of 16 rows); fragment u: + u * 16 rows
 #pragma unroll
-    for (int s = 0; s < FR::NSTEP; ++s) koff[s] = (FR::kslot(s, lkq) ^ ((lrow >> 1) & 7)) << 4;
+    for (int s = 0; s < Frag::NSTEP; ++s) koff[s] = (Frag::kslot(s, lkq) ^ ((lrow >> 1) & 7)) << 4;
     const int b_lane_off = lrow * 128;
     const int a_pix0 = (wm * 4 + (lrow >> 4)) * HW_ + (lrow & 15);  // halo pixel of this lane's row of A tile 0, fragment 0 at tap (0,0); tile 1: +2 patch rows, fragment u: + u
 
@@ -2864,20 +2500,20 @@ __global__ void __launch_bounds__(256, 2) conv3_halo4_kernel(GemmArgs g) {
         const int key = (((lrow & 15) + kx) >> 1) & 7;  // swizzle key = halo COLUMN / 2 (see conv3_halo_kernel)
         // fragments double-buffered in registers: the reads of k-step s + 1 are issued before the MFMAs of k-step s (counted lgkmcnt), so a
         // lone wave does not sit out an LDS round trip per k-step while its SIMD partner (the other block's wave) is in a barrier or a wait
-        f16x8 af[2][TM][FR::PER], bf[2][TN][FR::PER];
+        f16x8 af[2][TM][Frag::PER], bf[2][TN][Frag::PER];
         auto read_frags = [&](int s, int b) {
 #pragma unroll
-            for (int u = 0; u < FR::PER; ++u) {
+            for (int u = 0; u < Frag::PER; ++u) {
 #pragma unroll
-                for (int i = 0; i < TM; ++i) af[b][i][u] = *reinterpret_cast<const f16x8*>(ha + (pix + (i * 2 + u) * HW_) * 128 + ((FR::kslot(s, lkq) ^ key) << 4));
+                for (int i = 0; i < TM; ++i) af[b][i][u] = *reinterpret_cast<const f16x8*>(ha + (pix + (i * 2 + u) * HW_) * 128 + ((Frag::kslot(s, lkq) ^ key) << 4));
 #pragma unroll
                 for (int j = 0; j < TN; ++j) bf[b][j][u] = *reinterpret_cast<const f16x8*>(fb + koff[s] + j * 4096 + u * 2048);
             }
         };
         read_frags(0, 0);
 #pragma unroll
-        for (int s = 0; s < FR::NSTEP; ++s) {
-            if (s + 1 < FR::NSTEP) read_frags(s + 1, (s + 1) & 1);
+        for (int s = 0; s < Frag::NSTEP; ++s) {
+            if (s + 1 < Frag::NSTEP) read_frags(s + 1, (s + 1) & 1);
             __builtin_amdgcn_sched_barrier(0);   // keep the prefetch ahead of the MFMAs (the scheduler otherwise sinks it to save registers)
 #pragma unroll
             for (int j = 0; j < TN; ++j)
@@ -2929,12 +2565,12 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restr
     }
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool CONV, bool INTERLEAVE = true>
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool CONV>
 static int launch_gemm_t(odise_hip_ctx* ctx, GemmArgs& g, int batch) {
     constexpr int NT = 64 * WAVES_M * WAVES_N;
     constexpr int lds = plain_lds_bytes(BM, BN, WAVES_M);
     static_assert(epi_lds_bytes(BM, BN, WAVES_M, epi_wave_rows(BM, BN, WAVES_M, lds)) <= lds, "epilogue staging exceeds the LDS request");
-    auto kern = gemm_kernel<BM, BN, WAVES_M, WAVES_N, CONV, INTERLEAVE>;
+    auto kern = gemm_kernel<BM, BN, WAVES_M, WAVES_N, CONV>;
     if (lds > 65536) {
         static LdsAttrOnce once;  // per instantiation; tracked per device inside
         ODISE_TRY(ensure_dyn_lds(ctx, once, (const void*)kern, lds));
@@ -2975,25 +2611,6 @@ static int launch_gemm_pp2(odise_hip_ctx* ctx, GemmArgs& g, int batch) {
     static_assert((BN / WAVES_N / 32) % PT == 0, "whole phases");
     constexpr int lds = pp_lds_bytes(BM, BN, 8 / WAVES_N);
     auto kern = gemm_pp2_kernel<BM, BN, WAVES_N, PT, CONV>;
-    static LdsAttrOnce once;  // per instantiation; tracked per device inside
-    ODISE_TRY(ensure_dyn_lds(ctx, once, (const void*)kern, lds));
-    dim3 grid((unsigned)ceil_div(g.N, BN), (unsigned)ceil_div(g.M, BM), (unsigned)(g.splitk > 1 ? g.splitk : batch));
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, g);
-    ODISE_CHECK_HIP(hipGetLastError());
-    if (g.splitk > 1) {
-        const int64_t total = (int64_t)g.M * ceil_div(g.N, 8);
-        const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 2048);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, g.ws, g.splitk, g.M, g.N, g.epi);
-        ODISE_CHECK_HIP(hipGetLastError());
-    }
-    return ODISE_OK;
-}
-
-template <int BM, int BN, bool CONV, bool L16>
-static int launch_gemm8(odise_hip_ctx* ctx, GemmArgs& g, int batch) {
-    constexpr int lds = pp_lds_bytes(BM, BN, BM / 128);
-    static_assert(epi_lds_bytes(BM, BN, BM / 128, epi_wave_rows(BM, BN, BM / 128, lds)) <= lds, "epilogue staging exceeds the LDS request");
-    auto kern = gemm8_kernel<BM, BN, CONV, L16>;
     static LdsAttrOnce once;  // per instantiation; tracked per device inside
     ODISE_TRY(ensure_dyn_lds(ctx, once, (const void*)kern, lds));
     dim3 grid((unsigned)ceil_div(g.N, BN), (unsigned)ceil_div(g.M, BM), (unsigned)(g.splitk > 1 ? g.splitk : batch));
@@ -3050,8 +2667,10 @@ static int launch_conv3_halo4(odise_hip_ctx* ctx, GemmArgs& g) {
 }
 
 static int g_gemm_debug = 0;  // see GemmArgs::dbg
-static int g_epi_old = 0;     // tools only: 1 = keep the fp32-staged epilogue (odise_hip_gemm_debug bit 1 << 24), for same-process A/B runs
-static int g_conv_flags = 0;  // tools only: 1 = tap-major K order even when Cin % 64 == 0, 2 = never use the ping-pong kernel, 4 = one N-tile per phase at BN = 256
+// kernel-selection switches for A/B runs (odise_hip_gemm_debug(flags << 4); ODISE_GEMM_FLAGS in the tools build): 2 no ping-pong kernels,
+// 16 no 512x128 tile, 32 launch log (GEMMLOG), 64 no halo tiles, 512 / 1024 force / forbid the second ping-pong generation, 2048 no
+// two-blocks-per-CU halo tile, 32768 block-wide epilogues only, 131072 no halo tile on fused-upsample convolutions.  Other bits are ignored.
+static int g_conv_flags = 0;
 
 // Tile ids: 0:128x128 1:64x128 2:64x64 (4 waves)  3:256x320 4:256x256 5:256x128 (8 waves)  6:512x128 (8 waves, ping-pong only)
 //           7: 16x16-pixel patch x 256 channels, 8: 16x16-pixel patch x 128 channels (conv3_halo_kernel: 3x3 / stride 1 / pad 1 only)
@@ -3105,15 +2724,6 @@ static const TileCost kTileCostPP[2] = {
 static const TileCost kTileCostConv512 = {2.5, 16.0, 1};
 // the 256x256 ping-pong tile on implicit-GEMM convolutions (round 5: the dominant convolution 1063 us = 8 rounds of 72, 256 -> 256 at 256^2 1267 us = 16 of 36)
 static const TileCost kTileCostPPConv256 = {1.49, 25.5, 1};
-// the 256x256 tile as run by the 8-phase kernel on v_mfma_f32_16x16x32_f16 (round 5; fitted on tools/g8_shapes.py, profiles/r05_gemm8_by_shape.txt:
-// 9344x1024x4096 93.5 us = one 58 % round of 64 K-tiles, 9344x4096x1024 122.7 us = 2.3 rounds of 16, the dominant convolution 989 us = 8 rounds of 72)
-static const TileCost kTileCost8 = {1.21, 24.0, 1};
-// ... and on implicit-GEMM convolutions (every input pixel passes the LDS-DMA path nine times; the dominant convolution 1037 us = 8 rounds of 72,
-// 256 -> 256 at 256^2 1263 us = 16 rounds of 36: profiles/r05_conv_tiles_l16.txt)
-static const TileCost kTileCost8Conv = {1.41, 28.0, 1};
-// previous fit (before the lean epilogue / ping-pong kernel), kept selectable for A/B runs: ODISE_GEMM_FLAGS=8
-static const TileCost kTileCostOld[kNumTiles] = {{1.68, 9.5, 2}, {1.58, 4.1, 3}, {1.28, 2.4, 4}, {3.04, 29.0, 1}, {2.58, 22.0, 1},
-                                                 {1.75, 10.6, 1}, {2.25, 12.0, 1}, {1.92, 12.0, 1}, {1.32, 10.0, 1}, {2.64, 10.0, 2}};
 static thread_local int g_last_tile = -1;   // odise_hip_last_tile: tile | split-K << 8 of this thread's last GEMM / conv launch
 static int env_gemm_flags() {
 #ifdef ODISE_TOOLS
@@ -3169,19 +2779,11 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
     auto blocks = [&](int t) {
         return ((t >= 7 && t <= 9) ? halo_patches : ceil_div(g.M, kTileBM[t])) * ceil_div(g.N, kTileBN[t]) * (int64_t)batch;
     };
-    const bool no_interleave = force_tile >= 16;  // test hook: tile + 16 selects the non-interleaved issue order
-    if (no_interleave) force_tile -= 16;
     int tile = 2, best_split = 1;
     double best = 1e30;
     const int flags = g_conv_flags | env_gemm_flags();
-    const bool pp_base = !no_interleave && !(flags & 2) && g.K % 64 == 0 && (!CONV || g.cg.Cin % 64 == 0);   // what the halo tiles need (they gather the fused upsample themselves)
+    const bool pp_base = !(flags & 2) && g.K % 64 == 0 && (!CONV || g.cg.Cin % 64 == 0);   // what the halo tiles need (they gather the fused upsample themselves)
     const bool pp_ok = pp_base && !(CONV && g.cg.ups);
-    // the 8-phase kernels (gemm8_kernel) run the 256x256 / 512x128 tiles wherever the ping-pong kernels could (the convolution form keeps 32-bit
-    // element offsets) - on request only, ODISE_GEMM_FLAGS 16384: built as the guide's yardstick schedule and kept for A/B runs; once every main loop
-    // multiplied with 16x16x32 MFMAs and wrote its tile through the wave-private epilogue, the ping-pong kernels measured 3-7 % ahead of it on the
-    // same tiles (tools/g8_ablate.py: main loops 72.7 vs 76.3 us at 9472x4096x1024, full kernels 97 vs 104; profiles/r05_epilogue_forms.txt)
-    const bool g8_ok = pp_ok && (flags & 16384) && !(flags & (4096 | 512 | 1024)) &&
-                       (!CONV || (int64_t)(g.M / (g.cg.OH * g.cg.OW)) * g.cg.H * g.cg.W * g.cg.Cin < ((int64_t)1 << 31));
     for (int t = 0; t < kNumTiles; ++t) {
         if (force_tile >= 0 && force_tile < kNumTiles && t != force_tile) continue;
         if (!((tile_mask >> t) & 1)) continue;
@@ -3189,8 +2791,7 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
         if (t >= 7 && t <= 9 && (!halo_ok || !pp_base || (flags & 64))) continue;  // ODISE_GEMM_FLAGS=64: never use the halo kernels
         if (t == 9 && (flags & 2048)) continue;                        // ODISE_GEMM_FLAGS=2048: never use the two-blocks-per-CU halo kernel
         if (t == 9 && force_tile < 0 && g.N > 128) continue;           // (see kTileCost[9])
-        const TileCost& tc = (flags & 8) ? kTileCostOld[t] : (g8_ok && t == 4) ? (CONV ? kTileCost8Conv : kTileCost8) : (CONV && pp_ok && t == 4) ? kTileCostPPConv256 :
-                             (pp_ok && (t == 3 || t == 4)) ? kTileCostPP[t - 3] :
+        const TileCost& tc = (CONV && pp_ok && t == 4) ? kTileCostPPConv256 : (pp_ok && (t == 3 || t == 4)) ? kTileCostPP[t - 3] :
                              (CONV && t == 6) ? kTileCostConv512 : kTileCost[t];
         if (force_tile < 0) {
             if (kTileBM[t] > 64 && g.M <= kTileBM[t] / 2) continue;            // mostly-empty row tiles
@@ -3266,7 +2867,7 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
         // epilogue), a column-chunk count that divides the thread count, and row blocks that never straddle two images
         const int ohw = CONV ? g.cg.OH * g.cg.OW : 0;
         // kernels instantiated with the statistics epilogue: halo tiles, pp2 conv (256x256) and the 512x128 conv tile
-        const bool pp2_used = (tile == 4) && pp_ok && (g8_ok || (flags & 512) || (!(flags & 1024) && CONV));   // gemm8_kernel<.., CONV = true> carries the statistics epilogue too
+        const bool pp2_used = (tile == 4) && pp_ok && ((flags & 512) || (!(flags & 1024) && CONV));
         bool ok = CONV && g.splitk == 1 && g.epi.fast && g.N % 8 == 0 && ((tile >= 7 && tile <= 9) || (tile == 6 && pp_ok && !(flags & 512)) || pp2_used);
         if (ok && tile >= 7) g.stats_blocks = g.cg.halo_tx * g.cg.halo_ty;
         else if (ok && ohw % kTileBM[tile] == 0) g.stats_blocks = ohw / kTileBM[tile];
@@ -3276,8 +2877,8 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
     g.zeros = (const f16*)ctx->zeros;
     g.epi_block = (flags & 32768) ? 1 : 0;
 #ifdef ODISE_TOOLS
-    static const int freeze_k = (getenv("ODISE_GEMM_FREEZE_K") ? 16 : 0) | (getenv("ODISE_EPI_OLD") ? 32 : 0) | (getenv("ODISE_NO_RES_PREFETCH") ? 64 : 0);
-    g.dbg = g_gemm_debug | freeze_k | (g_epi_old ? 32 : 0);
+    static const int freeze_k = (getenv("ODISE_GEMM_FREEZE_K") ? 16 : 0) | (getenv("ODISE_NO_RES_PREFETCH") ? 64 : 0);
+    g.dbg = g_gemm_debug | freeze_k;
 #else
     g.dbg = 0;
 #endif
@@ -3291,11 +2892,6 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
     // second-generation ping-pong kernel (fragment reads under the MFMAs): measured +3..18 % on the implicit-GEMM convs and on
     // dense problems that do not fill the chip twice; the large dense GEMMs keep the first generation (-5..12 % there).
     // ODISE_GEMM_FLAGS: 512 forces it, 1024 forbids it.
-    if ((tile == 4 || tile == 6) && g8_ok) {   // ODISE_GEMM_FLAGS 8192: the 8-phase 256x256 kernel on the OTHER MFMA shape (32x32x16 in the product build)
-        if (tile == 6) return launch_gemm8<512, 128, CONV, kL16>(ctx, g, batch);
-        if (flags & 8192) return launch_gemm8<256, 256, CONV, !kL16>(ctx, g, batch);
-        return launch_gemm8<256, 256, CONV, kL16>(ctx, g, batch);
-    }
     const bool pp2_auto = !(flags & 1024) && ((CONV && tile != 6) || (!CONV && blocks(tile) * (g.splitk > 1 ? g.splitk : 1) <= 2 * cus));
     if ((tile == 3 || tile == 4 || tile == 6) && pp_ok && ((flags & 512) || pp2_auto)) {
         if (tile == 6) return launch_gemm_pp2<512, 128, 1, 2, CONV>(ctx, g, batch);
@@ -3305,13 +2901,7 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
     if ((tile == 3 || tile == 4 || tile == 6) && pp_ok) {
         if (tile == 6) return launch_gemm_pp<512, 128, 1, 2, CONV>(ctx, g, batch);
         if (tile == 3) return launch_gemm_pp<256, 320, 2, 1, CONV>(ctx, g, batch);
-        if (flags & 4) return launch_gemm_pp<256, 256, 2, 1, CONV>(ctx, g, batch);
         return launch_gemm_pp<256, 256, 2, 2, CONV>(ctx, g, batch);
-    }
-    if (no_interleave) {
-        if (tile == 3) return launch_gemm_t<256, 320, 4, 2, CONV, false>(ctx, g, batch);
-        if (tile == 4) return launch_gemm_t<256, 256, 4, 2, CONV, false>(ctx, g, batch);
-        if (tile == 0) return launch_gemm_t<128, 128, 2, 2, CONV, false>(ctx, g, batch);
     }
     switch (tile) {
         case 0: return launch_gemm_t<128, 128, 2, 2, CONV>(ctx, g, batch);
@@ -3398,7 +2988,7 @@ int conv_forced(odise_hip_ctx* ctx, const odise_conv_desc* d, int force_tile, in
     // chunk-major K order pays when the input stays in the 256 MiB Infinity Cache (shifted tap re-reads hit L2: +4..10 % on the
     // 64x64 / 32x32 latents); a streamed input prefers tap-major (whole 1-2 KiB pixel vectors in DRAM-page order: +10 % at 128^2+)
     const int64_t in_bytes = (int64_t)d->N * d->H * d->W * d->Cin * 2;
-    g.cg.chunk_major = (d->Cin % 64 == 0 && d->KH * d->KW > 1 && in_bytes <= (128ll << 20) && !((g_conv_flags | env_gemm_flags()) & 1)) ? 1 : 0;
+    g.cg.chunk_major = (d->Cin % 64 == 0 && d->KH * d->KW > 1 && in_bytes <= (128ll << 20)) ? 1 : 0;
     // a 1x1 stride-1 unpadded conv is a plain GEMM over pixels
     if (d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad_t == 0 && d->pad_l == 0 && !d->upsample2x && d->OH == d->H &&
         d->OW == d->W) {
@@ -3419,7 +3009,6 @@ int group_norm_from_colpart(odise_hip_ctx* ctx, const void* x, void* y, const fl
 extern "C" int odise_hip_gemm_debug(int flags) {
     odise::g_gemm_debug = flags & 15;
     odise::g_conv_flags = (flags >> 4) & 0xfffff;
-    odise::g_epi_old = (flags >> 24) & 1;
     return 0;
 }
 extern "C" int odise_hip_gemm(odise_hip_ctx* ctx, const odise_gemm_desc* d) { return odise::gemm_forced(ctx, d, -1, 0); }

@@ -11,9 +11,6 @@ from odise_amd import build as B
 
 # spilled VGPRs allowed per kernel family (regex on the mangled name -> limit); everything not listed must not spill at all
 ALLOWED = [
-    (r"gemm8_kernelILi256ELi256ELb0ELb1", 80),      # the opt-in 8-phase kernels (never chosen by the cost model) were born at the register limit
-    (r"gemm8_kernelILi512ELi128ELb0ELb1", 64),
-    (r"gemm8_kernelILi\d+ELi\d+ELb1", 40),
     (r"gemm_pp2_kernelILi256ELi256ELi2ELi2ELb1", 32),   # implicit-GEMM conv form: 24 spilled since round 4
     (r"gemm_pp2_kernelILi512ELi128ELi1ELi2ELb1", 64),
     (r"gemm_pp_kernelILi512ELi128ELi1ELi2ELb1", 32),

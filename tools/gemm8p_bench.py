@@ -3,8 +3,8 @@ the repo's main loops on the SAME uniform-random [-1, 1) fp16 operands, same pro
 
     8p        gemm8p_kernel<0>  (16x16x32 MFMA, 2M x 4N waves, 3 half-tiles of LDS-DMA in flight, vmcnt(6) once per K-tile, setprio, stagger)
     8p-noprio the same without s_setprio;  8p-lock: wave groups in lockstep
-    8p-m32    the same schedule, LDS image, DMA and read counts on v_mfma_f32_32x32x16_f16 (4 x 2 tiles per wave: the product kernels' MFMA shape)
-    pp2       gemm_pp2_kernel<256,256,2,2>  (the repo's ping-pong loop, 32x32x16 MFMA, fragment reads under the MFMAs; math-first epilogue)
+    8p-m32    the same schedule, LDS image, DMA and read counts on v_mfma_f32_32x32x16_f16 (4 x 2 tiles per wave: the MFMA shape of rounds 1-4)
+    pp2       gemm_pp2_kernel<256,256,2,2>  (the repo's ping-pong loop, 16x16x32 MFMA, fragment reads under the MFMAs; math-first epilogue)
     pp        gemm_pp_kernel<256,256,2,2>
 
 Measurement build only:  ODISE_HIP_LIB=odise_amd/lib/libodise_hip_tools.so python tools/gemm8p_bench.py [zero]

@@ -22,7 +22,7 @@ for (M, N, K) in [(65536, 2 * bn, 4096), (65536, 2 * bn, 640)]:
     ctx.lib.odise_hip_gemm_debug(0)
     A.free(); W.free(); O.free()
 X = rand((16, 128, 128, 512)); Wt = rand((2 * bn, 3, 3, 512), 4608 ** -0.5); O = ctx.empty((16, 128, 128, 2 * bn), np.float16)
-for name, dbg in (("full", 0), ("loop only", 4), ("loop, no dma", 5), ("loop, no dma/frag", 7), ("tap-major", 16)):
+for name, dbg in (("full", 0), ("loop only", 4), ("loop, no dma", 5), ("loop, no dma/frag", 7)):
     ctx.lib.odise_hip_gemm_debug(dbg)
     ms = timeit(lambda: ctx.conv2d(X, Wt, force_tile=tile, out=O))
     print(f"conv 16x128x128 512->{2*bn} tile {tile} {name:18s}: {ms*1e3:8.1f} us {2.0*16*128*128*2*bn*4608/(ms*1e-3)/1e12:7.1f} TF/s", flush=True)
