@@ -30,7 +30,7 @@ extern "C" {
 
 typedef struct odise_hip_ctx odise_hip_ctx;
 
-enum { ODISE_F16 = 0, ODISE_F32 = 1 };
+enum { ODISE_F16 = 0, ODISE_F32 = 1, ODISE_U8 = 2 };   /* ODISE_U8: uint8 / bool masks (odise_hip_rle_encode) */
 enum { ODISE_ACT_NONE = 0, ODISE_ACT_SILU = 1, ODISE_ACT_RELU = 2, ODISE_ACT_GELU = 3, ODISE_ACT_QUICKGELU = 4 };
 
 /* error codes */
@@ -375,6 +375,23 @@ int odise_hip_u8_hwc_to_f32_chw_padded(odise_hip_ctx* ctx, const void* src, floa
 int odise_hip_semantic_confusion(odise_hip_ctx* ctx, const float* sem_seg, const int* gt, int K, int npix, int64_t* conf);
 /* hist int32 [na*nb] += count of (a[p], b[p]) pairs with 0 <= a < na, 0 <= b < nb (segment-index co-occurrence of PQ matching) */
 int odise_hip_pair_histogram(odise_hip_ctx* ctx, const int* a, const int* b, int npix, int na, int nb, int* hist);
+/* COCO compressed RLE (pycocotools mask.encode of the Fortran-ordered mask, counts as text) of n masks: the per-mask part of the segm
+ * evaluators (COCOEvaluator / InstanceSegEvaluator(tasks=("segm",)) -> detectron2 instances_to_coco_json), byte-identical to
+ * `mask.encode(np.asfortranarray(m.astype(np.uint8)))["counts"].decode("utf-8")` (maskApi.c rleEncode + rleToString).
+ * masks: device row-major [n, h, w] (the layout of pred_masks), dtype ODISE_F32 or ODISE_U8 (bool); any nonzero value is 1.
+ * rle: device bytes, all strings packed back to back, no terminators; bytes past `capacity` are never written.
+ * offsets: device int64 [n+1], exclusive scan of string lengths (always complete; offsets[n] > capacity => strings not written,
+ * call again with capacity >= offsets[n]).  area: device int64 [n] (optional), the pixels of each mask.  Scratch comes from the context.
+ * h * w <= 2^30, n <= 65535.  Asynchronous on the context's stream. */
+int odise_hip_rle_encode(odise_hip_ctx* ctx, const void* masks, int dtype, int n, int h, int w,
+                         void* rle, int64_t capacity, int64_t* offsets, int64_t* area);
+/* the same for the instance head's selection of image b of the last head forward, straight from the mask logits (the pixels of
+ * odise_hip_instance_masks, with the taps of its x4 form where that form applies; no [topk,oh,ow] tensor): inst_table = device row
+ * [1 + 2*topk] of that image (inst_table of odise_post_desc; the count is read on the device); pad_h / pad_w = 4 x the mask-logit size,
+ * as in odise_hip_postprocess_batch.  offsets [topk+1], area [topk]: entries
+ * past the count are empty strings of area 0.  Enqueue it after odise_hip_postprocess_batch / odise_hip_infer of the same batch. */
+int odise_hip_instance_rle(odise_hip_ctx* ctx, int b, const int* inst_table, int topk, int pad_h, int pad_w, int img_h, int img_w,
+                           int out_h, int out_w, void* rle, int64_t capacity, int64_t* offsets, int64_t* area);
 
 /* ---- JPEG input -------------------------------------------------------------------------------------------
  * Replaces detectron2 `read_image(file, "RGB")` = PIL.Image.open -> EXIF transpose -> convert("RGB") of the DatasetMapper

@@ -16,7 +16,7 @@ HEADER_PATH = os.path.join(HERE, "..", "include", "odise_hip.h")
 TOOLS_HEADER_PATH = os.path.join(HERE, "..", "include", "odise_hip_tools.h")   # developer hooks: not part of the boundary
 LAB_HEADER_PATH = os.path.join(HERE, "..", "include", "odise_hip_lab.h")       # measurement build only (libodise_hip_tools.so)
 
-F16, F32 = 0, 1
+F16, F32, U8 = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_GELU, ACT_QUICKGELU = 0, 1, 2, 3, 4
 
 c_void_p, c_int, c_int64, c_float, c_size_t = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_size_t

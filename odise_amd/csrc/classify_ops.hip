@@ -10,17 +10,9 @@
 //                          (maskformer_model.py:286-320) writing the pixel-major sigmoid matrix for the semantic GEMM
 //   column_stats / panoptic_write / instance_masks
 #include "engine.h"
+#include "post_sample.h"
 
 namespace odise {
-
-__device__ __forceinline__ void bil_setup(int o, int in, int out, int& i0, int& i1, float& t) {
-    float s = ((float)o + 0.5f) * ((float)in / (float)out) - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    i0 = (int)s;
-    i0 = i0 < in - 1 ? i0 : in - 1;
-    i1 = i0 < in - 1 ? i0 + 1 : i0;
-    t = s - (float)i0;
-}
 
 // x [B,3,H,W] f32 in [0,1] -> y [B,S,S,8] f16: bilinear (align_corners=False) to SxS, then (v - mean) / std
 __global__ void __launch_bounds__(256) resize_bilinear_norm_kernel(const float* __restrict__ x, f16* __restrict__ y, int H, int W, int S) {
@@ -234,29 +226,6 @@ __global__ void __launch_bounds__(256) classify_rows_kernel(const float* __restr
     float* orow = out + row * (K + 1);
     for (int k = tid; k < K; k += blockDim.x) orow[k] = logf(expf(op[k] - mo) / so * (1.f - pn) + 1e-8f);
     if (tid == 0) orow[K] = logf(pn + 1e-8f);
-}
-
-__device__ __forceinline__ float sample_stage1(const f16* lr, int w4, int h4, int y, int x, int ph, int pw) {
-    int y0, y1, x0, x1;
-    float ty, tx;
-    bil_setup(y, h4, ph, y0, y1, ty);
-    bil_setup(x, w4, pw, x0, x1, tx);
-    const float v00 = (float)lr[y0 * w4 + x0], v01 = (float)lr[y0 * w4 + x1], v10 = (float)lr[y1 * w4 + x0], v11 = (float)lr[y1 * w4 + x1];
-    const float top = v00 + tx * (v01 - v00), bot = v10 + tx * (v11 - v10);
-    return top + ty * (bot - top);
-}
-
-// logit of query q at output pixel (oy, ox): bilinear(crop(bilinear(logits -> padded size)) -> output size)
-__device__ __forceinline__ float sample_mask(const f16* lr, const PostGeom& g, int oy, int ox) {
-    if (g.oh == g.ih && g.ow == g.iw) return sample_stage1(lr, g.w4, g.h4, oy, ox, g.ph, g.pw);
-    int y0, y1, x0, x1;
-    float ty, tx;
-    bil_setup(oy, g.ih, g.oh, y0, y1, ty);
-    bil_setup(ox, g.iw, g.ow, x0, x1, tx);
-    const float v00 = sample_stage1(lr, g.w4, g.h4, y0, x0, g.ph, g.pw), v01 = sample_stage1(lr, g.w4, g.h4, y0, x1, g.ph, g.pw);
-    const float v10 = sample_stage1(lr, g.w4, g.h4, y1, x0, g.ph, g.pw), v11 = sample_stage1(lr, g.w4, g.h4, y1, x1, g.ph, g.pw);
-    const float top = v00 + tx * (v01 - v00), bot = v10 + tx * (v11 - v10);
-    return top + ty * (bot - top);
 }
 
 // sigmoid of the per-pixel pass: v_exp_f32 + v_rcp_f32 (1 ulp each) instead of the library expf and the IEEE division (~20 VALU
@@ -707,21 +676,16 @@ __global__ void __launch_bounds__(256) instance_masks_x4_kernel(const f16* __res
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= g.oh * cw) return;
     const int oy = t / cw, cx = t - oy * cw;
-    const int cy = oy >> 2, ky = oy & 3;
-    const int ra = max(ky < 2 ? cy - 1 : cy, 0), rb = min(ky < 2 ? cy : cy + 1, g.h4 - 1);
-    const float ty = ky == 0 ? 0.625f : ky == 1 ? 0.875f : ky == 2 ? 0.125f : 0.375f;
+    int ra, rb;
+    float ty;
+    x4_rows(g, oy, ra, rb, ty);
     const int cl = max(cx - 1, 0), cr = min(cx + 1, g.w4 - 1);
     const f16* lr = logits + (int64_t)idx[n] * g.h4 * g.w4;
     const float al = (float)lr[ra * g.w4 + cl], ac = (float)lr[ra * g.w4 + cx], ar = (float)lr[ra * g.w4 + cr];
     const float bl = (float)lr[rb * g.w4 + cl], bc = (float)lr[rb * g.w4 + cx], br = (float)lr[rb * g.w4 + cr];
     float o[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const float tx = k == 0 ? 0.625f : k == 1 ? 0.875f : k == 2 ? 0.125f : 0.375f;
-        const float v00 = k < 2 ? al : ac, v01 = k < 2 ? ac : ar, v10 = k < 2 ? bl : bc, v11 = k < 2 ? bc : br;
-        const float top = v00 + tx * (v01 - v00), bot = v10 + tx * (v11 - v10);
-        o[k] = (top + ty * (bot - top)) > 0.f ? 1.f : 0.f;
-    }
+    for (int k = 0; k < 4; ++k) o[k] = x4_pixel(k, ty, al, ac, ar, bl, bc, br) > 0.f ? 1.f : 0.f;
     *reinterpret_cast<float4*>(out + (int64_t)n * g.oh * g.ow + (int64_t)oy * g.ow + 4 * cx) = make_float4(o[0], o[1], o[2], o[3]);
 }
 
@@ -1208,10 +1172,13 @@ int launch_panoptic_write(odise_hip_ctx* ctx, const int* ids, const int* map, in
     ODISE_CHECK_HIP(hipGetLastError());
     return ODISE_OK;
 }
+// the geometries instance_masks_x4_kernel serves (rle.hip samples its pixels with the same taps there)
+bool instance_masks_x4(const PostGeom& g) {
+    return g.oh == g.ih && g.ow == g.iw && g.ph == 4 * g.h4 && g.pw == 4 * g.w4 && g.ow % 4 == 0 && g_post_generic != 1;
+}
 int launch_instance_masks(odise_hip_ctx* ctx, const f16* logits, const int* idx, float* out, int n, const PostGeom& g, const int* n_dev) {
     if (n == 0) return ODISE_OK;
-    if (g.oh == g.ih && g.ow == g.iw && g.ph == 4 * g.h4 && g.pw == 4 * g.w4 && g.ow % 4 == 0 && ((uintptr_t)out & 15) == 0 &&
-        g_post_generic != 1) {
+    if (instance_masks_x4(g) && ((uintptr_t)out & 15) == 0) {
         dim3 grid4((unsigned)ceil_div(g.oh * (g.ow / 4), 256), (unsigned)n);
         hipLaunchKernelGGL(instance_masks_x4_kernel, grid4, dim3(256), 0, ctx->stream, logits, idx, out, g, n_dev);
         ODISE_CHECK_HIP(hipGetLastError());

@@ -118,6 +118,9 @@ struct odise_hip_ctx {
     void* probe = nullptr;           // odise::LaunchProbe* (api.cpp): HIP events around the launches of one kernel shape (odise_hip_probe_*)
     void* stages = nullptr;          // odise::StageLog* while odise_hip_stage_timeline is on: (name, HIP event on the current stream, host clock) at stage boundaries
     void* launch_log = nullptr;      // std::vector<odise::LaunchRec>* while odise_hip_launch_log is on: (shape, tile, split-K) of every GEMM / conv launch
+    // rle.hip: growable device scratch of odise_hip_rle_encode / odise_hip_instance_rle (bit-packed masks, per-thread scan state, string lengths)
+    void* rle_buf = nullptr;
+    size_t rle_bytes = 0;
 };
 
 namespace odise {
@@ -174,5 +177,6 @@ int launch_conv3_c8(odise_hip_ctx* ctx, const odise_conv_desc* d, float* gn_stat
 int gemm_forced(odise_hip_ctx* ctx, const odise_gemm_desc* d, int force_tile, int force_split, const LnEpi* ln = nullptr);   // force_tile < 0: the cost model's choice
 int gemm_ln(odise_hip_ctx* ctx, const odise_gemm_desc* d, const LnEpi& ln);   // 256x256 ping-pong tile, math-first epilogue
 void jpeg_release(odise_hip_ctx* ctx);
+void rle_release(odise_hip_ctx* ctx);
 void comm_release(odise_hip_ctx* ctx);
 }

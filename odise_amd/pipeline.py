@@ -139,6 +139,7 @@ class HipCategoryODISE(HipODISE):
         self.load_category_head(state)
         self.semantic_on, self.panoptic_on, self.instance_on = semantic_on, panoptic_on, instance_on
         self.semantic_argmax = False          # True: "sem_seg_argmax" int32 [h,w] instead of "sem_seg" [K,h,w] (never materialised)
+        self.instance_rle = False             # True: "pred_masks_rle" (COCO RLE strings, encoded from the mask logits) instead of "pred_masks" [n,h,w]
         self.object_mask_threshold, self.overlap_threshold = object_mask_threshold, overlap_threshold
         self.test_topk_per_image, self.size_divisibility = test_topk_per_image, size_divisibility
         assert size_divisibility == 64, "the feature extractor fixes size_divisibility at 64 (feature_extractor.py:126-128)"
@@ -286,7 +287,7 @@ class HipCategoryODISE(HipODISE):
                     bufs["pan"][i], bufs["pan_ext"][i] = ext, True
                 else:
                     bufs["pan"][i] = big(f"pan{i}", (oh * ow + 1 + 3 * MAX_SEGMENTS,), np.int32)
-            if self.instance_on:
+            if self.instance_on and not self.instance_rle:
                 bufs["masks"][i] = big(f"masks{i}", (topk, oh, ow), np.float32)
 
         def parr(lst):
@@ -300,12 +301,29 @@ class HipCategoryODISE(HipODISE):
             d.sem_argmax = parr(bufs["amax"])
         if self.panoptic_on:
             d.panoptic = parr(bufs["pan"])
-        if self.instance_on:
+        if self.instance_on and not self.instance_rle:
             d.inst_masks = parr(bufs["masks"])
+        if self.instance_on:
             bufs["itable"] = self._buf("inst_table", (n, 1 + 2 * topk), np.int32)
             bufs["iscores"] = self._buf("inst_scores", (n, topk), np.float32)
             d.inst_table, d.inst_scores = bufs["itable"].ptr, bufs["iscores"].ptr
         return d, bufs, keep
+
+    def _enqueue_rle(self, bufs, pad_hw, img_hw, out_sizes) -> None:
+        """instance_rle: one odise_hip_instance_rle per image behind the call that produced the selection (same stream), into pooled buffers."""
+        if not (self.instance_on and self.instance_rle):
+            return
+        topk = int(self.test_topk_per_image)
+        row = (1 + 2 * topk) * 4
+        pend = []
+        for i, (ihw, ohw) in enumerate(zip(img_hw, out_sizes)):
+            cur = self._pool.get((f"rle{i}", np.dtype(np.uint8).str))
+            cap = max(self.ctx.RLE_BYTES_PER_MASK * topk, cur.nbytes if cur is not None else 0)   # all of the pooled buffer, as grown by earlier retries
+            rb = (self._buf(f"rle{i}", (cap,), np.uint8), self._buf(f"rle_off{i}", (topk + 1,), np.int64), self._buf(f"rle_area{i}", (topk,), np.int64))
+            grow = (lambda nbytes, tag=f"rle{i}": self._buf(tag, (nbytes,), np.uint8))   # a retry grows the pooled buffer (kept for the next call)
+            pend.append(self.ctx.instance_rle_async(i, bufs["itable"].view((1 + 2 * topk,), np.int32, i * row), topk, pad_hw, ihw, ohw, bufs=rb,
+                                                    grow=grow))
+        bufs["rle"] = pend
 
     def _collect(self, bufs, out_sizes, to_host: bool) -> list:
         """Read the small tables back (one synchronisation) and assemble the reference's result dicts."""
@@ -329,7 +347,13 @@ class HipCategoryODISE(HipODISE):
                     info = [{"id": int(a), "isthing": bool(b), "category_id": int(c)} for a, b, c in tail[1:1 + 3 * int(tail[0])].reshape(-1, 3)]
                     seg = rec.view((oh, ow), np.int32)
                     r["panoptic_seg"] = (seg.numpy() if to_host else seg, info)
-            if self.instance_on:
+            if self.instance_on and self.instance_rle:
+                cnt = int(itable[i, 0])
+                rles, area = bufs["rle"][i].result()
+                assert len(rles) == cnt, (len(rles), cnt)
+                r["instances"] = {"pred_masks_rle": rles, "area": area, "scores": iscores[i, :cnt].copy(),
+                                  "pred_classes": itable[i, 1 + topk:1 + topk + cnt].astype(np.int64), "query_index": itable[i, 1:1 + cnt].copy()}
+            elif self.instance_on:
                 cnt = int(itable[i, 0])
                 masks = bufs["masks"][i].view((cnt, oh, ow))
                 r["instances"] = {"pred_masks": masks.numpy() if to_host else masks, "scores": iscores[i, :cnt].copy(),
@@ -347,6 +371,7 @@ class HipCategoryODISE(HipODISE):
         iarr = (C.c_int * (2 * n))(*[int(v) for s in ihw for v in s])
         d.B, d.pad_h, d.pad_w, d.img_hw, d.mask_cls = n, int(pad_hw[0]), int(pad_hw[1]), C.cast(iarr, C.c_void_p), dcls.ptr
         check(self.ctx.lib.odise_hip_postprocess_batch(self.ctx.h, C.byref(d)), "postprocess_batch")
+        self._enqueue_rle(bufs, pad_hw, ihw, sizes)
         return self._collect(bufs, sizes, to_host)
 
     def prefetch_device(self, images, layout: int, img_hw) -> None:
@@ -377,6 +402,8 @@ class HipCategoryODISE(HipODISE):
         d.mask_cls_out = mask_cls_out.ptr if mask_cls_out is not None else None
         d.post = post
         check(self.ctx.lib.odise_hip_infer(self.ctx.h, C.byref(d)), "infer")
+        hp = -(-max(int(h) for h, _ in img_hw) // 64) * 64, -(-max(int(w) for _, w in img_hw) // 64) * 64   # the library's padding (size_divisibility 64)
+        self._enqueue_rle(bufs, hp, img_hw, out_sizes)
         return self._collect(bufs, out_sizes, to_host)
 
     def __call__(self, *args, **kwargs):                                   # nn.Module-style call: the reference's wrappers do `self.model(batched_inputs)`

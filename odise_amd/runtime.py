@@ -12,7 +12,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._lib import ACT_NONE, F16, F32, AttnDesc, ConvDesc, GemmDesc, check
+from ._lib import ACT_NONE, F16, F32, U8, AttnDesc, ConvDesc, GemmDesc, check
 
 _NP = {F16: np.float16, F32: np.float32}
 
@@ -400,6 +400,41 @@ class Context:
         check(self.lib.odise_hip_pair_histogram(self.h, _p(a), _p(b), npix, int(na), int(nb), _p(hist)), "pair_histogram")
         return hist
 
+    # ---- COCO RLE of instance masks (segm evaluation; include/odise_hip.h odise_hip_rle_encode / odise_hip_instance_rle) ----------------
+    # Default string capacity per mask.  A string has one to seven characters per run and most runs of a real mask take two or three, so
+    # 8 KiB holds a mask with ~3000 runs - a blob spanning ~1500 columns; a selection that needs more costs one more pass (the retry).
+    RLE_BYTES_PER_MASK = 8192
+
+    def rle_encode_async(self, masks: DeviceArray, capacity: Optional[int] = None, bufs=None, grow=None) -> "RlePending":
+        """Enqueue the COCO RLE of masks [n, h, w] (float32, or uint8 / bool; nonzero = 1) on the context's stream."""
+        n, h, w = masks.shape
+        dt = {np.dtype(np.float32): F32, np.dtype(np.uint8): U8, np.dtype(np.bool_): U8}.get(np.dtype(masks.dtype))
+        if dt is None:
+            raise ValueError(f"rle_encode: masks of dtype {masks.dtype} (float32, uint8 or bool)")
+
+        def launch(buf, cap, off, area):
+            check(self.lib.odise_hip_rle_encode(self.h, _p(masks), dt, n, h, w, _p(buf), int(cap), _p(off), _p(area)), "rle_encode")
+        return RlePending(self, n, (h, w), launch, capacity, bufs, grow=grow)
+
+    def rle_encode(self, masks: DeviceArray, capacity: Optional[int] = None):
+        """-> ([{"size": [h, w], "counts": str}] per mask, area int64 [n]), the bytes of pycocotools' mask.encode."""
+        return self.rle_encode_async(masks, capacity).result()
+
+    def instance_rle_async(self, b: int, table_row, topk: int, pad_hw, img_hw, out_hw, capacity: Optional[int] = None, bufs=None,
+                           grow=None) -> "RlePending":
+        """Enqueue the RLE of image b's instance selection of the last head forward straight from its mask logits; table_row = that image's
+        device row [1 + 2 * topk] int32 of the instance table (DeviceArray or pointer)."""
+        topk = int(topk)
+
+        def launch(buf, cap, off, area):
+            check(self.lib.odise_hip_instance_rle(self.h, int(b), table_row, topk, int(pad_hw[0]), int(pad_hw[1]), int(img_hw[0]), int(img_hw[1]),
+                                                  int(out_hw[0]), int(out_hw[1]), _p(buf), int(cap), _p(off), _p(area)), "instance_rle")
+        return RlePending(self, topk, tuple(int(v) for v in out_hw), launch, capacity, bufs, trim=True, grow=grow)
+
+    def instance_rle(self, b: int, table_row, topk: int, pad_hw, img_hw, out_hw, capacity: Optional[int] = None):
+        """-> (RLE dicts of the selected instances in table order, area int64 [count])."""
+        return self.instance_rle_async(b, table_row, topk, pad_hw, img_hw, out_hw, capacity).result()
+
 
     def jpeg_decode(self, data: bytes, apply_orientation: bool = True, out: Optional[DeviceArray] = None) -> DeviceArray:
         """read_image(file, "RGB") for a baseline JPEG: host Huffman decoding, IDCT / upsampling / colour conversion / EXIF transpose on
@@ -414,6 +449,42 @@ class Context:
         check(self.lib.odise_hip_jpeg_decode(self.h, buf, C.c_int64(len(data)), _p(out), C.c_int64(out.nbytes), int(bool(apply_orientation)),
                                              C.byref(h), C.byref(w)), "jpeg_decode")
         return out.view((h.value, w.value, 3)) if out.shape != (h.value, w.value, 3) else out
+
+
+class RlePending:
+    """An enqueued RLE call.  `result()` reads the offsets back (one synchronisation); when the strings did not fit (offsets[n] > capacity,
+    nothing written) it enqueues the call once more with exactly offsets[n] bytes, then reads the strings.  `bufs` = (bytes, offsets, area)
+    device arrays to use instead of fresh ones (uint8 [capacity], int64 [n + 1], int64 [n]); `grow(nbytes) -> DeviceArray` provides the
+    buffer of the retry (a caller's pool; default: a new device array)."""
+
+    def __init__(self, ctx: Context, n: int, size, launch, capacity: Optional[int] = None, bufs=None, trim: bool = False, grow=None):
+        self.ctx, self.n, self.size, self.launch, self.trim = ctx, int(n), [int(size[0]), int(size[1])], launch, trim
+        self.grow = grow if grow is not None else (lambda nbytes: ctx.empty((nbytes,), np.uint8))
+        if bufs is None:
+            cap = int(capacity) if capacity is not None else Context.RLE_BYTES_PER_MASK * max(self.n, 1)
+            bufs = (ctx.empty((max(cap, 1),), np.uint8), ctx.empty((self.n + 1,), np.int64), ctx.empty((max(self.n, 1),), np.int64))
+        self.buf, self.off, self.area = bufs
+        self.capacity = self.buf.nbytes if capacity is None else int(capacity)
+        assert 0 <= self.capacity <= self.buf.nbytes and self.off.nbytes >= 8 * (self.n + 1) and self.area.nbytes >= 8 * self.n
+        launch(self.buf, self.capacity, self.off, self.area)
+
+    def result(self):
+        off = self.off.view((self.n + 1,), np.int64).numpy()
+        total = int(off[-1])
+        buf = self.buf
+        if total > self.capacity:                                       # nothing was written: once more with the exact size
+            buf = self.grow(total)
+            assert buf.nbytes >= total, (buf.nbytes, total)
+            self.launch(buf, total, self.off, self.area)
+            off = self.off.view((self.n + 1,), np.int64).numpy()
+            assert int(off[-1]) == total, (int(off[-1]), total)
+        raw = buf.view((total,), np.uint8).numpy().tobytes() if total else b""
+        area = self.area.view((self.n,), np.int64).numpy() if self.n else np.zeros((0,), np.int64)
+        rles = [{"size": list(self.size), "counts": raw[off[i]:off[i + 1]].decode("ascii")} for i in range(self.n)]
+        if self.trim:                                                   # instance selections: entries past the device-side count are empty
+            k = int(np.count_nonzero(np.diff(off)))
+            rles, area = rles[:k], area[:k]
+        return rles, area
 
 
 def _jpeg_info_struct(info: dict):
