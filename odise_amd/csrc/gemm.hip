@@ -21,6 +21,7 @@
 //   cost model.  Every variant keeps the same fp32 summation order: results are bit-identical across kernels for a given K order.
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 // Timing-only ablation switches (GemmArgs::dbg: drop the operand DMA / fragment reads / epilogue, freeze the K walk) and the
 // ODISE_GEMM_FLAGS / ODISE_GEMM_FREEZE_K environment switches exist only in the measurement build of the library
@@ -52,16 +53,16 @@ struct GemmEpi {
     int fast;  // 1: every vector access of a full 8-column chunk is aligned -> epi_fast8 (set by launch_gemm)
     int f16path;  // 1: fp16 output whose 16-byte row chunks are all aligned and whole -> the math-first epilogue (gemm_epilogue_f16; set by launch_gemm)
     // LayerNorm folded into the GEMMs around it (gemm_ln, math-first epilogue only; see gemm_epilogue_f16)
-    const float* ln_part;     // consumer, LN over the rows of A: [M][ln_P][2] partial (sum, sum of squares) of every row of the LN input
-    int ln_P;
-    float ln_inv_c, ln_eps;
-    const float* ln_colsum;   // ... [N]: sum over k of the gamma-folded fp16 weights of column n
-    float* ln_final_out;      // ... optional [M][2] = (-mean * rstd, rstd) of every row, written by the blocks of the first column tile
-    const float* ln_final;    // consumer, LN over the rows of W (swapped GEMM): [N][2] = (-mean * rstd, rstd) per output column
-    const float* ln_rowsum;   // ... [M]: sum over k of the folded weights of output row m
-    float* ln_stats_out;      // producer: [M][ceil(N / kLnPartCols)][2] partial (sum, sum of squares) of every output row (of the rounded fp16 values)
-    float* gn_stats;  // optional [row blocks][N][2]: per-channel (sum, sum of squares) of the block's fp16 outputs (GroupNorm statistics
-                      // fused into the producing conv; set by launch_gemm only when the chosen kernel supports it)
+    const float* ln_part = nullptr;     // consumer, LN over the rows of A: [M][ln_P][2] partial (sum, sum of squares) of every row of the LN input
+    int ln_P = 0;
+    float ln_inv_c = 0.f, ln_eps = 0.f;
+    const float* ln_colsum = nullptr;   // ... [N]: sum over k of the gamma-folded fp16 weights of column n
+    float* ln_final_out = nullptr;      // ... optional [M][2] = (-mean * rstd, rstd) of every row, written by the blocks of the first column tile
+    const float* ln_final = nullptr;    // consumer, LN over the rows of W (swapped GEMM): [N][2] = (-mean * rstd, rstd) per output column
+    const float* ln_rowsum = nullptr;   // ... [M]: sum over k of the folded weights of output row m
+    float* ln_stats_out = nullptr;      // producer: [M][ceil(N / kLnPartCols)][2] partial (sum, sum of squares) of every output row (of the rounded fp16 values)
+    float* gn_stats = nullptr;  // optional [row blocks][N][2]: per-channel (sum, sum of squares) of the block's fp16 outputs (GroupNorm statistics
+                                // fused into the producing conv; set by launch_gemm only when the chosen kernel supports it)
 };
 
 struct ConvGeom {
@@ -84,8 +85,9 @@ struct GemmArgs {
     const f16* zeros;  // >= 16 zero bytes (source of padded / out-of-range operand slots)
     int dbg;           // ablation switches (tools only): 1 = no operand DMA after the first tile, 2 = no fragment reads after the first
     int stats_blocks;  // out: row blocks per image of the fused GroupNorm statistics (0 = not produced, epi.gn_stats was cleared)
-    int epi_block;     // 1: never the wave-private epilogue (launch_gemm_select: ODISE_GEMM_FLAGS 32768)
+    int epi_block;     // 1: never the wave-private epilogue (launch_gemm_select: kFlagBlockEpilogue)
 };
+static_assert(std::is_trivially_copyable<GemmArgs>::value, "GemmArgs is the kernel argument");
 
 // Workgroup barrier that only orders LDS traffic.  `__syncthreads()` also drains the vector-memory counter, i.e. it waits for
 // every outstanding global STORE of the wave (vmcnt counts stores on CDNA4); between the epilogue passes that costs one HBM
@@ -1474,6 +1476,16 @@ template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
+// ... for a count that only becomes a constant once the phase loops are unrolled: folds to the one s_waitcnt.  The schedules below never
+// leave more than 15 loads in flight; a count outside 0..15, or one the compiler cannot fold, stops the build instead of waiting for a
+// different number of loads than the schedule says.
+__attribute__((error("s_waitcnt vmcnt: the count must fold to a constant in 0..15"))) __device__ void wait_vmcnt_bad_count();
+template <int N = 15>
+__device__ __forceinline__ void wait_vmcnt_folded(int n) {
+    if (n == N) wait_vmcnt<N>();
+    else if constexpr (N > 0) wait_vmcnt_folded<N - 1>(n);
+    else wait_vmcnt_bad_count();
+}
 
 // ---- Ping-pong pipelined variant of the 256 x BN tile (BN = 256 / 320, 8 waves as 4(M) x 2(N), K % 64 == 0) ---------------------
 // The plain kernel above drains every LDS-DMA at each K-tile boundary (vmcnt(0) + barrier) and all 8 waves read fragments,
@@ -1741,33 +1753,9 @@ __global__ void __launch_bounds__(512) gemm_pp_kernel(GemmArgs g) {
 #pragma unroll
                     for (int l = 0; l < NL; ++l)
                         if (l / LPP == p - 1) issue(l, cur, t2);
-                    switch (2 * NL + issued2 - need) {  // compile-time after unrolling
-                        case 4: wait_vmcnt<4>(); break;
-                        case 5: wait_vmcnt<5>(); break;
-                        case 6: wait_vmcnt<6>(); break;
-                        case 7: wait_vmcnt<7>(); break;
-                        case 8: wait_vmcnt<8>(); break;
-                        case 9: wait_vmcnt<9>(); break;
-                        case 10: wait_vmcnt<10>(); break;
-                        case 11: wait_vmcnt<11>(); break;
-                        case 12: wait_vmcnt<12>(); break;
-                        case 13: wait_vmcnt<13>(); break;
-                        case 14: wait_vmcnt<14>(); break;
-                        case 15: wait_vmcnt<15>(); break;
-                        default: wait_vmcnt<0>(); break;
-                    }
+                    wait_vmcnt_folded(2 * NL + issued2 - need);  // compile-time after unrolling
                 } else if (has1) {
-                    switch (2 * NL - need) {
-                        case 1: wait_vmcnt<1>(); break;
-                        case 2: wait_vmcnt<2>(); break;
-                        case 3: wait_vmcnt<3>(); break;
-                        case 4: wait_vmcnt<4>(); break;
-                        case 8: wait_vmcnt<8>(); break;
-                        case 9: wait_vmcnt<9>(); break;
-                        case 10: wait_vmcnt<10>(); break;
-                        case 11: wait_vmcnt<11>(); break;
-                        default: wait_vmcnt<0>(); break;
-                    }
+                    wait_vmcnt_folded(2 * NL - need);
                 } else {
                     wait_vmcnt<0>();
                 }
@@ -2565,18 +2553,12 @@ __global__ void __launch_bounds__(256) splitk_reduce_kernel(const float* __restr
     }
 }
 
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool CONV>
-static int launch_gemm_t(odise_hip_ctx* ctx, GemmArgs& g, int batch) {
-    constexpr int NT = 64 * WAVES_M * WAVES_N;
-    constexpr int lds = plain_lds_bytes(BM, BN, WAVES_M);
-    static_assert(epi_lds_bytes(BM, BN, WAVES_M, epi_wave_rows(BM, BN, WAVES_M, lds)) <= lds, "epilogue staging exceeds the LDS request");
-    auto kern = gemm_kernel<BM, BN, WAVES_M, WAVES_N, CONV>;
-    if (lds > 65536) {
-        static LdsAttrOnce once;  // per instantiation; tracked per device inside
-        ODISE_TRY(ensure_dyn_lds(ctx, once, (const void*)kern, lds));
-    }
-    dim3 grid((unsigned)ceil_div(g.N, BN), (unsigned)ceil_div(g.M, BM), (unsigned)(g.splitk > 1 ? g.splitk : batch));
-    hipLaunchKernelGGL(kern, grid, dim3(NT), lds, ctx->stream, g);
+// Launches one of the tile kernels above and, with split-K, the reduction of its fp32 partials.  `once` belongs to the kernel instantiation:
+// a request above the 64 KiB every kernel may use is opted in to once per kernel and device (the small plain tiles stay below and never
+// touch `once`; the ping-pong and halo launchers assert that they are above).
+static int launch_tile_kernel(odise_hip_ctx* ctx, void (*kern)(GemmArgs), LdsAttrOnce& once, dim3 grid, int threads, int lds, const GemmArgs& g) {
+    if (lds > 65536) ODISE_TRY(ensure_dyn_lds(ctx, once, (const void*)kern, lds));
+    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, ctx->stream, g);
     ODISE_CHECK_HIP(hipGetLastError());
     if (g.splitk > 1) {
         const int64_t total = (int64_t)g.M * ceil_div(g.N, 8);
@@ -2585,64 +2567,50 @@ static int launch_gemm_t(odise_hip_ctx* ctx, GemmArgs& g, int batch) {
         ODISE_CHECK_HIP(hipGetLastError());
     }
     return ODISE_OK;
+}
+// grid of the im2col kernels: column tiles x row tiles x (splits | batch)
+static dim3 gemm_grid(const GemmArgs& g, int BM, int BN, int batch) {
+    return dim3((unsigned)ceil_div(g.N, BN), (unsigned)ceil_div(g.M, BM), (unsigned)(g.splitk > 1 ? g.splitk : batch));
+}
+// ... of the halo kernels: column tiles x 16x16-pixel patches of every image x splits
+static dim3 halo_grid(const GemmArgs& g, int BN) {
+    const int n_img = g.M / (g.cg.OH * g.cg.OW);
+    return dim3((unsigned)ceil_div(g.N, BN), (unsigned)(n_img * g.cg.halo_tx * g.cg.halo_ty), (unsigned)(g.splitk > 1 ? g.splitk : 1));
+}
+
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool CONV>
+static int launch_gemm_t(odise_hip_ctx* ctx, GemmArgs& g, int batch) {
+    constexpr int lds = plain_lds_bytes(BM, BN, WAVES_M);
+    static_assert(epi_lds_bytes(BM, BN, WAVES_M, epi_wave_rows(BM, BN, WAVES_M, lds)) <= lds, "epilogue staging exceeds the LDS request");
+    static LdsAttrOnce once;  // per instantiation; tracked per device inside
+    return launch_tile_kernel(ctx, gemm_kernel<BM, BN, WAVES_M, WAVES_N, CONV>, once, gemm_grid(g, BM, BN, batch), 64 * WAVES_M * WAVES_N, lds, g);
 }
 
 template <int BM, int BN, int WAVES_N, int PT, bool CONV>
 static int launch_gemm_pp(odise_hip_ctx* ctx, GemmArgs& g, int batch) {
     constexpr int lds = pp_lds_bytes(BM, BN, 8 / WAVES_N);
     static_assert(epi_lds_bytes(BM, BN, 8 / WAVES_N, epi_wave_rows(BM, BN, 8 / WAVES_N, lds)) <= lds, "epilogue staging exceeds the LDS request");
-    auto kern = gemm_pp_kernel<BM, BN, WAVES_N, PT, CONV>;
-    static LdsAttrOnce once;  // per instantiation; tracked per device inside
-    ODISE_TRY(ensure_dyn_lds(ctx, once, (const void*)kern, lds));
-    dim3 grid((unsigned)ceil_div(g.N, BN), (unsigned)ceil_div(g.M, BM), (unsigned)(g.splitk > 1 ? g.splitk : batch));
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, g);
-    ODISE_CHECK_HIP(hipGetLastError());
-    if (g.splitk > 1) {
-        const int64_t total = (int64_t)g.M * ceil_div(g.N, 8);
-        const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 2048);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, g.ws, g.splitk, g.M, g.N, g.epi);
-        ODISE_CHECK_HIP(hipGetLastError());
-    }
-    return ODISE_OK;
+    static_assert(lds > 65536, "the ping-pong tiles always opt in to dynamic LDS");
+    static LdsAttrOnce once;
+    return launch_tile_kernel(ctx, gemm_pp_kernel<BM, BN, WAVES_N, PT, CONV>, once, gemm_grid(g, BM, BN, batch), 512, lds, g);
 }
 
 template <int BM, int BN, int WAVES_N, int PT, bool CONV>
 static int launch_gemm_pp2(odise_hip_ctx* ctx, GemmArgs& g, int batch) {
     static_assert((BN / WAVES_N / 32) % PT == 0, "whole phases");
     constexpr int lds = pp_lds_bytes(BM, BN, 8 / WAVES_N);
-    auto kern = gemm_pp2_kernel<BM, BN, WAVES_N, PT, CONV>;
-    static LdsAttrOnce once;  // per instantiation; tracked per device inside
-    ODISE_TRY(ensure_dyn_lds(ctx, once, (const void*)kern, lds));
-    dim3 grid((unsigned)ceil_div(g.N, BN), (unsigned)ceil_div(g.M, BM), (unsigned)(g.splitk > 1 ? g.splitk : batch));
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, g);
-    ODISE_CHECK_HIP(hipGetLastError());
-    if (g.splitk > 1) {
-        const int64_t total = (int64_t)g.M * ceil_div(g.N, 8);
-        const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 2048);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, g.ws, g.splitk, g.M, g.N, g.epi);
-        ODISE_CHECK_HIP(hipGetLastError());
-    }
-    return ODISE_OK;
+    static_assert(lds > 65536, "the ping-pong tiles always opt in to dynamic LDS");
+    static LdsAttrOnce once;
+    return launch_tile_kernel(ctx, gemm_pp2_kernel<BM, BN, WAVES_N, PT, CONV>, once, gemm_grid(g, BM, BN, batch), 512, lds, g);
 }
 
 template <int BN, int PT>
 static int launch_conv3_halo(odise_hip_ctx* ctx, GemmArgs& g) {
     constexpr int lds = halo_lds_bytes(BN);
     static_assert(epi_lds_bytes(256, BN, 4, epi_wave_rows(256, BN, 4, lds)) <= lds, "epilogue staging exceeds the LDS request");
-    auto kern = conv3_halo_kernel<BN, PT>;
-    static LdsAttrOnce once;  // per instantiation; tracked per device inside
-    ODISE_TRY(ensure_dyn_lds(ctx, once, (const void*)kern, lds));
-    const int n_img = g.M / (g.cg.OH * g.cg.OW);
-    dim3 grid((unsigned)ceil_div(g.N, BN), (unsigned)(n_img * g.cg.halo_tx * g.cg.halo_ty), (unsigned)(g.splitk > 1 ? g.splitk : 1));
-    hipLaunchKernelGGL(kern, grid, dim3(512), lds, ctx->stream, g);
-    ODISE_CHECK_HIP(hipGetLastError());
-    if (g.splitk > 1) {
-        const int64_t total = (int64_t)g.M * ceil_div(g.N, 8);
-        const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 2048);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, g.ws, g.splitk, g.M, g.N, g.epi);
-        ODISE_CHECK_HIP(hipGetLastError());
-    }
-    return ODISE_OK;
+    static_assert(lds > 65536, "the halo tiles always opt in to dynamic LDS");
+    static LdsAttrOnce once;
+    return launch_tile_kernel(ctx, conv3_halo_kernel<BN, PT>, once, halo_grid(g, BN), 512, lds, g);
 }
 
 template <int BN>
@@ -2650,26 +2618,24 @@ static int launch_conv3_halo4(odise_hip_ctx* ctx, GemmArgs& g) {
     constexpr int lds = halo4_lds_bytes(BN);
     static_assert(2 * lds <= 160 * 1024, "two blocks must fit a CU's LDS");
     static_assert(epi_lds_bytes(256, BN, 4, epi_wave_rows(256, BN, 4, lds)) <= lds, "epilogue staging exceeds the LDS request");
-    auto kern = conv3_halo4_kernel<BN>;
-    static LdsAttrOnce once;  // per instantiation; tracked per device inside
-    ODISE_TRY(ensure_dyn_lds(ctx, once, (const void*)kern, lds));
-    const int n_img = g.M / (g.cg.OH * g.cg.OW);
-    dim3 grid((unsigned)ceil_div(g.N, BN), (unsigned)(n_img * g.cg.halo_tx * g.cg.halo_ty), (unsigned)(g.splitk > 1 ? g.splitk : 1));
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, ctx->stream, g);
-    ODISE_CHECK_HIP(hipGetLastError());
-    if (g.splitk > 1) {
-        const int64_t total = (int64_t)g.M * ceil_div(g.N, 8);
-        const int blocks = (int)std::min<int64_t>(ceil_div(total, 256), 2048);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, g.ws, g.splitk, g.M, g.N, g.epi);
-        ODISE_CHECK_HIP(hipGetLastError());
-    }
-    return ODISE_OK;
+    static_assert(lds > 65536, "the halo tiles always opt in to dynamic LDS");
+    static LdsAttrOnce once;
+    return launch_tile_kernel(ctx, conv3_halo4_kernel<BN>, once, halo_grid(g, BN), 256, lds, g);
 }
 
 static int g_gemm_debug = 0;  // see GemmArgs::dbg
-// kernel-selection switches for A/B runs (odise_hip_gemm_debug(flags << 4); ODISE_GEMM_FLAGS in the tools build): 2 no ping-pong kernels,
-// 16 no 512x128 tile, 32 launch log (GEMMLOG), 64 no halo tiles, 512 / 1024 force / forbid the second ping-pong generation, 2048 no
-// two-blocks-per-CU halo tile, 32768 block-wide epilogues only, 131072 no halo tile on fused-upsample convolutions.  Other bits are ignored.
+// kernel-selection switches for A/B runs (odise_hip_gemm_debug(flags << 4); ODISE_GEMM_FLAGS in the tools build).  Other bits are ignored.
+enum SelectFlag : int {
+    kFlagNoPingPong = 2,           // no ping-pong kernels (nor the halo tiles, which share their preconditions)
+    kFlagNo512x128 = 16,           // no 512x128 tile
+    kFlagLaunchLog = 32,           // log every launch (GEMMLOG; tools/gemm_eff.py joins the log with a rocprofv3 kernel trace: per-shape TFLOP/s)
+    kFlagNoHalo = 64,              // never use the halo kernels
+    kFlagForcePP2 = 512,           // force ...
+    kFlagNoPP2 = 1024,             // ... / forbid the second ping-pong generation
+    kFlagNoHalo4 = 2048,           // never use the two-blocks-per-CU halo kernel
+    kFlagBlockEpilogue = 32768,    // block-wide epilogues only
+    kFlagNoHaloUpsample = 131072,  // no halo tile on fused-upsample convolutions
+};
 static int g_conv_flags = 0;
 
 // Tile ids: 0:128x128 1:64x128 2:64x64 (4 waves)  3:256x320 4:256x256 5:256x128 (8 waves)  6:512x128 (8 waves, ping-pong only)
@@ -2679,7 +2645,13 @@ static int g_conv_flags = 0;
 //  bit-identical, and measured 5-20 % SLOWER than the 8-wave ping-pong kernels on 19 of the step's 22 dense shapes, never more than 9 % faster
 //  (profiles/r03_gemm4_two_blocks_dense.txt): two operand streams through LDS-DMA at half the tile size cost more than the overlap of
 //  neighbouring blocks returns, where the convolution's input patch is fetched once for nine K-tiles.  Not kept.)
-static const int kNumTiles = 10;
+enum Tile : int {
+    kTile128x128 = 0, kTile64x128 = 1, kTile64x64 = 2, kTile256x320 = 3, kTile256x256 = 4, kTile256x128 = 5, kTile512x128 = 6,
+    kTileHalo256 = 7, kTileHalo128 = 8, kTileHalo128x4 = 9, kNumTiles = 10
+};
+static bool is_halo_tile(int t) { return t >= kTileHalo256 && t <= kTileHalo128x4; }
+// the 256-row tiles and 512x128 run a ping-pong kernel whenever its preconditions hold (512x128 has no other form)
+static bool has_pingpong_form(int t) { return t == kTile256x320 || t == kTile256x256 || t == kTile512x128; }
 static const int kTileBM[kNumTiles] = {128, 64, 64, 256, 256, 256, 512, 256, 256, 256};
 static const int kTileBN[kNumTiles] = {128, 128, 64, 320, 256, 128, 128, 256, 128, 128};
 
@@ -2758,7 +2730,7 @@ static int launch_gemm(odise_hip_ctx* ctx, GemmArgs& g, int batch, int force_til
     return rc;
 }
 
-static int flags_early() { return g_conv_flags | env_gemm_flags(); }   // (ODISE_GEMM_FLAGS 131072: no halo tile for the fused-upsample convolutions, A/B)
+static int select_flags() { return g_conv_flags | env_gemm_flags(); }
 template <bool CONV>
 static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int force_tile, int force_split, unsigned tile_mask) {
     const int64_t cus = ctx->cu_count;
@@ -2771,31 +2743,32 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
         // plain kernel; the decoder's 512 -> 512 upsampling convolution ran 2.4 ms on the un-pipelined implicit GEMM, the UNet's three likewise)
         const int up = g.cg.ups ? 1 : 0;
         halo_ok = g.cg.KH == 3 && g.cg.KW == 3 && g.cg.stride == 1 && g.cg.pad_t == 1 && g.cg.pad_l == 1 && g.cg.Cin % 64 == 0 &&
-                  g.cg.OH == (g.cg.H << up) && g.cg.OW == (g.cg.W << up) && batch == 1 && !(up && (flags_early() & 131072));
+                  g.cg.OH == (g.cg.H << up) && g.cg.OW == (g.cg.W << up) && batch == 1 && !(up && (select_flags() & kFlagNoHaloUpsample));
         g.cg.halo_tx = (int)ceil_div(g.cg.OW, 16);
         g.cg.halo_ty = (int)ceil_div(g.cg.OH, 16);
         halo_patches = (int64_t)(g.M / (g.cg.OH * g.cg.OW)) * g.cg.halo_tx * g.cg.halo_ty;
     }
     auto blocks = [&](int t) {
-        return ((t >= 7 && t <= 9) ? halo_patches : ceil_div(g.M, kTileBM[t])) * ceil_div(g.N, kTileBN[t]) * (int64_t)batch;
+        return (is_halo_tile(t) ? halo_patches : ceil_div(g.M, kTileBM[t])) * ceil_div(g.N, kTileBN[t]) * (int64_t)batch;
     };
-    int tile = 2, best_split = 1;
+    int tile = kTile64x64, best_split = 1;
     double best = 1e30;
-    const int flags = g_conv_flags | env_gemm_flags();
-    const bool pp_base = !(flags & 2) && g.K % 64 == 0 && (!CONV || g.cg.Cin % 64 == 0);   // what the halo tiles need (they gather the fused upsample themselves)
+    const int flags = select_flags();
+    const bool pp_base = !(flags & kFlagNoPingPong) && g.K % 64 == 0 && (!CONV || g.cg.Cin % 64 == 0);   // what the halo tiles need (they gather the fused upsample themselves)
     const bool pp_ok = pp_base && !(CONV && g.cg.ups);
     for (int t = 0; t < kNumTiles; ++t) {
         if (force_tile >= 0 && force_tile < kNumTiles && t != force_tile) continue;
         if (!((tile_mask >> t) & 1)) continue;
-        if (t == 6 && (!pp_ok || (flags & 16))) continue;
-        if (t >= 7 && t <= 9 && (!halo_ok || !pp_base || (flags & 64))) continue;  // ODISE_GEMM_FLAGS=64: never use the halo kernels
-        if (t == 9 && (flags & 2048)) continue;                        // ODISE_GEMM_FLAGS=2048: never use the two-blocks-per-CU halo kernel
-        if (t == 9 && force_tile < 0 && g.N > 128) continue;           // (see kTileCost[9])
-        const TileCost& tc = (CONV && pp_ok && t == 4) ? kTileCostPPConv256 : (pp_ok && (t == 3 || t == 4)) ? kTileCostPP[t - 3] :
-                             (CONV && t == 6) ? kTileCostConv512 : kTileCost[t];
+        if (t == kTile512x128 && (!pp_ok || (flags & kFlagNo512x128))) continue;
+        if (is_halo_tile(t) && (!halo_ok || !pp_base || (flags & kFlagNoHalo))) continue;
+        if (t == kTileHalo128x4 && (flags & kFlagNoHalo4)) continue;
+        if (t == kTileHalo128x4 && force_tile < 0 && g.N > 128) continue;   // (see kTileCost[kTileHalo128x4])
+        const TileCost& tc = (CONV && pp_ok && t == kTile256x256) ? kTileCostPPConv256 :
+                             (pp_ok && (t == kTile256x320 || t == kTile256x256)) ? kTileCostPP[t - kTile256x320] :
+                             (CONV && t == kTile512x128) ? kTileCostConv512 : kTileCost[t];
         if (force_tile < 0) {
             if (kTileBM[t] > 64 && g.M <= kTileBM[t] / 2) continue;            // mostly-empty row tiles
-            if (kTileBN[t] > 64 && g.N <= kTileBN[t] / 2 && t != 2) continue;  // mostly-empty column tiles
+            if (kTileBN[t] > 64 && g.N <= kTileBN[t] / 2 && t != kTile64x64) continue;  // mostly-empty column tiles
         }
         const int64_t nb = blocks(t);
         const int64_t slots = cus * tc.slots_per_cu;
@@ -2804,7 +2777,7 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
             if (force_split > 0 && sp != std::min(force_split, std::max(1, nk))) continue;
             if (sp > 1 && (size_t)sp * g.M * g.N * sizeof(float) > ctx->ws_bytes) break;
             // the halo kernel splits K in whole 64-channel chunks (9 K-tiles each)
-            const int per = (t >= 7 && t <= 9) ? (int)ceil_div(nk / 9, sp) * 9 : (int)ceil_div(nk, sp);
+            const int per = is_halo_tile(t) ? (int)ceil_div(nk / 9, sp) * 9 : (int)ceil_div(nk, sp);
             const int eff_sp = (int)ceil_div(nk, per);
             // Full residency rounds run at the calibrated K-tile time; the last (or only) partial round still costs most of a
             // block's time: an under-filled chip delivers operands only a little faster per block (measured with
@@ -2818,19 +2791,19 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
             if (t_us < best) { best = t_us; tile = t; best_split = eff_sp; }
         }
     }
-    if (force_tile >= 0 && force_tile < kNumTiles && !(force_tile == 6 && !pp_ok) && !(force_tile >= 7 && force_tile <= 9 && !(halo_ok && pp_base)))
+    if (force_tile >= 0 && force_tile < kNumTiles && !(force_tile == kTile512x128 && !pp_ok) && !(is_halo_tile(force_tile) && !(halo_ok && pp_base)))
         tile = force_tile;
     g.splitk = 1;
     g.ktiles_per_split = nk;
     if (force_split > 0 && batch == 1) best_split = std::min(force_split, nk);
     if (best_split > 1 && batch == 1) {
-        g.ktiles_per_split = (tile >= 7 && tile <= 9) ? (int)ceil_div(nk / 9, best_split) * 9 : (int)ceil_div(nk, best_split);
+        g.ktiles_per_split = is_halo_tile(tile) ? (int)ceil_div(nk / 9, best_split) * 9 : (int)ceil_div(nk, best_split);
         g.splitk = (int)ceil_div(nk, g.ktiles_per_split);
         ODISE_REQUIRE((size_t)g.splitk * g.M * g.N * sizeof(float) <= ctx->ws_bytes, "gemm: split-K workspace too small");
     }
     g_last_tile = tile | (best_split << 8);
     if (ctx->launch_log) launch_log_push(ctx, LaunchRec{(int)CONV, g.M, g.N, g.K, tile, g.splitk});
-    if (flags & 32) {  // ODISE_GEMM_FLAGS=32: log every launch (tools/gemm_eff.py joins the log with a rocprofv3 kernel trace: per-shape TFLOP/s)
+    if (flags & kFlagLaunchLog) {
         fprintf(stderr, "GEMMLOG conv=%d M=%d N=%d K=%d batch=%d cin=%d kh=%d h=%d w=%d stride=%d ups=%d tile=%d split=%d pp=%d\n", (int)CONV, g.M, g.N,
                 g.K, batch, g.cg.Cin, g.cg.KH, g.cg.H, g.cg.W, g.cg.stride, g.cg.ups, tile, best_split, (int)pp_ok);
     }
@@ -2857,8 +2830,8 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
     if (g.epi.ln_part || g.epi.ln_final || g.epi.ln_stats_out) {
         // the LayerNorm terms only exist in the math-first epilogue (256x256 / 256x128 tiles); the producer's partial sums are per 128 columns =
         // the wave columns of the 256x256 tile
-        ODISE_REQUIRE(!CONV && (tile == 4 || tile == 5) && g.splitk == 1 && g.epi.f16path && !g.epi.geglu && batch == 1 &&
-                          (!g.epi.ln_stats_out || (tile == 4 && g.N % kLnPartCols == 0)),
+        ODISE_REQUIRE(!CONV && (tile == kTile256x256 || tile == kTile256x128) && g.splitk == 1 && g.epi.f16path && !g.epi.geglu && batch == 1 &&
+                          (!g.epi.ln_stats_out || (tile == kTile256x256 && g.N % kLnPartCols == 0)),
                       "gemm_ln: M=%d N=%d K=%d cannot take the folded-LayerNorm path", g.M, g.N, g.K);
     }
     g.stats_blocks = 0;
@@ -2867,48 +2840,47 @@ static int launch_gemm_select(odise_hip_ctx* ctx, GemmArgs& g, int batch, int fo
         // epilogue), a column-chunk count that divides the thread count, and row blocks that never straddle two images
         const int ohw = CONV ? g.cg.OH * g.cg.OW : 0;
         // kernels instantiated with the statistics epilogue: halo tiles, pp2 conv (256x256) and the 512x128 conv tile
-        const bool pp2_used = (tile == 4) && pp_ok && ((flags & 512) || (!(flags & 1024) && CONV));
-        bool ok = CONV && g.splitk == 1 && g.epi.fast && g.N % 8 == 0 && ((tile >= 7 && tile <= 9) || (tile == 6 && pp_ok && !(flags & 512)) || pp2_used);
-        if (ok && tile >= 7) g.stats_blocks = g.cg.halo_tx * g.cg.halo_ty;
+        const bool pp2_used = (tile == kTile256x256) && pp_ok && ((flags & kFlagForcePP2) || (!(flags & kFlagNoPP2) && CONV));
+        bool ok = CONV && g.splitk == 1 && g.epi.fast && g.N % 8 == 0 &&
+                  (is_halo_tile(tile) || (tile == kTile512x128 && pp_ok && !(flags & kFlagForcePP2)) || pp2_used);
+        if (ok && is_halo_tile(tile)) g.stats_blocks = g.cg.halo_tx * g.cg.halo_ty;
         else if (ok && ohw % kTileBM[tile] == 0) g.stats_blocks = ohw / kTileBM[tile];
         else ok = false;
         if (!ok) { g.epi.gn_stats = nullptr; g.stats_blocks = 0; }
     }
     g.zeros = (const f16*)ctx->zeros;
-    g.epi_block = (flags & 32768) ? 1 : 0;
+    g.epi_block = (flags & kFlagBlockEpilogue) ? 1 : 0;
 #ifdef ODISE_TOOLS
     static const int freeze_k = (getenv("ODISE_GEMM_FREEZE_K") ? 16 : 0) | (getenv("ODISE_NO_RES_PREFETCH") ? 64 : 0);
     g.dbg = g_gemm_debug | freeze_k;
 #else
     g.dbg = 0;
 #endif
-    // the 256-row tiles run the ping-pong pipelined kernel whenever its preconditions hold
-    if (tile >= 7) {
+    if (is_halo_tile(tile)) {
         g.cg.chunk_major = 1;
-        if (tile == 9) return launch_conv3_halo4<128>(ctx, g);
-        return tile == 7 ? launch_conv3_halo<256, 2>(ctx, g) : launch_conv3_halo<128, 1>(ctx, g);
+        if (tile == kTileHalo128x4) return launch_conv3_halo4<128>(ctx, g);
+        return tile == kTileHalo256 ? launch_conv3_halo<256, 2>(ctx, g) : launch_conv3_halo<128, 1>(ctx, g);
     }
     g.cg.halo_tx = g.cg.halo_ty = 0;
     // second-generation ping-pong kernel (fragment reads under the MFMAs): measured +3..18 % on the implicit-GEMM convs and on
     // dense problems that do not fill the chip twice; the large dense GEMMs keep the first generation (-5..12 % there).
-    // ODISE_GEMM_FLAGS: 512 forces it, 1024 forbids it.
-    const bool pp2_auto = !(flags & 1024) && ((CONV && tile != 6) || (!CONV && blocks(tile) * (g.splitk > 1 ? g.splitk : 1) <= 2 * cus));
-    if ((tile == 3 || tile == 4 || tile == 6) && pp_ok && ((flags & 512) || pp2_auto)) {
-        if (tile == 6) return launch_gemm_pp2<512, 128, 1, 2, CONV>(ctx, g, batch);
-        if (tile == 3) return launch_gemm_pp2<256, 320, 2, 1, CONV>(ctx, g, batch);
+    const bool pp2_auto = !(flags & kFlagNoPP2) && ((CONV && tile != kTile512x128) || (!CONV && blocks(tile) * (g.splitk > 1 ? g.splitk : 1) <= 2 * cus));
+    if (has_pingpong_form(tile) && pp_ok && ((flags & kFlagForcePP2) || pp2_auto)) {
+        if (tile == kTile512x128) return launch_gemm_pp2<512, 128, 1, 2, CONV>(ctx, g, batch);
+        if (tile == kTile256x320) return launch_gemm_pp2<256, 320, 2, 1, CONV>(ctx, g, batch);
         return launch_gemm_pp2<256, 256, 2, 2, CONV>(ctx, g, batch);
     }
-    if ((tile == 3 || tile == 4 || tile == 6) && pp_ok) {
-        if (tile == 6) return launch_gemm_pp<512, 128, 1, 2, CONV>(ctx, g, batch);
-        if (tile == 3) return launch_gemm_pp<256, 320, 2, 1, CONV>(ctx, g, batch);
+    if (has_pingpong_form(tile) && pp_ok) {
+        if (tile == kTile512x128) return launch_gemm_pp<512, 128, 1, 2, CONV>(ctx, g, batch);
+        if (tile == kTile256x320) return launch_gemm_pp<256, 320, 2, 1, CONV>(ctx, g, batch);
         return launch_gemm_pp<256, 256, 2, 2, CONV>(ctx, g, batch);
     }
     switch (tile) {
-        case 0: return launch_gemm_t<128, 128, 2, 2, CONV>(ctx, g, batch);
-        case 1: return launch_gemm_t<64, 128, 2, 2, CONV>(ctx, g, batch);
-        case 3: return launch_gemm_t<256, 320, 4, 2, CONV>(ctx, g, batch);
-        case 4: return launch_gemm_t<256, 256, 4, 2, CONV>(ctx, g, batch);
-        case 5: return launch_gemm_t<256, 128, 4, 2, CONV>(ctx, g, batch);
+        case kTile128x128: return launch_gemm_t<128, 128, 2, 2, CONV>(ctx, g, batch);
+        case kTile64x128: return launch_gemm_t<64, 128, 2, 2, CONV>(ctx, g, batch);
+        case kTile256x320: return launch_gemm_t<256, 320, 4, 2, CONV>(ctx, g, batch);
+        case kTile256x256: return launch_gemm_t<256, 256, 4, 2, CONV>(ctx, g, batch);
+        case kTile256x128: return launch_gemm_t<256, 128, 4, 2, CONV>(ctx, g, batch);
         default: return launch_gemm_t<64, 64, 2, 2, CONV>(ctx, g, batch);
     }
 }
@@ -2939,9 +2911,6 @@ int gemm_forced(odise_hip_ctx* ctx, const odise_gemm_desc* d, int force_tile, in
     g.epi.ldg = d->ldg > 0 ? d->ldg : d->N;
     g.epi.act = d->act; g.epi.geglu = d->geglu; g.epi.alpha = d->alpha;
     g.epi.strideC = d->strideC; g.epi.strideR = d->strideR;
-    g.epi.gn_stats = nullptr;
-    g.epi.ln_part = nullptr; g.epi.ln_P = 0; g.epi.ln_inv_c = 0.f; g.epi.ln_eps = 0.f; g.epi.ln_colsum = nullptr; g.epi.ln_final_out = nullptr;
-    g.epi.ln_final = nullptr; g.epi.ln_rowsum = nullptr; g.epi.ln_stats_out = nullptr;
     if (ln) {
         g.epi.ln_part = ln->part; g.epi.ln_P = ln->P; g.epi.ln_inv_c = ln->inv_c; g.epi.ln_eps = ln->eps; g.epi.ln_colsum = ln->colsum;
         g.epi.ln_final_out = ln->final_out; g.epi.ln_final = ln->fin; g.epi.ln_rowsum = ln->rowsum; g.epi.ln_stats_out = ln->stats_out;
@@ -2949,7 +2918,7 @@ int gemm_forced(odise_hip_ctx* ctx, const odise_gemm_desc* d, int force_tile, in
     }
     g.cg = ConvGeom{};
     // folded LayerNorm: no split-K, a tile with the math-first epilogue (the producer of the statistics: the 256x256 one)
-    if (ln) return launch_gemm<false>(ctx, g, batch, force_tile, 1, ln->stats_out ? (1u << 4) : (1u << 4) | (1u << 5));
+    if (ln) return launch_gemm<false>(ctx, g, batch, force_tile, 1, ln->stats_out ? (1u << kTile256x256) : (1u << kTile256x256) | (1u << kTile256x128));
     return launch_gemm<false>(ctx, g, batch, force_tile, force_split);
 }
 
@@ -2979,8 +2948,6 @@ int conv_forced(odise_hip_ctx* ctx, const odise_conv_desc* d, int force_tile, in
     g.epi.act = d->act; g.epi.geglu = 0; g.epi.alpha = 1.0f;
     g.epi.strideC = 0; g.epi.strideR = 0;
     g.epi.gn_stats = gn_stats;
-    g.epi.ln_part = nullptr; g.epi.ln_P = 0; g.epi.ln_inv_c = 0.f; g.epi.ln_eps = 0.f; g.epi.ln_colsum = nullptr; g.epi.ln_final_out = nullptr;
-    g.epi.ln_final = nullptr; g.epi.ln_rowsum = nullptr; g.epi.ln_stats_out = nullptr;
     if (stats_blocks) *stats_blocks = 0;
     g.cg.H = d->H; g.cg.W = d->W; g.cg.Cin = d->Cin; g.cg.KH = d->KH; g.cg.KW = d->KW;
     g.cg.stride = d->stride; g.cg.pad_t = d->pad_t; g.cg.pad_l = d->pad_l; g.cg.OH = d->OH; g.cg.OW = d->OW;
