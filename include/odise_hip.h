@@ -373,6 +373,19 @@ int odise_hip_u8_hwc_to_f32_chw_padded(odise_hip_ctx* ctx, const void* src, floa
 /* conf int64 [(K+1)*(K+1)] += count of (argmax_k sem_seg[k,p], gt[p]); gt outside [0,K] (ignore label) counts in column K.
  * The caller zeroes conf before the first image and sums it across ranks (all-gather / all-reduce of (K+1)^2 int64). */
 int odise_hip_semantic_confusion(odise_hip_ctx* ctx, const float* sem_seg, const int* gt, int K, int npix, int64_t* conf);
+/* The evaluator's second matrix (_b_conf_matrix, Boundary IoU; detectron2 fills it when OpenCV is importable and K < 255).
+ * _mask_to_boundary(m) = m - erode(m): a 3x3 minimum behind a one-pixel ring of zeros, `radius` times; equivalently e = 0 within
+ * `radius` of an edge and the (2 radius + 1)^2 window minimum elsewhere.  m - e is a LABEL DIFFERENCE in 0..K, as in the evaluator.
+ * radius of an H x W picture: max(1, int(round(0.02 * sqrt(H*H + W*W)))), Python's round; negative error for H or W < 1.  No context. */
+int odise_hip_boundary_radius(int H, int W);
+/* boundary int32 [H,W] = _mask_to_boundary(labels int32 [H,W] (device), values outside [0,K] taken as K); radius <= 0: the formula.
+ * 1 <= K <= 254.  Scratch comes from the context.  Asynchronous on the context's stream. */
+int odise_hip_label_boundary(odise_hip_ctx* ctx, const int* labels, int K, int H, int W, int radius, int* boundary);
+/* One SemSegEvaluator.process step of a picture: sem_seg fp32 [K,H,W], gt int32 [H,W].  conf (optional) += exactly what
+ * odise_hip_semantic_confusion adds; b_conf int64 [(K+1)*(K+1)] += count of (boundary(argmax)[p], boundary(gt)[p]), rows = prediction.
+ * Neither is cleared.  radius <= 0: the formula.  K > 254 is ODISE_ERR_ARG (the evaluator computes no Boundary IoU there) and writes nothing. */
+int odise_hip_semantic_boundary_confusion(odise_hip_ctx* ctx, const float* sem_seg, const int* gt, int K, int H, int W, int radius,
+                                          int64_t* conf, int64_t* b_conf);
 /* hist int32 [na*nb] += count of (a[p], b[p]) pairs with 0 <= a < na, 0 <= b < nb (segment-index co-occurrence of PQ matching) */
 int odise_hip_pair_histogram(odise_hip_ctx* ctx, const int* a, const int* b, int npix, int na, int nb, int* hist);
 /* COCO compressed RLE (pycocotools mask.encode of the Fortran-ordered mask, counts as text) of n masks: the per-mask part of the segm

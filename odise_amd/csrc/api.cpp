@@ -66,6 +66,7 @@ extern "C" int odise_hip_destroy(odise_hip_ctx* ctx) {
     models_destroy(ctx);
     odise::jpeg_release(ctx);
     odise::rle_release(ctx);
+    odise::boundary_release(ctx);
     odise::comm_release(ctx);
     odise::probe_release(ctx);
     odise::launch_log_release(ctx);

@@ -121,6 +121,9 @@ struct odise_hip_ctx {
     // rle.hip: growable device scratch of odise_hip_rle_encode / odise_hip_instance_rle (bit-packed masks, per-thread scan state, string lengths)
     void* rle_buf = nullptr;
     size_t rle_bytes = 0;
+    // eval_ops.hip: growable device scratch of odise_hip_label_boundary / odise_hip_semantic_boundary_confusion (byte label maps, their erosions)
+    void* boundary_buf = nullptr;
+    size_t boundary_bytes = 0;
 };
 
 namespace odise {
@@ -178,5 +181,6 @@ int gemm_forced(odise_hip_ctx* ctx, const odise_gemm_desc* d, int force_tile, in
 int gemm_ln(odise_hip_ctx* ctx, const odise_gemm_desc* d, const LnEpi& ln);   // 256x256 ping-pong tile, math-first epilogue
 void jpeg_release(odise_hip_ctx* ctx);
 void rle_release(odise_hip_ctx* ctx);
+void boundary_release(odise_hip_ctx* ctx);
 void comm_release(odise_hip_ctx* ctx);
 }

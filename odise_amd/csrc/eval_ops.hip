@@ -10,10 +10,25 @@
 //                                  (K+1)^2 confusion counts (rows = prediction, ignore label mapped to K by the caller).
 //   odise_hip_pair_histogram       the per-pixel part of panopticapi pq_compute_single_core (COCOPanopticEvaluator,
 //                                  d2_evaluator.py:49): co-occurrence counts of (ground-truth segment, predicted segment) indices.
+//   odise_hip_label_boundary / odise_hip_semantic_boundary_confusion
+//                                  the second per-pixel job of SemSegEvaluator.process (K < 255, OpenCV importable): prediction and ground
+//                                  truth both go through _mask_to_boundary - a 3x3 grey-scale erosion behind a zero ring, repeated
+//                                  r = max(1, round(0.02 * diagonal)) times, subtracted from the map - and the pairs of the two LABEL
+//                                  DIFFERENCES are counted in a second (K+1)^2 matrix (_b_conf_matrix, Boundary IoU).  r erosions are one
+//                                  (2r+1)^2 minimum with zeros outside the picture, so:
+//                                    labels  arg-max (+ the confusion counts) -> two byte maps [H][pitch], four labels per dword
+//                                    min     row direction, then column direction, each by window growing: a pass takes the minimum of up
+//                                            to four shifted copies of the previous pass's windows (1 -> 4 -> 16 -> ... pixels, the last pass
+//                                            places ceil((2r+1) / s) windows of s over the 2r+1), reads outside the picture give 0.  The cost
+//                                            per pixel grows with log4(r), the passes run in global memory (the maps are 1-7 MB and stay in
+//                                            the L2 / MALL), so r may exceed any tile; 2r+1 > min(H, W) erodes everything and skips them.
+//                                    count   b = m - e per byte (m >= e: a plain dword subtraction), cell (0, 0) - every pixel away from a
+//                                            boundary - in a register, the rest through the per-block LDS histogram.
 // All of it is HBM-bound integer / byte work: coalesced row-major sweeps, per-block LDS histograms flushed with integer atomics
 // (deterministic: integer addition commutes).
 #include <math.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "common.h"
@@ -121,7 +136,18 @@ __global__ void __launch_bounds__(256) u8_hwc_to_f32_chw_pad_kernel(const uint8_
     dst[idx] = (y < H && x < W) ? (float)src[((int64_t)y * W + x) * C + c] * scale : 0.f;
 }
 
-// per pixel: first-maximum argmax over K planes (torch.argmax semantics for distinct values; ties -> lowest class), count (pred, gt)
+// first-maximum argmax over the K planes of pixel p (torch.argmax semantics for distinct values; ties -> lowest class)
+__device__ __forceinline__ int argmax_first(const float* __restrict__ sem, int K, int64_t npix, int64_t p) {
+    float best = sem[p];
+    int bi = 0;
+    for (int k = 1; k < K; ++k) {
+        const float v = sem[(int64_t)k * npix + p];
+        if (v > best) { best = v; bi = k; }
+    }
+    return bi;
+}
+
+// per pixel: argmax, count (pred, gt)
 __global__ void __launch_bounds__(256) semantic_confusion_kernel(const float* __restrict__ sem, const int* __restrict__ gt, int K, int npix,
                                                                 unsigned long long* __restrict__ conf) {
     extern __shared__ unsigned int hist[];  // [(K+1)*(K+1)] when it fits, else unused
@@ -132,12 +158,7 @@ __global__ void __launch_bounds__(256) semantic_confusion_kernel(const float* __
         __syncthreads();
     }
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
-        float best = sem[p];
-        int bi = 0;
-        for (int k = 1; k < K; ++k) {
-            const float v = sem[(int64_t)k * npix + p];
-            if (v > best) { best = v; bi = k; }
-        }
+        const int bi = argmax_first(sem, K, npix, p);
         int g = gt[p];
         g = (g < 0 || g > K) ? K : g;
         const int cell = bi * (K + 1) + g;
@@ -149,6 +170,139 @@ __global__ void __launch_bounds__(256) semantic_confusion_kernel(const float* __
         for (int i = threadIdx.x; i < n; i += blockDim.x)
             if (hist[i]) atomicAdd(&conf[i], (unsigned long long)hist[i]);
     }
+}
+
+// ---- Boundary IoU counters ------------------------------------------------------------------------------------------------------------------
+// A byte label map is [H][Pd] dwords, Pd = ceil(W / 4), byte x & 3 of dword x >> 2; the bytes past W in a row's last dword are never
+// initialised: every dword read masks them (`tail`).  Two maps (prediction, ground truth) lie back to back and share a launch (blockIdx.y).
+struct LabelGrid {
+    int H, W, Pd;
+    unsigned tail;   // the valid bytes of a row's last dword
+};
+constexpr int kMinTaps = 4;
+struct MinTaps {
+    int n, off[kMinTaps];
+};
+
+__device__ __forceinline__ unsigned min_u8x4(unsigned a, unsigned b) {   // per byte, as two pairs of 16-bit lanes (v_pk_min_u16)
+    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+    const unsigned m = 0x00ff00ffu;
+    const u16x2 lo = __builtin_elementwise_min(__builtin_bit_cast(u16x2, a & m), __builtin_bit_cast(u16x2, b & m));
+    const u16x2 hi = __builtin_elementwise_min(__builtin_bit_cast(u16x2, (a >> 8) & m), __builtin_bit_cast(u16x2, (b >> 8) & m));
+    return __builtin_bit_cast(unsigned, lo) | (__builtin_bit_cast(unsigned, hi) << 8);
+}
+// dword xd of a row, 0 outside it
+__device__ __forceinline__ unsigned label_dword(const unsigned* __restrict__ row, int xd, const LabelGrid& G) {
+    if ((unsigned)xd >= (unsigned)G.Pd) return 0u;
+    const unsigned v = row[xd];
+    return xd == G.Pd - 1 ? v & G.tail : v;
+}
+// pixels 4 xd + dx .. 4 xd + dx + 3 of row y, 0 outside the picture
+__device__ __forceinline__ unsigned label_window(const unsigned* __restrict__ map, int y, int xd, int dx, const LabelGrid& G) {
+    if ((unsigned)y >= (unsigned)G.H) return 0u;
+    const unsigned* row = map + (int64_t)y * G.Pd;
+    const int q = xd + (dx >> 2), t = dx & 3;
+    const unsigned lo = label_dword(row, q, G), hi = t ? label_dword(row, q + 1, G) : 0u;
+    return __builtin_amdgcn_alignbyte(hi, lo, (unsigned)t);
+}
+
+__device__ __forceinline__ void store_label(unsigned* __restrict__ map, int64_t p, const LabelGrid& G, int v) {
+    const int y = (int)(p / G.W), x = (int)(p - (int64_t)y * G.W);
+    ((uint8_t*)map)[(int64_t)y * G.Pd * 4 + x] = (uint8_t)v;
+}
+
+// int32 labels -> one byte map, values outside [0, K] -> K
+__global__ void __launch_bounds__(256) pack_labels_kernel(const int* __restrict__ labels, int K, LabelGrid G, unsigned* __restrict__ map) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (int64_t)G.H * G.W) return;
+    const int g = labels[p];
+    store_label(map, p, G, (g < 0 || g > K) ? K : g);
+}
+
+// semantic_confusion_kernel that also keeps what it counted: maps[0] = argmax, maps[1] = ground truth (ignore -> K); conf may be null
+__global__ void __launch_bounds__(256) semantic_labels_kernel(const float* __restrict__ sem, const int* __restrict__ gt, int K, LabelGrid G,
+                                                             unsigned long long* __restrict__ conf, unsigned* __restrict__ maps) {
+    extern __shared__ unsigned int hist[];
+    const int n = (K + 1) * (K + 1);
+    const bool use_lds = conf && n <= 12288;
+    const int64_t npix = (int64_t)G.H * G.W;
+    if (use_lds) {
+        for (int i = threadIdx.x; i < n; i += blockDim.x) hist[i] = 0;
+        __syncthreads();
+    }
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+        const int bi = argmax_first(sem, K, npix, p);
+        int g = gt[p];
+        g = (g < 0 || g > K) ? K : g;
+        store_label(maps, p, G, bi);
+        store_label(maps + (int64_t)G.H * G.Pd, p, G, g);
+        const int cell = bi * (K + 1) + g;
+        if (use_lds) atomicAdd(&hist[cell], 1u);
+        else if (conf) atomicAdd(&conf[cell], 1ull);
+    }
+    if (use_lds) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < n; i += blockDim.x)
+            if (hist[i]) atomicAdd(&conf[i], (unsigned long long)hist[i]);
+    }
+}
+
+// dst = per-byte minimum of taps.n copies of src shifted by taps.off pixels along the rows (vertical == 0) or the columns; 0 outside
+__global__ void __launch_bounds__(256) min_taps_kernel(const unsigned* __restrict__ src, unsigned* __restrict__ dst, LabelGrid G, MinTaps taps,
+                                                      int vertical) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, per_map = (int64_t)G.H * G.Pd;
+    if (i >= per_map) return;
+    const int y = (int)(i / G.Pd), xd = (int)(i - (int64_t)y * G.Pd);
+    const unsigned* map = src + blockIdx.y * per_map;
+    unsigned v = ~0u;
+#pragma unroll
+    for (int k = 0; k < kMinTaps; ++k)
+        if (k < taps.n) v = min_u8x4(v, vertical ? label_window(map, y + taps.off[k], xd, 0, G) : label_window(map, y, xd, taps.off[k], G));
+    dst[blockIdx.y * per_map + i] = v;
+}
+
+// boundary int32 [H, W] = m - e of one map
+__global__ void __launch_bounds__(256) unpack_boundary_kernel(const unsigned* __restrict__ m, const unsigned* __restrict__ e, LabelGrid G,
+                                                             int* __restrict__ boundary) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (int64_t)G.H * G.W) return;
+    const int y = (int)(p / G.W), x = (int)(p - (int64_t)y * G.W);
+    const int64_t b = (int64_t)y * G.Pd * 4 + x;
+    boundary[p] = (int)((const uint8_t*)m)[b] - (int)((const uint8_t*)e)[b];
+}
+
+// b_conf[(m0 - e0) * (K + 1) + (m1 - e1)] += 1 per pixel; m, e = [2][H][Pd]
+__global__ void __launch_bounds__(256) boundary_confusion_kernel(const unsigned* __restrict__ m, const unsigned* __restrict__ e, int K, LabelGrid G,
+                                                                unsigned long long* __restrict__ b_conf) {
+    extern __shared__ unsigned int hist[];  // [(K+1)*(K+1)] when it fits, else unused
+    __shared__ unsigned int zeros;          // cell (0, 0): all pixels that lie on no boundary in either map
+    const int n = (K + 1) * (K + 1);
+    const bool use_lds = n <= 12288;
+    if (use_lds)
+        for (int i = threadIdx.x; i < n; i += blockDim.x) hist[i] = 0;
+    if (threadIdx.x == 0) zeros = 0;
+    __syncthreads();
+    const int64_t per_map = (int64_t)G.H * G.Pd;
+    unsigned own_zeros = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < per_map; i += (int64_t)gridDim.x * blockDim.x) {
+        const int xd = (int)(i % G.Pd);
+        const int nb = min(4, G.W - 4 * xd);
+        // m >= e in every byte, so the dword difference borrows nowhere below the (ignored) bytes past W
+        const unsigned bp = m[i] - e[i], bg = m[per_map + i] - e[per_map + i];
+        for (int j = 0; j < nb; ++j) {
+            const int cell = (int)((bp >> (8 * j)) & 255u) * (K + 1) + (int)((bg >> (8 * j)) & 255u);
+            if (cell == 0) ++own_zeros;
+            else if (cell >= n) continue;   // cannot happen for labels <= K; never write past the matrix
+            else if (use_lds) atomicAdd(&hist[cell], 1u);
+            else atomicAdd(&b_conf[cell], 1ull);
+        }
+    }
+    if (own_zeros) atomicAdd(&zeros, own_zeros);
+    __syncthreads();
+    if (threadIdx.x == 0 && zeros) atomicAdd(&b_conf[0], (unsigned long long)zeros);
+    if (use_lds)
+        for (int i = threadIdx.x; i < n; i += blockDim.x)
+            if (hist[i]) atomicAdd(&b_conf[i], (unsigned long long)hist[i]);
 }
 
 __global__ void __launch_bounds__(256) pair_histogram_kernel(const int* __restrict__ a, const int* __restrict__ b, int npix, int na, int nb,
@@ -179,6 +333,80 @@ static int upload_coeffs(odise_hip_ctx* ctx, const ResampleCoeffs& c, int** d_bo
     ODISE_CHECK_HIP(hipMalloc((void**)d_kk, c.kk.size() * sizeof(int)));
     ODISE_CHECK_HIP(hipMemcpyAsync(*d_bounds, c.bounds.data(), c.bounds.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     ODISE_CHECK_HIP(hipMemcpyAsync(*d_kk, c.kk.data(), c.kk.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    return ODISE_OK;
+}
+
+void boundary_release(odise_hip_ctx* ctx) {
+    if (ctx->boundary_buf) (void)hipFree(ctx->boundary_buf);
+    ctx->boundary_buf = nullptr;
+    ctx->boundary_bytes = 0;
+}
+
+static int boundary_radius(int H, int W) {   // _mask_to_boundary: max(1, int(round(0.02 * sqrt(h^2 + w^2)))), Python's round (half to even)
+    const double r = nearbyint(0.02 * sqrt((double)H * H + (double)W * W));
+    return r < 1.0 ? 1 : (int)r;
+}
+
+struct BoundaryMaps {
+    LabelGrid G;
+    int64_t per_map;   // dwords
+    unsigned *m, *e;   // [nmaps] label maps and, after erode_maps, their erosions
+    unsigned* tmp;
+};
+// the context's scratch for the byte maps of one picture (grown on demand; earlier calls on the stream may still read the old buffer)
+static int boundary_maps(odise_hip_ctx* ctx, int H, int W, int nmaps, BoundaryMaps* b) {
+    b->G.H = H; b->G.W = W; b->G.Pd = (int)ceil_div(W, 4);
+    b->G.tail = (W & 3) ? (1u << (8 * (W & 3))) - 1u : ~0u;
+    b->per_map = (int64_t)H * b->G.Pd;
+    const size_t each = (size_t)round_up(nmaps * b->per_map * 4, 256), need = 3 * each;
+    if (ctx->boundary_bytes < need) {
+        ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+        boundary_release(ctx);
+        if (hipMalloc(&ctx->boundary_buf, need) != hipSuccess) {
+            ctx->boundary_buf = nullptr;
+            set_error("boundary: out of device memory (%zu bytes of scratch)", need);
+            return ODISE_ERR_NOMEM;
+        }
+        ctx->boundary_bytes = need;
+    }
+    char* p = (char*)ctx->boundary_buf;
+    b->m = (unsigned*)p;
+    b->e = (unsigned*)(p + each);
+    b->tmp = (unsigned*)(p + 2 * each);
+    return ODISE_OK;
+}
+
+// b->e = the (2r+1)^2 minimum of b->m with zeros outside the picture
+static int erode_maps(odise_hip_ctx* ctx, BoundaryMaps* b, int nmaps, int r) {
+    const LabelGrid& G = b->G;
+    if (2 * (int64_t)r + 1 > std::min(G.H, G.W)) {   // every window leaves the picture
+        ODISE_CHECK_HIP(hipMemsetAsync(b->e, 0, (size_t)nmaps * b->per_map * 4, ctx->stream));
+        return ODISE_OK;
+    }
+    const int w = 2 * r + 1;
+    const dim3 grid((unsigned)ceil_div(b->per_map, 256), (unsigned)nmaps);
+    const unsigned* cur = b->m;
+    for (int vertical = 0; vertical < 2; ++vertical) {
+        int s = 1;   // cur holds the minima of the windows [x, x + s)
+        for (bool last = false; !last; s *= kMinTaps) {
+            MinTaps taps;
+            last = ceil_div(w, s) <= kMinTaps;
+            taps.n = last ? (int)ceil_div(w, s) : kMinTaps;
+            for (int k = 0; k < kMinTaps; ++k) taps.off[k] = last ? (k < taps.n - 1 ? k * s - r : r + 1 - s) : k * s;
+            unsigned* dst = cur == b->e ? b->tmp : b->e;
+            hipLaunchKernelGGL(min_taps_kernel, grid, dim3(256), 0, ctx->stream, cur, dst, G, taps, vertical);
+            ODISE_CHECK_HIP(hipGetLastError());
+            cur = dst;
+        }
+    }
+    if (cur != b->e) std::swap(b->e, b->tmp);
+    return ODISE_OK;
+}
+
+static int boundary_args(const char* what, int K, int H, int W) {
+    ODISE_REQUIRE(K >= 1 && H >= 1 && W >= 1 && (int64_t)H * W <= INT32_MAX, "%s: bad dims (K %d, %dx%d)", what, K, H, W);
+    ODISE_REQUIRE(K <= 254, "%s: K = %d; SemSegEvaluator switches Boundary IoU off for 255 classes and more (labels and the ignore label share a byte)",
+                  what, K);
     return ODISE_OK;
 }
 
@@ -251,6 +479,45 @@ extern "C" int odise_hip_semantic_confusion(odise_hip_ctx* ctx, const float* sem
     const size_t lds = n <= 12288 ? (size_t)n * sizeof(unsigned int) : 0;
     const int blocks = (int)std::min<int64_t>(ceil_div(npix, 256), 4 * ctx->cu_count);
     hipLaunchKernelGGL(semantic_confusion_kernel, dim3(blocks), dim3(256), lds, ctx->stream, sem_seg, gt, K, npix, (unsigned long long*)conf);
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}
+
+extern "C" int odise_hip_boundary_radius(int H, int W) {
+    ODISE_REQUIRE(H >= 1 && W >= 1, "boundary_radius: bad size %dx%d", H, W);
+    return boundary_radius(H, W);
+}
+
+extern "C" int odise_hip_label_boundary(odise_hip_ctx* ctx, const int* labels, int K, int H, int W, int radius, int* boundary) {
+    ODISE_TRY(boundary_args("label_boundary", K, H, W));
+    ODISE_REQUIRE(ctx && labels && boundary, "label_boundary: null argument");
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    BoundaryMaps b;
+    ODISE_TRY(boundary_maps(ctx, H, W, 1, &b));
+    const dim3 per_pixel((unsigned)ceil_div((int64_t)H * W, 256));
+    hipLaunchKernelGGL(pack_labels_kernel, per_pixel, dim3(256), 0, ctx->stream, labels, K, b.G, b.m);
+    ODISE_CHECK_HIP(hipGetLastError());
+    ODISE_TRY(erode_maps(ctx, &b, 1, radius > 0 ? radius : boundary_radius(H, W)));
+    hipLaunchKernelGGL(unpack_boundary_kernel, per_pixel, dim3(256), 0, ctx->stream, b.m, b.e, b.G, boundary);
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}
+
+extern "C" int odise_hip_semantic_boundary_confusion(odise_hip_ctx* ctx, const float* sem_seg, const int* gt, int K, int H, int W, int radius,
+                                                     int64_t* conf, int64_t* b_conf) {
+    ODISE_TRY(boundary_args("semantic_boundary_confusion", K, H, W));
+    ODISE_REQUIRE(ctx && sem_seg && gt && b_conf, "semantic_boundary_confusion: null argument");
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    BoundaryMaps b;
+    ODISE_TRY(boundary_maps(ctx, H, W, 2, &b));
+    const int n = (K + 1) * (K + 1);
+    const size_t lds = n <= 12288 ? (size_t)n * sizeof(unsigned int) : 0;
+    int blocks = (int)std::min<int64_t>(ceil_div((int64_t)H * W, 256), 4 * ctx->cu_count);
+    hipLaunchKernelGGL(semantic_labels_kernel, dim3(blocks), dim3(256), conf ? lds : 0, ctx->stream, sem_seg, gt, K, b.G, (unsigned long long*)conf, b.m);
+    ODISE_CHECK_HIP(hipGetLastError());
+    ODISE_TRY(erode_maps(ctx, &b, 2, radius > 0 ? radius : boundary_radius(H, W)));
+    blocks = (int)std::min<int64_t>(ceil_div(b.per_map, 256), 4 * ctx->cu_count);
+    hipLaunchKernelGGL(boundary_confusion_kernel, dim3(blocks), dim3(256), lds, ctx->stream, b.m, b.e, K, b.G, (unsigned long long*)b_conf);
     ODISE_CHECK_HIP(hipGetLastError());
     return ODISE_OK;
 }

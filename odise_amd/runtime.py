@@ -393,6 +393,35 @@ class Context:
         check(self.lib.odise_hip_semantic_confusion(self.h, _p(sem_seg), _p(gt), K, npix, _p(conf)), "semantic_confusion")
         return conf
 
+    # Boundary IoU counters of SemSegEvaluator (include/odise_hip.h odise_hip_boundary_radius ..; host restatement: odise_amd/sem_boundary.py)
+    def boundary_radius(self, H: int, W: int) -> int:
+        """The evaluator's erosion count for an H x W picture: max(1, int(round(0.02 * sqrt(H*H + W*W))))."""
+        r = self.lib.odise_hip_boundary_radius(int(H), int(W))
+        check(min(r, 0), "boundary_radius")
+        return r
+
+    def label_boundary(self, labels: DeviceArray, K: int, radius: int = 0, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """labels int32 [H,W] (values outside [0,K] count as K) -> int32 [H,W] _mask_to_boundary(labels); radius <= 0: the formula."""
+        H, W = labels.shape
+        assert labels.dtype == np.int32
+        if out is None:
+            out = self.empty((H, W), np.int32)
+        assert out.dtype == np.int32 and out.shape == (H, W)
+        check(self.lib.odise_hip_label_boundary(self.h, _p(labels), int(K), H, W, int(radius), _p(out)), "label_boundary")
+        return out
+
+    def semantic_boundary_confusion(self, sem_seg: DeviceArray, gt: DeviceArray, conf: Optional[DeviceArray] = None,
+                                    b_conf: Optional[DeviceArray] = None, radius: int = 0):
+        """One SemSegEvaluator.process step: sem_seg f32 [K,H,W], gt int32 [H,W] -> (conf, b_conf), int64 [(K+1),(K+1)] each, accumulated.
+        conf None: only the boundary matrix is counted (None is returned in its place); b_conf None: a fresh zeroed matrix."""
+        K, H, W = sem_seg.shape
+        assert gt.shape == (H, W) and gt.dtype == np.int32 and sem_seg.dtype == np.float32
+        if b_conf is None:
+            b_conf = self.zeros((K + 1, K + 1), np.int64)
+        check(self.lib.odise_hip_semantic_boundary_confusion(self.h, _p(sem_seg), _p(gt), K, H, W, int(radius), _p(conf), _p(b_conf)),
+              "semantic_boundary_confusion")
+        return conf, b_conf
+
     def pair_histogram(self, a: DeviceArray, b: DeviceArray, na: int, nb: int, hist: Optional[DeviceArray] = None) -> DeviceArray:
         npix = int(np.prod(a.shape))
         if hist is None:
