@@ -362,7 +362,10 @@ int odise_hip_infer_prefetch(odise_hip_ctx* ctx, const odise_infer_desc* next);
 /* ---- input resize and evaluator reductions of the eval loop --------------------------------------------
  * Replaces, on device buffers: detectron2 T.ResizeShortestEdge -> PIL.Image.resize(BILINEAR) of the DatasetMapper
  * (configs/common/data/pano_open_d2_eval.py:74-107) and the per-pixel parts of the evaluators configured there
- * (odise/evaluation/d2_evaluator.py:49 COCOPanopticEvaluator -> panopticapi pq_compute_single_core, :63 SemSegEvaluator.process). */
+ * (odise/evaluation/d2_evaluator.py:49 COCOPanopticEvaluator -> panopticapi pq_compute_single_core, :63 SemSegEvaluator.process).
+ * Per picture each evaluator is one asynchronous call that adds into a small accumulator: odise_hip_semantic_confusion /
+ * odise_hip_semantic_boundary_confusion (SemSegEvaluator), odise_hip_panoptic_quality (COCOPanopticEvaluator, straight from the panoptic
+ * record), odise_hip_instance_rle (the segm evaluators).  odise_hip_pair_histogram is the bare per-pixel part of the panoptic one. */
 /* src uint8 [H,W,C] -> dst uint8 [OH,OW,C], bit-identical to Pillow's 8-bit bilinear resampler (horizontal pass, then vertical) */
 int odise_hip_resize_bilinear_u8(odise_hip_ctx* ctx, const void* src, int H, int W, int C, void* dst, int OH, int OW);
 /* dst fp32 [C,H,W] = scale * src uint8 [H,W,C] */
@@ -388,6 +391,46 @@ int odise_hip_semantic_boundary_confusion(odise_hip_ctx* ctx, const float* sem_s
                                           int64_t* conf, int64_t* b_conf);
 /* hist int32 [na*nb] += count of (a[p], b[p]) pairs with 0 <= a < na, 0 <= b < nb (segment-index co-occurrence of PQ matching) */
 int odise_hip_pair_histogram(odise_hip_ctx* ctx, const int* a, const int* b, int npix, int na, int nb, int* hist);
+/* One picture of COCOPanopticEvaluator's metric (d2_evaluator.py:49 -> panopticapi pq_compute_single_core) without the PNG round trip:
+ * the prediction is the panoptic record of odise_post_desc as it lies in HBM, the ground truth the annotation PNG as decoded plus its
+ * segments_info table.  `stats` is ADDED to and never cleared: the caller zeroes it before the first picture, sums it across ranks once
+ * (odise_amd.distributed.sum_pq_stats) and turns it into PQ / SQ / RQ on the host (odise_amd/panoptic_quality.py, which also restates
+ * the rules below in numpy).  Ids are 24-bit values (the PNG format), 0 = VOID on both sides; in a table the first row of an id counts.
+ *   pred area of a segment = its pixels in pred_ids; inter[g][p] = pixels with gt id g and pred id p; gt ids that are not in gt_segments
+ *   take part in nothing except as "not VOID".
+ *   matching   pairs (g, p) with both ids in their tables, inter > 0, iscrowd[g] == 0 and equal categories:
+ *              union = area_pred[p] + area_gt[g] - inter[g][p] - inter[VOID][p]  (area_gt from the table, i.e. the annotation JSON);
+ *              iou = inter / union as a double division of the two integers (a union <= 0 matches nothing); iou > 0.5: tp[cat] += 1,
+ *              iou[cat] += iou, g and p are matched.  The pairs are added one by one in ascending (g, p) order onto the value already in
+ *              `stats`, so the sums of a stream of pictures are bit-identical to the single-process evaluator and from run to run.
+ *   fn         unmatched gt rows in table order: a crowd row sets crowd_of[cat] (the last one wins) and counts nothing, every other row
+ *              - with or without pixels in the map - counts fn[cat] += 1.
+ *   fp         unmatched pred rows: ign = inter[VOID][p] (+ inter[crowd_of[cat_p]][p]); ign / area_pred[p] > 0.5 skips the row, otherwise
+ *              fp[cat_p] += 1.  Both thresholds are strict.
+ * flags (OR-ed in; a picture that raises one adds nothing to stats; the reference raises KeyError for the first two):
+ *   1 = a non-zero id of pred_ids is missing from pred_segments, 2 = a pred_segments row has no pixel, 4 = a predicted category outside
+ *   [0, num_categories).
+ * ODISE_ERR_ARG and nothing written: a null pointer, H * W > 2^29 - 1, n_gt > 254, a ground-truth category outside [0, num_categories), iscrowd not 0 / 1.
+ * Asynchronous on the context's stream.  Scratch belongs to the context: it is allocated once, at the first call, at the caps (a matrix of
+ * 256 x (ODISE_MAX_SEGMENTS + 2) int32, the device table, 8 pinned table slots; about 140 KB), never resized, and released with the
+ * context.  The pixel pass sizes its LDS histogram to the real n_gt but, since n is read on the device, to ODISE_MAX_SEGMENTS on the
+ * predicted side (at most 48 KiB); tables beyond that count in the matrix directly. */
+typedef struct { double iou; int64_t tp, fp, fn; } odise_pq_stat;      /* one per category, 32 bytes */
+typedef struct {
+    int H, W;
+    const int32_t* pred_ids;      /* device [H*W] panoptic ids: the first H*W ints of the panoptic record */
+    const int32_t* pred_segments; /* device: n | n rows (id, isthing, category_id) - the tail of the same record; n is read on the device,
+                                     n <= ODISE_MAX_SEGMENTS */
+    const void* gt;               /* device: gt_layout 0 = uint8 [H,W,3] RGB as Pillow decodes the annotation PNG (id = R + 256 G + 65536 B,
+                                     converted on the device), 1 = int32 [H*W] ids */
+    int gt_layout;
+    const int32_t* gt_segments;   /* HOST [n_gt][4] rows (id, category_id, iscrowd, area); copied before the call returns */
+    int n_gt;                     /* 0 .. 254 */
+    int num_categories;           /* both tables carry categories 0 .. num_categories - 1 (the caller maps dataset ids) */
+    odise_pq_stat* stats;         /* device [num_categories] */
+    int32_t* flags;               /* device [1] */
+} odise_pq_desc;
+int odise_hip_panoptic_quality(odise_hip_ctx* ctx, const odise_pq_desc* d);
 /* COCO compressed RLE (pycocotools mask.encode of the Fortran-ordered mask, counts as text) of n masks: the per-mask part of the segm
  * evaluators (COCOEvaluator / InstanceSegEvaluator(tasks=("segm",)) -> detectron2 instances_to_coco_json), byte-identical to
  * `mask.encode(np.asfortranarray(m.astype(np.uint8)))["counts"].decode("utf-8")` (maskApi.c rleEncode + rleToString).

@@ -18,6 +18,8 @@ int odise_hip_sizeof_conv_desc(void);
 int odise_hip_sizeof_attn_desc(void);
 int odise_hip_sizeof_post_desc(void);
 int odise_hip_sizeof_infer_desc(void);
+int odise_hip_sizeof_pq_desc(void);
+int odise_hip_sizeof_pq_stat(void);
 
 /* odise_hip_gemm / odise_hip_conv2d with the tile shape and the split-K factor forced instead of chosen by the cost model
  * (tile ids: gemm.hip kTileBM / kTileBN; -1 / 0 = automatic) */

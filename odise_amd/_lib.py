@@ -84,6 +84,17 @@ class InferDesc(C.Structure):
                 ("post", PostDesc)]
 
 
+class PqStat(C.Structure):
+    """odise_pq_stat (include/odise_hip.h): one per category."""
+    _fields_ = [("iou", C.c_double), ("tp", c_int64), ("fp", c_int64), ("fn", c_int64)]
+
+
+class PqDesc(C.Structure):
+    """odise_pq_desc (include/odise_hip.h)."""
+    _fields_ = [("H", c_int), ("W", c_int), ("pred_ids", c_void_p), ("pred_segments", c_void_p), ("gt", c_void_p), ("gt_layout", c_int),
+                ("gt_segments", c_void_p), ("n_gt", c_int), ("num_categories", c_int), ("stats", c_void_p), ("flags", c_void_p)]
+
+
 MAX_SEGMENTS = 100          # ODISE_MAX_SEGMENTS
 COMM_ID_BYTES = 128         # ODISE_COMM_ID_BYTES
 

@@ -67,6 +67,7 @@ extern "C" int odise_hip_destroy(odise_hip_ctx* ctx) {
     odise::jpeg_release(ctx);
     odise::rle_release(ctx);
     odise::boundary_release(ctx);
+    odise::pq_release(ctx);
     odise::comm_release(ctx);
     odise::probe_release(ctx);
     odise::launch_log_release(ctx);
@@ -352,3 +353,5 @@ extern "C" int odise_hip_sizeof_conv_desc(void) { return (int)sizeof(odise_conv_
 extern "C" int odise_hip_sizeof_attn_desc(void) { return (int)sizeof(odise_attn_desc); }
 extern "C" int odise_hip_sizeof_post_desc(void) { return (int)sizeof(odise_post_desc); }
 extern "C" int odise_hip_sizeof_infer_desc(void) { return (int)sizeof(odise_infer_desc); }
+extern "C" int odise_hip_sizeof_pq_desc(void) { return (int)sizeof(odise_pq_desc); }
+extern "C" int odise_hip_sizeof_pq_stat(void) { return (int)sizeof(odise_pq_stat); }

@@ -124,6 +124,7 @@ struct odise_hip_ctx {
     // eval_ops.hip: growable device scratch of odise_hip_label_boundary / odise_hip_semantic_boundary_confusion (byte label maps, their erosions)
     void* boundary_buf = nullptr;
     size_t boundary_bytes = 0;
+    void* pq = nullptr;              // odise::PqScratch* (pq.hip): the pair-count matrix and the ground-truth table staging of odise_hip_panoptic_quality
 };
 
 namespace odise {
@@ -182,5 +183,6 @@ int gemm_ln(odise_hip_ctx* ctx, const odise_gemm_desc* d, const LnEpi& ln);   //
 void jpeg_release(odise_hip_ctx* ctx);
 void rle_release(odise_hip_ctx* ctx);
 void boundary_release(odise_hip_ctx* ctx);
+void pq_release(odise_hip_ctx* ctx);
 void comm_release(odise_hip_ctx* ctx);
 }

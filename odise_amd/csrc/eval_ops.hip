@@ -9,7 +9,9 @@
 //   odise_hip_semantic_confusion   detectron2 SemSegEvaluator.process (odise/evaluation/d2_evaluator.py:63): argmax over classes,
 //                                  (K+1)^2 confusion counts (rows = prediction, ignore label mapped to K by the caller).
 //   odise_hip_pair_histogram       the per-pixel part of panopticapi pq_compute_single_core (COCOPanopticEvaluator,
-//                                  d2_evaluator.py:49): co-occurrence counts of (ground-truth segment, predicted segment) indices.
+//                                  d2_evaluator.py:49): co-occurrence counts of (ground-truth segment, predicted segment) indices of
+//                                  pre-indexed maps.  The evaluator's whole per-picture step - ids to slots, counts, matching, the add
+//                                  into (iou, tp, fp, fn) - is odise_hip_panoptic_quality in pq.hip.
 //   odise_hip_label_boundary / odise_hip_semantic_boundary_confusion
 //                                  the second per-pixel job of SemSegEvaluator.process (K < 255, OpenCV importable): prediction and ground
 //                                  truth both go through _mask_to_boundary - a 3x3 grey-scale erosion behind a zero ring, repeated

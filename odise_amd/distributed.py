@@ -95,6 +95,30 @@ def sum_confusion(conf: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def sum_pq_stats(stats, flags=None):
+    """Panoptic evaluation's exchange step: every rank accumulates (iou, tp, fp, fn) per category over its image shard
+    (odise_hip_panoptic_quality); one all-gather of the [C] records, added in rank order, replaces the pickled gather of per-image
+    predictions behind COCOPanopticEvaluator.evaluate.  `stats`: panoptic_quality.PQStats.  The counts are exact; the iou sums are
+    ((rank 0 + rank 1) + rank 2) ..., the same on every rank and from run to run for a given world size.
+    With `flags` (this rank's malformed-prediction bits) the same all-gather carries them and the result is (total, the OR over all
+    ranks): a rank that saw nothing wrong must not report a total that silently lacks another rank's picture."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return stats if flags is None else (stats, int(flags))
+    from .panoptic_quality import STAT_DTYPE, PQStats
+    rec = stats.to_records().view(np.uint8).reshape(-1)                                 # C x 32 bytes, bit for bit
+    tail = np.array([0 if flags is None else int(flags)], np.int64).view(np.uint8)
+    local = torch.from_numpy(np.concatenate([rec, tail]))
+    parts = [torch.empty_like(local) for _ in range(dist.get_world_size())]
+    dist.all_gather(parts, local)
+    total, seen = None, 0
+    for p in parts:
+        p = p.numpy()
+        part = PQStats.from_records(p[:rec.size].view(STAT_DTYPE))
+        total = part if total is None else total + part
+        seen |= int(p[rec.size:].view(np.int64)[0])
+    return total if flags is None else (total, seen)
+
+
 class Exchange:
     """The library-owned RCCL exchange (include/odise_hip.h: odise_hip_comm_*).  `broadcast(id_bytes_or_None) -> id_bytes` must deliver
     rank 0's unique id to every rank (e.g. `gloo_broadcast`); a world of one rank needs none and takes the same code path."""

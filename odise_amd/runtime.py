@@ -429,6 +429,48 @@ class Context:
         check(self.lib.odise_hip_pair_histogram(self.h, _p(a), _p(b), npix, int(na), int(nb), _p(hist)), "pair_histogram")
         return hist
 
+    # ---- panoptic quality statistics (include/odise_hip.h odise_hip_panoptic_quality; host restatement: odise_amd/panoptic_quality.py) ----
+    def panoptic_quality(self, pred_ids: DeviceArray, pred_segments: DeviceArray, gt: DeviceArray, gt_segments, num_categories: int,
+                         stats: Optional[DeviceArray] = None, flags: Optional[DeviceArray] = None):
+        """One picture of COCOPanopticEvaluator.process + pq_compute_single_core, enqueued: pred_ids int32 [H,W] panoptic ids and
+        pred_segments int32 [n | n x (id, isthing, category)] (the two parts of a panoptic record), gt uint8 [H,W,3] (the annotation PNG
+        as decoded) or int32 [H,W] ids, gt_segments HOST rows (id, category, iscrowd, area) -> (stats, flags): `stats` [num_categories]
+        records (panoptic_quality.STAT_DTYPE) added to, `flags` int32 [1] OR-ed into; fresh zeroed ones when none are given."""
+        from ._lib import PqDesc
+        from .panoptic_quality import STAT_DTYPE
+        if gt.dtype == np.uint8:
+            assert len(gt.shape) == 3 and gt.shape[2] == 3, gt.shape
+            layout = 0
+        else:
+            assert gt.dtype == np.int32 and len(gt.shape) == 2, (gt.dtype, gt.shape)
+            layout = 1
+        H, W = gt.shape[:2]
+        assert pred_ids.dtype == np.int32 and int(np.prod(pred_ids.shape)) == H * W, (pred_ids.dtype, pred_ids.shape, (H, W))
+        assert pred_segments.dtype == np.int32
+        table = np.ascontiguousarray(np.asarray(gt_segments, np.int64).reshape(-1, 4), np.int32)
+        if stats is None:
+            stats = self.zeros((int(num_categories),), STAT_DTYPE)
+        if flags is None:
+            flags = self.zeros((1,), np.int32)
+        assert stats.dtype == STAT_DTYPE and stats.shape == (int(num_categories),) and flags.dtype == np.int32
+        d = PqDesc()
+        d.H, d.W, d.pred_ids, d.pred_segments, d.gt, d.gt_layout = H, W, pred_ids.ptr, pred_segments.ptr, gt.ptr, layout
+        d.gt_segments, d.n_gt, d.num_categories = table.ctypes.data, table.shape[0], int(num_categories)
+        d.stats, d.flags = stats.ptr, flags.ptr
+        check(self.lib.odise_hip_panoptic_quality(self.h, C.byref(d)), "panoptic_quality")
+        return stats, flags
+
+    def panoptic_quality_record(self, record: DeviceArray, hw, gt: DeviceArray, gt_segments, num_categories: int,
+                                stats: Optional[DeviceArray] = None, flags: Optional[DeviceArray] = None):
+        """`panoptic_quality` of a panoptic record int32 [h*w | 1 | 3*MAX_SEGMENTS] as odise_hip_infer / postprocess_batch leave it on the
+        device (also a row of the exchange buffer): the map and the table are two offsets into it, nothing travels to the host."""
+        from ._lib import MAX_SEGMENTS
+        h, w = int(hw[0]), int(hw[1])
+        assert record.dtype == np.int32 and int(np.prod(record.shape)) >= h * w + 1 + 3 * MAX_SEGMENTS, (record.shape, hw)
+        flat = record.view((h * w + 1 + 3 * MAX_SEGMENTS,), np.int32)
+        return self.panoptic_quality(flat.view((h, w), np.int32), flat.view((1 + 3 * MAX_SEGMENTS,), np.int32, h * w * 4), gt, gt_segments,
+                                     num_categories, stats, flags)
+
     # ---- COCO RLE of instance masks (segm evaluation; include/odise_hip.h odise_hip_rle_encode / odise_hip_instance_rle) ----------------
     # Default string capacity per mask.  A string has one to seven characters per run and most runs of a real mask take two or three, so
     # 8 KiB holds a mask with ~3000 runs - a blob spanning ~1500 columns; a selection that needs more costs one more pass (the retry).
