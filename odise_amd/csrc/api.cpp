@@ -19,6 +19,28 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 void models_destroy(odise_hip_ctx* ctx);  // unet.cpp
+
+void scratch_release(DeviceScratch& buf) {
+    if (buf.ptr) (void)(buf.pinned ? hipHostFree(buf.ptr) : hipFree(buf.ptr));   // whether or not the free succeeds, the pointer is gone
+    buf.ptr = nullptr;
+    buf.cap = 0;
+}
+
+int scratch_reserve(DeviceScratch& buf, size_t need, int headroom_div, const Drain& drain, const char* owner) {
+    if (buf.cap >= need) return ODISE_OK;
+    if (drain.device) ODISE_CHECK_HIP(hipDeviceSynchronize());   // a failing drain leaves the buffer as it was
+    for (hipStream_t s : drain.streams)
+        if (s) ODISE_CHECK_HIP(hipStreamSynchronize(s));
+    scratch_release(buf);
+    const size_t want = need + (headroom_div ? need / headroom_div : 0);
+    if ((buf.pinned ? hipHostMalloc(&buf.ptr, want, hipHostMallocDefault) : hipMalloc(&buf.ptr, want)) != hipSuccess) {
+        buf.ptr = nullptr;
+        set_error("%s: out of %s memory (%zu bytes of scratch)", owner, buf.pinned ? "pinned host" : "device", want);
+        return ODISE_ERR_NOMEM;
+    }
+    buf.cap = want;
+    return ODISE_OK;
+}
 }  // namespace odise
 
 using namespace odise;
@@ -65,8 +87,8 @@ extern "C" int odise_hip_destroy(odise_hip_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     models_destroy(ctx);
     odise::jpeg_release(ctx);
-    odise::rle_release(ctx);
-    odise::boundary_release(ctx);
+    odise::scratch_release(ctx->rle);
+    odise::scratch_release(ctx->boundary);
     odise::pq_release(ctx);
     odise::comm_release(ctx);
     odise::probe_release(ctx);

@@ -53,29 +53,13 @@ struct ClassifyModel {
     };
     std::vector<Bank> banks;
     uint64_t bank_clock = 0;
-    void* post_buf = nullptr;
-    size_t post_cap = 0;
-    void* in_buf = nullptr;
-    size_t in_cap = 0;
+    DeviceScratch post, in;   // grown behind a whole-device drain: the second lane reads these buffers too (postprocess_batch)
     // postprocess_batch: image b's pixel pass writes set b % kPostSets of (S, ids); ev_set[i] = the decision chain that read set i is done
     static constexpr int kPostSets = 4;
     hipEvent_t ev_set[kPostSets] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 static int g_sem_tile = -1;   // tools hook (odise_hip_sem_tile): force the tile of the semantic GEMM for A/B runs; -1 = the rule in postprocess_batch
-
-static int scratch_reserve(odise_hip_ctx* ctx, void** buf, size_t* cap, size_t bytes) {
-    if (*cap >= bytes) return ODISE_OK;
-    (void)ctx;
-    ODISE_CHECK_HIP(hipDeviceSynchronize());   // the second lane reads these buffers too (postprocess_batch)
-    if (*buf) ODISE_CHECK_HIP(hipFree(*buf));
-    *buf = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 8;
-    ODISE_CHECK_HIP(hipMalloc(buf, want));
-    *cap = want;
-    return ODISE_OK;
-}
 
 // releases the arena mark on every exit path
 struct ArenaScope {
@@ -90,8 +74,8 @@ void classify_destroy(ModelStore* ms) {
         for (auto& bk : ms->classify->banks) {
             (void)hipFree(bk.T1); (void)hipFree(bk.T2); (void)hipFree(bk.seg); (void)hipFree(bk.ovl);
         }
-        if (ms->classify->post_buf) (void)hipFree(ms->classify->post_buf);
-        if (ms->classify->in_buf) (void)hipFree(ms->classify->in_buf);
+        scratch_release(ms->classify->post);
+        scratch_release(ms->classify->in);
         for (hipEvent_t& ev : ms->classify->ev_set)
             if (ev) { (void)hipEventDestroy(ev); ev = nullptr; }
         free_allocs(ms->classify->owned);
@@ -352,8 +336,8 @@ extern "C" int odise_hip_postprocess_pixels(odise_hip_ctx* ctx, int b, const flo
     if (need_S && !S) {   // outputs much larger than the network input: the arena (sized by the input) is too small for S
         ClassifyModel* cm = ms->classify;
         if (!cm) { set_error("postprocess_pixels: call odise_hip_classify_build first"); return ODISE_ERR_STATE; }
-        ODISE_TRY(scratch_reserve(ctx, &cm->post_buf, &cm->post_cap, (size_t)npix * g.Qpad * 2));
-        S = (f16*)cm->post_buf;
+        ODISE_TRY(scratch_reserve(cm->post, (size_t)npix * g.Qpad * 2, 8, drain_device(), "postprocess_pixels"));
+        S = (f16*)cm->post.ptr;
     }
     if (counts) ODISE_CHECK_HIP(hipMemsetAsync(counts, 0, 3 * (size_t)ho.Q * sizeof(int), ctx->stream));
     int* cnt = counts;
@@ -423,9 +407,9 @@ extern "C" int odise_hip_maskclip_embed(odise_hip_ctx* ctx, const float* image, 
         // this path allocates ABOVE whatever an earlier head call left in the arena (its outputs stay valid for a later classify /
         // post-processing call), so the requirement counts from the current mark; if the arena has to grow it is reallocated, and the
         // head outputs that pointed into the old one are invalidated instead of dangling
-        const char* base0 = ms->arena.base;
+        const void* base0 = ms->arena.mem.ptr;
         ODISE_TRY(ensure_arena(ctx, ms, ms->arena.off + ((size_t)1 << 30) + (size_t)B * (T + Q) * 1024 * 2 * 64));
-        if (ms->arena.base != base0) maskgen_invalidate_outputs(ms);
+        if (ms->arena.mem.ptr != base0) maskgen_invalidate_outputs(ms);
     }
     Exec ex{ctx, ms};
     ArenaScope scope(ms->arena);
@@ -488,8 +472,8 @@ extern "C" int odise_hip_postprocess_batch(odise_hip_ctx* ctx, const odise_post_
     const int nsets = std::min(B, (int)ClassifyModel::kPostSets);
     const size_t ids_set = ((size_t)max_pix * 4 + 255) & ~(size_t)255, S_set = ((size_t)max_pix * Qpad * 2 + 255) & ~(size_t)255;
     const size_t o_ids = take(ids_set * nsets), o_S = take(S_set * nsets), o_partial = take(partial_set * nsets);
-    ODISE_TRY(scratch_reserve(ctx, &c->post_buf, &c->post_cap, off));
-    char* base = (char*)c->post_buf;
+    ODISE_TRY(scratch_reserve(c->post, off, 8, drain_device(), "postprocess_batch"));
+    char* base = (char*)c->post.ptr;
     float* kscore = (float*)(base + o_kscore);
     int* label = (int*)(base + o_label);
     int* map = (int*)(base + o_map);
@@ -629,8 +613,8 @@ extern "C" int odise_hip_infer(odise_hip_ctx* ctx, const odise_infer_desc* d) {
     ODISE_TRY(odise_hip_maskgen_info(ctx, &Q, nullptr, nullptr));
     const size_t n_pad = (size_t)B * 3 * Hp * Wp, n_img = (size_t)B * 3 * H * W, n_cls = (size_t)B * Q * (c->K + 1);
     const bool same = Hp == H && Wp == W;
-    ODISE_TRY(scratch_reserve(ctx, &c->in_buf, &c->in_cap, (n_pad + (same ? 0 : n_img) + n_cls) * 4 + 1024));
-    float* padded = (float*)c->in_buf;
+    ODISE_TRY(scratch_reserve(c->in, (n_pad + (same ? 0 : n_img) + n_cls) * 4 + 1024, 8, drain_device(), "infer"));
+    float* padded = (float*)c->in.ptr;
     float* img01 = same ? padded : padded + n_pad;
     float* mask_cls = (same ? padded + n_pad : img01 + n_img);
     for (int b = 0; b < B; ++b) {

@@ -73,6 +73,24 @@ __device__ __forceinline__ float act_apply(float v, int act) {
     }
 }
 
+// A buffer that grows on demand and is never shrunk: device memory, or pinned host memory when `pinned` (set once by its owner).
+struct DeviceScratch {
+    void* ptr = nullptr;
+    size_t cap = 0;
+    bool pinned = false;
+};
+// What scratch_reserve waits for before it frees the old buffer: everything that may still read it.
+struct Drain {
+    bool device = false;                           // the whole device
+    hipStream_t streams[2] = {nullptr, nullptr};   // else these streams (null = none; no stream of the library is the null stream)
+};
+static inline Drain drain_device() { Drain d; d.device = true; return d; }
+static inline Drain drain_streams(hipStream_t a = nullptr, hipStream_t b = nullptr) { Drain d; d.streams[0] = a; d.streams[1] = b; return d; }
+// Returns at once when `buf` holds `need` bytes.  Otherwise: drain, free, allocate need + need / headroom_div (0 = exactly need).  When the
+// allocation fails buf is {nullptr, 0}, the error names `owner` and the byte count, and the code is ODISE_ERR_NOMEM.
+int scratch_reserve(DeviceScratch& buf, size_t need, int headroom_div, const Drain& drain, const char* owner);
+void scratch_release(DeviceScratch& buf);   // the caller knows that nothing reads it any more
+
 }  // namespace odise
 
 // The context: one device, one stream, a split-K workspace, an activation arena and the weight store.
@@ -89,10 +107,7 @@ struct odise_hip_ctx {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     void* models = nullptr;  // odise::ModelStore* (weights + unet), see unet.cpp
     // jpeg.hip: pinned host staging for entropy-decoded coefficients, device coefficients + planes, upload-complete event
-    void* jpeg_host = nullptr;
-    size_t jpeg_host_bytes = 0;
-    void* jpeg_dev = nullptr;
-    size_t jpeg_dev_bytes = 0;
+    odise::DeviceScratch jpeg_host{nullptr, 0, true}, jpeg_dev;
     hipEvent_t jpeg_ev = nullptr;
     // second lane (engine.h Lane2): the feature extractor runs its two independent branches - CLIP conditioning -> UNet, and VAE encoder ->
     // VAE decoder - on two streams with separate split-K workspaces, joined by events
@@ -118,12 +133,8 @@ struct odise_hip_ctx {
     void* probe = nullptr;           // odise::LaunchProbe* (api.cpp): HIP events around the launches of one kernel shape (odise_hip_probe_*)
     void* stages = nullptr;          // odise::StageLog* while odise_hip_stage_timeline is on: (name, HIP event on the current stream, host clock) at stage boundaries
     void* launch_log = nullptr;      // std::vector<odise::LaunchRec>* while odise_hip_launch_log is on: (shape, tile, split-K) of every GEMM / conv launch
-    // rle.hip: growable device scratch of odise_hip_rle_encode / odise_hip_instance_rle (bit-packed masks, per-thread scan state, string lengths)
-    void* rle_buf = nullptr;
-    size_t rle_bytes = 0;
-    // eval_ops.hip: growable device scratch of odise_hip_label_boundary / odise_hip_semantic_boundary_confusion (byte label maps, their erosions)
-    void* boundary_buf = nullptr;
-    size_t boundary_bytes = 0;
+    odise::DeviceScratch rle;        // rle.hip: odise_hip_rle_encode / odise_hip_instance_rle (bit-packed masks, per-thread scan state, string lengths)
+    odise::DeviceScratch boundary;   // eval_ops.hip: odise_hip_label_boundary / odise_hip_semantic_boundary_confusion (byte label maps, their erosions)
     void* pq = nullptr;              // odise::PqScratch* (pq.hip): the pair-count matrix and the ground-truth table staging of odise_hip_panoptic_quality
 };
 
@@ -181,8 +192,6 @@ int launch_conv3_c8(odise_hip_ctx* ctx, const odise_conv_desc* d, float* gn_stat
 int gemm_forced(odise_hip_ctx* ctx, const odise_gemm_desc* d, int force_tile, int force_split, const LnEpi* ln = nullptr);   // force_tile < 0: the cost model's choice
 int gemm_ln(odise_hip_ctx* ctx, const odise_gemm_desc* d, const LnEpi& ln);   // 256x256 ping-pong tile, math-first epilogue
 void jpeg_release(odise_hip_ctx* ctx);
-void rle_release(odise_hip_ctx* ctx);
-void boundary_release(odise_hip_ctx* ctx);
 void pq_release(odise_hip_ctx* ctx);
 void comm_release(odise_hip_ctx* ctx);
 }

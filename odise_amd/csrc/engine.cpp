@@ -32,11 +32,7 @@ void models_destroy(odise_hip_ctx* ctx) {
     maskgen_destroy(ms);
     classify_destroy(ms);
     for (void* p : ms->dev_allocs) (void)hipFree(p);
-    if (ms->arena.base) (void)hipFree(ms->arena.base);
-    if (ms->arena2.base) (void)hipFree(ms->arena2.base);
-    if (ms->mclip.buf) (void)hipFree(ms->mclip.buf);
-    for (Arena& a : ms->pf.arena)
-        if (a.base) (void)hipFree(a.base);
+    for (DeviceScratch* b : {&ms->arena.mem, &ms->arena2.mem, &ms->pf.arena[0].mem, &ms->pf.arena[1].mem, &ms->mclip.buf}) scratch_release(*b);
     delete ms;
     ctx->models = nullptr;
 }
@@ -76,16 +72,7 @@ int ensure_prefetch_lane(odise_hip_ctx* ctx, ModelStore* ms, int slot, size_t ar
         }
         ctx->stream3 = st; ctx->ws3 = ws; ctx->ev_pf_go = go; ctx->ev_pf_done = done;
     }
-    Arena& a = ms->pf.arena[slot];
-    if (a.cap < arena_bytes) {
-        ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream3));
-        ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        if (a.base) ODISE_CHECK_HIP(hipFree(a.base));
-        a = Arena();
-        ODISE_CHECK_HIP(hipMalloc((void**)&a.base, arena_bytes));
-        a.cap = arena_bytes;
-    }
-    return ODISE_OK;
+    return ms->pf.arena[slot].reserve(arena_bytes, drain_streams(ctx->stream3, ctx->stream), "prefetch arena");
 }
 
 int ensure_lane2(odise_hip_ctx* ctx, ModelStore* ms, size_t arena_bytes) {
@@ -106,15 +93,7 @@ int ensure_lane2(odise_hip_ctx* ctx, ModelStore* ms, size_t arena_bytes) {
         ODISE_CHECK_HIP(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
         ODISE_CHECK_HIP(hipEventCreateWithFlags(&ctx->ev_mclip, hipEventDisableTiming));
     }
-    if (ms->arena2.cap < arena_bytes) {
-        ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream2));
-        if (ms->arena2.base) ODISE_CHECK_HIP(hipFree(ms->arena2.base));
-        ms->arena2 = Arena();
-        ODISE_CHECK_HIP(hipMalloc((void**)&ms->arena2.base, arena_bytes));
-        ms->arena2.cap = arena_bytes;
-    }
-    return ODISE_OK;
+    return ms->arena2.reserve(arena_bytes, drain_streams(ctx->stream, ctx->stream2), "second-lane arena");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -207,7 +186,7 @@ int Packer::norm(const std::string& key, NormW& out) {
 // ---------------------------------------------------------------------------------------------------------------
 void* Exec::alloc_bytes(size_t bytes) {
     void* p = ms->arena.alloc(bytes);
-    if (!p) set_error("arena exhausted: need %zu more bytes (capacity %zu, used %zu)", bytes, ms->arena.cap, ms->arena.off);
+    if (!p) set_error("arena exhausted: need %zu more bytes (capacity %zu, used %zu)", bytes, ms->arena.mem.cap, ms->arena.off);
     return p;
 }
 

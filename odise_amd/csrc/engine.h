@@ -26,12 +26,19 @@ struct HostTensor {
 // working set of a block stays small (L2 / Infinity-Cache resident) and pointers are identical call to call
 // (required for hipGraph replay).
 struct Arena {
-    char* base = nullptr;
-    size_t cap = 0, off = 0, peak = 0;
+    DeviceScratch mem;
+    size_t off = 0, peak = 0;
+    // exactly `bytes`, behind `drain`; a new slab starts empty
+    int reserve(size_t bytes, const Drain& drain, const char* owner) {
+        if (mem.cap >= bytes) return ODISE_OK;
+        ODISE_TRY(scratch_reserve(mem, bytes, 0, drain, owner));
+        off = peak = 0;
+        return ODISE_OK;
+    }
     void* alloc(size_t bytes) {
         off = (off + 255) & ~(size_t)255;
-        if (off + bytes > cap) return nullptr;
-        void* p = base + off;
+        if (off + bytes > mem.cap) return nullptr;
+        void* p = (char*)mem.ptr + off;
         off += bytes;
         if (off > peak) peak = off;
         return p;
@@ -109,8 +116,7 @@ struct Prefetch {
 // vt + l * vt_stride of a matrix with ldvt columns: the rows / columns of the other images (dead once the block's attention has run) lie where the
 // next blocks' picture rows / columns go and are overwritten by them - one buffer of layers x pictures + 1 x others instead of layers x everything.
 struct ClipKV {
-    void* buf = nullptr;     // device, grows
-    size_t cap = 0;
+    DeviceScratch buf;       // device, grows
     f16* qk = nullptr;       // block l, picture b, token t: qk + l * qk_stride + (b * TP + t) * 2 * width  (q | k halves)
     f16* vt = nullptr;       // block l, channel c, picture b, token t: vt + l * vt_stride + c * ldvt + b * TP + t
     f16* cls = nullptr;      // [width] the class-token row after ln_pre: what every mask token starts from (clip.py:268-270)

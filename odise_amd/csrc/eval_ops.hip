@@ -25,15 +25,15 @@
 //                                            per pixel grows with log4(r), the passes run in global memory (the maps are 1-7 MB and stay in
 //                                            the L2 / MALL), so r may exceed any tile; 2r+1 > min(H, W) erodes everything and skips them.
 //                                    count   b = m - e per byte (m >= e: a plain dword subtraction), cell (0, 0) - every pixel away from a
-//                                            boundary - in a register, the rest through the per-block LDS histogram.
-// All of it is HBM-bound integer / byte work: coalesced row-major sweeps, per-block LDS histograms flushed with integer atomics
-// (deterministic: integer addition commutes).
+//                                            boundary - in a register, the rest through the per-block histogram.
+// All of it is HBM-bound integer / byte work: coalesced row-major sweeps, per-block histograms (lds_hist.h).
 #include <math.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "common.h"
+#include "lds_hist.h"
 
 namespace odise {
 
@@ -149,31 +149,6 @@ __device__ __forceinline__ int argmax_first(const float* __restrict__ sem, int K
     return bi;
 }
 
-// per pixel: argmax, count (pred, gt)
-__global__ void __launch_bounds__(256) semantic_confusion_kernel(const float* __restrict__ sem, const int* __restrict__ gt, int K, int npix,
-                                                                unsigned long long* __restrict__ conf) {
-    extern __shared__ unsigned int hist[];  // [(K+1)*(K+1)] when it fits, else unused
-    const int n = (K + 1) * (K + 1);
-    const bool use_lds = n <= 12288;
-    if (use_lds) {
-        for (int i = threadIdx.x; i < n; i += blockDim.x) hist[i] = 0;
-        __syncthreads();
-    }
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
-        const int bi = argmax_first(sem, K, npix, p);
-        int g = gt[p];
-        g = (g < 0 || g > K) ? K : g;
-        const int cell = bi * (K + 1) + g;
-        if (use_lds) atomicAdd(&hist[cell], 1u);
-        else atomicAdd(&conf[cell], 1ull);
-    }
-    if (use_lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += blockDim.x)
-            if (hist[i]) atomicAdd(&conf[i], (unsigned long long)hist[i]);
-    }
-}
-
 // ---- Boundary IoU counters ------------------------------------------------------------------------------------------------------------------
 // A byte label map is [H][Pd] dwords, Pd = ceil(W / 4), byte x & 3 of dword x >> 2; the bytes past W in a row's last dword are never
 // initialised: every dword read masks them (`tail`).  Two maps (prediction, ground truth) lie back to back and share a launch (blockIdx.y).
@@ -221,32 +196,29 @@ __global__ void __launch_bounds__(256) pack_labels_kernel(const int* __restrict_
     store_label(map, p, G, (g < 0 || g > K) ? K : g);
 }
 
-// semantic_confusion_kernel that also keeps what it counted: maps[0] = argmax, maps[1] = ground truth (ignore -> K); conf may be null
-__global__ void __launch_bounds__(256) semantic_labels_kernel(const float* __restrict__ sem, const int* __restrict__ gt, int K, LabelGrid G,
-                                                             unsigned long long* __restrict__ conf, unsigned* __restrict__ maps) {
-    extern __shared__ unsigned int hist[];
+// per pixel: argmax, count (pred, gt) in conf.  kKeepMaps: also keep what was counted, maps[0] = argmax, maps[1] = ground truth
+// (ignore -> K), and conf may be null
+template <bool kKeepMaps>
+__global__ void __launch_bounds__(256) semantic_confusion_kernel(const float* __restrict__ sem, const int* __restrict__ gt, int K, int npix_, LabelGrid G,
+                                                                unsigned long long* __restrict__ conf, unsigned* __restrict__ maps) {
+    const int64_t npix = kKeepMaps ? (int64_t)G.H * G.W : npix_;   // without maps there is no grid
     const int n = (K + 1) * (K + 1);
-    const bool use_lds = conf && n <= 12288;
-    const int64_t npix = (int64_t)G.H * G.W;
-    if (use_lds) {
-        for (int i = threadIdx.x; i < n; i += blockDim.x) hist[i] = 0;
-        __syncthreads();
-    }
+    const bool count = !kKeepMaps || conf;
+    const LdsHist<unsigned long long> H(conf, n, count && n <= kLdsHistCells);
+    H.clear();
+    H.sync();
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
         const int bi = argmax_first(sem, K, npix, p);
         int g = gt[p];
         g = (g < 0 || g > K) ? K : g;
-        store_label(maps, p, G, bi);
-        store_label(maps + (int64_t)G.H * G.Pd, p, G, g);
-        const int cell = bi * (K + 1) + g;
-        if (use_lds) atomicAdd(&hist[cell], 1u);
-        else if (conf) atomicAdd(&conf[cell], 1ull);
+        if (kKeepMaps) {
+            store_label(maps, p, G, bi);
+            store_label(maps + (int64_t)G.H * G.Pd, p, G, g);
+        }
+        if (count) H.add(bi * (K + 1) + g, 1u);
     }
-    if (use_lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += blockDim.x)
-            if (hist[i]) atomicAdd(&conf[i], (unsigned long long)hist[i]);
-    }
+    H.sync();
+    H.flush();
 }
 
 // dst = per-byte minimum of taps.n copies of src shifted by taps.off pixels along the rows (vertical == 0) or the columns; 0 outside
@@ -276,12 +248,10 @@ __global__ void __launch_bounds__(256) unpack_boundary_kernel(const unsigned* __
 // b_conf[(m0 - e0) * (K + 1) + (m1 - e1)] += 1 per pixel; m, e = [2][H][Pd]
 __global__ void __launch_bounds__(256) boundary_confusion_kernel(const unsigned* __restrict__ m, const unsigned* __restrict__ e, int K, LabelGrid G,
                                                                 unsigned long long* __restrict__ b_conf) {
-    extern __shared__ unsigned int hist[];  // [(K+1)*(K+1)] when it fits, else unused
     __shared__ unsigned int zeros;          // cell (0, 0): all pixels that lie on no boundary in either map
     const int n = (K + 1) * (K + 1);
-    const bool use_lds = n <= 12288;
-    if (use_lds)
-        for (int i = threadIdx.x; i < n; i += blockDim.x) hist[i] = 0;
+    const LdsHist<unsigned long long> H(b_conf, n, n <= kLdsHistCells);
+    H.clear();
     if (threadIdx.x == 0) zeros = 0;
     __syncthreads();
     const int64_t per_map = (int64_t)G.H * G.Pd;
@@ -295,39 +265,27 @@ __global__ void __launch_bounds__(256) boundary_confusion_kernel(const unsigned*
             const int cell = (int)((bp >> (8 * j)) & 255u) * (K + 1) + (int)((bg >> (8 * j)) & 255u);
             if (cell == 0) ++own_zeros;
             else if (cell >= n) continue;   // cannot happen for labels <= K; never write past the matrix
-            else if (use_lds) atomicAdd(&hist[cell], 1u);
-            else atomicAdd(&b_conf[cell], 1ull);
+            else H.add(cell, 1u);
         }
     }
     if (own_zeros) atomicAdd(&zeros, own_zeros);
     __syncthreads();
     if (threadIdx.x == 0 && zeros) atomicAdd(&b_conf[0], (unsigned long long)zeros);
-    if (use_lds)
-        for (int i = threadIdx.x; i < n; i += blockDim.x)
-            if (hist[i]) atomicAdd(&b_conf[i], (unsigned long long)hist[i]);
+    H.flush();
 }
 
 __global__ void __launch_bounds__(256) pair_histogram_kernel(const int* __restrict__ a, const int* __restrict__ b, int npix, int na, int nb,
                                                             unsigned int* __restrict__ out) {
-    extern __shared__ unsigned int hist[];
     const int n = na * nb;
-    const bool use_lds = n <= 12288;
-    if (use_lds) {
-        for (int i = threadIdx.x; i < n; i += blockDim.x) hist[i] = 0;
-        __syncthreads();
-    }
+    const LdsHist<unsigned> H(out, n, n <= kLdsHistCells);
+    H.clear();
+    H.sync();
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
         const int ia = a[p], ib = b[p];
-        if ((unsigned)ia < (unsigned)na && (unsigned)ib < (unsigned)nb) {
-            if (use_lds) atomicAdd(&hist[ia * nb + ib], 1u);
-            else atomicAdd(&out[ia * nb + ib], 1u);
-        }
+        if ((unsigned)ia < (unsigned)na && (unsigned)ib < (unsigned)nb) H.add(ia * nb + ib, 1u);
     }
-    if (use_lds) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += blockDim.x)
-            if (hist[i]) atomicAdd(&out[i], hist[i]);
-    }
+    H.sync();
+    H.flush();
 }
 
 static int upload_coeffs(odise_hip_ctx* ctx, const ResampleCoeffs& c, int** d_bounds, int** d_kk) {
@@ -336,12 +294,6 @@ static int upload_coeffs(odise_hip_ctx* ctx, const ResampleCoeffs& c, int** d_bo
     ODISE_CHECK_HIP(hipMemcpyAsync(*d_bounds, c.bounds.data(), c.bounds.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     ODISE_CHECK_HIP(hipMemcpyAsync(*d_kk, c.kk.data(), c.kk.size() * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
     return ODISE_OK;
-}
-
-void boundary_release(odise_hip_ctx* ctx) {
-    if (ctx->boundary_buf) (void)hipFree(ctx->boundary_buf);
-    ctx->boundary_buf = nullptr;
-    ctx->boundary_bytes = 0;
 }
 
 static int boundary_radius(int H, int W) {   // _mask_to_boundary: max(1, int(round(0.02 * sqrt(h^2 + w^2)))), Python's round (half to even)
@@ -361,17 +313,8 @@ static int boundary_maps(odise_hip_ctx* ctx, int H, int W, int nmaps, BoundaryMa
     b->G.tail = (W & 3) ? (1u << (8 * (W & 3))) - 1u : ~0u;
     b->per_map = (int64_t)H * b->G.Pd;
     const size_t each = (size_t)round_up(nmaps * b->per_map * 4, 256), need = 3 * each;
-    if (ctx->boundary_bytes < need) {
-        ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        boundary_release(ctx);
-        if (hipMalloc(&ctx->boundary_buf, need) != hipSuccess) {
-            ctx->boundary_buf = nullptr;
-            set_error("boundary: out of device memory (%zu bytes of scratch)", need);
-            return ODISE_ERR_NOMEM;
-        }
-        ctx->boundary_bytes = need;
-    }
-    char* p = (char*)ctx->boundary_buf;
+    ODISE_TRY(scratch_reserve(ctx->boundary, need, 0, drain_streams(ctx->stream), "boundary"));
+    char* p = (char*)ctx->boundary.ptr;
     b->m = (unsigned*)p;
     b->e = (unsigned*)(p + each);
     b->tmp = (unsigned*)(p + 2 * each);
@@ -477,10 +420,9 @@ extern "C" int odise_hip_u8_hwc_to_f32_chw_padded(odise_hip_ctx* ctx, const void
 
 extern "C" int odise_hip_semantic_confusion(odise_hip_ctx* ctx, const float* sem_seg, const int* gt, int K, int npix, int64_t* conf) {
     ODISE_REQUIRE(ctx && sem_seg && gt && conf && K >= 1 && npix > 0, "semantic_confusion: bad argument");
-    const int n = (K + 1) * (K + 1);
-    const size_t lds = n <= 12288 ? (size_t)n * sizeof(unsigned int) : 0;
     const int blocks = (int)std::min<int64_t>(ceil_div(npix, 256), 4 * ctx->cu_count);
-    hipLaunchKernelGGL(semantic_confusion_kernel, dim3(blocks), dim3(256), lds, ctx->stream, sem_seg, gt, K, npix, (unsigned long long*)conf);
+    hipLaunchKernelGGL(semantic_confusion_kernel<false>, dim3(blocks), dim3(256), lds_hist_bytes((K + 1) * (K + 1)), ctx->stream, sem_seg, gt, K, npix,
+                       LabelGrid{}, (unsigned long long*)conf, (unsigned*)nullptr);
     ODISE_CHECK_HIP(hipGetLastError());
     return ODISE_OK;
 }
@@ -512,10 +454,10 @@ extern "C" int odise_hip_semantic_boundary_confusion(odise_hip_ctx* ctx, const f
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
     BoundaryMaps b;
     ODISE_TRY(boundary_maps(ctx, H, W, 2, &b));
-    const int n = (K + 1) * (K + 1);
-    const size_t lds = n <= 12288 ? (size_t)n * sizeof(unsigned int) : 0;
+    const size_t lds = lds_hist_bytes((K + 1) * (K + 1));
     int blocks = (int)std::min<int64_t>(ceil_div((int64_t)H * W, 256), 4 * ctx->cu_count);
-    hipLaunchKernelGGL(semantic_labels_kernel, dim3(blocks), dim3(256), conf ? lds : 0, ctx->stream, sem_seg, gt, K, b.G, (unsigned long long*)conf, b.m);
+    hipLaunchKernelGGL(semantic_confusion_kernel<true>, dim3(blocks), dim3(256), conf ? lds : 0, ctx->stream, sem_seg, gt, K, H * W, b.G,
+                       (unsigned long long*)conf, b.m);
     ODISE_CHECK_HIP(hipGetLastError());
     ODISE_TRY(erode_maps(ctx, &b, 2, radius > 0 ? radius : boundary_radius(H, W)));
     blocks = (int)std::min<int64_t>(ceil_div(b.per_map, 256), 4 * ctx->cu_count);
@@ -526,10 +468,8 @@ extern "C" int odise_hip_semantic_boundary_confusion(odise_hip_ctx* ctx, const f
 
 extern "C" int odise_hip_pair_histogram(odise_hip_ctx* ctx, const int* a, const int* b, int npix, int na, int nb, int* hist) {
     ODISE_REQUIRE(ctx && a && b && hist && npix > 0 && na > 0 && nb > 0, "pair_histogram: bad argument");
-    const int n = na * nb;
-    const size_t lds = n <= 12288 ? (size_t)n * sizeof(unsigned int) : 0;
     const int blocks = (int)std::min<int64_t>(ceil_div(npix, 256), 4 * ctx->cu_count);
-    hipLaunchKernelGGL(pair_histogram_kernel, dim3(blocks), dim3(256), lds, ctx->stream, a, b, npix, na, nb, (unsigned int*)hist);
+    hipLaunchKernelGGL(pair_histogram_kernel, dim3(blocks), dim3(256), lds_hist_bytes(na * nb), ctx->stream, a, b, npix, na, nb, (unsigned int*)hist);
     ODISE_CHECK_HIP(hipGetLastError());
     return ODISE_OK;
 }

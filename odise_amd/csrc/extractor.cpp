@@ -607,16 +607,9 @@ static int maskclip_kv_layout(odise_hip_ctx* ctx, ModelStore* ms, int B, int oth
     const size_t Mp = (size_t)B * TP, Mo = (size_t)others * TP;
     const size_t rows = Mp * L + Mo;   // block l writes rows / columns [l * Mp, l * Mp + Mp + Mo): the tail is overwritten by the blocks after it
     const size_t need = (rows * 2 * Wd + (size_t)Wd * rows + Wd) * sizeof(f16) + 256;
-    if (kv.cap < need) {
-        // nothing enqueued may still read the old buffer (the mask-token pass of the previous call runs on the main stream, a tower on the second)
-        ODISE_CHECK_HIP(hipDeviceSynchronize());
-        if (kv.buf) ODISE_CHECK_HIP(hipFree(kv.buf));
-        kv.buf = nullptr;
-        kv.cap = 0;
-        ODISE_CHECK_HIP(hipMalloc(&kv.buf, need + need / 8));
-        kv.cap = need + need / 8;
-    }
-    kv.qk = (f16*)kv.buf;
+    // nothing enqueued may still read the old buffer (the mask-token pass of the previous call runs on the main stream, a tower on the second)
+    ODISE_TRY(scratch_reserve(kv.buf, need, 8, drain_device(), "maskclip key / value store"));
+    kv.qk = (f16*)kv.buf.ptr;
     kv.vt = kv.qk + rows * 2 * Wd;
     kv.cls = kv.vt + (size_t)Wd * rows;
     kv.B = B; kv.TP = TP; kv.layers = L; kv.width = Wd;
@@ -651,7 +644,7 @@ int maskclip_mask_pass(Exec& ex, int Q, const uint8_t* mask, int64_t ldm, int64_
     ExtractorModel* e = ex.ms->extractor;
     const ClipKV& kv = ex.ms->mclip;
     const int B = kv.B, TP = kv.TP, Wd = e->clip_width, T = e->clip_tokens, heads = e->clip_heads, D = Wd / heads;
-    ODISE_REQUIRE(kv.buf && kv.layers == (int)e->clip_blocks.size() && kv.width == Wd, "maskclip: the image-token pass has not run for this tower");
+    ODISE_REQUIRE(kv.buf.ptr && kv.layers == (int)e->clip_blocks.size() && kv.width == Wd, "maskclip: the image-token pass has not run for this tower");
     const int64_t M = (int64_t)B * Q;
     const size_t mk = ex.ms->arena.mark();
     f16* x = (f16*)ex.alloc_bytes((size_t)M * Wd * 2);
@@ -855,7 +848,7 @@ int maskclip_planned_pass(odise_hip_ctx* ctx, ModelStore* ms) {
     const ExtractorModel* e = ms->extractor;
     const size_t rows = (size_t)kv.plan_B * round_up(e->clip_tokens, 8);
     const size_t need = rows * e->clip_width * 2 * 9 + (size_t)kv.plan_B * e->clip_image * e->clip_image * 16 * 2 + ((size_t)16 << 20);
-    if (ms->arena2.cap - ms->arena2.off < need) return ODISE_OK;
+    if (ms->arena2.mem.cap - ms->arena2.off < need) return ODISE_OK;
     Lane2 lane(ctx, ms);
     Exec ex{ctx, ms};
     ODISE_TRY(maskclip_image_pass(ex, kv.plan_image, kv.plan_B, kv.plan_H, kv.plan_W));

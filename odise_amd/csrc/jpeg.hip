@@ -737,11 +737,9 @@ static void fill_info(const JpegHeader& H, odise_jpeg_info* info) {
 }
 
 void jpeg_release(odise_hip_ctx* ctx) {
-    if (ctx->jpeg_host) (void)hipHostFree(ctx->jpeg_host);
-    if (ctx->jpeg_dev) (void)hipFree(ctx->jpeg_dev);
+    scratch_release(ctx->jpeg_host);
+    scratch_release(ctx->jpeg_dev);
     if (ctx->jpeg_ev) (void)hipEventDestroy(ctx->jpeg_ev);
-    ctx->jpeg_host = ctx->jpeg_dev = nullptr;
-    ctx->jpeg_host_bytes = ctx->jpeg_dev_bytes = 0;
     ctx->jpeg_ev = nullptr;
 }
 
@@ -817,29 +815,14 @@ static int jpeg_device_stage(odise_hip_ctx* ctx, const JpegDims& D, Fill&& fill,
     P.blocks = nblk;
     if (!ctx->jpeg_ev) ODISE_CHECK_HIP(hipEventCreateWithFlags(&ctx->jpeg_ev, hipEventDisableTiming));
     else ODISE_CHECK_HIP(hipEventSynchronize(ctx->jpeg_ev));
-    if (ctx->jpeg_host_bytes < coef_bytes) {
-        if (ctx->jpeg_host) (void)hipHostFree(ctx->jpeg_host);
-        ctx->jpeg_host = nullptr;
-        ctx->jpeg_host_bytes = 0;
-        const size_t want = coef_bytes + coef_bytes / 4;
-        if (hipHostMalloc(&ctx->jpeg_host, want, hipHostMallocDefault) != hipSuccess) { set_error("jpeg_decode: cannot pin %zu bytes", want); return ODISE_ERR_NOMEM; }
-        ctx->jpeg_host_bytes = want;
-    }
-    if (ctx->jpeg_dev_bytes < (size_t)poff) {
-        ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->jpeg_dev) (void)hipFree(ctx->jpeg_dev);
-        ctx->jpeg_dev = nullptr;
-        ctx->jpeg_dev_bytes = 0;
-        const size_t want = (size_t)poff + (size_t)poff / 4;
-        if (hipMalloc(&ctx->jpeg_dev, want) != hipSuccess) { set_error("jpeg_decode: out of device memory (%zu bytes)", want); return ODISE_ERR_NOMEM; }
-        ctx->jpeg_dev_bytes = want;
-    }
-    int16_t* hc = (int16_t*)ctx->jpeg_host;
+    ODISE_TRY(scratch_reserve(ctx->jpeg_host, coef_bytes, 4, drain_streams(), "jpeg_decode"));   // jpeg_ev above: the last upload from it is done
+    ODISE_TRY(scratch_reserve(ctx->jpeg_dev, (size_t)poff, 4, drain_streams(ctx->stream), "jpeg_decode"));
+    int16_t* hc = (int16_t*)ctx->jpeg_host.ptr;
     const int frc = fill(hc);
     if (frc != ODISE_OK) return frc;
-    ODISE_CHECK_HIP(hipMemcpyAsync(ctx->jpeg_dev, hc, coef_bytes, hipMemcpyHostToDevice, ctx->stream));
+    ODISE_CHECK_HIP(hipMemcpyAsync(ctx->jpeg_dev.ptr, hc, coef_bytes, hipMemcpyHostToDevice, ctx->stream));
     ODISE_CHECK_HIP(hipEventRecord(ctx->jpeg_ev, ctx->stream));
-    uint8_t* dev = (uint8_t*)ctx->jpeg_dev;
+    uint8_t* dev = (uint8_t*)ctx->jpeg_dev.ptr;
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)ceil_div(nblk, 32)), dim3(256), 0, ctx->stream, (const int16_t*)dev, dev, P);
     ODISE_CHECK_HIP(hipGetLastError());
     G.W = D.width;

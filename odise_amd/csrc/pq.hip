@@ -8,9 +8,8 @@
 //   pq_pixel_kernel   one sweep over the pixels.  Four pixels per lane and step: the prediction as one 16-byte load, the RGB ground truth as
 //                     three dwords.  Ids become table SLOTS (0 = VOID, 1 + row, last = "not in the table") through the two id tables held
 //                     in LDS; a lane keeps its last (id -> slot) of either side, so on smooth maps the translation is a compare.  Pairs
-//                     are counted in an LDS histogram of (n_gt + 2) x (n + 2) cells; a lane counts a run of equal pairs in a register and
-//                     touches the LDS when the pair changes.  Non-zero cells are flushed with integer atomics into the context's matrix
-//                     (deterministic: integer addition commutes).  Tables too large for the LDS histogram count in the matrix directly.
+//                     are counted in the per-block histogram (lds_hist.h) of (n_gt + 2) x (n + 2) cells over the context's matrix; a lane
+//                     counts a run of equal pairs in a register and touches the histogram when the pair changes.
 //   pq_match_kernel   one block over that matrix: areas (column sums), the flags, the candidate pairs and their IoU in parallel, then the
 //                     ORDERED part - the IoU sum of a category is added pair by pair in ascending (gt id, pred id) order by one thread
 //                     per category, starting from the value already in `stats`, which makes a stream of pictures bit-identical to the
@@ -18,6 +17,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "lds_hist.h"
 
 namespace odise {
 
@@ -25,7 +25,6 @@ constexpr int kPqMaxGt = 254;                               // ground-truth rows
 constexpr int kPqGtSlots = kPqMaxGt + 2;                    // + VOID + "not in the table"
 constexpr int kPqPredSlots = ODISE_MAX_SEGMENTS + 2;
 constexpr int kPqMatrixCells = kPqGtSlots * kPqPredSlots;   // the context's matrix holds the caps; a picture uses (n_gt + 2) x (n + 2) of it
-constexpr int kPqLdsCells = 12288;                          // LDS histogram up to 48 KiB, as the other evaluator histograms
 constexpr int kPqRing = 8;                                  // pinned staging slots of the ground-truth table (calls in flight before the host waits)
 constexpr int kPqMatchThreads = 512;
 
@@ -53,21 +52,20 @@ struct PqLane {
 };
 
 template <bool LDS>
-__device__ __forceinline__ void pq_flush_run(PqLane& L, unsigned* hist, int* matrix) {
+__device__ __forceinline__ void pq_flush_run(PqLane& L, const LdsHist<int>& H) {
     if (L.run) {
-        if (LDS) atomicAdd(&hist[L.cell], (unsigned)L.run);
-        else atomicAdd(&matrix[L.cell], L.run);
+        if (LDS) H.add_lds(L.cell, (unsigned)L.run);
+        else H.add_global(L.cell, (unsigned)L.run);
     }
 }
 
 template <bool LDS>
-__device__ __forceinline__ void pq_count(PqLane& L, int gid, int pid, const int* gt_ids, int n_gt, const int* pred_ids_tab, int n, unsigned* hist,
-                                         int* matrix) {
+__device__ __forceinline__ void pq_count(PqLane& L, int gid, int pid, const int* gt_ids, int n_gt, const int* pred_ids_tab, int n, const LdsHist<int>& H) {
     if (gid != L.last_gid) { L.last_gid = gid; L.last_gslot = pq_find_slot(gt_ids, 1, n_gt, gid); }
     if (pid != L.last_pid) { L.last_pid = pid; L.last_pslot = pq_find_slot(pred_ids_tab, 1, n, pid); }
     const int cell = L.last_gslot * (n + 2) + L.last_pslot;   // < (n_gt + 2) * (n + 2) <= kPqMatrixCells
     if (cell == L.cell) { ++L.run; return; }
-    pq_flush_run<LDS>(L, hist, matrix);
+    pq_flush_run<LDS>(L, H);
     L.cell = cell;
     L.run = 1;
 }
@@ -77,16 +75,14 @@ __device__ __forceinline__ void pq_count(PqLane& L, int gid, int pid, const int*
 __global__ void __launch_bounds__(256) pq_pixel_kernel(const int* __restrict__ pred, const int* __restrict__ pred_segments, const void* __restrict__ gt,
                                                       int gt_layout, const int* __restrict__ gt_table, int n_gt, int npix, int vec, int lds_cells,
                                                       int* __restrict__ matrix) {
-    extern __shared__ unsigned int pq_hist[];   // [(n_gt + 2) * (n + 2)] when it fits, else unused
     __shared__ int gt_ids[kPqMaxGt];
     __shared__ int pred_tab[ODISE_MAX_SEGMENTS];
     const int n = pq_clamp_n(pred_segments[0]);
     const int cells = (n_gt + 2) * (n + 2);
-    const bool use_lds = cells <= lds_cells;
+    const LdsHist<int> H(matrix, cells, cells <= lds_cells);
     for (int i = threadIdx.x; i < n_gt; i += blockDim.x) gt_ids[i] = gt_table[4 * i];
     for (int i = threadIdx.x; i < n; i += blockDim.x) pred_tab[i] = pred_segments[1 + 3 * i];
-    if (use_lds)
-        for (int i = threadIdx.x; i < cells; i += blockDim.x) pq_hist[i] = 0;
+    H.clear();
     __syncthreads();
 
     PqLane L;
@@ -111,16 +107,16 @@ __global__ void __launch_bounds__(256) pq_pixel_kernel(const int* __restrict__ p
                 const int4 g = ((const int4*)gt)[q];
                 g0 = g.x; g1 = g.y; g2 = g.z; g3 = g.w;
             }
-            if (use_lds) {
-                pq_count<true>(L, g0, p.x, gt_ids, n_gt, pred_tab, n, pq_hist, matrix);
-                pq_count<true>(L, g1, p.y, gt_ids, n_gt, pred_tab, n, pq_hist, matrix);
-                pq_count<true>(L, g2, p.z, gt_ids, n_gt, pred_tab, n, pq_hist, matrix);
-                pq_count<true>(L, g3, p.w, gt_ids, n_gt, pred_tab, n, pq_hist, matrix);
+            if (H.lds) {
+                pq_count<true>(L, g0, p.x, gt_ids, n_gt, pred_tab, n, H);
+                pq_count<true>(L, g1, p.y, gt_ids, n_gt, pred_tab, n, H);
+                pq_count<true>(L, g2, p.z, gt_ids, n_gt, pred_tab, n, H);
+                pq_count<true>(L, g3, p.w, gt_ids, n_gt, pred_tab, n, H);
             } else {
-                pq_count<false>(L, g0, p.x, gt_ids, n_gt, pred_tab, n, pq_hist, matrix);
-                pq_count<false>(L, g1, p.y, gt_ids, n_gt, pred_tab, n, pq_hist, matrix);
-                pq_count<false>(L, g2, p.z, gt_ids, n_gt, pred_tab, n, pq_hist, matrix);
-                pq_count<false>(L, g3, p.w, gt_ids, n_gt, pred_tab, n, pq_hist, matrix);
+                pq_count<false>(L, g0, p.x, gt_ids, n_gt, pred_tab, n, H);
+                pq_count<false>(L, g1, p.y, gt_ids, n_gt, pred_tab, n, H);
+                pq_count<false>(L, g2, p.z, gt_ids, n_gt, pred_tab, n, H);
+                pq_count<false>(L, g3, p.w, gt_ids, n_gt, pred_tab, n, H);
             }
         }
     }
@@ -130,17 +126,13 @@ __global__ void __launch_bounds__(256) pq_pixel_kernel(const int* __restrict__ p
         int gid;
         if (gt_layout == 0) gid = (int)gt8[3 * i] | ((int)gt8[3 * i + 1] << 8) | ((int)gt8[3 * i + 2] << 16);
         else gid = gt32[i];
-        if (use_lds) pq_count<true>(L, gid, pid, gt_ids, n_gt, pred_tab, n, pq_hist, matrix);
-        else pq_count<false>(L, gid, pid, gt_ids, n_gt, pred_tab, n, pq_hist, matrix);
+        if (H.lds) pq_count<true>(L, gid, pid, gt_ids, n_gt, pred_tab, n, H);
+        else pq_count<false>(L, gid, pid, gt_ids, n_gt, pred_tab, n, H);
     }
-    if (use_lds) {
-        pq_flush_run<true>(L, pq_hist, matrix);
-        __syncthreads();
-        for (int i = threadIdx.x; i < cells; i += blockDim.x)
-            if (pq_hist[i]) atomicAdd(&matrix[i], (int)pq_hist[i]);
-    } else {
-        pq_flush_run<false>(L, pq_hist, matrix);
-    }
+    if (H.lds) pq_flush_run<true>(L, H);
+    else pq_flush_run<false>(L, H);
+    __syncthreads();
+    H.flush();
 }
 
 // intersection over union of a candidate pair, as the double division of the two integers; a union <= 0 (only a JSON area that disagrees
@@ -334,7 +326,7 @@ extern "C" int odise_hip_panoptic_quality(odise_hip_ctx* ctx, const odise_pq_des
     }
     const int npix = d->H * d->W;
     const int vec = ((uintptr_t)d->pred_ids & 15) == 0 && ((uintptr_t)d->gt & (d->gt_layout == 0 ? 3 : 15)) == 0;
-    const int lds_cells = std::min((d->n_gt + 2) * kPqPredSlots, kPqLdsCells);   // n is read on the device: room for the most it can be
+    const int lds_cells = std::min((d->n_gt + 2) * kPqPredSlots, kLdsHistCells);   // n is read on the device: room for the most it can be
     const int blocks = (int)std::min<int64_t>(ceil_div(ceil_div(npix, 4), 256), 8 * ctx->cu_count);
     hipLaunchKernelGGL(pq_pixel_kernel, dim3(blocks), dim3(256), (size_t)lds_cells * sizeof(unsigned), ctx->stream, (const int*)d->pred_ids,
                        (const int*)d->pred_segments, d->gt, d->gt_layout, (const int*)s->gt_table, d->n_gt, npix, vec, lds_cells, s->matrix);

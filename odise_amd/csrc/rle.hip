@@ -279,12 +279,6 @@ __global__ void __launch_bounds__(kRleThreads) rle_write_kernel(const unsigned l
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
-void rle_release(odise_hip_ctx* ctx) {
-    if (ctx->rle_buf) (void)hipFree(ctx->rle_buf);
-    ctx->rle_buf = nullptr;
-    ctx->rle_bytes = 0;
-}
-
 static RleGrid rle_grid(int h, int w) {
     RleGrid G;
     G.h = h; G.w = w; G.R = (int)ceil_div(h, 64);
@@ -301,18 +295,8 @@ struct RleScratch {
 static int rle_scratch(odise_hip_ctx* ctx, int n, const RleGrid& G, RleScratch* s) {
     const size_t wb = (size_t)round_up((int64_t)n * G.nw * 8, 256), sb = (size_t)round_up((int64_t)n * kRleThreads * sizeof(RleState), 256);
     const size_t need = wb + sb + (size_t)n * 8;
-    if (ctx->rle_bytes < need) {
-        ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        rle_release(ctx);
-        const size_t want = need + need / 8;
-        if (hipMalloc(&ctx->rle_buf, want) != hipSuccess) {
-            ctx->rle_buf = nullptr;
-            set_error("rle: out of device memory (%zu bytes of scratch)", want);
-            return ODISE_ERR_NOMEM;
-        }
-        ctx->rle_bytes = want;
-    }
-    char* p = (char*)ctx->rle_buf;
+    ODISE_TRY(scratch_reserve(ctx->rle, need, 8, drain_streams(ctx->stream), "rle"));
+    char* p = (char*)ctx->rle.ptr;
     s->words = (unsigned long long*)p;
     s->state = (RleState*)(p + wb);
     s->len = (long long*)(p + wb + sb);

@@ -55,7 +55,7 @@ struct UNetModel {
     int mc = 320, ted = 1280, cdim = 768;  // model_channels, time-embed width, context width (read from the weights)
     // cached timestep embedding input (constant per t)
     int cached_t = -1, cached_B = 0;
-    f16* temb_in = nullptr;  // [maxB, 320]
+    DeviceScratch temb_in;   // f16 [maxB, 320]
     // graph replay
     bool use_graph = false;
     hipGraphExec_t graph_exec = nullptr;
@@ -73,7 +73,8 @@ void unet_destroy(ModelStore* ms) {
     if (!ms->unet) return;
     if (ms->unet->graph_exec) (void)hipGraphExecDestroy(ms->unet->graph_exec);
     free_allocs(ms->unet->owned);
-    if (ms->unet->temb_in) { (void)hipDeviceSynchronize(); (void)hipFree(ms->unet->temb_in); }
+    if (ms->unet->temb_in.ptr) (void)hipDeviceSynchronize();
+    scratch_release(ms->unet->temb_in);
     delete ms->unet;
     ms->unet = nullptr;
 }
@@ -340,13 +341,7 @@ static int run_st(UNetRun& r, const STBlockW& w, const Act& x, Act& out) {
 }
 
 int ensure_arena(odise_hip_ctx* ctx, ModelStore* ms, size_t bytes) {
-    if (ms->arena.cap >= bytes) return ODISE_OK;
-    ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    if (ms->arena.base) ODISE_CHECK_HIP(hipFree(ms->arena.base));
-    ms->arena = Arena();
-    ODISE_CHECK_HIP(hipMalloc((void**)&ms->arena.base, bytes));
-    ms->arena.cap = bytes;
-    return ODISE_OK;
+    return ms->arena.reserve(bytes, drain_streams(ctx->stream), "arena");
 }
 
 // the launch sequence proper (graph-capturable: no allocation, no sync, no host<->device copy)
@@ -369,7 +364,7 @@ int unet_launch(odise_hip_ctx* ctx, ModelStore* ms, UNetModel* u, const float* x
     f16* emb_silu = (f16*)ex.alloc_bytes((size_t)B * u->ted * 2);
     float* emb_out = (float*)ex.alloc_bytes((size_t)B * u->emb_total * 4);
     if (!te_h || !emb_silu || !emb_out) return ODISE_ERR_NOMEM;
-    ODISE_TRY(ex.linear(u->temb_in, B, u->te0, te_h, ODISE_ACT_SILU));
+    ODISE_TRY(ex.linear((const f16*)u->temb_in.ptr, B, u->te0, te_h, ODISE_ACT_SILU));
     {
         odise_gemm_desc d;
         memset(&d, 0, sizeof(d));
@@ -495,11 +490,9 @@ int unet_prepare_timestep(odise_hip_ctx* ctx, ModelStore* ms, UNetModel* u, int 
                 te[(size_t)b * u->mc + half + i] = (f16)(float)sin((double)t * f);
             }
         }
-        ODISE_CHECK_HIP(hipDeviceSynchronize());   // either lane may still read the previous table
-        if (u->temb_in) ODISE_CHECK_HIP(hipFree(u->temb_in));
-        u->temb_in = nullptr;
-        ODISE_CHECK_HIP(hipMalloc((void**)&u->temb_in, te.size() * 2));
-        ODISE_CHECK_HIP(hipMemcpy(u->temb_in, te.data(), te.size() * 2, hipMemcpyHostToDevice));
+        ODISE_CHECK_HIP(hipDeviceSynchronize());   // either lane may still read the previous table, which is overwritten (or reallocated) here
+        ODISE_TRY(scratch_reserve(u->temb_in, te.size() * 2, 0, drain_device(), "unet timestep table"));
+        ODISE_CHECK_HIP(hipMemcpy(u->temb_in.ptr, te.data(), te.size() * 2, hipMemcpyHostToDevice));
         u->cached_t = t;
         u->cached_B = B;
         if (u->graph_exec) { (void)hipGraphExecDestroy(u->graph_exec); u->graph_exec = nullptr; }
@@ -525,7 +518,7 @@ static int unet_forward(odise_hip_ctx* ctx, const float* x_t, const float* conte
     if (!u->use_graph) return unet_launch(ctx, ms, u, x_t, nullptr, context, cond_emb, B, h, w, true);
 
     const bool same = u->graph_exec && u->graph_B == B && u->graph_h == h && u->graph_w == w && u->graph_x == x_t &&
-                      u->graph_ctx == context && u->graph_ce == cond_emb && u->graph_arena == ms->arena.base;
+                      u->graph_ctx == context && u->graph_ce == cond_emb && u->graph_arena == ms->arena.mem.ptr;
     if (!same) {
         if (u->graph_exec) { (void)hipGraphExecDestroy(u->graph_exec); u->graph_exec = nullptr; }
         hipGraph_t graph = nullptr;
@@ -540,7 +533,7 @@ static int unet_forward(odise_hip_ctx* ctx, const float* x_t, const float* conte
         ODISE_CHECK_HIP(hipGraphInstantiate(&u->graph_exec, graph, nullptr, nullptr, 0));
         ODISE_CHECK_HIP(hipGraphDestroy(graph));
         u->graph_B = B; u->graph_h = h; u->graph_w = w;
-        u->graph_x = x_t; u->graph_ctx = context; u->graph_ce = cond_emb; u->graph_arena = ms->arena.base;
+        u->graph_x = x_t; u->graph_ctx = context; u->graph_ce = cond_emb; u->graph_arena = ms->arena.mem.ptr;
     }
     ODISE_CHECK_HIP(hipGraphLaunch(u->graph_exec, ctx->stream));
     return ODISE_OK;

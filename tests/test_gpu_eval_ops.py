@@ -53,3 +53,37 @@ def test_pair_histogram_matches_numpy(ctx, na, nb):
     b = rng.integers(0, nb, (400, 500)).astype(np.int32)
     got = ctx.pair_histogram(ctx.to_device(a), ctx.to_device(b), na, nb).numpy()
     np.testing.assert_array_equal(got, pair_histogram(a, b, na, nb))
+
+
+# The counting kernels keep a per-block histogram in LDS up to 12288 cells (csrc/lds_hist.h) and count in global memory above it.
+# (K + 1)^2 cells: K = 109 (12100) is the last size in LDS, K = 110 (12321) the first in global memory; 150 and 254 are the evaluators' sizes.
+@pytest.mark.parametrize("K", [109, 110, 150, 254])
+def test_semantic_confusion_on_both_sides_of_the_histogram_limit(ctx, K):
+    h, w = 67, 131
+    rng = np.random.default_rng(K)
+    sem = rng.standard_normal((K, h, w)).astype(np.float32)
+    g = rng.integers(0, K, (h, w)).astype(np.int32)
+    g[rng.random((h, w)) < 0.1] = K
+    ref = np.zeros((K + 1, K + 1), np.int64)
+    np.add.at(ref, (sem.argmax(axis=0).reshape(-1), g.reshape(-1)), 1)
+    d_sem, d_g = ctx.to_device(sem), ctx.to_device(g)
+    conf = ctx.semantic_confusion(d_sem, d_g)
+    np.testing.assert_array_equal(conf.numpy(), ref)
+    conf = ctx.semantic_confusion(d_sem, d_g, conf)                               # adds to what is there
+    np.testing.assert_array_equal(conf.numpy(), 2 * ref)
+
+
+@pytest.mark.parametrize("na,nb", [(7, 5), (130, 100)])                           # 35 cells; 13000 cells
+def test_pair_histogram_on_both_sides_of_the_histogram_limit(ctx, na, nb):
+    rng = np.random.default_rng(na)
+    a = rng.integers(-2, na + 3, 1000).astype(np.int32)                           # some ids outside the range on either side: not counted
+    b = rng.integers(-2, nb + 3, 1000).astype(np.int32)
+    ok = (a >= 0) & (a < na) & (b >= 0) & (b < nb)
+    assert 0 < ok.sum() < ok.size
+    ref = np.zeros((na, nb), np.int32)
+    np.add.at(ref, (a[ok], b[ok]), 1)
+    d_a, d_b = ctx.to_device(a), ctx.to_device(b)
+    hist = ctx.pair_histogram(d_a, d_b, na, nb)
+    np.testing.assert_array_equal(hist.numpy(), ref)
+    hist = ctx.pair_histogram(d_a, d_b, na, nb, hist)
+    np.testing.assert_array_equal(hist.numpy(), 2 * ref)
