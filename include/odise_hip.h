@@ -310,7 +310,11 @@ int odise_hip_instance_masks(odise_hip_ctx* ctx, int b, const int* idx, int n, i
  *   sem_argmax[b]  int32 [oh*ow]                       argmax over classes of the same scores WITHOUT materialising [K, oh, ow]
  *                                                      (what detectron2's SemSegEvaluator keeps; A-847 at 1280x1280 is 5.5 GB otherwise)
  *   panoptic[b]    int32 record [oh*ow | 1 | 3*ODISE_MAX_SEGMENTS]: panoptic ids, n_segments, (id, isthing, category_id) rows -
- *                  the per-image record of the multi-GPU exchange (odise_hip_allgather_predictions)
+ *                  the per-image record of the multi-GPU exchange (odise_hip_allgather_predictions).  The reference's list of segments
+ *                  is unbounded, the record is not: of more than ODISE_MAX_SEGMENTS surviving segments the first ODISE_MAX_SEGMENTS in
+ *                  query order are kept; a later one gets no id and consumes none (its pixels are 0 in the map), a later query of a
+ *                  stuff class that was emitted before the cap still merges into that segment.  Every non-zero id of the map has a
+ *                  row, rows past n_segments are zero.
  *   inst_masks[b]  fp32 [topk, oh, ow] (first n valid) ; inst_table (device, [B][1 + 2*topk] int32: n | query index | class) ;
  *                  inst_scores (device, [B][topk] fp32), sorted by class score descending (instance_inference, :344-380) */
 #define ODISE_MAX_SEGMENTS 100

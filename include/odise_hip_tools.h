@@ -82,6 +82,14 @@ int odise_hip_set_lanes(odise_hip_ctx* ctx, int lanes);
  * parity tests feed to the fp32 oracle head to attribute a re-decided query (tests/fullsize.py ideal_on_device_features) */
 int odise_hip_backbone_maps(odise_hip_ctx* ctx, float** out4, int* shape_bchw4x4);
 
+/* Mask logits chosen by the caller in place of the head's (tests of the post-processing kernels: tests/test_gpu_postprocess.py).  pred_masks
+ * fp32 device [B,Q,h4,w4], 1 <= Q <= 304, is rounded to fp16 into storage the context owns (released with it; no arena reset or growth
+ * of a later call touches it) and becomes "the mask logits of the last head forward" with this B / Q / h4 / w4 for odise_hip_postprocess_batch / _postprocess_pixels /
+ * _instance_masks / _instance_rle.  No head weights are needed.  There are no mask embeddings behind these logits: odise_hip_classify
+ * returns ODISE_ERR_STATE until a real odise_hip_head_forward / odise_hip_predictor_forward has run, which takes over again.  The call
+ * also brings up the context's second lane and a small arena if the backbone stage has not done so yet. */
+int odise_hip_set_head_masks(odise_hip_ctx* ctx, const float* pred_masks, int B, int Q, int h4, int w4);
+
 /* probe (probe.hip): MFMA output layout (tests/test_gpu_probe.py).  The rate probes and yardstick kernels live in odise_hip_lab.h and only
  * in the measurement build of the library. */
 int odise_hip_mfma_probe(odise_hip_ctx* ctx, float* host_out);

@@ -262,6 +262,10 @@ static int classify_impl(odise_hip_ctx* ctx, const float* image, int B, int H, i
     HeadOutputs ho;
     ODISE_TRY(head_outputs(ms, &ho));
     ODISE_REQUIRE(ho.B == B, "classify: batch %d differs from the last head_forward (%d)", B, ho.B);
+    if (!ho.mask_embed) {   // mask logits set by odise_hip_set_head_masks: there is no embedding to classify
+        set_error("classify: the current mask logits come without mask embeddings (odise_hip_set_head_masks): run odise_hip_head_forward");
+        return ODISE_ERR_STATE;
+    }
     int S = 0, patch = 0, T = 0, cdim = 0;
     if (clip_dims(ms, &S, &patch, &T, &cdim) != ODISE_OK) {
         set_error("classify: the CLIP tower is not built (odise_hip_extractor_build)");

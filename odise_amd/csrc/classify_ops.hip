@@ -234,12 +234,15 @@ __global__ void __launch_bounds__(256) classify_rows_kernel(const float* __restr
 __device__ __forceinline__ float post_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
 
 // fp16 sigmoid for the pixel-major matrix S.  The instance head counts a pixel as inside the mask iff its LOGIT is positive
-// (maskformer_model.py:371 `mask_pred > 0`) and averages sigmoid over exactly those pixels (:376-377); sigmoid(v) for 0 < v < ~1e-3
-// rounds to 0.5 in fp16, so such pixels get the next representable value above 0.5: `S > 0.5` then reproduces `logit > 0` exactly.
+// (maskformer_model.py:371 `mask_pred > 0`) and averages sigmoid over exactly those pixels (:376-377); sigmoid(v) for |v| < ~1e-3 rounds to
+// 0.5 in fp16 on either side of zero, so a non-positive logit never gets more than the last fp16 value below 0.5 (and a positive one never less
+// than 0.5): `S >= 0.5` then reproduces `logit > 0` exactly, and no value moves by more than one fp16 step of its own size - the semantic
+// scores, which read the same matrix, keep the 2^-11 relative error of a plain rounding.  (Lifting the positive side to the next value ABOVE
+// 0.5 instead cost those pixels 2^-10: tests/test_gpu_postprocess.py, generic geometry.)
 __device__ __forceinline__ f16 sig_f16(float sg, float v) {
     const f16 h = (f16)sg;
-    const bool lift = (v > 0.f) & !(h > (f16)0.5f);   // bitwise: one select, no branch
-    return lift ? (f16)0.50048828125f : h;
+    const f16 half = (f16)0.5f, below = (f16)0.499755859375f;
+    return v > 0.f ? (h < half ? half : h) : (h > below ? below : h);   // selects, no branch
 }
 
 // thread per output pixel.  kscore[q] = panoptic score of query q if it is kept (label != null, score > threshold) else < 0.
@@ -380,7 +383,7 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_kernel(const f16* _
 // puts the fp16 sigmoids into an LDS image of the tile's S rows; the tile is then written out as ONE contiguous 53 KB run of the matrix
 // (256 pixels x 208 bytes are adjacent in memory), 16 bytes per lane, whole 128-byte lines.  The panoptic arg-max is finished across the
 // four query slices through LDS (ties to the lowest query, like the sequential walk), the area counters as before.
-constexpr float kStatUnit = 2048.0f;  // instance statistics: fp16 values above 0.5 are whole multiples of 2^-11 (column_stats_kernel)
+constexpr float kStatUnit = 2048.0f;  // instance statistics: fp16 values from 0.5 up are whole multiples of 2^-11 (column_stats_kernel)
 constexpr int PT_PIX = 256;          // pixels of a tile
 constexpr int PT_CELLS = 64;         // cell columns of a tile (one per lane)
 // Round 6: the semantic head rides in the same kernel (`sem` != nullptr).  sem_seg[c, p] = sum_q P[q, c] sigmoid(mask)[q, p]
@@ -520,7 +523,7 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_tiled_kernel(const 
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const float a = (float)(i < 4 ? lo[i & 3] : hi[i & 3]);
-                    if (a > 0.5f) { s[i] += (unsigned int)(a * kStatUnit); c[i] += 1u; }
+                    if (a >= 0.5f) { s[i] += (unsigned int)(a * kStatUnit); c[i] += 1u; }
                 }
             }
 #pragma unroll
@@ -595,8 +598,8 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_tiled_kernel(const 
         for (int i = tid; i < 2 * Qpad; i += 256) stats_partial[(int64_t)blockIdx.x * 2 * Qpad + i] = st[i];
 }
 
-// per-query sum over pixels of sigmoid * [sigmoid > 0.5] and count of [sigmoid > 0.5] from S (instance mask scores,
-// maskformer_model.py:376-377).  The fp16 values above 0.5 are whole multiples of 2^-11, so the sums are taken as INTEGERS in that unit: exact,
+// per-query sum over pixels of sigmoid * [S >= 0.5] and count of [S >= 0.5] (= [logit > 0], sig_f16) from S (instance mask scores,
+// maskformer_model.py:376-377).  The fp16 values from 0.5 up are whole multiples of 2^-11, so the sums are taken as INTEGERS in that unit: exact,
 // whatever the order - every form of the pixel pass (this kernel over S, or the tiled pass's own statistics epilogue) gives the same bits.
 // Block partials [nblocks][2][Qpad] u32 (a block covers < 2^20 pixels), folded by column_fold_kernel.
 __global__ void __launch_bounds__(256) column_stats_kernel(const f16* __restrict__ S, unsigned int* __restrict__ partial, int npix, int Qpad,
@@ -616,7 +619,7 @@ __global__ void __launch_bounds__(256) column_stats_kernel(const f16* __restrict
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 const float a = (float)t[i];
-                if (a > 0.5f) { s[i] += (unsigned int)(a * kStatUnit); c[i] += 1u; }
+                if (a >= 0.5f) { s[i] += (unsigned int)(a * kStatUnit); c[i] += 1u; }
             }
         }
 #pragma unroll
@@ -746,7 +749,8 @@ __global__ void __launch_bounds__(256) post_decide_kernel(const float* __restric
 }
 
 // One thread per image walks the kept queries in order (maskformer_model.py:312-340): areas from the integer counters of the
-// per-pixel pass, overlap test, stuff merging by class, sequential segment ids.  map [Q] = segment id of every query (0 = none);
+// per-pixel pass, overlap test, stuff merging by class, sequential segment ids, at most max_segments of them (odise_post_desc: the walk goes on
+// past the cap only to merge stuff).  map [Q] = segment id of every query (0 = none);
 // table = n_segments | (id, isthing, category_id) x n  (the tail of the image's prediction record, odise_amd/distributed.py).
 __global__ void panoptic_decide_kernel(const int* __restrict__ cnt, const float* __restrict__ ks, const int* __restrict__ lb,
                                        const uint8_t* __restrict__ isthing, int* __restrict__ mp, int* __restrict__ table, int Q, int K,
@@ -764,13 +768,16 @@ __global__ void panoptic_decide_kernel(const int* __restrict__ cnt, const float*
         if (mask_area > 0 && original_area > 0 && inter > 0) {
             if ((double)mask_area / (double)original_area < overlap_threshold) continue;
             const bool thing = isthing[cls] != 0;
+            // the record holds max_segments rows: a segment past the cap gets no id (its pixels stay 0) and consumes none, so that every id
+            // in the map has a row; a query of a stuff class that was emitted before the cap still merges into it
+            if (n >= max_segments && (thing || !stuff[cls])) continue;
             if (!thing) {
                 if (stuff[cls]) { mp[q] = stuff[cls]; continue; }
                 stuff[cls] = current + 1;
             }
             ++current;
             mp[q] = current;
-            if (table && n < max_segments) {
+            if (table) {
                 table[1 + 3 * n] = current;
                 table[2 + 3 * n] = thing ? 1 : 0;
                 table[3 + 3 * n] = cls;

@@ -109,12 +109,18 @@ struct MaskGenModel : BackboneW, HeadW {
     float* class_logits = nullptr;  // [B, Q, 2] of the final prediction head
     int out_B = 0, out_h = 0, out_w = 0;
     double last_macs = 0.0;
+    // odise_hip_set_head_masks (tools hook): mask logits chosen by the caller stand in for the head's.  fp16 copy in storage of its own (the arena
+    // is recycled by every stage); injected_Q != 0 while pred_masks points into it.  Arena resets and reallocations (maskgen_invalidate_outputs)
+    // leave it current; a real head / predictor pass takes over again
+    DeviceScratch injected;
+    int injected_Q = 0;
 };
 
 void maskgen_destroy(ModelStore* ms) {
     if (ms->maskgen) {
         free_allocs(ms->maskgen->owned_backbone);
         free_allocs(ms->maskgen->owned_head);
+        scratch_release(ms->maskgen->injected);
     }
     delete ms->maskgen;
     ms->maskgen = nullptr;
@@ -948,6 +954,7 @@ static int predictor_forward(odise_hip_ctx* ctx, PixDec& pd) {
     ODISE_TRY(ex.layer_norm(pooled_x, tq, MQ, g->post_ln, 1e-5f));
     ODISE_TRY(mlp3(ex, g->post_mlp, tq, MQ, t1, t2, mask_embed));
     g->pred_masks = masks; g->mask_embed = mask_embed; g->mask_pooled = pooled_x;
+    g->injected_Q = 0;
     g->out_B = B; g->out_h = s2.h; g->out_w = s2.w;
     g->last_macs = ms->macs;
     return ODISE_OK;
@@ -964,12 +971,12 @@ static int head_forward(odise_hip_ctx* ctx, const Act feats[4]) {
 
 int head_outputs(ModelStore* ms, HeadOutputs* out) {
     MaskGenModel* g = ms->maskgen;
-    if (!g || !g->head_built || !g->pred_masks) {
+    if (!g || !(g->head_built || g->injected_Q) || !g->pred_masks) {
         set_error("no head outputs available: call odise_hip_head_forward first");
         return ODISE_ERR_STATE;
     }
     out->pred_masks = g->pred_masks; out->mask_embed = g->mask_embed;
-    out->B = g->out_B; out->Q = g->Q; out->C = g->C; out->h4 = g->out_h; out->w4 = g->out_w;
+    out->B = g->out_B; out->Q = g->injected_Q ? g->injected_Q : g->Q; out->C = g->C; out->h4 = g->out_h; out->w4 = g->out_w;
     out->logit_scale = g->logit_scale;
     out->class_logits = g->class_logits;
     return ODISE_OK;
@@ -978,7 +985,8 @@ int head_outputs(ModelStore* ms, HeadOutputs* out) {
 void maskgen_invalidate_outputs(ModelStore* ms) {
     MaskGenModel* g = ms->maskgen;
     if (!g) return;
-    g->pred_masks = nullptr; g->mask_embed = nullptr; g->mask_pooled = nullptr; g->class_logits = nullptr;
+    if (!g->injected_Q) g->pred_masks = nullptr;   // logits set by odise_hip_set_head_masks live in storage of their own and stay current
+    g->mask_embed = nullptr; g->mask_pooled = nullptr; g->class_logits = nullptr;
     for (Act& f : g->feats) f.p = nullptr;
 }
 
@@ -1001,6 +1009,31 @@ extern "C" int odise_hip_backbone_forward(odise_hip_ctx* ctx, const float* image
     ODISE_REQUIRE(ctx, "backbone_forward: null context");
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));   // the caller may be a new host thread, or hold another device current
     return backbone_forward(ctx, image, B, H, W, out4);
+}
+
+// test hook (include/odise_hip_tools.h): mask logits chosen by the caller become "the outputs of the last head forward" for the post-processing
+// entry points (which read nothing else of the head).  No head weights are needed.  mask_embed / mask_pooled / class_logits stay null: callers
+// of head_outputs() that read them (odise_hip_classify) refuse with ODISE_ERR_STATE.
+extern "C" int odise_hip_set_head_masks(odise_hip_ctx* ctx, const float* pred_masks, int B, int Q, int h4, int w4) {
+    ODISE_REQUIRE(ctx && pred_masks, "set_head_masks: null argument");
+    ODISE_REQUIRE(B >= 1 && Q >= 1 && Q <= 304 && h4 >= 1 && w4 >= 1 && (int64_t)B * Q * h4 * w4 < (1ll << 31), "set_head_masks: bad shape %dx%dx%dx%d", B, Q,
+                  h4, w4);
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    ModelStore* ms = store_of(ctx);
+    MaskGenModel* g = maskgen_of(ms);
+    const size_t n = (size_t)B * Q * h4 * w4;
+    // a previous injection may still be read by queued post-processing kernels of either lane: grow behind a whole-device drain
+    ODISE_TRY(scratch_reserve(g->injected, n * sizeof(f16), 0, drain_device(), "set_head_masks"));
+    // the per-image entry points take their temporaries from the arena, the batch call runs its decision chains on the second lane when the
+    // backbone stage has brought it up: provide both as that stage would (an existing arena / lane is kept as it is)
+    const void* base0 = ms->arena.mem.ptr;
+    ODISE_TRY(ensure_arena(ctx, ms, (size_t)64 << 20));
+    if (ms->arena.mem.ptr != base0) maskgen_invalidate_outputs(ms);   // a smaller arena was replaced: the backbone maps in it are gone
+    ODISE_TRY(ensure_lane2(ctx, ms, 0));
+    ODISE_TRY(odise_hip_cast_f32_to_f16(ctx, pred_masks, g->injected.ptr, n));
+    g->pred_masks = (f16*)g->injected.ptr; g->mask_embed = nullptr; g->mask_pooled = nullptr; g->class_logits = nullptr;
+    g->injected_Q = Q; g->out_B = B; g->out_h = h4; g->out_w = w4;
+    return ODISE_OK;
 }
 
 // test / attribution hook (include/odise_hip_tools.h): the s2..s5 maps of the last backbone pass that are still resident in the arena
