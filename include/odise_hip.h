@@ -369,7 +369,10 @@ int odise_hip_infer_prefetch(odise_hip_ctx* ctx, const odise_infer_desc* next);
  * (odise/evaluation/d2_evaluator.py:49 COCOPanopticEvaluator -> panopticapi pq_compute_single_core, :63 SemSegEvaluator.process).
  * Per picture each evaluator is one asynchronous call that adds into a small accumulator: odise_hip_semantic_confusion /
  * odise_hip_semantic_boundary_confusion (SemSegEvaluator), odise_hip_panoptic_quality (COCOPanopticEvaluator, straight from the panoptic
- * record), odise_hip_instance_rle (the segm evaluators).  odise_hip_pair_histogram is the bare per-pixel part of the panoptic one. */
+ * record), odise_hip_instance_eval (InstanceSegEvaluator / COCOEvaluator with tasks=("segm",), d2_evaluator.py:29,104: COCOeval.evaluateImg
+ * of a picture, straight from the mask logits; one fixed-size row per detection, reduced on the host by odise_amd/instance_eval.py).
+ * odise_hip_pair_histogram is the bare per-pixel part of the panoptic one, odise_hip_mask_iou that of the segm one; odise_hip_instance_rle
+ * writes the RLE strings of coco_instances_results.json, which the metric no longer needs. */
 /* src uint8 [H,W,C] -> dst uint8 [OH,OW,C], bit-identical to Pillow's 8-bit bilinear resampler (horizontal pass, then vertical) */
 int odise_hip_resize_bilinear_u8(odise_hip_ctx* ctx, const void* src, int H, int W, int C, void* dst, int OH, int OW);
 /* dst fp32 [C,H,W] = scale * src uint8 [H,W,C] */
@@ -452,6 +455,52 @@ int odise_hip_rle_encode(odise_hip_ctx* ctx, const void* masks, int dtype, int n
  * past the count are empty strings of area 0.  Enqueue it after odise_hip_postprocess_batch / odise_hip_infer of the same batch. */
 int odise_hip_instance_rle(odise_hip_ctx* ctx, int b, const int* inst_table, int topk, int pad_h, int pad_w, int img_h, int img_w,
                            int out_h, int out_w, void* rle, int64_t capacity, int64_t* offsets, int64_t* area);
+/* pycocotools' mask.iou of n dense masks (layout / dtype as odise_hip_rle_encode) against n_gt run-length masks of the same size.
+ * gt_runs: device uint32, the UNCOMPRESSED counts of all masks back to back - runs over the column-major order j = x * h + y, starting
+ * with the zeros and alternating (coco_rle.string_to_counts of a compressed string); zero-length runs are legal anywhere.
+ * gt_offsets: device int64 [n_gt + 1], the first count of every mask.  iscrowd: device uint8 [n_gt] or NULL (none is).
+ * iou: device double [n][n_gt] = rleIou: inter == 0 -> 0, crowd -> inter / area_d, else inter / (area_d + area_g - inter), the double
+ * division of exact integers.  inter int32 [n][n_gt], area_d int64 [n], area_g int64 [n_gt]: optional.
+ * flags: device int32 [1], OR-ed: 1 = the counts of a mask do not sum to h * w (its missing tail is zeros, what lies past the end is
+ * dropped; no access leaves a buffer).  n == 0 or n_gt == 0 writes nothing and succeeds.  n, n_gt <= 65535, n * n_gt <= 2^26,
+ * h * w <= 2^30.  Scratch comes from the context.  Asynchronous on the context's stream. */
+int odise_hip_mask_iou(odise_hip_ctx* ctx, const void* masks, int dtype, int n, int h, int w, const uint32_t* gt_runs,
+                       const int64_t* gt_offsets, int n_gt, const uint8_t* iscrowd, double* iou, int32_t* inter, int64_t* area_d,
+                       int64_t* area_g, int32_t* flags);
+/* One picture of COCOeval.evaluateImg for iouType "segm", useCats = 1, maxDets 100, in all four area ranges ([0, 1e10], [0, 32^2],
+ * [32^2, 96^2], [96^2, 1e10], ends included) and at the ten IoU thresholds the caller passes (np.linspace(.5, .95, 10) as doubles).
+ * Per (category, range a, threshold t): detections in descending score, ties in table order; a ground truth is ignored when it is a
+ * crowd or its area lies outside range a (the caller computes these bits from the annotation's float area); non-ignored ground truths
+ * come first, each group in annotation order.  A detection starts from best = min(t, 1 - 1e-10) and walks the ground truths: one already
+ * matched at (a, t) that is no crowd is skipped; the walk stops at the first ignored one once a non-ignored match is held; iou < best is
+ * skipped; otherwise best = iou and the match moves there (on equal values to the later one).  A matched detection takes the ignore bit of
+ * its ground truth; an unmatched one is ignored when its own area (pixels of its mask) lies outside range a.
+ * Row k is the detection of rank k by score: what COCOeval.accumulate needs of it (odise_amd/instance_eval.py accumulate / summarize).
+ * ODISE_ERR_ARG and nothing written: a null pointer, topk outside 1..100, n_gt outside 0..1024, the geometry errors of
+ * odise_hip_instance_rle.  Polygon ground truth is not decoded here: whoever holds the annotations converts it to RLE.
+ * The matching is one block: a wave per category, so a picture whose detections and ground truths all share one category is matched
+ * by one wave.  Scratch comes from the context.  Asynchronous on the context's stream; no host synchronisation. */
+typedef struct { float score; int32_t category; int32_t area; int32_t image; uint64_t matched, ignored; } odise_inst_eval_row; /* 32 bytes; bit 10*a + t */
+typedef struct {
+    int h, w;                       /* output size of the picture */
+    /* detections, one of: */
+    const void* masks; int dtype;   /* dense [topk,h,w] (ODISE_F32 / ODISE_U8), or NULL = from the mask logits of image b of the last head forward: */
+    int b, pad_h, pad_w, img_h, img_w;   /* as odise_hip_instance_rle */
+    const int32_t* inst_table;      /* device [1 + 2*topk]: n | query index | class  (n read on the device) */
+    const float* inst_scores;       /* device [topk] */
+    int topk;                       /* 1..100: the evaluator looks at no more than 100 detections per picture and category */
+    /* ground truth, all device: */
+    const uint32_t* gt_runs; const int64_t* gt_offsets;   /* as odise_hip_mask_iou */
+    const int32_t* gt_rows;         /* [n_gt][3]: contiguous category, iscrowd, bits 0..3 = area outside range a */
+    int n_gt;                       /* 0..1024 */
+    int num_categories; int image;  /* `image` is copied into every row */
+    const double* iou_thresholds;   /* HOST [10], copied by value into the launch */
+    odise_inst_eval_row* rows;      /* device [topk]; rows past n are zeroed */
+    int32_t* n_rows;                /* device [1] */
+    int32_t* flags;                 /* device [1], OR-ed: 1 = a gt mask's runs do not sum to h*w, 2 = a detection's class outside [0,num_categories),
+                                       4 = a gt category outside it / iscrowd not 0|1.  A picture that raises one writes n_rows = 0 and zeroed rows. */
+} odise_inst_eval_desc;
+int odise_hip_instance_eval(odise_hip_ctx* ctx, const odise_inst_eval_desc* d);
 
 /* ---- JPEG input -------------------------------------------------------------------------------------------
  * Replaces detectron2 `read_image(file, "RGB")` = PIL.Image.open -> EXIF transpose -> convert("RGB") of the DatasetMapper

@@ -95,6 +95,14 @@ class PqDesc(C.Structure):
                 ("gt_segments", c_void_p), ("n_gt", c_int), ("num_categories", c_int), ("stats", c_void_p), ("flags", c_void_p)]
 
 
+class InstEvalDesc(C.Structure):
+    """odise_inst_eval_desc (include/odise_hip.h)."""
+    _fields_ = [("h", c_int), ("w", c_int), ("masks", c_void_p), ("dtype", c_int), ("b", c_int), ("pad_h", c_int), ("pad_w", c_int),
+                ("img_h", c_int), ("img_w", c_int), ("inst_table", c_void_p), ("inst_scores", c_void_p), ("topk", c_int),
+                ("gt_runs", c_void_p), ("gt_offsets", c_void_p), ("gt_rows", c_void_p), ("n_gt", c_int), ("num_categories", c_int),
+                ("image", c_int), ("iou_thresholds", c_void_p), ("rows", c_void_p), ("n_rows", c_void_p), ("flags", c_void_p)]
+
+
 MAX_SEGMENTS = 100          # ODISE_MAX_SEGMENTS
 COMM_ID_BYTES = 128         # ODISE_COMM_ID_BYTES
 

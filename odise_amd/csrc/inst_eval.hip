@@ -1,0 +1,380 @@
+// inst_eval.hip — instance masks against ground truth on the device: odise_hip_mask_iou (pycocotools' mask.iou of dense masks against
+// run-length masks) and odise_hip_instance_eval (COCOeval.evaluateImg for iouType "segm", useCats = 1: the per-picture part of
+// InstanceSegEvaluator / COCOEvaluator(tasks=("segm",)), odise/evaluation/d2_evaluator.py:29,104).  Host restatement: odise_amd/instance_eval.py.
+//
+//   1. pack     the detections into words [n][w][R] (rle_pack.h: the kernels of rle.hip, the pixels of odise_hip_instance_rle).
+//   2. decode   the ground truth from uncompressed COCO run lengths into the same layout.  One block per mask walks its runs 1024 at a time:
+//               a block scan gives the end position of every run of the chunk, then a thread per word of the chunk's span searches the first
+//               run that reaches into its word and walks on from there.  Every position is clamped to h * w: counts that sum to anything
+//               else raise flag 1 and never move a read or a write outside the mask.
+//   3. inter    inter[d][g] = sum of popcount(words_d & words_g), tiled like a small GEMM: a block holds 32 words of 64 detections and 32
+//               ground truths in LDS and a thread forms 4 x 2 pairs from them; the word axis is split over blockIdx.z and the partial
+//               counts meet in integer atomics (exact, and the same from run to run).  Areas are the popcounts of one side.
+//   4. iou      rleIou in double: inter == 0 -> 0, crowd -> inter / area_d, else inter / (area_d + area_g - inter).
+//   5. match    one block.  Detections in descending score (ties keep table order), ground truths of a category in annotation order.  The 40
+//               (area range, threshold) cells of a detection are the lanes 10 a + t of ONE wave, which walks the ground truths of the
+//               detection's category once: a lane keeps the best available non-ignored one and the best available ignored one (>= on equal
+//               values: the later one wins) and takes the second only when there is no first - evaluateImg's loop over the ground truths
+//               sorted by ignore, with its break.  The IoUs of 64 ground truths are computed by the 64 lanes at once and handed round by
+//               lane index.  Categories are independent, so the 16 waves of the block share the detections by category.  The matched /
+//               ignored words of a row are the ballots of the wave.
+#include <algorithm>
+
+#include "rle_pack.h"
+
+namespace odise {
+
+constexpr int kInstMaxDet = 100;       // the evaluator looks at no more than 100 detections per picture and category
+constexpr int kInstMaxGt = 1024;
+constexpr int kInstCells = 40;         // 4 area ranges x 10 thresholds, bit 10 a + t
+constexpr int kInterTD = 64, kInterTG = 32, kInterKC = 32;   // tile of the intersection kernel: detections, ground truths, words per step
+
+typedef unsigned long long u64;
+
+__device__ __forceinline__ double rle_iou(int inter, long long area_d, long long area_g, bool crowd) {
+    if (inter == 0) return 0.0;
+    return crowd ? (double)inter / (double)area_d : (double)inter / (double)(area_d + area_g - inter);
+}
+
+// ---- 2. decode ----------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ u64 bit_range(int a, int b) {   // bits a .. b - 1, 0 <= a < b <= 64
+    const u64 m = b - a == 64 ? ~0ull : (1ull << (b - a)) - 1ull;
+    return m << a;
+}
+
+__global__ void __launch_bounds__(kRleThreads) inst_decode_kernel(const uint32_t* __restrict__ runs, const long long* __restrict__ offsets,
+                                                                 u64* __restrict__ words, RleGrid G, int* __restrict__ flag) {
+    __shared__ long long ends[kRleThreads];
+    __shared__ long long ls[kRleThreads / 64];
+    const int tid = threadIdx.x;
+    u64* wd = words + (int64_t)blockIdx.x * G.nw;
+    for (int64_t i = tid; i < G.nw; i += kRleThreads) wd[i] = 0ull;
+    const long long r0 = offsets[blockIdx.x];
+    const long long m = max(0ll, offsets[blockIdx.x + 1] - r0);
+    const long long hw = (long long)G.h * G.w;
+    long long carry = 0;   // positions before the chunk
+    __syncthreads();
+    for (long long c0 = 0; c0 < m; c0 += kRleThreads) {
+        const long long v = c0 + tid < m ? (long long)runs[r0 + c0 + tid] : 0ll;
+        long long total;
+        const long long ex = block_scan_sum(v, ls, total);
+        ends[tid] = carry + ex + v;   // run c0 + tid covers positions [carry + ex, ends[tid])
+        __syncthreads();
+        const long long A = carry, B = min(carry + total, hw);
+        if (A < B) {   // the chunk covers positions [A, B) of the mask; ends[cl - 1] >= B
+            const int cl = (int)min((long long)kRleThreads, m - c0);
+            const int xa = (int)(A / G.h), xb = (int)((B - 1) / G.h);
+            const int64_t wlo = (int64_t)xa * G.R + (((int)A - xa * G.h) >> 6), whi = (int64_t)xb * G.R + (((int)(B - 1) - xb * G.h) >> 6);
+            for (int64_t wi = wlo + tid; wi <= whi; wi += kRleThreads) {
+                const int x = (int)(wi / G.R), r = (int)(wi - (int64_t)x * G.R);
+                const long long p0 = (long long)x * G.h + 64 * r, p1 = (long long)x * G.h + min(64 * r + 64, G.h);
+                long long pos = max(p0, A);
+                const long long pe = min(p1, B);
+                int lo = 0, hi = cl - 1;   // the first run that ends behind pos
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (ends[mid] > pos) hi = mid;
+                    else lo = mid + 1;
+                }
+                u64 bits = 0ull;
+                for (int k = lo; k < cl && pos < pe; ++k) {   // zero-length runs pass without a bit
+                    const long long e = min(ends[k], pe);
+                    if (e > pos) {
+                        if ((c0 + k) & 1) bits |= bit_range((int)(pos - p0), (int)(e - p0));
+                        pos = e;
+                    }
+                }
+                if (bits) wd[wi] |= bits;   // a word on the edge of two chunks is written in both, a barrier apart
+            }
+        }
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0 && carry != hw) atomicOr(flag, 1);
+}
+
+// ---- 3. intersections and areas -----------------------------------------------------------------------------------------------------------
+// inter[n][n_gt] += over the words [blockIdx.z * per, + per) of the masks; `per` is a multiple of kInterKC
+__global__ void __launch_bounds__(256) inst_inter_kernel(const u64* __restrict__ wd_d, const u64* __restrict__ wd_g, int n, int n_gt, int64_t nw,
+                                                        int64_t per, int* __restrict__ inter) {
+    __shared__ u64 sd[kInterTD][kInterKC + 1];
+    __shared__ u64 sg[kInterTG][kInterKC + 1];
+    const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
+    const int d0 = blockIdx.x * kInterTD, g0 = blockIdx.y * kInterTG;
+    const int64_t k_begin = (int64_t)blockIdx.z * per, k_end = min(nw, k_begin + per);
+    int acc[4][2] = {};
+    for (int64_t k0 = k_begin; k0 < k_end; k0 += kInterKC) {
+        for (int e = tid; e < (kInterTD + kInterTG) * kInterKC; e += 256) {
+            const int row = e / kInterKC, kk = e - row * kInterKC;
+            const int64_t k = k0 + kk;
+            if (row < kInterTD) sd[row][kk] = (d0 + row < n && k < k_end) ? wd_d[(int64_t)(d0 + row) * nw + k] : 0ull;
+            else sg[row - kInterTD][kk] = (g0 + row - kInterTD < n_gt && k < k_end) ? wd_g[(int64_t)(g0 + row - kInterTD) * nw + k] : 0ull;
+        }
+        __syncthreads();
+#pragma unroll 4
+        for (int kk = 0; kk < kInterKC; ++kk) {
+            const u64 b0 = sg[tx][kk], b1 = sg[tx + 16][kk];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const u64 a = sd[ty + 16 * i][kk];
+                acc[i][0] += __popcll(a & b0);
+                acc[i][1] += __popcll(a & b1);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int d = d0 + ty + 16 * i, g = g0 + tx + 16 * j;
+            if (d < n && g < n_gt && acc[i][j]) atomicAdd(&inter[(int64_t)d * n_gt + g], acc[i][j]);
+        }
+}
+
+// area[row] = ones of a row of words; one block per row
+__global__ void __launch_bounds__(256) inst_area_kernel(const u64* __restrict__ words, int64_t nw, long long* __restrict__ area) {
+    __shared__ long long part[4];
+    const u64* wd = words + (int64_t)blockIdx.x * nw;
+    long long s = 0;
+    for (int64_t i = threadIdx.x; i < nw; i += 256) s += __popcll(wd[i]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_down(s, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) area[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// ---- 4. iou (odise_hip_mask_iou) ----------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) inst_iou_kernel(const int* __restrict__ inter, const long long* __restrict__ area, int n, int n_gt,
+                                                      const uint8_t* __restrict__ iscrowd, double* __restrict__ iou, int* __restrict__ inter_out,
+                                                      long long* __restrict__ area_d, long long* __restrict__ area_g) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)n * n_gt) return;
+    const int d = (int)(i / n_gt), g = (int)(i - (int64_t)d * n_gt);
+    const int in = inter[i];
+    iou[i] = rle_iou(in, area[d], area[n + g], iscrowd && iscrowd[g] != 0);
+    if (inter_out) inter_out[i] = in;
+    if (area_d && g == 0) area_d[d] = area[d];
+    if (area_g && d == 0) area_g[g] = area[n + g];
+}
+
+// ---- 5. match -----------------------------------------------------------------------------------------------------------------------------
+struct InstMatchArgs {
+    const int* inst_table;       // n | query index [topk] | class [topk]
+    const float* inst_scores;    // [topk]
+    const int* gt_rows;          // [n_gt][3]
+    const int* inter;            // [topk][n_gt]
+    const long long* area;       // [topk + n_gt]
+    const int* status;           // flag 1 of this picture's decode
+    odise_inst_eval_row* rows;
+    int* n_rows;
+    int* flags;
+    int topk, n_gt, num_categories, image;
+    double thr[10];
+};
+
+__device__ __forceinline__ bool inst_area_outside(int area, int a) {   // [0, 1e10], [0, 32^2], [32^2, 96^2], [96^2, 1e10], ends included
+    return a == 1 ? area > 1024 : a == 2 ? (area < 1024 || area > 9216) : a == 3 ? area < 9216 : false;
+}
+
+__global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A) {
+    __shared__ int g_cat[kInstMaxGt], g_flag[kInstMaxGt], g_area[kInstMaxGt], g_sorted[kInstMaxGt];   // g_flag: iscrowd | outside bits << 1
+    __shared__ u64 g_matched[kInstMaxGt];                                                             // bit = cell
+    __shared__ int d_cls[kInstMaxDet], d_area[kInstMaxDet], d_order[kInstMaxDet], d_lo[kInstMaxDet], d_cnt[kInstMaxDet];
+    __shared__ float d_score[kInstMaxDet];
+    __shared__ int bad;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int topk = A.topk, n_gt = A.n_gt;
+    const int n = min(max(A.inst_table[0], 0), topk);
+    if (tid == 0) bad = A.status[0];
+    __syncthreads();
+    int f = 0;
+    for (int j = tid; j < n_gt; j += kRleThreads) {
+        const int cat = A.gt_rows[3 * j], crowd = A.gt_rows[3 * j + 1];
+        if ((unsigned)cat >= (unsigned)A.num_categories || (unsigned)crowd > 1u) f |= 4;
+        g_cat[j] = cat;
+        g_flag[j] = (crowd & 1) | ((A.gt_rows[3 * j + 2] & 15) << 1);
+        g_area[j] = (int)A.area[topk + j];
+        g_matched[j] = 0ull;
+    }
+    for (int i = tid; i < n; i += kRleThreads) {
+        d_cls[i] = A.inst_table[1 + topk + i];
+        if ((unsigned)d_cls[i] >= (unsigned)A.num_categories) f |= 2;
+        const float s = A.inst_scores[i];
+        d_score[i] = s == s ? s : -INFINITY;
+        d_area[i] = (int)A.area[i];
+    }
+    if (f) atomicOr(&bad, f);
+    __syncthreads();
+    const odise_inst_eval_row zero = {};
+    if (bad) {   // the picture counts nothing
+        for (int i = tid; i < topk; i += kRleThreads) A.rows[i] = zero;
+        if (tid == 0) {
+            A.n_rows[0] = 0;
+            atomicOr(A.flags, bad);
+        }
+        return;
+    }
+    for (int i = n + tid; i < topk; i += kRleThreads) A.rows[i] = zero;
+    if (tid == 0) A.n_rows[0] = n;
+    // descending score, ties in table order; the ground truths of a detection's category: g_sorted[d_lo .. d_lo + d_cnt), annotation order
+    for (int i = tid; i < n; i += kRleThreads) {
+        int r = 0, lo = 0, cnt = 0;
+        for (int j = 0; j < n; ++j) r += (d_score[j] > d_score[i] || (d_score[j] == d_score[i] && j < i)) ? 1 : 0;
+        d_order[r] = i;
+        for (int j = 0; j < n_gt; ++j) {
+            lo += g_cat[j] < d_cls[i] ? 1 : 0;
+            cnt += g_cat[j] == d_cls[i] ? 1 : 0;
+        }
+        d_lo[i] = lo;
+        d_cnt[i] = cnt;
+    }
+    for (int j = tid; j < n_gt; j += kRleThreads) {
+        int r = 0;
+        for (int k = 0; k < n_gt; ++k) r += (g_cat[k] < g_cat[j] || (g_cat[k] == g_cat[j] && k < j)) ? 1 : 0;
+        g_sorted[r] = j;
+    }
+    __syncthreads();
+
+    const bool cell = lane < kInstCells;
+    const int a = cell ? lane / 10 : 0, t = cell ? lane - 10 * a : 0;
+    const double thr = fmin(A.thr[t], 1.0 - 1e-10);
+    for (int k = 0; k < n; ++k) {
+        const int d = d_order[k];
+        if ((d_cls[d] & (kRleThreads / 64 - 1)) != wave) continue;   // a category belongs to one wave: its ground truths are touched by no other
+        const int ad = d_area[d], lo = d_lo[d], cnt = d_cnt[d];
+        double best1 = thr, best2 = thr;
+        int m1 = -1, m2 = -1;
+        for (int base = 0; base < cnt; base += 64) {
+            double mine = 0.0;
+            if (base + lane < cnt) {
+                const int j = g_sorted[lo + base + lane];
+                mine = rle_iou(A.inter[(int64_t)d * n_gt + j], ad, g_area[j], g_flag[j] & 1);
+            }
+            const int step = min(64, cnt - base);
+            for (int q = 0; q < step; ++q) {
+                const int j = g_sorted[lo + base + q];
+                const double iou = __shfl(mine, q);
+                const int gf = g_flag[j];
+                const bool crowd = gf & 1, ign = crowd || ((gf >> (1 + a)) & 1), matched = (g_matched[j] >> lane) & 1ull;
+                if (!ign) {
+                    if (!matched && iou >= best1) { best1 = iou; m1 = j; }
+                } else if ((crowd || !matched) && iou >= best2) { best2 = iou; m2 = j; }
+            }
+        }
+        const int m = m1 >= 0 ? m1 : m2;
+        bool ig;
+        if (m >= 0) {
+            ig = m1 < 0;   // the ignore bit of the ground truth it took
+            if (cell) atomicOr(&g_matched[m], 1ull << lane);
+        } else {
+            ig = inst_area_outside(ad, a);
+        }
+        const u64 mw = __ballot(cell && m >= 0), iw = __ballot(cell && ig);
+        if (lane == 0) {
+            odise_inst_eval_row row;
+            row.score = A.inst_scores[d]; row.category = d_cls[d]; row.area = ad; row.image = A.image;
+            row.matched = mw; row.ignored = iw;
+            A.rows[k] = row;
+        }
+    }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------------------
+struct InstScratch {
+    u64 *words_d, *words_g;
+    long long* area;   // [n + n_gt]
+    int* inter;        // [n][n_gt], then one int: the status of the call
+    size_t inter_bytes;
+};
+static int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, InstScratch* s) {
+    const size_t wb = (size_t)round_up((int64_t)(n + n_gt) * G.nw * 8, 256), ab = (size_t)round_up((int64_t)(n + n_gt) * 8, 256);
+    s->inter_bytes = ((size_t)n * n_gt + 1) * sizeof(int);
+    ODISE_TRY(scratch_reserve(ctx->rle, wb + ab + s->inter_bytes, 8, drain_streams(ctx->stream), "rle"));
+    char* p = (char*)ctx->rle.ptr;
+    s->words_d = (u64*)p;
+    s->words_g = s->words_d + (int64_t)n * G.nw;
+    s->area = (long long*)(p + wb);
+    s->inter = (int*)(p + wb + ab);
+    return ODISE_OK;
+}
+
+// stages 2 and 3 behind the packed detections: ground-truth words, inter, area; flag 1 goes to `flag`
+static int inst_overlaps(odise_hip_ctx* ctx, const InstScratch& s, const RleGrid& G, int n, const uint32_t* gt_runs, const int64_t* gt_offsets, int n_gt,
+                         int* flag) {
+    if (n_gt) {
+        hipLaunchKernelGGL(inst_decode_kernel, dim3((unsigned)n_gt), dim3(kRleThreads), 0, ctx->stream, gt_runs, (const long long*)gt_offsets, s.words_g,
+                           G, flag);
+        ODISE_CHECK_HIP(hipGetLastError());
+        // split the word axis until the grid fills the chip about twice
+        const int64_t tiles = ceil_div(n, kInterTD) * ceil_div(n_gt, kInterTG), steps = ceil_div(G.nw, kInterKC);
+        const int64_t kz = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(steps, 1024), 2 * ctx->cu_count / tiles));
+        const int64_t per = ceil_div(steps, kz) * kInterKC;
+        const dim3 grid((unsigned)ceil_div(n, kInterTD), (unsigned)ceil_div(n_gt, kInterTG), (unsigned)ceil_div(G.nw, per));
+        hipLaunchKernelGGL(inst_inter_kernel, grid, dim3(256), 0, ctx->stream, (const u64*)s.words_d, (const u64*)s.words_g, n, n_gt, G.nw, per,
+                           s.inter);
+        ODISE_CHECK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(inst_area_kernel, dim3((unsigned)(n + n_gt)), dim3(256), 0, ctx->stream, (const u64*)s.words_d, G.nw, s.area);
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}
+
+}  // namespace odise
+
+using namespace odise;
+
+extern "C" int odise_hip_mask_iou(odise_hip_ctx* ctx, const void* masks, int dtype, int n, int h, int w, const uint32_t* gt_runs,
+                                  const int64_t* gt_offsets, int n_gt, const uint8_t* iscrowd, double* iou, int32_t* inter, int64_t* area_d,
+                                  int64_t* area_g, int32_t* flags) {
+    ODISE_REQUIRE(ctx && flags, "mask_iou: null argument");
+    ODISE_REQUIRE(n >= 0 && n <= 65535 && n_gt >= 0 && n_gt <= 65535 && (int64_t)n * n_gt <= (1 << 26), "mask_iou: %d x %d masks out of range", n, n_gt);
+    ODISE_REQUIRE(h >= 1 && w >= 1 && (int64_t)h * w <= kRleMaxPixels, "mask_iou: mask size %dx%d out of range", h, w);
+    ODISE_REQUIRE(dtype == ODISE_F32 || dtype == ODISE_U8, "mask_iou: dtype %d (ODISE_F32 or ODISE_U8)", dtype);
+    if (n == 0 || n_gt == 0) return ODISE_OK;
+    ODISE_REQUIRE(masks && gt_runs && gt_offsets && iou, "mask_iou: null argument");
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    const RleGrid G = rle_grid(h, w);
+    InstScratch s;
+    ODISE_TRY(inst_scratch(ctx, n, n_gt, G, &s));
+    ODISE_CHECK_HIP(hipMemsetAsync(s.inter, 0, s.inter_bytes, ctx->stream));
+    ODISE_TRY(rle_pack_dense(ctx, masks, dtype, n, G, s.words_d));
+    ODISE_TRY(inst_overlaps(ctx, s, G, n, gt_runs, gt_offsets, n_gt, (int*)flags));
+    hipLaunchKernelGGL(inst_iou_kernel, dim3((unsigned)ceil_div((int64_t)n * n_gt, 256)), dim3(256), 0, ctx->stream, (const int*)s.inter,
+                       (const long long*)s.area, n, n_gt, iscrowd, iou, (int*)inter, (long long*)area_d, (long long*)area_g);
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}
+
+extern "C" int odise_hip_instance_eval(odise_hip_ctx* ctx, const odise_inst_eval_desc* d) {
+    ODISE_REQUIRE(ctx && d, "instance_eval: null argument");
+    ODISE_REQUIRE(d->inst_table && d->inst_scores && d->iou_thresholds && d->rows && d->n_rows && d->flags, "instance_eval: null pointer");
+    ODISE_REQUIRE(d->topk >= 1 && d->topk <= kInstMaxDet, "instance_eval: topk %d (1..%d)", d->topk, kInstMaxDet);
+    ODISE_REQUIRE(d->n_gt >= 0 && d->n_gt <= kInstMaxGt, "instance_eval: %d ground-truth masks (0..%d)", d->n_gt, kInstMaxGt);
+    ODISE_REQUIRE(d->n_gt == 0 || (d->gt_runs && d->gt_offsets && d->gt_rows), "instance_eval: null ground truth");
+    ODISE_REQUIRE(d->num_categories >= 1, "instance_eval: num_categories %d", d->num_categories);
+    ODISE_REQUIRE(d->h >= 1 && d->w >= 1 && (int64_t)d->h * d->w <= kRleMaxPixels, "instance_eval: mask size %dx%d out of range", d->h, d->w);
+    ODISE_REQUIRE(!d->masks || d->dtype == ODISE_F32 || d->dtype == ODISE_U8, "instance_eval: dtype %d (ODISE_F32 or ODISE_U8)", d->dtype);
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    PostGeom g;
+    const f16* logits = nullptr;
+    if (!d->masks) ODISE_TRY(rle_instance_geom(ctx, "instance_eval", d->b, d->pad_h, d->pad_w, d->img_h, d->img_w, d->h, d->w, &g, &logits));
+    const RleGrid G = rle_grid(d->h, d->w);
+    InstScratch s;
+    ODISE_TRY(inst_scratch(ctx, d->topk, d->n_gt, G, &s));
+    ODISE_CHECK_HIP(hipMemsetAsync(s.inter, 0, s.inter_bytes, ctx->stream));
+    int* status = s.inter + (size_t)d->topk * d->n_gt;
+    if (d->masks) ODISE_TRY(rle_pack_dense(ctx, d->masks, d->dtype, d->topk, G, s.words_d));
+    else ODISE_TRY(rle_pack_logits(ctx, logits, (const int*)d->inst_table, d->topk, g, G, s.words_d));
+    ODISE_TRY(inst_overlaps(ctx, s, G, d->topk, d->gt_runs, d->gt_offsets, d->n_gt, status));
+    InstMatchArgs A;
+    A.inst_table = (const int*)d->inst_table; A.inst_scores = d->inst_scores; A.gt_rows = (const int*)d->gt_rows;
+    A.inter = s.inter; A.area = s.area; A.status = status;
+    A.rows = d->rows; A.n_rows = (int*)d->n_rows; A.flags = (int*)d->flags;
+    A.topk = d->topk; A.n_gt = d->n_gt; A.num_categories = d->num_categories; A.image = d->image;
+    for (int t = 0; t < 10; ++t) A.thr[t] = d->iou_thresholds[t];
+    hipLaunchKernelGGL(inst_match_kernel, dim3(1), dim3(kRleThreads), 0, ctx->stream, A);
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}

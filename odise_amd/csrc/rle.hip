@@ -19,18 +19,10 @@
 // Integer scans only, no atomics: the output is deterministic.
 #include <string.h>
 
-#include "engine.h"
-#include "post_sample.h"
+#include "rle_pack.h"   // RleGrid, kRleThreads, block_scan_sum: shared with inst_eval.hip
 
 namespace odise {
 
-constexpr int kRleThreads = 1024;          // count / write: one block per mask (16 waves)
-constexpr int64_t kRleMaxPixels = 1 << 30; // per mask (the post-processing's own output limit); positions stay in int
-
-struct RleGrid {
-    int h, w, R;      // mask size, words per column
-    int64_t nw;       // words per mask = w * R
-};
 struct RleTail {      // transitions of a range of words and the last three of their positions (q2 the newest; -1 where fewer)
     int c, q0, q1, q2;
 };
@@ -48,7 +40,7 @@ __device__ __forceinline__ RleTail tail_cat(const RleTail& l, const RleTail& r) 
     return o;
 }
 
-// exclusive block scans over the 1024 threads (wave scan by shuffles, then the 16 wave totals through LDS)
+// exclusive block scan over the 1024 threads (wave scan by shuffles, then the 16 wave totals through LDS); the sum form is in rle_pack.h
 __device__ RleTail block_scan_tail(const RleTail& v, RleTail* lds) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     RleTail inc = v;
@@ -68,26 +60,6 @@ __device__ RleTail block_scan_tail(const RleTail& v, RleTail* lds) {
     __syncthreads();
     return tail_cat(pre, ex);
 }
-__device__ long long block_scan_sum(long long v, long long* lds, long long& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    long long inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const long long u = __shfl_up(inc, o);
-        if (lane >= o) inc += u;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    long long pre = 0;
-    total = 0;
-    for (int k = 0; k < kRleThreads / 64; ++k) {
-        if (k < wave) pre += lds[k];
-        total += lds[k];
-    }
-    __syncthreads();
-    return pre + inc - v;
-}
-
 // f(position) for every transition in words [a, b) of one mask, in order; returns the ones in the range.  The words are loaded kRleBatch at a
 // time (independent loads in flight): one load per loop trip made the walk a chain of memory latencies.
 constexpr int kRleBatch = 8;
@@ -279,11 +251,41 @@ __global__ void __launch_bounds__(kRleThreads) rle_write_kernel(const unsigned l
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
-static RleGrid rle_grid(int h, int w) {
-    RleGrid G;
-    G.h = h; G.w = w; G.R = (int)ceil_div(h, 64);
-    G.nw = (int64_t)w * G.R;
-    return G;
+int rle_pack_dense(odise_hip_ctx* ctx, const void* masks, int dtype, int n, const RleGrid& G, unsigned long long* words) {
+    const dim3 grid((unsigned)ceil_div(G.nw, 256), (unsigned)n);
+    if (dtype == ODISE_F32) hipLaunchKernelGGL(rle_pack_dense_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)masks, words, G);
+    else hipLaunchKernelGGL(rle_pack_dense_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, (const uint8_t*)masks, words, G);
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}
+
+int rle_instance_geom(odise_hip_ctx* ctx, const char* what, int b, int pad_h, int pad_w, int img_h, int img_w, int out_h, int out_w, PostGeom* g,
+                      const f16** logits) {
+    ModelStore* ms = store_of(ctx);
+    HeadOutputs ho;
+    ODISE_TRY(head_outputs(ms, &ho));
+    ODISE_REQUIRE(b >= 0 && b < ho.B, "%s: image index %d out of range", what, b);
+    ODISE_REQUIRE(pad_h == 4 * ho.h4 && pad_w == 4 * ho.w4, "%s: padded size %dx%d does not match the mask logits (%dx%d x 4)", what, pad_h, pad_w,
+                  ho.h4, ho.w4);
+    ODISE_REQUIRE(img_h >= 1 && img_w >= 1 && img_h <= pad_h && img_w <= pad_w && out_h >= 1 && out_w >= 1 && (int64_t)out_h * out_w <= kRleMaxPixels,
+                  "%s: bad geometry (image %dx%d, padded %dx%d, output %dx%d)", what, img_h, img_w, pad_h, pad_w, out_h, out_w);
+    g->h4 = ho.h4; g->w4 = ho.w4; g->ph = pad_h; g->pw = pad_w; g->ih = img_h; g->iw = img_w; g->oh = out_h; g->ow = out_w;
+    g->Q = ho.Q; g->Qpad = (int)round_up(ho.Q, 8);
+    *logits = ho.pred_masks + (size_t)b * ho.Q * ho.h4 * ho.w4;
+    return ODISE_OK;
+}
+
+int rle_pack_logits(odise_hip_ctx* ctx, const f16* logits, const int* inst_table, int topk, const PostGeom& g, const RleGrid& G,
+                    unsigned long long* words) {
+    if (instance_masks_x4(g)) {
+        const dim3 grid((unsigned)ceil_div((int64_t)G.R * (g.ow / 4), 256), (unsigned)topk);
+        hipLaunchKernelGGL(rle_pack_x4_kernel, grid, dim3(256), 0, ctx->stream, logits, inst_table + 1, words, g, G, inst_table);
+    } else {
+        const dim3 grid((unsigned)ceil_div(G.nw, 256), (unsigned)topk);
+        hipLaunchKernelGGL(rle_pack_generic_kernel, grid, dim3(256), 0, ctx->stream, logits, inst_table + 1, words, g, G, inst_table);
+    }
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
 }
 
 struct RleScratch {
@@ -338,10 +340,7 @@ extern "C" int odise_hip_rle_encode(odise_hip_ctx* ctx, const void* masks, int d
     const RleGrid G = rle_grid(h, w);
     RleScratch s;
     ODISE_TRY(rle_scratch(ctx, n, G, &s));
-    const dim3 grid((unsigned)ceil_div(G.nw, 256), (unsigned)n);
-    if (dtype == ODISE_F32) hipLaunchKernelGGL(rle_pack_dense_kernel<float>, grid, dim3(256), 0, ctx->stream, (const float*)masks, s.words, G);
-    else hipLaunchKernelGGL(rle_pack_dense_kernel<uint8_t>, grid, dim3(256), 0, ctx->stream, (const uint8_t*)masks, s.words, G);
-    ODISE_CHECK_HIP(hipGetLastError());
+    ODISE_TRY(rle_pack_dense(ctx, masks, dtype, n, G, s.words));
     return rle_finish(ctx, s, G, n, rle, capacity, offsets, area, nullptr);
 }
 
@@ -351,28 +350,12 @@ extern "C" int odise_hip_instance_rle(odise_hip_ctx* ctx, int b, const int* inst
     ODISE_REQUIRE(topk >= 1 && topk <= 4096, "instance_rle: topk %d out of range", topk);
     ODISE_REQUIRE(capacity >= 0 && (rle || capacity == 0), "instance_rle: capacity %lld without an output buffer", (long long)capacity);
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    ModelStore* ms = store_of(ctx);
-    HeadOutputs ho;
-    ODISE_TRY(head_outputs(ms, &ho));
-    ODISE_REQUIRE(b >= 0 && b < ho.B, "instance_rle: image index %d out of range", b);
-    ODISE_REQUIRE(pad_h == 4 * ho.h4 && pad_w == 4 * ho.w4, "instance_rle: padded size %dx%d does not match the mask logits (%dx%d x 4)", pad_h,
-                  pad_w, ho.h4, ho.w4);
-    ODISE_REQUIRE(img_h >= 1 && img_w >= 1 && img_h <= pad_h && img_w <= pad_w && out_h >= 1 && out_w >= 1 && (int64_t)out_h * out_w <= kRleMaxPixels,
-                  "instance_rle: bad geometry (image %dx%d, padded %dx%d, output %dx%d)", img_h, img_w, pad_h, pad_w, out_h, out_w);
     PostGeom g;
-    g.h4 = ho.h4; g.w4 = ho.w4; g.ph = pad_h; g.pw = pad_w; g.ih = img_h; g.iw = img_w; g.oh = out_h; g.ow = out_w;
-    g.Q = ho.Q; g.Qpad = (int)round_up(ho.Q, 8);
+    const f16* logits = nullptr;
+    ODISE_TRY(rle_instance_geom(ctx, "instance_rle", b, pad_h, pad_w, img_h, img_w, out_h, out_w, &g, &logits));
     const RleGrid G = rle_grid(out_h, out_w);
     RleScratch s;
     ODISE_TRY(rle_scratch(ctx, topk, G, &s));
-    const f16* logits = ho.pred_masks + (size_t)b * ho.Q * ho.h4 * ho.w4;
-    if (instance_masks_x4(g)) {
-        const dim3 grid((unsigned)ceil_div((int64_t)G.R * (out_w / 4), 256), (unsigned)topk);
-        hipLaunchKernelGGL(rle_pack_x4_kernel, grid, dim3(256), 0, ctx->stream, logits, inst_table + 1, s.words, g, G, inst_table);
-    } else {
-        const dim3 grid((unsigned)ceil_div(G.nw, 256), (unsigned)topk);
-        hipLaunchKernelGGL(rle_pack_generic_kernel, grid, dim3(256), 0, ctx->stream, logits, inst_table + 1, s.words, g, G, inst_table);
-    }
-    ODISE_CHECK_HIP(hipGetLastError());
+    ODISE_TRY(rle_pack_logits(ctx, logits, inst_table, topk, g, G, s.words));
     return rle_finish(ctx, s, G, topk, rle, capacity, offsets, area, inst_table);
 }

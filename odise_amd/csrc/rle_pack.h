@@ -1,0 +1,58 @@
+// rle_pack.h — what rle.hip (COCO RLE strings) and inst_eval.hip (mask IoU and segm matching) share: the bit-packed mask layout, the block
+// scan and the launchers of the pack kernels (defined in rle.hip, compiled once).
+//   word (x, r) of a mask holds pixels (64 r .. 64 r + 63, x), bit k = row 64 r + k, stored [n][w][R], R = ceil(h / 64): the words of a
+//   mask are consecutive pieces of the column-major order j = x * h + y.
+#pragma once
+#include "engine.h"
+#include "post_sample.h"
+
+namespace odise {
+
+constexpr int kRleThreads = 1024;          // one block per mask (16 waves)
+constexpr int64_t kRleMaxPixels = 1 << 30; // per mask (the post-processing's own output limit); positions stay in int
+
+struct RleGrid {
+    int h, w, R;      // mask size, words per column
+    int64_t nw;       // words per mask = w * R
+};
+static inline RleGrid rle_grid(int h, int w) {
+    RleGrid G;
+    G.h = h; G.w = w; G.R = (int)ceil_div(h, 64);
+    G.nw = (int64_t)w * G.R;
+    return G;
+}
+
+// exclusive block scan of a sum over kRleThreads threads (wave scan by shuffles, then the 16 wave totals through LDS); ends in a barrier
+__device__ inline long long block_scan_sum(long long v, long long* lds, long long& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long long inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const long long u = __shfl_up(inc, o);
+        if (lane >= o) inc += u;
+    }
+    if (lane == 63) lds[wave] = inc;
+    __syncthreads();
+    long long pre = 0;
+    total = 0;
+    for (int k = 0; k < kRleThreads / 64; ++k) {
+        if (k < wave) pre += lds[k];
+        total += lds[k];
+    }
+    __syncthreads();
+    return pre + inc - v;
+}
+
+// words [n][G.nw] of n dense masks [n, h, w] (ODISE_F32 / ODISE_U8; any nonzero value is 1), on the context's stream
+int rle_pack_dense(odise_hip_ctx* ctx, const void* masks, int dtype, int n, const RleGrid& G, unsigned long long* words);
+
+// The instance selection of image b of the last head forward: checks the geometry (the errors carry `what`), fills the sampling geometry
+// and the image's mask logits.
+int rle_instance_geom(odise_hip_ctx* ctx, const char* what, int b, int pad_h, int pad_w, int img_h, int img_w, int out_h, int out_w, PostGeom* g,
+                      const f16** logits);
+// words [topk][G.nw] of the selection inst_table = n | query index [topk] | .., sampled from the mask logits with the taps of
+// instance_masks(_x4)_kernel; masks past the count n (read on the device) are not written
+int rle_pack_logits(odise_hip_ctx* ctx, const f16* logits, const int* inst_table, int topk, const PostGeom& g, const RleGrid& G,
+                    unsigned long long* words);
+
+}  // namespace odise

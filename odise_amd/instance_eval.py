@@ -1,0 +1,255 @@
+"""Host restatement of the segm evaluation of instance masks (numpy): the reference of `Context.mask_iou` / `Context.instance_eval`
+(csrc/inst_eval.hip) and the metric arithmetic of InstanceSegEvaluator / COCOEvaluator(tasks=("segm",)), which stays on the host.
+
+`image_rows` is pycocotools' `COCOeval.evaluateImg` for iouType "segm", useCats = 1 and maxDets 100, written the way it is written there -
+Python loops over the detections and the ground truths sorted by ignore - for all four area ranges and the ten IoU thresholds at once:
+
+    iou                      maskApi.c rleIou on exact pixel counts: inter == 0 -> 0, a crowd ground truth -> inter / area_d, otherwise
+                             inter / (area_d + area_g - inter)
+    detections               of a category in descending score, ties in table order (mergesort on -score)
+    ground truths            ignore = iscrowd or the annotation's area outside the range; non-ignored first, each group in annotation order
+    matching                 best = min(t, 1 - 1e-10); a ground truth already matched that is no crowd is skipped; the walk stops at the
+                             first ignored one once a non-ignored match is held; iou < best is skipped; otherwise the match moves there
+    ignored detections       a matched one takes the ignore bit of its ground truth, an unmatched one is ignored when its own area (the
+                             pixels of its mask) lies outside the range
+
+What it keeps of a detection is one `ROW_DTYPE` record (odise_inst_eval_row): score, category, area, image and the matched / ignored
+bits of the 40 (range a, threshold t) cells, bit 10 a + t.  `accumulate` is `COCOeval.accumulate` over such rows and the count of
+non-ignored ground truths per (category, range), `summarize` the twelve COCO numbers, `results` detectron2's dict.
+
+Ground truth is RLE only (compressed or uncompressed); polygons (`rleFrPoly`) are not rasterised here: whoever holds the annotations
+converts them.  ADE20K's instance annotations are RLE already.
+"""
+from __future__ import annotations
+
+from typing import Dict, Sequence
+
+import numpy as np
+
+from . import coco_rle
+
+# odise_inst_eval_row (include/odise_hip.h)
+ROW_DTYPE = np.dtype([("score", "<f4"), ("category", "<i4"), ("area", "<i4"), ("image", "<i4"), ("matched", "<u8"), ("ignored", "<u8")])
+IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)     # cocoeval.Params.setDetParams
+REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+MAX_DETS = (1, 10, 100)
+AREA_RNG = ((0 ** 2, 1e5 ** 2), (0 ** 2, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e5 ** 2))    # all, small, medium, large; ends included
+MAX_DETECTIONS, MAX_GT = 100, 1024
+FLAG_BAD_RUNS, FLAG_BAD_CLASS, FLAG_BAD_GT = 1, 2, 4
+FLAG_NAMES = {FLAG_BAD_RUNS: "the run lengths of a ground-truth mask do not sum to h * w",
+              FLAG_BAD_CLASS: "a predicted class is outside [0, num_categories)",
+              FLAG_BAD_GT: "a ground-truth category is outside [0, num_categories) or iscrowd is not 0 / 1"}
+
+
+def flag_names(flags: int) -> list:
+    return [name for bit, name in FLAG_NAMES.items() if flags & bit]
+
+
+# ---- masks --------------------------------------------------------------------------------------------------------------------------------
+def decode_runs(counts, h: int, w: int) -> np.ndarray:
+    """uint8 [h, w] mask of uncompressed run lengths over the column-major order (zeros first, alternating; zero-length runs anywhere).
+    Counts that do not sum to h * w are what flag 1 reports: the missing tail is zeros, what lies past the end is dropped."""
+    cnts = np.asarray(counts, np.int64).reshape(-1)
+    vals = (np.arange(cnts.size) & 1).astype(np.uint8)
+    flat = np.repeat(vals, cnts)[: h * w]
+    flat = np.concatenate([flat, np.zeros(h * w - flat.size, np.uint8)])
+    return flat.reshape((h, w), order="F")
+
+
+def rle_iou(inter: int, area_d: int, area_g: int, crowd: bool) -> float:
+    if inter == 0:
+        return 0.0
+    return float(np.float64(inter) / np.float64(area_d)) if crowd else float(np.float64(inter) / np.float64(area_d + area_g - inter))
+
+
+def mask_iou(dense_masks, gt_counts, iscrowd=None) -> np.ndarray:
+    """float64 [n, n_gt]: pycocotools' mask.iou of dense masks [n, h, w] (nonzero = 1) against run-length masks."""
+    d = np.asarray(dense_masks) != 0
+    n, h, w = d.shape
+    g = np.stack([decode_runs(c, h, w) for c in gt_counts]).astype(bool) if len(gt_counts) else np.zeros((0, h, w), bool)
+    crowd = np.zeros(len(g), bool) if iscrowd is None else np.asarray(iscrowd).astype(bool)
+    area_d, area_g = d.reshape(n, h * w).sum(1), g.reshape(len(g), h * w).sum(1)
+    out = np.zeros((n, len(g)), np.float64)
+    for i in range(n):
+        for j in range(len(g)):
+            out[i, j] = rle_iou(int(np.count_nonzero(d[i] & g[j])), int(area_d[i]), int(area_g[j]), bool(crowd[j]))
+    return out
+
+
+# ---- ground truth -------------------------------------------------------------------------------------------------------------------------
+def annotation_counts(segmentation) -> np.ndarray:
+    """Uncompressed counts of an RLE dict: `counts` a compressed string / bytes or a list of run lengths."""
+    c = segmentation["counts"]
+    if isinstance(c, (bytes, bytearray)):
+        c = c.decode("utf-8")
+    return coco_rle.string_to_counts(c) if isinstance(c, str) else np.asarray(c, np.int64)
+
+
+def gt_rows(annotations, to_contiguous: Dict[int, int]):
+    """The annotation dicts of a picture (category_id as in the dataset, iscrowd, area, segmentation = RLE dict) ->
+    (rows int32 [n_gt, 3] = contiguous category | iscrowd | bits 0..3: area outside range a, runs uint32 (all masks back to back),
+    offsets int64 [n_gt + 1]).  The area is the annotation's float `area` (the evaluator compares that, not the mask); without one, the
+    pixels of the mask."""
+    rows = np.zeros((len(annotations), 3), np.int32)
+    runs, offsets = [], [0]
+    for i, ann in enumerate(annotations):
+        seg = ann["segmentation"]
+        if not isinstance(seg, dict):
+            raise ValueError("instance evaluation takes RLE ground truth; convert polygon annotations to RLE first")
+        cnts = annotation_counts(seg)
+        area = float(ann["area"]) if "area" in ann else float(cnts[1::2].sum())
+        outside = sum(1 << a for a, (lo, hi) in enumerate(AREA_RNG) if area < lo or area > hi)
+        rows[i] = (to_contiguous[int(ann["category_id"])], int(ann.get("iscrowd", 0)), outside)
+        runs.append(np.asarray(cnts, np.uint32))
+        offsets.append(offsets[-1] + len(cnts))
+    return rows, (np.concatenate(runs) if runs else np.zeros(0, np.uint32)), np.asarray(offsets, np.int64)
+
+
+def npig(rows, K: int) -> np.ndarray:
+    """int64 [K, 4]: the ground truths of a category that are not ignored in range a (no crowd, area inside)."""
+    out = np.zeros((K, 4), np.int64)
+    for cat, crowd, outside in np.asarray(rows, np.int64).reshape(-1, 3):
+        for a in range(4):
+            if not crowd and not (outside >> a) & 1:
+                out[cat, a] += 1
+    return out
+
+
+# ---- evaluateImg --------------------------------------------------------------------------------------------------------------------------
+def area_outside(area, a: int) -> bool:
+    return bool(area < AREA_RNG[a][0] or area > AREA_RNG[a][1])
+
+
+def image_rows(masks, scores, classes, gt_counts, gt_table, image: int = 0, iou_thrs=IOU_THRS, num_categories=None):
+    """COCOeval.evaluateImg of one picture -> (rows ROW_DTYPE [n] in descending score, flags).  masks [n, h, w] (nonzero = 1), n <= 100;
+    gt_counts: the run lengths of every ground truth; gt_table: `gt_rows`' table.  A picture that raises a flag has no rows."""
+    d = np.asarray(masks) != 0
+    n, h, w = d.shape
+    scores, classes = np.asarray(scores, np.float32).reshape(-1), np.asarray(classes, np.int64).reshape(-1)
+    table = np.asarray(gt_table, np.int64).reshape(-1, 3)
+    n_gt = len(table)
+    assert n <= MAX_DETECTIONS and len(scores) >= n and len(classes) >= n and len(gt_counts) == n_gt
+    flags = 0
+    if any(int(np.asarray(c, np.int64).sum()) != h * w for c in gt_counts):
+        flags |= FLAG_BAD_RUNS
+    if num_categories is not None:
+        if n and (classes[:n].min() < 0 or classes[:n].max() >= num_categories):
+            flags |= FLAG_BAD_CLASS
+        if n_gt and (table[:, 0].min() < 0 or table[:, 0].max() >= num_categories):
+            flags |= FLAG_BAD_GT
+    if n_gt and not np.isin(table[:, 1], (0, 1)).all():
+        flags |= FLAG_BAD_GT
+    if flags:
+        return np.zeros(0, ROW_DTYPE), flags
+    ious = mask_iou(d, gt_counts, table[:, 1])
+    order = np.argsort(-scores[:n], kind="mergesort")
+    rows = np.zeros(n, ROW_DTYPE)
+    rows["score"], rows["category"], rows["image"] = scores[order], classes[order], image
+    rows["area"] = d.reshape(n, h * w).sum(1)[order]
+    pos = {int(dd): k for k, dd in enumerate(order)}
+    for c in np.unique(classes[:n]):
+        dt = [int(i) for i in order if classes[i] == c]
+        gt_c = [j for j in range(n_gt) if table[j, 0] == c]
+        for a in range(4):
+            ignore = [bool(table[j, 1]) or bool((table[j, 2] >> a) & 1) for j in gt_c]
+            gtind = np.argsort(np.asarray(ignore, np.int64), kind="mergesort") if gt_c else []
+            gt = [gt_c[i] for i in gtind]
+            gt_ig = [ignore[i] for i in gtind]
+            crowd = [bool(table[j, 1]) for j in gt]
+            for t, thr in enumerate(iou_thrs):
+                gtm = [False] * len(gt)
+                for i in dt:
+                    iou = min(float(thr), 1 - 1e-10)
+                    m = -1
+                    for gind, j in enumerate(gt):
+                        if gtm[gind] and not crowd[gind]:      # already matched, and not a crowd
+                            continue
+                        if m > -1 and not gt_ig[m] and gt_ig[gind]:   # a regular match is held and only ignored ones follow
+                            break
+                        if ious[i, j] < iou:
+                            continue
+                        iou = ious[i, j]
+                        m = gind
+                    bit = np.uint64(1 << (10 * a + t))
+                    if m > -1:
+                        gtm[m] = True
+                        rows["matched"][pos[i]] |= bit
+                        ig = gt_ig[m]
+                    else:
+                        ig = area_outside(int(rows["area"][pos[i]]), a)
+                    if ig:
+                        rows["ignored"][pos[i]] |= bit
+    return rows, 0
+
+
+# ---- accumulate / summarize ---------------------------------------------------------------------------------------------------------------
+def accumulate(rows, npig_ka, K: int):
+    """COCOeval.accumulate for maxDets (1, 10, 100) and recThrs linspace(0, 1, 101) -> (precision [T, R, K, A, M], recall [T, K, A, M]),
+    -1 where a (category, range) has no non-ignored ground truth.  rows: ROW_DTYPE of any number of pictures, every picture's rows in
+    descending score; they are ordered by `image` first (stable), so the result does not depend on how the pictures were sharded."""
+    rows = np.asarray(rows, ROW_DTYPE).reshape(-1)
+    rows = rows[np.argsort(rows["image"], kind="stable")]
+    npig_ka = np.asarray(npig_ka, np.int64).reshape(K, 4)
+    T, R, A, M = len(IOU_THRS), len(REC_THRS), 4, len(MAX_DETS)
+    precision, recall = -np.ones((T, R, K, A, M)), -np.ones((T, K, A, M))
+    for k in range(K):
+        rk = rows[rows["category"] == k]
+        first = np.flatnonzero(np.r_[True, rk["image"][1:] != rk["image"][:-1]]) if len(rk) else np.zeros(0, np.int64)
+        rank = np.arange(len(rk)) - np.repeat(first, np.diff(np.r_[first, len(rk)]))         # position among the picture's rows of category k
+        for mi, max_det in enumerate(MAX_DETS):
+            sel = rk[rank < max_det]
+            sel = sel[np.argsort(-sel["score"], kind="mergesort")]
+            for a in range(A):
+                n_pos = int(npig_ka[k, a])
+                if n_pos == 0:
+                    continue
+                for t in range(T):
+                    bit = np.uint64(10 * a + t)
+                    dtm = ((sel["matched"] >> bit) & np.uint64(1)).astype(bool)
+                    dt_ig = ((sel["ignored"] >> bit) & np.uint64(1)).astype(bool)
+                    tp = np.cumsum(dtm & ~dt_ig).astype(np.float64)
+                    fp = np.cumsum(~dtm & ~dt_ig).astype(np.float64)
+                    nd = len(tp)
+                    rc = tp / n_pos
+                    pr = tp / (fp + tp + np.spacing(1))
+                    recall[t, k, a, mi] = rc[-1] if nd else 0
+                    pr = np.maximum.accumulate(pr[::-1])[::-1] if nd else pr       # the right-to-left running maximum
+                    q = np.zeros(R)
+                    inds = np.searchsorted(rc, REC_THRS, side="left")
+                    ok = inds < nd                                                  # entries past the end stay 0
+                    q[ok] = pr[inds[ok]]
+                    precision[t, :, k, a, mi] = q
+    return precision, recall
+
+
+def _mean_valid(s: np.ndarray) -> float:
+    s = s[s > -1]
+    return float(np.mean(s)) if s.size else -1.0
+
+
+def summarize(precision, recall) -> np.ndarray:
+    """COCOeval.summarize: AP, AP50, AP75, APs, APm, APl (maxDets 100), AR at maxDets 1 / 10 / 100, ARs, ARm, ARl (maxDets 100)."""
+    t50, t75 = int(np.flatnonzero(np.isclose(IOU_THRS, .5))[0]), int(np.flatnonzero(np.isclose(IOU_THRS, .75))[0])
+    s = np.zeros(12)
+    s[0] = _mean_valid(precision[:, :, :, 0, 2])
+    s[1] = _mean_valid(precision[t50:t50 + 1, :, :, 0, 2])
+    s[2] = _mean_valid(precision[t75:t75 + 1, :, :, 0, 2])
+    for i, a in enumerate((1, 2, 3)):
+        s[3 + i] = _mean_valid(precision[:, :, :, a, 2])
+        s[9 + i] = _mean_valid(recall[:, :, a, 2])
+    for i in range(3):
+        s[6 + i] = _mean_valid(recall[:, :, 0, i])
+    return s
+
+
+def results(precision, recall, class_names: Sequence[str]) -> dict:
+    """detectron2 COCOEvaluator._derive_coco_results for "segm": AP, AP50, AP75, APs, APm, APl (x 100, NaN where nothing is > -1) and
+    AP-<class name> per category."""
+    s = summarize(precision, recall)
+    out = {name: float(s[i] * 100) if s[i] >= 0 else float("nan") for i, name in enumerate(("AP", "AP50", "AP75", "APs", "APm", "APl"))}
+    assert len(class_names) == precision.shape[2], (len(class_names), precision.shape)
+    for k, name in enumerate(class_names):
+        p = precision[:, :, k, 0, -1]
+        p = p[p > -1]
+        out["AP-" + name] = float(np.mean(p) * 100) if p.size else float("nan")
+    return out

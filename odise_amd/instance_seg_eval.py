@@ -1,0 +1,96 @@
+"""InstanceSegEvaluator / COCOEvaluator(tasks=("segm",)) (odise/evaluation/d2_evaluator.py:29,104) on the device: `process` enqueues one
+`odise_hip_instance_eval` per picture on the instance selection of `odise_hip_infer` - the masks are sampled from the mask logits, matched
+against the ground truth and reduced to one 32-byte row per detection, no RLE string and no JSON - and `evaluate` reads the rows back
+once, gathers them across ranks and does COCOeval.accumulate / summarize on the host (odise_amd/instance_eval.py).
+
+Ground truth is RLE (compressed or uncompressed) only: polygon annotations have to be converted by whoever holds them."""
+from __future__ import annotations
+
+from typing import Dict, Sequence
+
+import numpy as np
+
+from . import distributed as D
+from . import instance_eval as IE
+from .runtime import Context, DeviceArray
+
+
+class HipInstanceSegEvaluator:
+    CHUNK = 64          # pictures per block of the row buffer: it grows by whole blocks, rows already written stay where they are
+
+    def __init__(self, ctx: Context, thing_dataset_id_to_contiguous_id: Dict[int, int], class_names: Sequence[str], topk: int = 100):
+        """thing_dataset_id_to_contiguous_id: the annotation's category ids -> 0..K-1, the space the model's pred_classes live in;
+        class_names [K] per contiguous id; topk: the model's test_topk_per_image (at most 100, COCOeval's last maxDets)."""
+        self.ctx = ctx
+        self.to_contiguous = {int(k): int(v) for k, v in thing_dataset_id_to_contiguous_id.items()}
+        self.class_names = list(class_names)
+        self.K, self.topk = len(self.class_names), int(topk)
+        assert all(0 <= v < self.K for v in self.to_contiguous.values()), "contiguous ids must lie in [0, len(class_names))"
+        assert 1 <= self.topk <= IE.MAX_DETECTIONS, self.topk
+        self.flags = ctx.zeros((1,), np.int32)
+        self.reset()
+
+    def reset(self) -> None:
+        from ._lib import check
+        check(self.ctx.lib.odise_hip_memset(self.ctx.h, self.flags.ptr, 0, 4), "memset")
+        self._chunks, self._pictures = [], 0
+        self._npig = np.zeros((self.K, 4), np.int64)
+
+    def _slot(self):
+        """(rows [topk], n_rows [1]) of the next picture."""
+        i = self._pictures % self.CHUNK
+        if i == 0:
+            self._chunks.append((self.ctx.empty((self.CHUNK * self.topk,), IE.ROW_DTYPE), self.ctx.zeros((self.CHUNK,), np.int32)))
+        rows, counts = self._chunks[-1]
+        self._pictures += 1
+        return rows.view((self.topk,), IE.ROW_DTYPE, i * self.topk * IE.ROW_DTYPE.itemsize), counts.view((1,), np.int32, 4 * i)
+
+    def process(self, b: int, inst_table_row, inst_scores_row, pad_hw, img_hw, out_hw, annotations, image_index: int, pred_masks=None) -> None:
+        """One picture: inst_table_row [1 + 2 topk] / inst_scores_row [topk] = image b's rows of the device instance table of the last
+        call (HipCategoryODISE.keep_instance_selection -> last_selection), pad_hw / img_hw / out_hw as in `Context.instance_rle`;
+        annotations: the picture's dicts (category_id as in the dataset, iscrowd, area, segmentation = RLE dict); image_index: any number
+        that orders the pictures the same way on every run (the position in the dataset).  With `pred_masks` (DeviceArray [topk, h, w],
+        float32 or uint8) the detections are those dense masks instead of the mask logits.
+        The ground truth goes up as one packed upload, which WAITS for the stream, and the temporary is freed on return by the library's
+        synchronising free - which is also what keeps it alive until the kernels have read it.  The kernels themselves never wait."""
+        table, runs, offsets = IE.gt_rows(annotations, self.to_contiguous)
+        assert len(table) <= IE.MAX_GT, f"{len(table)} ground-truth masks in one picture (at most {IE.MAX_GT})"
+        self._npig += IE.npig(table, self.K)
+        gt = self.ctx.instance_gt_to_device(table, runs, offsets)
+        rows, n_rows = self._slot()
+        self.ctx.instance_eval(out_hw, inst_table_row, inst_scores_row, self.topk, gt, self.K, int(image_index), rows, n_rows, self.flags,
+                               masks=pred_masks, b=b, pad_hw=pad_hw, img_hw=img_hw)
+
+    def process_selection(self, selection: dict, annotations_per_image, image_indices) -> None:
+        """`process` for every picture of a batch from `HipCategoryODISE.last_selection`."""
+        topk = selection["topk"]
+        assert topk == self.topk, (topk, self.topk)
+        for b, (anns, idx) in enumerate(zip(annotations_per_image, image_indices)):
+            self.process(b, selection["inst_table"].view((1 + 2 * topk,), np.int32, b * (1 + 2 * topk) * 4),
+                         selection["inst_scores"].view((topk,), np.float32, b * topk * 4), selection["pad_hw"], selection["img_hw"][b],
+                         selection["out_hw"][b], anns, idx)
+
+    def rows(self) -> np.ndarray:
+        """This rank's rows so far (one read per block of pictures)."""
+        out = []
+        for c, (rows, counts) in enumerate(self._chunks):
+            host, n = rows.numpy().reshape(self.CHUNK, self.topk), counts.numpy()
+            used = min(self.CHUNK, self._pictures - c * self.CHUNK)
+            out += [host[i, :n[i]] for i in range(used)]
+        return np.concatenate(out) if out else np.zeros(0, IE.ROW_DTYPE)
+
+    def evaluate(self) -> dict:
+        import torch
+        import torch.distributed as dist
+        rows, flags, npig = self.rows(), int(self.flags.numpy()[0]), self._npig
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            parts = [None] * dist.get_world_size()
+            dist.all_gather_object(parts, (rows, flags))
+            rows = np.concatenate([p[0] for p in parts])
+            for p in parts:
+                flags |= int(p[1])                                           # every rank raises when any rank saw a flag
+            npig = D.sum_confusion(torch.from_numpy(npig.copy())).numpy()
+        if flags:
+            raise RuntimeError("instance evaluation: malformed input(s): " + "; ".join(IE.flag_names(flags)))
+        self.precision, self.recall = IE.accumulate(rows, npig, self.K)
+        return IE.results(self.precision, self.recall, self.class_names)

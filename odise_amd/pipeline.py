@@ -140,6 +140,8 @@ class HipCategoryODISE(HipODISE):
         self.semantic_on, self.panoptic_on, self.instance_on = semantic_on, panoptic_on, instance_on
         self.semantic_argmax = False          # True: "sem_seg_argmax" int32 [h,w] instead of "sem_seg" [K,h,w] (never materialised)
         self.instance_rle = False             # True: "pred_masks_rle" (COCO RLE strings, encoded from the mask logits) instead of "pred_masks" [n,h,w]
+        self.keep_instance_selection = False  # True: `last_selection` = the device inst_table / inst_scores of the last call (HipInstanceSegEvaluator.process)
+        self.last_selection = None
         self.object_mask_threshold, self.overlap_threshold = object_mask_threshold, overlap_threshold
         self.test_topk_per_image, self.size_divisibility = test_topk_per_image, size_divisibility
         assert size_divisibility == 64, "the feature extractor fixes size_divisibility at 64 (feature_extractor.py:126-128)"
@@ -325,6 +327,14 @@ class HipCategoryODISE(HipODISE):
                                                     grow=grow))
         bufs["rle"] = pend
 
+    def _keep_selection(self, bufs, pad_hw, img_hw, out_sizes) -> None:
+        """keep_instance_selection: what an evaluator needs to go on from the selection on the same stream, nothing read back.  The buffers
+        are the pooled ones: they hold this batch until the next call."""
+        if self.instance_on and self.keep_instance_selection:
+            self.last_selection = {"inst_table": bufs["itable"], "inst_scores": bufs["iscores"], "topk": int(self.test_topk_per_image),
+                                   "pad_hw": (int(pad_hw[0]), int(pad_hw[1])), "img_hw": [tuple(int(v) for v in s) for s in img_hw],
+                                   "out_hw": [tuple(int(v) for v in s) for s in out_sizes]}
+
     def _collect(self, bufs, out_sizes, to_host: bool) -> list:
         """Read the small tables back (one synchronisation) and assemble the reference's result dicts."""
         from ._lib import MAX_SEGMENTS
@@ -372,6 +382,7 @@ class HipCategoryODISE(HipODISE):
         d.B, d.pad_h, d.pad_w, d.img_hw, d.mask_cls = n, int(pad_hw[0]), int(pad_hw[1]), C.cast(iarr, C.c_void_p), dcls.ptr
         check(self.ctx.lib.odise_hip_postprocess_batch(self.ctx.h, C.byref(d)), "postprocess_batch")
         self._enqueue_rle(bufs, pad_hw, ihw, sizes)
+        self._keep_selection(bufs, pad_hw, ihw, sizes)
         return self._collect(bufs, sizes, to_host)
 
     def prefetch_device(self, images, layout: int, img_hw) -> None:
@@ -404,6 +415,7 @@ class HipCategoryODISE(HipODISE):
         check(self.ctx.lib.odise_hip_infer(self.ctx.h, C.byref(d)), "infer")
         hp = -(-max(int(h) for h, _ in img_hw) // 64) * 64, -(-max(int(w) for _, w in img_hw) // 64) * 64   # the library's padding (size_divisibility 64)
         self._enqueue_rle(bufs, hp, img_hw, out_sizes)
+        self._keep_selection(bufs, hp, img_hw, out_sizes)
         return self._collect(bufs, out_sizes, to_host)
 
     def __call__(self, *args, **kwargs):                                   # nn.Module-style call: the reference's wrappers do `self.model(batched_inputs)`

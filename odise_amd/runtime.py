@@ -507,6 +507,67 @@ class Context:
         return self.instance_rle_async(b, table_row, topk, pad_hw, img_hw, out_hw, capacity).result()
 
 
+    # ---- segm evaluation of instance masks (include/odise_hip.h odise_hip_mask_iou / odise_hip_instance_eval; host restatement:
+    # odise_amd/instance_eval.py) ------------------------------------------------------------------------------------------------------
+    def instance_gt_to_device(self, gt_table, runs, offsets) -> dict:
+        """The ground truth of one picture (instance_eval.gt_rows) as ONE packed upload: offsets int64 [n_gt + 1] | table int32 [n_gt, 3] |
+        runs uint32 -> {"n_gt", "offsets", "rows", "runs"} (views of one device buffer).  The upload waits for the stream."""
+        table = np.ascontiguousarray(np.asarray(gt_table, np.int32).reshape(-1, 3))
+        runs, offsets = np.ascontiguousarray(runs, np.uint32), np.ascontiguousarray(offsets, np.int64)
+        n_gt = table.shape[0]
+        assert offsets.shape == (n_gt + 1,) and int(offsets[-1]) == runs.size, (offsets.shape, n_gt, runs.size)
+        buf = self.to_device(np.concatenate([offsets.view(np.uint8), table.reshape(-1).view(np.uint8), runs.view(np.uint8)]))
+        ob, tb = offsets.nbytes, table.nbytes
+        return {"n_gt": n_gt, "offsets": buf.view((n_gt + 1,), np.int64), "rows": buf.view((n_gt, 3), np.int32, ob),
+                "runs": buf.view((runs.size,), np.uint32, ob + tb)}
+
+    def mask_iou(self, masks: DeviceArray, gt_counts, iscrowd=None, flags: Optional[DeviceArray] = None, with_counts: bool = False):
+        """pycocotools' mask.iou of dense device masks [n, h, w] (float32 / uint8 / bool) against run-length masks: gt_counts = a list of
+        uncompressed count arrays (uploaded here, which waits) or an `instance_gt_to_device` dict -> (iou float64 [n, n_gt] on the device,
+        flags int32 [1]); with_counts adds (inter int32 [n, n_gt], area_d int64 [n], area_g int64 [n_gt]).  Temporaries uploaded here are
+        freed on return by the library's synchronising free."""
+        n, h, w = masks.shape
+        dt = {np.dtype(np.float32): F32, np.dtype(np.uint8): U8, np.dtype(np.bool_): U8}.get(np.dtype(masks.dtype))
+        if dt is None:
+            raise ValueError(f"mask_iou: masks of dtype {masks.dtype} (float32, uint8 or bool)")
+        if not isinstance(gt_counts, dict):
+            offs = np.concatenate(([0], np.cumsum([len(c) for c in gt_counts]))).astype(np.int64)
+            runs = np.concatenate([np.asarray(c, np.uint32) for c in gt_counts]) if len(gt_counts) else np.zeros(0, np.uint32)
+            gt_counts = self.instance_gt_to_device(np.zeros((len(offs) - 1, 3), np.int32), runs, offs)
+        n_gt = gt_counts["n_gt"]
+        crowd = None if iscrowd is None else (iscrowd if isinstance(iscrowd, DeviceArray) else self.to_device(np.asarray(iscrowd, np.uint8)))
+        if flags is None:
+            flags = self.zeros((1,), np.int32)
+        iou = self.empty((n, n_gt), np.float64)
+        extra = (self.empty((n, n_gt), np.int32), self.empty((n,), np.int64), self.empty((n_gt,), np.int64)) if with_counts else (None, None, None)
+        check(self.lib.odise_hip_mask_iou(self.h, _p(masks), dt, n, h, w, _p(gt_counts["runs"]), _p(gt_counts["offsets"]), n_gt, _p(crowd), _p(iou),
+                                          _p(extra[0]), _p(extra[1]), _p(extra[2]), _p(flags)), "mask_iou")
+        return (iou, flags) + (extra if with_counts else ())
+
+    def instance_eval(self, out_hw, table_row, scores_row, topk: int, gt: dict, num_categories: int, image: int, rows, n_rows, flags,
+                      masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0), img_hw=(0, 0), iou_thresholds=None) -> None:
+        """Enqueue COCOeval.evaluateImg of one picture (odise_hip_instance_eval): detections = the selection table_row [1 + 2 topk] /
+        scores_row [topk] of image b of the last head forward, sampled from its mask logits (pad_hw / img_hw as in `instance_rle`), or the
+        dense `masks` [topk, h, w] when given; gt = `instance_gt_to_device`; rows (instance_eval.ROW_DTYPE [topk]), n_rows and flags
+        (int32 [1]) are device arrays or pointers."""
+        from ._lib import InstEvalDesc
+        from .instance_eval import IOU_THRS
+        thr = np.ascontiguousarray(IOU_THRS if iou_thresholds is None else iou_thresholds, np.float64)
+        assert thr.shape == (10,), thr.shape
+        d = InstEvalDesc()
+        d.h, d.w = int(out_hw[0]), int(out_hw[1])
+        if masks is not None:
+            assert tuple(masks.shape) == (int(topk), d.h, d.w), (masks.shape, topk, out_hw)
+            d.masks, d.dtype = masks.ptr, (F32 if masks.dtype == np.float32 else U8)
+        d.b, d.pad_h, d.pad_w, d.img_h, d.img_w = int(b), int(pad_hw[0]), int(pad_hw[1]), int(img_hw[0]), int(img_hw[1])
+        ptr = lambda a: a.ptr if isinstance(a, DeviceArray) else a
+        d.inst_table, d.inst_scores, d.topk = ptr(table_row), ptr(scores_row), int(topk)
+        d.gt_runs, d.gt_offsets, d.gt_rows, d.n_gt = gt["runs"].ptr, gt["offsets"].ptr, gt["rows"].ptr, int(gt["n_gt"])
+        d.num_categories, d.image, d.iou_thresholds = int(num_categories), int(image), thr.ctypes.data
+        d.rows, d.n_rows, d.flags = ptr(rows), ptr(n_rows), ptr(flags)
+        check(self.lib.odise_hip_instance_eval(self.h, C.byref(d)), "instance_eval")
+
+
     def jpeg_decode(self, data: bytes, apply_orientation: bool = True, out: Optional[DeviceArray] = None) -> DeviceArray:
         """read_image(file, "RGB") for a baseline JPEG: host Huffman decoding, IDCT / upsampling / colour conversion / EXIF transpose on
         the device -> uint8 [H,W,3], bit-identical to Pillow.  Baseline, extended-sequential and progressive files; raises `UnsupportedInput` for arithmetic-coded / CMYK / RGB-coded ones."""
