@@ -1,7 +1,7 @@
 /*
  * odise_hip_tools.h — developer / measurement hooks of libodise_hip.so.  NOT part of the drop-in boundary (include/odise_hip.h):
  * nothing on the product path calls these; tools/ (tile calibration, A/B runs of kernel generations, the MFMA and LDS rate probes)
- * and the ABI self-check of tests/test_lib_abi.py do.
+ * the ABI self-check of tests/test_lib_abi.py and the op-level tests of the small kernels (tests/test_gpu_glue_ops.py) do.
  */
 #ifndef ODISE_HIP_TOOLS_H
 #define ODISE_HIP_TOOLS_H
@@ -101,6 +101,62 @@ int odise_hip_mfma_probe(odise_hip_ctx* ctx, float* host_out);
  * plain = 1 runs the form that interpolates both source rows of every sample row anew (the two forms must agree to the bit). */
 int odise_hip_maskclip_token_mask(odise_hip_ctx* ctx, const void* logits_f16, void* out_u8, int B, int Q, int h, int w, int S, int patch, int T,
                                   int64_t ldm, int plain);
+
+/* ---- the small kernels between the GEMM stages, one hook per kernel (tests/test_gpu_glue_ops.py holds each to the float64 restatement of
+ * tests/glue_reference.py).  All pointers are device pointers unless named host; f16 maps are NHWC with C a multiple of 8 and 16-byte aligned;
+ * every call is enqueued on the context's stream.  A bad size or pointer is ODISE_ERR_ARG and nothing is launched; window boxes live on the
+ * device and are the caller's to keep inside the image. */
+/* slide-window crops (feature_extractor.py:216-224): crops [B*K,C,S,S] f32 = img [B,C,H,W] f32 [:, :, y1:y1+S, x1:x1+S], boxes [K][2] int (y1, x1) */
+int odise_hip_crop_extract(odise_hip_ctx* ctx, const float* img, float* crops, int B, int C, int H, int W, int S, int K, const int* boxes_dev);
+/* the same with windows of s x s resized to S x S (feature_extractor.py:197-215, 69-77: T.Resize(BICUBIC) of the cropped tensor =
+ * F.interpolate(mode="bicubic", align_corners=False), A = -0.75, taps clamped to the window) */
+int odise_hip_crop_resize_bicubic(odise_hip_ctx* ctx, const float* img, float* crops, int B, int C, int H, int W, int s, int S, int K,
+                                  const int* boxes_dev);
+/* CLIP preprocess (clip.py:94: T.Resize(S, BICUBIC) of the short side + T.CenterCrop(S) + T.Normalize): out [N,S,S,8] f16, channels 3..7 zero,
+ * from image01 [N,3,H,W] f32 */
+int odise_hip_clip_preprocess(odise_hip_ctx* ctx, const float* image01, void* out_f16, int N, int H, int W, int S);
+/* MaskCLIP's image resize (clip.py:327-332: F.interpolate(image, (S, S), mode="bilinear", align_corners=False)) + CLIP normalise: out [B,S,S,8] f16 */
+int odise_hip_resize_bilinear_norm(odise_hip_ctx* ctx, const float* image01, void* out_f16, int B, int H, int W, int S);
+/* F.interpolate(x, size=(OH, OW)) in its default nearest mode (feature_extractor.py:165-168): y [N,OH,OW,C] from x [N,H,W,C] */
+int odise_hip_upsample_nearest(odise_hip_ctx* ctx, const void* x_f16, void* y_f16, int N, int H, int W, int OH, int OW, int C);
+/* overlap-add of the per-window features over count_mat (feature_extractor.py:229-248): feat [B*K,ch,cw,C] f16, boxes [K][2] int in feature
+ * pixels -> out_f16 [B,OH,OW,C] and / or out_nchw [B,C,OH,OW] f32 (either may be NULL); a pixel no window covers is 0 */
+int odise_hip_stitch(odise_hip_ctx* ctx, const void* feat_f16, void* out_f16, float* out_nchw, int B, int K, const int* boxes_dev, int ch, int cw, int OH,
+                     int OW, int C);
+/* src + level_embed (+ positional table) (msdeformattn.py:71-75, odise.py:657-660): y [N,P,C] = x [N,P,C] + vec [C] + table [P,C]; vec / table f32, may be NULL */
+int odise_hip_add_vec_table(odise_hip_ctx* ctx, const void* x_f16, const float* vec, const float* table, void* y_f16, int64_t N, int P, int C);
+/* query_feat.weight.unsqueeze(0).repeat(B, 1, 1) (odise.py:663-664): y [B][n] = x [n] f16, n a multiple of 8 */
+int odise_hip_broadcast_rows(odise_hip_ctx* ctx, const void* x_f16, void* y_f16, int64_t n, int B);
+/* cur_fpn + F.interpolate(out[-1], size=cur_fpn.shape[-2:], mode="bilinear", align_corners=False) (msdeformattn.py:347):
+ * y [N,OH,OW,C] = a [N,OH,OW,C] + resize(b [N,H,W,C]); a = NULL: the resized map alone */
+int odise_hip_bilinear_add(odise_hip_ctx* ctx, const void* a_f16, const void* b_f16, void* y_f16, int N, int H, int W, int OH, int OW, int C);
+/* MaskPooling's prologue (odise.py:949-955: mask = (mask.sigmoid() > 0.5); denorm = mask.sum(-1) + 1e-8): m01 [rows,HW] f16, inv [rows] f32 = 1 / denorm;
+ * _f16 takes fp16 logits (HW a multiple of 8), _f32 the fp32 ones of odise_hip_mask_pooling */
+int odise_hip_mask_binarize_f16(odise_hip_ctx* ctx, const void* mask_f16, void* m01_f16, float* inv, int64_t rows, int HW);
+int odise_hip_mask_binarize_f32(odise_hip_ctx* ctx, const float* mask, void* m01_f16, float* inv, int64_t rows, int HW);
+/* the masked-attention rows (odise.py:760-774: F.interpolate(outputs_mask, size, mode="bilinear").sigmoid() < 0.5, and :683: a row that masks every
+ * key is cleared): out [rows][ldm] u8 (1 = masked; columns oh*ow..ldm-1 are 1) from logits [rows,H,W] of dtype ODISE_F16 / ODISE_F32 */
+int odise_hip_attn_mask(odise_hip_ctx* ctx, const void* logits, int dtype, void* out_u8, int64_t rows, int H, int W, int oh, int ow, int64_t ldm);
+/* the VAE AttnBlock's torch.softmax(scale * x, dim=-1) on fp16 rows of `cols` <= 8192 values, row stride ld (a multiple of 8); y may be x */
+int odise_hip_softmax_rows(odise_hip_ctx* ctx, const void* x_f16, void* y_f16, int64_t rows, int cols, int64_t ld, float scale);
+/* torch.cat([class_embedding, patches]) + positional_embedding (clip.py:179-190) with `extra` copies of the class token appended (clip.py:268-270):
+ * tok [B,TP,Cw] f16 from patches [B,T-1,Cw] f16, cls [Cw] f32, pos [T,Cw] f32; rows T+extra..TP-1 are zero */
+int odise_hip_clip_assemble(odise_hip_ctx* ctx, const void* patches_f16, const float* cls, const float* pos, void* tok_f16, int B, int T, int extra, int TP,
+                            int Cw);
+/* uncond + tanh(alpha) * (proj + pos) (ldm.py:706-709) folded to out [B,T,Cw] = A1 [T,Cw] + A2 [T,Cw] * proj [B,Cw] (all f32) */
+int odise_hip_cond_inputs(odise_hip_ctx* ctx, const float* proj, const float* A1, const float* A2, float* out, int B, int T, int Cw);
+/* quant_conv mean * scale_factor -> q_sample (gaussian_diffusion.py:275-292) and post_quant_conv (ldm.py:459-467, 535-538, 577-598): h [B,P,8] f16,
+ * noise [4,P] f32 -> xt, zdec [B,P,8] f16 (channels 4..7 zero), latent [B,4,P] f32 (may be NULL).  The weights are HOST arrays: wq [4][8], bq [4],
+ * wp [4][4], bp [4]; qa = sqrt(alpha_bar_t), qb = sqrt(1 - alpha_bar_t) */
+int odise_hip_latent_heads(odise_hip_ctx* ctx, const void* h_f16, const float* noise, void* xt_f16, void* zdec_f16, float* latent, int B, int P,
+                           const float* wq_4x8, const float* bq_4, const float* wp_4x4, const float* bp_4, float scale, float qa, float qb);
+/* F.normalize(x, dim=-1) (eps 1e-12): y [rows,C] f16 from x of dtype ODISE_F16 / ODISE_F32 */
+int odise_hip_l2_normalize(odise_hip_ctx* ctx, const void* x, int dtype, void* y_f16, int64_t rows, int C);
+/* the open-vocabulary class scores (helper.py:79-109 max over synonyms; odise.py:1506-1536 geometric ensemble; odise.py:300-323 null merge and
+ * log): L1 [rows,Ktot+1] (null last) / L2 [rows,Ktot] f32 cosines, seg [K+1] / ovl [K] int, binary [rows,2] f32 or NULL (odise.py:559-565) ->
+ * out [rows,K+1] f32 log-probabilities */
+int odise_hip_classify_rows(odise_hip_ctx* ctx, const float* L1, const float* L2, const int* seg_dev, const int* ovl_dev, const float* binary, float* out,
+                            int64_t rows, int K, int Ktot, float ls1, float ls2, float alpha, float beta);
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,14 @@ extern "C" int odise_hip_concat_channels(odise_hip_ctx* ctx, const void* a, cons
     return ODISE_OK;
 }
 
+// test hook (include/odise_hip_tools.h): the fp32 MaskPooling prologue on its own, as odise_hip_mask_pooling launches it
+extern "C" int odise_hip_mask_binarize_f32(odise_hip_ctx* ctx, const float* mask, void* m01_f16, float* inv, int64_t rows, int HW) {
+    ODISE_REQUIRE(ctx && mask && m01_f16 && inv && rows >= 1 && rows < (1ll << 31) && HW >= 1, "mask_binarize_f32: bad argument");
+    hipLaunchKernelGGL(mask_binarize_kernel, dim3((unsigned)rows), dim3(256), 0, ctx->stream, mask, (f16*)m01_f16, inv, HW);
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}
+
 // MaskPooling.forward (odise/modeling/meta_arch/odise.py:937-963):
 //   pooled[b,q,c] = sum_hw x[b,c,hw] * m01[b,q,hw] / (sum_hw m01[b,q,hw] + 1e-8)
 // realised as one split-K MFMA GEMM per image: A = m01 [Q,HW] (exact in fp16), W = x [C,HW] cast to fp16,

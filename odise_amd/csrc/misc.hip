@@ -220,7 +220,9 @@ int launch_image_to_nhwc(odise_hip_ctx* ctx, const float* x, f16* y, int N, int 
 int launch_clip_preprocess(odise_hip_ctx* ctx, const float* x, f16* y, int N, int H, int W, int S) {
     int RH, RW;
     if (H <= W) { RH = S; RW = (int)((int64_t)S * W / H); } else { RH = (int)((int64_t)S * H / W); RW = S; }
-    const int top = (int)lround((RH - S) / 2.0), left = (int)lround((RW - S) / 2.0);
+    // torchvision center_crop: int(round((RH - S) / 2.0)) with Python's round - halves to EVEN (margin 5 -> 2, not 3); RH, RW >= S
+    const auto half_even = [](int m) { return m / 2 + ((m & 1) & (m / 2 & 1)); };
+    const int top = half_even(RH - S), left = half_even(RW - S);
     dim3 grid((unsigned)ceil_div(S * S, 256), (unsigned)N);
     hipLaunchKernelGGL(resize_bicubic_norm_kernel, grid, dim3(256), 0, ctx->stream, x, y, H, W, RH, RW, S, top, left, 0.48145466f,
                        0.4578275f, 0.40821073f, 1.f / 0.26862954f, 1.f / 0.26130258f, 1.f / 0.27577711f);
