@@ -477,7 +477,7 @@ int odise_hip_mask_iou(odise_hip_ctx* ctx, const void* masks, int dtype, int n, 
  * its ground truth; an unmatched one is ignored when its own area (pixels of its mask) lies outside range a.
  * Row k is the detection of rank k by score: what COCOeval.accumulate needs of it (odise_amd/instance_eval.py accumulate / summarize).
  * ODISE_ERR_ARG and nothing written: a null pointer, topk outside 1..100, n_gt outside 0..1024, the geometry errors of
- * odise_hip_instance_rle.  Polygon ground truth is not decoded here: whoever holds the annotations converts it to RLE.
+ * odise_hip_instance_rle.  Polygon ground truth goes through odise_hip_instance_eval_poly below.
  * The matching is one block: a wave per category, so a picture whose detections and ground truths all share one category is matched
  * by one wave.  Scratch comes from the context.  Asynchronous on the context's stream; no host synchronisation. */
 typedef struct { float score; int32_t category; int32_t area; int32_t image; uint64_t matched, ignored; } odise_inst_eval_row; /* 32 bytes; bit 10*a + t */
@@ -498,9 +498,35 @@ typedef struct {
     odise_inst_eval_row* rows;      /* device [topk]; rows past n are zeroed */
     int32_t* n_rows;                /* device [1] */
     int32_t* flags;                 /* device [1], OR-ed: 1 = a gt mask's runs do not sum to h*w, 2 = a detection's class outside [0,num_categories),
-                                       4 = a gt category outside it / iscrowd not 0|1.  A picture that raises one writes n_rows = 0 and zeroed rows. */
+                                       4 = a gt category outside it / iscrowd not 0|1 (odise_hip_instance_eval_poly: or runs AND polygons on one gt; 8 = a bad
+                                       polygon).  A picture that raises one writes n_rows = 0 and zeroed rows. */
 } odise_inst_eval_desc;
 int odise_hip_instance_eval(odise_hip_ctx* ctx, const odise_inst_eval_desc* d);
+/* pycocotools' annToRLE of polygon annotations (mask.frPyObjects of every polygon + mask.merge as a union): maskApi.c rleFrPoly bit for
+ * bit - vertices scaled by 5 and rounded as (int)(5 v + .5), every edge walked in max(dx, dy) + 1 points with separately rounded
+ * multiply and add (no fused multiply-add), a crossing wherever two consecutive points differ in x; the mask is the running parity of the
+ * crossings over the column-major order, and an annotation is the OR of its polygons.
+ * xy: device double, the vertices x0 y0 x1 y1 .. of all polygons back to back.  poly_offsets: device int64 [n_poly + 1], the first VERTEX
+ * of every polygon (poly_offsets[n_poly] vertices are read from xy).  ann_polys: device int32 [n_ann + 1], the first polygon of every
+ * annotation; an annotation with no polygons is the empty mask.  rle / capacity / offsets / area: exactly as odise_hip_rle_encode.
+ * flags: device int32 [1], OR-ed: 8 = a polygon has fewer than 3 vertices, or a coordinate is NaN or larger than 2^26 in magnitude (5 x
+ * must fit an int); such a polygon contributes nothing.  Polygon ranges are clamped to [0, n_poly]: no access leaves a buffer.
+ * n_ann <= 65535, n_poly >= 0, h * w <= 2^30.  Scratch comes from the context.  Asynchronous on the context's stream. */
+int odise_hip_polygon_rle(odise_hip_ctx* ctx, const double* xy, const int64_t* poly_offsets, const int32_t* ann_polys, int n_ann, int n_poly,
+                          int h, int w, void* rle, int64_t capacity, int64_t* offsets, int64_t* area, int32_t* flags);
+/* odise_hip_instance_eval with ground truth that is polygons, run lengths, or both in one picture (COCO: polygons for every object, RLE
+ * for the crowds).  p: the polygons as in odise_hip_polygon_rle, gt_polys [n_gt + 1] the polygon range of every ground truth.  A ground
+ * truth with a non-empty polygon range must have an EMPTY run range in d->gt_offsets (flag 4 otherwise); its mask is rasterised into the
+ * words the run-length decoder fills for the others, and intersections, IoU and matching are those of odise_hip_instance_eval.
+ * Flag 8 (odise_hip_polygon_rle) joins the flags of the descriptor: the picture writes n_rows = 0 and zeroed rows.
+ * p == NULL is odise_hip_instance_eval. */
+typedef struct {
+    const double* xy;               /* device: vertices of all polygons */
+    const int64_t* poly_offsets;    /* device [n_poly + 1], in vertices */
+    const int32_t* gt_polys;        /* device [n_gt + 1] */
+    int n_poly;
+} odise_inst_poly_gt;
+int odise_hip_instance_eval_poly(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p);
 
 /* ---- JPEG input -------------------------------------------------------------------------------------------
  * Replaces detectron2 `read_image(file, "RGB")` = PIL.Image.open -> EXIF transpose -> convert("RGB") of the DatasetMapper

@@ -103,6 +103,11 @@ class InstEvalDesc(C.Structure):
                 ("image", c_int), ("iou_thresholds", c_void_p), ("rows", c_void_p), ("n_rows", c_void_p), ("flags", c_void_p)]
 
 
+class InstPolyGt(C.Structure):
+    """odise_inst_poly_gt (include/odise_hip.h)."""
+    _fields_ = [("xy", c_void_p), ("poly_offsets", c_void_p), ("gt_polys", c_void_p), ("n_poly", c_int)]
+
+
 MAX_SEGMENTS = 100          # ODISE_MAX_SEGMENTS
 COMM_ID_BYTES = 128         # ODISE_COMM_ID_BYTES
 

@@ -379,3 +379,4 @@ extern "C" int odise_hip_sizeof_pq_desc(void) { return (int)sizeof(odise_pq_desc
 extern "C" int odise_hip_sizeof_pq_stat(void) { return (int)sizeof(odise_pq_stat); }
 extern "C" int odise_hip_sizeof_inst_eval_desc(void) { return (int)sizeof(odise_inst_eval_desc); }
 extern "C" int odise_hip_sizeof_inst_eval_row(void) { return (int)sizeof(odise_inst_eval_row); }
+extern "C" int odise_hip_sizeof_inst_poly_gt(void) { return (int)sizeof(odise_inst_poly_gt); }

@@ -1,12 +1,14 @@
 // inst_eval.hip — instance masks against ground truth on the device: odise_hip_mask_iou (pycocotools' mask.iou of dense masks against
-// run-length masks) and odise_hip_instance_eval (COCOeval.evaluateImg for iouType "segm", useCats = 1: the per-picture part of
-// InstanceSegEvaluator / COCOEvaluator(tasks=("segm",)), odise/evaluation/d2_evaluator.py:29,104).  Host restatement: odise_amd/instance_eval.py.
+// run-length masks) and odise_hip_instance_eval / odise_hip_instance_eval_poly (COCOeval.evaluateImg for iouType "segm", useCats = 1: the
+// per-picture part of InstanceSegEvaluator / COCOEvaluator(tasks=("segm",)), odise/evaluation/d2_evaluator.py:29,104).  Host restatement:
+// odise_amd/instance_eval.py.
 //
 //   1. pack     the detections into words [n][w][R] (rle_pack.h: the kernels of rle.hip, the pixels of odise_hip_instance_rle).
 //   2. decode   the ground truth from uncompressed COCO run lengths into the same layout.  One block per mask walks its runs 1024 at a time:
 //               a block scan gives the end position of every run of the chunk, then a thread per word of the chunk's span searches the first
 //               run that reaches into its word and walks on from there.  Every position is clamped to h * w: counts that sum to anything
-//               else raise flag 1 and never move a read or a write outside the mask.
+//               else raise flag 1 and never move a read or a write outside the mask.  A ground truth given as polygons
+//               (odise_hip_instance_eval_poly) is left empty here and rasterised into the same words by poly.hip right behind.
 //   3. inter    inter[d][g] = sum of popcount(words_d & words_g), tiled like a small GEMM: a block holds 32 words of 64 detections and 32
 //               ground truths in LDS and a thread forms 4 x 2 pairs from them; the word axis is split over blockIdx.z and the partial
 //               counts meet in integer atomics (exact, and the same from run to run).  Areas are the popcounts of one side.
@@ -43,14 +45,16 @@ __device__ __forceinline__ u64 bit_range(int a, int b) {   // bits a .. b - 1, 0
 }
 
 __global__ void __launch_bounds__(kRleThreads) inst_decode_kernel(const uint32_t* __restrict__ runs, const long long* __restrict__ offsets,
-                                                                 u64* __restrict__ words, RleGrid G, int* __restrict__ flag) {
+                                                                 u64* __restrict__ words, RleGrid G, int* __restrict__ flag,
+                                                                 const int* __restrict__ polys) {
     __shared__ long long ends[kRleThreads];
     __shared__ long long ls[kRleThreads / 64];
     const int tid = threadIdx.x;
     u64* wd = words + (int64_t)blockIdx.x * G.nw;
     for (int64_t i = tid; i < G.nw; i += kRleThreads) wd[i] = 0ull;
     const long long r0 = offsets[blockIdx.x];
-    const long long m = max(0ll, offsets[blockIdx.x + 1] - r0);
+    const bool poly = polys && polys[blockIdx.x + 1] > polys[blockIdx.x];   // the polygon kernel fills this mask (and checks that it has no runs)
+    const long long m = poly ? 0ll : max(0ll, offsets[blockIdx.x + 1] - r0);
     const long long hw = (long long)G.h * G.w;
     long long carry = 0;   // positions before the chunk
     __syncthreads();
@@ -90,7 +94,7 @@ __global__ void __launch_bounds__(kRleThreads) inst_decode_kernel(const uint32_t
         carry += total;
         __syncthreads();
     }
-    if (tid == 0 && carry != hw) atomicOr(flag, 1);
+    if (tid == 0 && carry != hw && !poly) atomicOr(flag, 1);
 }
 
 // ---- 3. intersections and areas -----------------------------------------------------------------------------------------------------------
@@ -287,26 +291,30 @@ struct InstScratch {
     long long* area;   // [n + n_gt]
     int* inter;        // [n][n_gt], then one int: the status of the call
     size_t inter_bytes;
+    u64* toggle;       // with polygon ground truth: the toggle planes of poly.hip, [n_gt] masks
 };
-static int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, InstScratch* s) {
+static int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, InstScratch* s, bool polygons = false) {
     const size_t wb = (size_t)round_up((int64_t)(n + n_gt) * G.nw * 8, 256), ab = (size_t)round_up((int64_t)(n + n_gt) * 8, 256);
     s->inter_bytes = ((size_t)n * n_gt + 1) * sizeof(int);
-    ODISE_TRY(scratch_reserve(ctx->rle, wb + ab + s->inter_bytes, 8, drain_streams(ctx->stream), "rle"));
+    const size_t ib = (size_t)round_up((int64_t)s->inter_bytes, 256);
+    ODISE_TRY(scratch_reserve(ctx->rle, wb + ab + ib + (polygons ? (size_t)n_gt * G.nw * 8 : 0), 8, drain_streams(ctx->stream), "rle"));
     char* p = (char*)ctx->rle.ptr;
     s->words_d = (u64*)p;
     s->words_g = s->words_d + (int64_t)n * G.nw;
     s->area = (long long*)(p + wb);
     s->inter = (int*)(p + wb + ab);
+    s->toggle = (u64*)(p + wb + ab + ib);
     return ODISE_OK;
 }
 
-// stages 2 and 3 behind the packed detections: ground-truth words, inter, area; flag 1 goes to `flag`
+// stages 2 and 3 behind the packed detections: ground-truth words, inter, area; flag 1 (and 4, 8 of polygon ground truth) goes to `flag`
 static int inst_overlaps(odise_hip_ctx* ctx, const InstScratch& s, const RleGrid& G, int n, const uint32_t* gt_runs, const int64_t* gt_offsets, int n_gt,
-                         int* flag) {
+                         int* flag, const odise_inst_poly_gt* p = nullptr) {
     if (n_gt) {
         hipLaunchKernelGGL(inst_decode_kernel, dim3((unsigned)n_gt), dim3(kRleThreads), 0, ctx->stream, gt_runs, (const long long*)gt_offsets, s.words_g,
-                           G, flag);
+                           G, flag, p ? (const int*)p->gt_polys : nullptr);
         ODISE_CHECK_HIP(hipGetLastError());
+        if (p) ODISE_TRY(poly_fill_words(ctx, p->xy, p->poly_offsets, p->gt_polys, n_gt, p->n_poly, G, s.words_g, s.toggle, false, gt_offsets, flag));
         // split the word axis until the grid fills the chip about twice
         const int64_t tiles = ceil_div(n, kInterTD) * ceil_div(n_gt, kInterTG), steps = ceil_div(G.nw, kInterKC);
         const int64_t kz = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(steps, 1024), 2 * ctx->cu_count / tiles));
@@ -347,12 +355,17 @@ extern "C" int odise_hip_mask_iou(odise_hip_ctx* ctx, const void* masks, int dty
     return ODISE_OK;
 }
 
-extern "C" int odise_hip_instance_eval(odise_hip_ctx* ctx, const odise_inst_eval_desc* d) {
+extern "C" int odise_hip_instance_eval(odise_hip_ctx* ctx, const odise_inst_eval_desc* d) { return odise_hip_instance_eval_poly(ctx, d, nullptr); }
+
+extern "C" int odise_hip_instance_eval_poly(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p) {
     ODISE_REQUIRE(ctx && d, "instance_eval: null argument");
     ODISE_REQUIRE(d->inst_table && d->inst_scores && d->iou_thresholds && d->rows && d->n_rows && d->flags, "instance_eval: null pointer");
     ODISE_REQUIRE(d->topk >= 1 && d->topk <= kInstMaxDet, "instance_eval: topk %d (1..%d)", d->topk, kInstMaxDet);
     ODISE_REQUIRE(d->n_gt >= 0 && d->n_gt <= kInstMaxGt, "instance_eval: %d ground-truth masks (0..%d)", d->n_gt, kInstMaxGt);
     ODISE_REQUIRE(d->n_gt == 0 || (d->gt_runs && d->gt_offsets && d->gt_rows), "instance_eval: null ground truth");
+    ODISE_REQUIRE(!p || p->n_poly >= 0, "instance_eval: %d polygons", p->n_poly);
+    if (p && (d->n_gt == 0 || p->n_poly == 0)) p = nullptr;   // nothing to rasterise
+    ODISE_REQUIRE(!p || (p->xy && p->poly_offsets && p->gt_polys), "instance_eval: null polygon ground truth");
     ODISE_REQUIRE(d->num_categories >= 1, "instance_eval: num_categories %d", d->num_categories);
     ODISE_REQUIRE(d->h >= 1 && d->w >= 1 && (int64_t)d->h * d->w <= kRleMaxPixels, "instance_eval: mask size %dx%d out of range", d->h, d->w);
     ODISE_REQUIRE(!d->masks || d->dtype == ODISE_F32 || d->dtype == ODISE_U8, "instance_eval: dtype %d (ODISE_F32 or ODISE_U8)", d->dtype);
@@ -362,12 +375,12 @@ extern "C" int odise_hip_instance_eval(odise_hip_ctx* ctx, const odise_inst_eval
     if (!d->masks) ODISE_TRY(rle_instance_geom(ctx, "instance_eval", d->b, d->pad_h, d->pad_w, d->img_h, d->img_w, d->h, d->w, &g, &logits));
     const RleGrid G = rle_grid(d->h, d->w);
     InstScratch s;
-    ODISE_TRY(inst_scratch(ctx, d->topk, d->n_gt, G, &s));
+    ODISE_TRY(inst_scratch(ctx, d->topk, d->n_gt, G, &s, p != nullptr));
     ODISE_CHECK_HIP(hipMemsetAsync(s.inter, 0, s.inter_bytes, ctx->stream));
     int* status = s.inter + (size_t)d->topk * d->n_gt;
     if (d->masks) ODISE_TRY(rle_pack_dense(ctx, d->masks, d->dtype, d->topk, G, s.words_d));
     else ODISE_TRY(rle_pack_logits(ctx, logits, (const int*)d->inst_table, d->topk, g, G, s.words_d));
-    ODISE_TRY(inst_overlaps(ctx, s, G, d->topk, d->gt_runs, d->gt_offsets, d->n_gt, status));
+    ODISE_TRY(inst_overlaps(ctx, s, G, d->topk, d->gt_runs, d->gt_offsets, d->n_gt, status, p));
     InstMatchArgs A;
     A.inst_table = (const int*)d->inst_table; A.inst_scores = d->inst_scores; A.gt_rows = (const int*)d->gt_rows;
     A.inter = s.inter; A.area = s.area; A.status = status;

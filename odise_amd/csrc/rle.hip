@@ -288,26 +288,20 @@ int rle_pack_logits(odise_hip_ctx* ctx, const f16* logits, const int* inst_table
     return ODISE_OK;
 }
 
-struct RleScratch {
-    unsigned long long* words;
-    RleState* state;
-    long long* len;
-};
-// the context's scratch for n masks (grown on demand; earlier calls on the stream may still read the old buffer)
-static int rle_scratch(odise_hip_ctx* ctx, int n, const RleGrid& G, RleScratch* s) {
+int rle_scratch(odise_hip_ctx* ctx, int n, const RleGrid& G, RleScratch* s, size_t extra) {
     const size_t wb = (size_t)round_up((int64_t)n * G.nw * 8, 256), sb = (size_t)round_up((int64_t)n * kRleThreads * sizeof(RleState), 256);
-    const size_t need = wb + sb + (size_t)n * 8;
-    ODISE_TRY(scratch_reserve(ctx->rle, need, 8, drain_streams(ctx->stream), "rle"));
+    const size_t lb = (size_t)round_up((int64_t)n * 8, 256);
+    ODISE_TRY(scratch_reserve(ctx->rle, wb + sb + lb + extra, 8, drain_streams(ctx->stream), "rle"));
     char* p = (char*)ctx->rle.ptr;
     s->words = (unsigned long long*)p;
     s->state = (RleState*)(p + wb);
     s->len = (long long*)(p + wb + sb);
+    s->extra = p + wb + sb + lb;
     return ODISE_OK;
 }
 
-// count -> offsets -> write, after the words of n masks are packed
-static int rle_finish(odise_hip_ctx* ctx, const RleScratch& s, const RleGrid& G, int n, void* rle, int64_t capacity, int64_t* offsets, int64_t* area,
-                      const int* n_dev) {
+int rle_finish(odise_hip_ctx* ctx, const RleScratch& s, const RleGrid& G, int n, void* rle, int64_t capacity, int64_t* offsets, int64_t* area,
+               const int* n_dev) {
     hipLaunchKernelGGL(rle_count_kernel, dim3((unsigned)n), dim3(kRleThreads), 0, ctx->stream, s.words, G, s.state, s.len, (long long*)area, n_dev);
     ODISE_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(rle_offsets_kernel, dim3(1), dim3(kRleThreads), 0, ctx->stream, s.len, (long long*)offsets, n);

@@ -1,5 +1,6 @@
-// rle_pack.h — what rle.hip (COCO RLE strings) and inst_eval.hip (mask IoU and segm matching) share: the bit-packed mask layout, the block
-// scan and the launchers of the pack kernels (defined in rle.hip, compiled once).
+// rle_pack.h — what rle.hip (COCO RLE strings), inst_eval.hip (mask IoU and segm matching) and poly.hip (polygon rasterisation) share: the
+// bit-packed mask layout, the block scan, the launchers of the pack kernels and the string passes (defined in rle.hip, compiled once) and
+// the launcher of the polygon kernel (poly.hip).
 //   word (x, r) of a mask holds pixels (64 r .. 64 r + 63, x), bit k = row 64 r + k, stored [n][w][R], R = ceil(h / 64): the words of a
 //   mask are consecutive pieces of the column-major order j = x * h + y.
 #pragma once
@@ -54,5 +55,25 @@ int rle_instance_geom(odise_hip_ctx* ctx, const char* what, int b, int pad_h, in
 // instance_masks(_x4)_kernel; masks past the count n (read on the device) are not written
 int rle_pack_logits(odise_hip_ctx* ctx, const f16* logits, const int* inst_table, int topk, const PostGeom& g, const RleGrid& G,
                     unsigned long long* words);
+
+// The context's scratch of the string passes for n masks (grown on demand; earlier calls on the stream may still read the old buffer) and
+// `extra` bytes behind it for the caller.
+struct RleState;
+struct RleScratch {
+    unsigned long long* words;
+    RleState* state;
+    long long* len;
+    void* extra;
+};
+int rle_scratch(odise_hip_ctx* ctx, int n, const RleGrid& G, RleScratch* s, size_t extra = 0);
+// count -> offsets -> write, after the words of n masks are packed
+int rle_finish(odise_hip_ctx* ctx, const RleScratch& s, const RleGrid& G, int n, void* rle, int64_t capacity, int64_t* offsets, int64_t* area,
+               const int* n_dev);
+
+// words [n_ann][G.nw] of polygon annotations (poly.hip): annotation a is the OR of the rasterised polygons [ann_polys[a], ann_polys[a + 1]).
+// toggle: [n_ann][G.nw] words of scratch.  fill_empty: an annotation without polygons gets the empty mask (otherwise its words are left as
+// they are).  run_offsets (optional, [n_ann + 1]): an annotation with polygons AND a non-empty range here raises flag 4.  Flag 8: a bad polygon.
+int poly_fill_words(odise_hip_ctx* ctx, const double* xy, const int64_t* poly_offsets, const int32_t* ann_polys, int n_ann, int n_poly,
+                    const RleGrid& G, unsigned long long* words, unsigned long long* toggle, bool fill_empty, const int64_t* run_offsets, int* flag);
 
 }  // namespace odise

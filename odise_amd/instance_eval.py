@@ -17,8 +17,8 @@ What it keeps of a detection is one `ROW_DTYPE` record (odise_inst_eval_row): sc
 bits of the 40 (range a, threshold t) cells, bit 10 a + t.  `accumulate` is `COCOeval.accumulate` over such rows and the count of
 non-ignored ground truths per (category, range), `summarize` the twelve COCO numbers, `results` detectron2's dict.
 
-Ground truth is RLE only (compressed or uncompressed); polygons (`rleFrPoly`) are not rasterised here: whoever holds the annotations
-converts them.  ADE20K's instance annotations are RLE already.
+Ground truth is RLE (compressed or uncompressed) or polygons: `gt_rows(..., polygons=True)` packs the polygons for the device, which
+rasterises them (csrc/poly.hip; host reference: odise_amd/coco_poly.py).
 """
 from __future__ import annotations
 
@@ -26,7 +26,7 @@ from typing import Dict, Sequence
 
 import numpy as np
 
-from . import coco_rle
+from . import coco_poly, coco_rle
 
 # odise_inst_eval_row (include/odise_hip.h)
 ROW_DTYPE = np.dtype([("score", "<f4"), ("category", "<i4"), ("area", "<i4"), ("image", "<i4"), ("matched", "<u8"), ("ignored", "<u8")])
@@ -35,10 +35,12 @@ REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=
 MAX_DETS = (1, 10, 100)
 AREA_RNG = ((0 ** 2, 1e5 ** 2), (0 ** 2, 32 ** 2), (32 ** 2, 96 ** 2), (96 ** 2, 1e5 ** 2))    # all, small, medium, large; ends included
 MAX_DETECTIONS, MAX_GT = 100, 1024
-FLAG_BAD_RUNS, FLAG_BAD_CLASS, FLAG_BAD_GT = 1, 2, 4
+FLAG_BAD_RUNS, FLAG_BAD_CLASS, FLAG_BAD_GT, FLAG_BAD_POLYGON = 1, 2, 4, 8
 FLAG_NAMES = {FLAG_BAD_RUNS: "the run lengths of a ground-truth mask do not sum to h * w",
               FLAG_BAD_CLASS: "a predicted class is outside [0, num_categories)",
-              FLAG_BAD_GT: "a ground-truth category is outside [0, num_categories) or iscrowd is not 0 / 1"}
+              FLAG_BAD_GT: "a ground-truth category is outside [0, num_categories), iscrowd is not 0 / 1, or a ground truth has both runs "
+                           "and polygons",
+              FLAG_BAD_POLYGON: "a polygon has fewer than three vertices, or a coordinate is NaN or larger than 2^26 in magnitude"}
 
 
 def flag_names(flags: int) -> list:
@@ -85,24 +87,43 @@ def annotation_counts(segmentation) -> np.ndarray:
     return coco_rle.string_to_counts(c) if isinstance(c, str) else np.asarray(c, np.int64)
 
 
-def gt_rows(annotations, to_contiguous: Dict[int, int]):
+def gt_rows(annotations, to_contiguous: Dict[int, int], polygons: bool = False, hw=None):
     """The annotation dicts of a picture (category_id as in the dataset, iscrowd, area, segmentation = RLE dict) ->
     (rows int32 [n_gt, 3] = contiguous category | iscrowd | bits 0..3: area outside range a, runs uint32 (all masks back to back),
     offsets int64 [n_gt + 1]).  The area is the annotation's float `area` (the evaluator compares that, not the mask); without one, the
-    pixels of the mask."""
+    pixels of the mask.
+    polygons=True also takes annotations whose segmentation is a list of polygons (flat lists x0 y0 x1 y1 ..), on a picture of
+    hw = (h, w), and returns three more: xy float64 (all vertices), poly_offsets int64 [n_poly + 1] in vertices, gt_polys int32
+    [n_gt + 1] - the arguments of odise_hip_instance_eval_poly.  A polygon annotation has an empty run range; without an `area` its mask
+    is rasterised on the host (coco_poly) for the pixel count.  A malformed polygon (odd length, fewer than 6 numbers) raises ValueError."""
     rows = np.zeros((len(annotations), 3), np.int32)
     runs, offsets = [], [0]
+    xy, poly_offsets, gt_polys = [], [0], [0]
     for i, ann in enumerate(annotations):
         seg = ann["segmentation"]
         if not isinstance(seg, dict):
-            raise ValueError("instance evaluation takes RLE ground truth; convert polygon annotations to RLE first")
-        cnts = annotation_counts(seg)
-        area = float(ann["area"]) if "area" in ann else float(cnts[1::2].sum())
+            if not polygons:
+                raise ValueError("instance evaluation takes RLE ground truth; convert polygon annotations to RLE first")
+            if hw is None:
+                raise ValueError("polygon ground truth needs the picture's (h, w)")
+            for poly in seg:
+                poly = coco_poly.check_polygon(poly)
+                xy.append(poly)
+                poly_offsets.append(poly_offsets[-1] + poly.size // 2)
+            cnts = np.zeros(0, np.int64)
+            area = float(ann["area"]) if "area" in ann else float(coco_poly.annotation_to_counts(seg, int(hw[0]), int(hw[1]))[1::2].sum())
+        else:
+            cnts = annotation_counts(seg)
+            area = float(ann["area"]) if "area" in ann else float(cnts[1::2].sum())
         outside = sum(1 << a for a, (lo, hi) in enumerate(AREA_RNG) if area < lo or area > hi)
         rows[i] = (to_contiguous[int(ann["category_id"])], int(ann.get("iscrowd", 0)), outside)
         runs.append(np.asarray(cnts, np.uint32))
         offsets.append(offsets[-1] + len(cnts))
-    return rows, (np.concatenate(runs) if runs else np.zeros(0, np.uint32)), np.asarray(offsets, np.int64)
+        gt_polys.append(len(poly_offsets) - 1)
+    out = rows, (np.concatenate(runs) if runs else np.zeros(0, np.uint32)), np.asarray(offsets, np.int64)
+    if polygons:
+        out += ((np.concatenate(xy) if xy else np.zeros(0, np.float64)), np.asarray(poly_offsets, np.int64), np.asarray(gt_polys, np.int32))
+    return out
 
 
 def npig(rows, K: int) -> np.ndarray:

@@ -3,7 +3,8 @@
 against the ground truth and reduced to one 32-byte row per detection, no RLE string and no JSON - and `evaluate` reads the rows back
 once, gathers them across ranks and does COCOeval.accumulate / summarize on the host (odise_amd/instance_eval.py).
 
-Ground truth is RLE (compressed or uncompressed) only: polygon annotations have to be converted by whoever holds them."""
+Ground truth is what COCO's instance annotations hold: polygons (rasterised on the device, pycocotools' annToRLE bit for bit) for the
+objects, RLE (compressed or uncompressed) for the crowds, mixed freely in one picture."""
 from __future__ import annotations
 
 from typing import Dict, Sequence
@@ -48,15 +49,16 @@ class HipInstanceSegEvaluator:
     def process(self, b: int, inst_table_row, inst_scores_row, pad_hw, img_hw, out_hw, annotations, image_index: int, pred_masks=None) -> None:
         """One picture: inst_table_row [1 + 2 topk] / inst_scores_row [topk] = image b's rows of the device instance table of the last
         call (HipCategoryODISE.keep_instance_selection -> last_selection), pad_hw / img_hw / out_hw as in `Context.instance_rle`;
-        annotations: the picture's dicts (category_id as in the dataset, iscrowd, area, segmentation = RLE dict); image_index: any number
+        annotations: the picture's dicts (category_id as in the dataset, iscrowd, area, segmentation = RLE dict or a list of polygons);
+        image_index: any number
         that orders the pictures the same way on every run (the position in the dataset).  With `pred_masks` (DeviceArray [topk, h, w],
         float32 or uint8) the detections are those dense masks instead of the mask logits.
         The ground truth goes up as one packed upload, which WAITS for the stream, and the temporary is freed on return by the library's
         synchronising free - which is also what keeps it alive until the kernels have read it.  The kernels themselves never wait."""
-        table, runs, offsets = IE.gt_rows(annotations, self.to_contiguous)
+        table, runs, offsets, xy, poly_offsets, gt_polys = IE.gt_rows(annotations, self.to_contiguous, polygons=True, hw=out_hw)
         assert len(table) <= IE.MAX_GT, f"{len(table)} ground-truth masks in one picture (at most {IE.MAX_GT})"
         self._npig += IE.npig(table, self.K)
-        gt = self.ctx.instance_gt_to_device(table, runs, offsets)
+        gt = self.ctx.instance_gt_to_device(table, runs, offsets, *((xy, poly_offsets, gt_polys) if len(poly_offsets) > 1 else ()))
         rows, n_rows = self._slot()
         self.ctx.instance_eval(out_hw, inst_table_row, inst_scores_row, self.topk, gt, self.K, int(image_index), rows, n_rows, self.flags,
                                masks=pred_masks, b=b, pad_hw=pad_hw, img_hw=img_hw)

@@ -506,20 +506,57 @@ class Context:
         """-> (RLE dicts of the selected instances in table order, area int64 [count])."""
         return self.instance_rle_async(b, table_row, topk, pad_hw, img_hw, out_hw, capacity).result()
 
+    def polygon_rle(self, annotations_polys, hw, capacity: Optional[int] = None):
+        """pycocotools' annToRLE on the device (odise_hip_polygon_rle): annotations_polys = [[polygon, ..] per annotation], a polygon a flat
+        list x0 y0 x1 y1 ..; an annotation is the union of its polygons, one without polygons the empty mask -> (RLE dicts of size hw,
+        area int64 [n]): the bytes of mask.merge(mask.frPyObjects(polygons, h, w)).  Malformed polygons raise ValueError on the host.
+        The polygons go up as one packed upload, which waits for the stream."""
+        from . import coco_poly
+        xy, poly_offsets, ann_polys = coco_poly.pack_polygons(annotations_polys)
+        n, n_poly, h, w = len(ann_polys) - 1, len(poly_offsets) - 1, int(hw[0]), int(hw[1])
+        buf = self.to_device(np.concatenate([poly_offsets.view(np.uint8), xy.view(np.uint8), ann_polys.view(np.uint8)]))
+        d_off, d_xy = buf.view((n_poly + 1,), np.int64), buf.view((xy.size,), np.float64, poly_offsets.nbytes)
+        d_ann = buf.view((n + 1,), np.int32, poly_offsets.nbytes + xy.nbytes)
+        flags = self.zeros((1,), np.int32)
+
+        def launch(out, cap, off, area):
+            check(self.lib.odise_hip_polygon_rle(self.h, _p(d_xy), _p(d_off), _p(d_ann), n, n_poly, h, w, _p(out), int(cap), _p(off), _p(area),
+                                                 _p(flags)), "polygon_rle")
+        rles, area = RlePending(self, n, (h, w), launch, capacity).result()
+        f = int(flags.numpy()[0])
+        if f:
+            raise RuntimeError(f"polygon_rle: malformed polygon(s) (flags {f})")
+        return rles, area
+
 
     # ---- segm evaluation of instance masks (include/odise_hip.h odise_hip_mask_iou / odise_hip_instance_eval; host restatement:
     # odise_amd/instance_eval.py) ------------------------------------------------------------------------------------------------------
-    def instance_gt_to_device(self, gt_table, runs, offsets) -> dict:
+    def instance_gt_to_device(self, gt_table, runs, offsets, xy=None, poly_offsets=None, gt_polys=None) -> dict:
         """The ground truth of one picture (instance_eval.gt_rows) as ONE packed upload: offsets int64 [n_gt + 1] | table int32 [n_gt, 3] |
-        runs uint32 -> {"n_gt", "offsets", "rows", "runs"} (views of one device buffer).  The upload waits for the stream."""
+        runs uint32 -> {"n_gt", "offsets", "rows", "runs"} (views of one device buffer).  With the polygon part of
+        `gt_rows(..., polygons=True)` the same upload carries poly_offsets int64 | xy float64 in front of the table and gt_polys int32
+        behind it, and the dict gains {"n_poly", "xy", "poly_offsets", "gt_polys"}.  The upload waits for the stream."""
         table = np.ascontiguousarray(np.asarray(gt_table, np.int32).reshape(-1, 3))
         runs, offsets = np.ascontiguousarray(runs, np.uint32), np.ascontiguousarray(offsets, np.int64)
         n_gt = table.shape[0]
         assert offsets.shape == (n_gt + 1,) and int(offsets[-1]) == runs.size, (offsets.shape, n_gt, runs.size)
-        buf = self.to_device(np.concatenate([offsets.view(np.uint8), table.reshape(-1).view(np.uint8), runs.view(np.uint8)]))
-        ob, tb = offsets.nbytes, table.nbytes
-        return {"n_gt": n_gt, "offsets": buf.view((n_gt + 1,), np.int64), "rows": buf.view((n_gt, 3), np.int32, ob),
-                "runs": buf.view((runs.size,), np.uint32, ob + tb)}
+        parts = [offsets]
+        if gt_polys is not None:
+            xy, poly_offsets = np.ascontiguousarray(xy, np.float64).reshape(-1), np.ascontiguousarray(poly_offsets, np.int64)
+            gt_polys = np.ascontiguousarray(gt_polys, np.int32)
+            n_poly = poly_offsets.size - 1
+            assert gt_polys.shape == (n_gt + 1,) and int(gt_polys[-1]) == n_poly and 2 * int(poly_offsets[-1]) == xy.size, \
+                (gt_polys.shape, n_gt, n_poly, xy.size)
+            parts += [poly_offsets, xy]                                  # the 8-byte items first: every view stays aligned
+        parts += [table.reshape(-1)] + ([gt_polys] if gt_polys is not None else []) + [runs]
+        buf = self.to_device(np.concatenate([p.view(np.uint8) for p in parts]))
+        at = np.concatenate(([0], np.cumsum([p.nbytes for p in parts]))).tolist()
+        gt = {"n_gt": n_gt, "offsets": buf.view((n_gt + 1,), np.int64), "rows": buf.view((n_gt, 3), np.int32, at[-3 if gt_polys is None else -4]),
+              "runs": buf.view((runs.size,), np.uint32, at[-2])}
+        if gt_polys is not None:
+            gt.update(n_poly=n_poly, poly_offsets=buf.view((n_poly + 1,), np.int64, at[1]), xy=buf.view((xy.size,), np.float64, at[2]),
+                      gt_polys=buf.view((n_gt + 1,), np.int32, at[-3]))
+        return gt
 
     def mask_iou(self, masks: DeviceArray, gt_counts, iscrowd=None, flags: Optional[DeviceArray] = None, with_counts: bool = False):
         """pycocotools' mask.iou of dense device masks [n, h, w] (float32 / uint8 / bool) against run-length masks: gt_counts = a list of
@@ -549,8 +586,8 @@ class Context:
         """Enqueue COCOeval.evaluateImg of one picture (odise_hip_instance_eval): detections = the selection table_row [1 + 2 topk] /
         scores_row [topk] of image b of the last head forward, sampled from its mask logits (pad_hw / img_hw as in `instance_rle`), or the
         dense `masks` [topk, h, w] when given; gt = `instance_gt_to_device`; rows (instance_eval.ROW_DTYPE [topk]), n_rows and flags
-        (int32 [1]) are device arrays or pointers."""
-        from ._lib import InstEvalDesc
+        (int32 [1]) are device arrays or pointers.  A gt that carries polygons goes through odise_hip_instance_eval_poly."""
+        from ._lib import InstEvalDesc, InstPolyGt
         from .instance_eval import IOU_THRS
         thr = np.ascontiguousarray(IOU_THRS if iou_thresholds is None else iou_thresholds, np.float64)
         assert thr.shape == (10,), thr.shape
@@ -565,7 +602,12 @@ class Context:
         d.gt_runs, d.gt_offsets, d.gt_rows, d.n_gt = gt["runs"].ptr, gt["offsets"].ptr, gt["rows"].ptr, int(gt["n_gt"])
         d.num_categories, d.image, d.iou_thresholds = int(num_categories), int(image), thr.ctypes.data
         d.rows, d.n_rows, d.flags = ptr(rows), ptr(n_rows), ptr(flags)
-        check(self.lib.odise_hip_instance_eval(self.h, C.byref(d)), "instance_eval")
+        if "gt_polys" in gt:
+            p = InstPolyGt()
+            p.xy, p.poly_offsets, p.gt_polys, p.n_poly = gt["xy"].ptr, gt["poly_offsets"].ptr, gt["gt_polys"].ptr, int(gt["n_poly"])
+            check(self.lib.odise_hip_instance_eval_poly(self.h, C.byref(d), C.byref(p)), "instance_eval_poly")
+        else:
+            check(self.lib.odise_hip_instance_eval(self.h, C.byref(d)), "instance_eval")
 
 
     def jpeg_decode(self, data: bytes, apply_orientation: bool = True, out: Optional[DeviceArray] = None) -> DeviceArray:
