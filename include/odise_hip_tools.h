@@ -30,6 +30,10 @@ int odise_hip_gemm_forced(odise_hip_ctx* ctx, const odise_gemm_desc* d, int tile
 int odise_hip_conv2d_forced(odise_hip_ctx* ctx, const odise_conv_desc* d, int tile, int splitk);
 /* tile id | split-K factor << 8 that the calling thread's last odise_hip_gemm / odise_hip_conv2d launch ran with (-1: none yet) */
 int odise_hip_last_tile(void);
+/* kernel | DPAD << 8 | nsplit << 16 of the calling thread's last odise_hip_attention launch (-1: none yet).  kernel: 0 = tiled (attn_kernel),
+ * 1 = K / V^T-resident (attn_kvres_kernel), 2 = pipelined self-attention (attn_sa_kernel); DPAD = the padded head dim of the instance that
+ * ran; nsplit = blocks the keys were split over (1: no split, no combine pass).  tests/test_gpu_attention_ref.py asserts which kernel a case reached */
+int odise_hip_last_attention(void);
 /* a GEMM with a LayerNorm folded into its epilogue, as the CLIP towers chain them (csrc/common.h LnEpi; any pointer may be NULL):
  *   producer  stats_out [M][N/64][2]: partial (sum, sum of squares) of every output row, per 64 columns
  *   consumer  part [M][parts][2] + colsum [N]: C = act(rstd_m (A W'^T - mean_m colsum) + bias_n) (+ residual), the row statistics finished from

@@ -32,6 +32,8 @@ struct AttnArgs {
     float* part;  // [B, H, nsplit, Lq, D + 2] fp32: unnormalised O^T rows, running max (log2 domain), running sum
 };
 
+static thread_local int g_last_attention = -1;   // odise_hip_last_attention: kernel | DPAD << 8 | nsplit << 16 of this thread's last launch
+
 template <int DPAD>
 __global__ void __launch_bounds__(256) attn_kernel(AttnArgs a) {
     constexpr int KS = DPAD / 16;          // MFMA k-steps of QK^T
@@ -496,6 +498,7 @@ static int launch_attn_kvres(odise_hip_ctx* ctx, AttnArgs& a) {
     int qsplit = (int)std::max<int64_t>(1, std::min<int64_t>(ctx->cu_count / pairs, ceil_div(nqt, KVR_WAVES)));
     a.nsplit = 1;
     a.part = nullptr;
+    g_last_attention = 1 | (64 << 8) | (1 << 16);
     dim3 grid((unsigned)qsplit, (unsigned)a.H, (unsigned)a.B);
     hipLaunchKernelGGL(attn_kvres_kernel<KVR_WAVES>, grid, dim3(64 * KVR_WAVES), KVR_LDS, ctx->stream, a, qsplit);
     ODISE_CHECK_HIP(hipGetLastError());
@@ -719,6 +722,7 @@ static int launch_attn_sa(odise_hip_ctx* ctx, AttnArgs& a) {
     constexpr int LDS = 2 * 64 * (DPAD + 8) * 2 + 3 * DT * 32 * 68 * 2;
     a.nsplit = 1;
     a.part = nullptr;
+    g_last_attention = 2 | (DPAD << 8) | (1 << 16);
     dim3 grid((unsigned)(a.Lq / 128), (unsigned)a.H, (unsigned)a.B);
     hipLaunchKernelGGL((attn_sa_kernel<DPAD>), grid, dim3(256), LDS, ctx->stream, a);
     ODISE_CHECK_HIP(hipGetLastError());
@@ -787,6 +791,7 @@ static int launch_attn(odise_hip_ctx* ctx, AttnArgs& a) {
             a.part = (float*)ctx->ws;
         }
     }
+    g_last_attention = 0 | (DPAD << 8) | (a.nsplit << 16);
     dim3 grid((unsigned)(qblocks * a.nsplit), (unsigned)a.H, (unsigned)a.B);
     hipLaunchKernelGGL((attn_kernel<DPAD>), grid, dim3(256), lds, ctx->stream, a);
     ODISE_CHECK_HIP(hipGetLastError());
@@ -800,6 +805,8 @@ static int launch_attn(odise_hip_ctx* ctx, AttnArgs& a) {
 
 }  // namespace odise
 
+extern "C" int odise_hip_last_attention(void) { return odise::g_last_attention; }
+
 extern "C" int odise_hip_attention(odise_hip_ctx* ctx, const odise_attn_desc* d) {
     using namespace odise;
     ODISE_REQUIRE(ctx && d, "attention: null argument");
@@ -812,6 +819,13 @@ extern "C" int odise_hip_attention(odise_hip_ctx* ctx, const odise_attn_desc* d)
     ODISE_REQUIRE(d->ldvt >= round_up(d->Lk, 8), "attention: ldvt=%lld must be >= Lk rounded up to 8", (long long)d->ldvt);
     ODISE_REQUIRE(!d->mask || (d->ldmask % 4 == 0 && d->ldmask >= round_up(d->Lk, 4)), "attention: ldmask must be a multiple of 4 and >= Lk");
     ODISE_REQUIRE((d->D * d->H) % 4 == 0, "attention: H*D must be a multiple of 4");
+    // the kernels read Q / K / V^T in 16-byte, the mask in 4-byte and write O in 8-byte pieces: every image's rows must stay aligned
+    ODISE_REQUIRE(d->strideQ % 8 == 0 && d->strideK % 8 == 0 && d->strideVt % 8 == 0 && d->strideO % 4 == 0,
+                  "attention: batch strides must keep 16-byte rows (strideQ / strideK / strideVt multiples of 8, strideO of 4)");
+    ODISE_REQUIRE(!d->mask || d->strideMask % 4 == 0, "attention: strideMask=%lld must be a multiple of 4", (long long)d->strideMask);
+    ODISE_REQUIRE((uintptr_t)d->Q % 16 == 0 && (uintptr_t)d->K % 16 == 0 && (uintptr_t)d->Vt % 16 == 0, "attention: Q, K and Vt must be 16-byte aligned");
+    ODISE_REQUIRE((uintptr_t)d->O % 8 == 0, "attention: O must be 8-byte aligned");
+    ODISE_REQUIRE(!d->mask || (uintptr_t)d->mask % 4 == 0, "attention: mask must be 4-byte aligned");
     AttnArgs a;
     a.B = d->B; a.H = d->H; a.Lq = d->Lq; a.Lk = d->Lk; a.D = d->D;
     a.Q = (const f16*)d->Q; a.ldq = d->ldq; a.strideQ = d->strideQ;

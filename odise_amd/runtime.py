@@ -312,21 +312,48 @@ class Context:
         return y
 
     def attention(self, Q: DeviceArray, K: DeviceArray, Vt: DeviceArray, heads: int, scale: float,
-                  mask: Optional[DeviceArray] = None, Lk: Optional[int] = None, out: Optional[DeviceArray] = None) -> DeviceArray:
-        """Q [B,Lq,H*D], K [B,Lk,H*D], Vt [B,H*D,ldvt] (transposed V) -> O [B,Lq,H*D] (all f16)."""
-        B, Lq, HD = Q.shape
+                  mask: Optional[DeviceArray] = None, Lk: Optional[int] = None, out: Optional[DeviceArray] = None, *,
+                  B: Optional[int] = None, Lq: Optional[int] = None, D: Optional[int] = None,
+                  ldq: Optional[int] = None, ldk: Optional[int] = None, ldvt: Optional[int] = None, ldo: Optional[int] = None,
+                  ldmask: Optional[int] = None, strideQ: Optional[int] = None, strideK: Optional[int] = None, strideVt: Optional[int] = None,
+                  strideO: Optional[int] = None, strideMask: Optional[int] = None, offQ: int = 0, offK: int = 0, offVt: int = 0, offO: int = 0,
+                  offMask: int = 0) -> DeviceArray:
+        """Q [B,Lq,H*D], K [B,Lk,H*D], Vt [B,H*D,ldvt] (transposed V) -> O [B,Lq,H*D] (all f16).
+
+        The keyword arguments lay the operands out as the model's call sites do (odise_attn_desc, include/odise_hip.h): leading dimensions and
+        batch strides in elements, `off*` = element offsets of the first operand element into its buffer (K = Q + C inside one q|k buffer),
+        and B / Lq / D where the buffers' shapes no longer say them (`heads` stays H).  With any of them the arrays are plain buffers of any
+        shape, and `out` is required unless O is packed.  Defaults: the packed layout the shapes describe."""
+        explicit = not all(v is None for v in (B, Lq, D, ldq, ldk, ldvt, ldo, ldmask, strideQ, strideK, strideVt, strideO, strideMask)) \
+            or bool(offQ or offK or offVt or offO or offMask)
+        if not explicit:
+            B, Lq, HD = Q.shape
+            D = HD // heads
+        else:
+            assert D is not None and Lq is not None and B is not None and Lk is not None, "attention: explicit layouts name B, Lq, Lk and D"
+            HD = heads * D
         Lk = Lk if Lk is not None else K.shape[1]
-        D = HD // heads
+        if out is None:
+            assert ldo in (None, HD) and strideO in (None, Lq * HD) and offO == 0, "attention: a strided O needs `out`"
         O = out if out is not None else self.empty((B, Lq, HD), np.float16)
         d = AttnDesc()
         d.B, d.H, d.Lq, d.Lk, d.D = B, heads, Lq, Lk, D
-        d.Q, d.ldq, d.strideQ = Q.ptr, HD, Lq * HD
-        d.K, d.ldk, d.strideK = K.ptr, HD, K.shape[1] * HD
-        d.Vt, d.ldvt, d.strideVt = Vt.ptr, Vt.shape[2], Vt.shape[1] * Vt.shape[2]
-        d.O, d.ldo, d.strideO = O.ptr, HD, Lq * HD
+        d.ldq = HD if ldq is None else int(ldq)
+        d.ldk = HD if ldk is None else int(ldk)
+        d.ldvt = Vt.shape[2] if ldvt is None else int(ldvt)
+        d.ldo = HD if ldo is None else int(ldo)
+        d.strideQ = Lq * d.ldq if strideQ is None else int(strideQ)
+        d.strideK = (Lk if explicit else K.shape[1]) * d.ldk if strideK is None else int(strideK)
+        d.strideVt = (HD if explicit else Vt.shape[1]) * d.ldvt if strideVt is None else int(strideVt)
+        d.strideO = Lq * d.ldo if strideO is None else int(strideO)
+        d.Q, d.K, d.Vt, d.O = Q.ptr + 2 * int(offQ), K.ptr + 2 * int(offK), Vt.ptr + 2 * int(offVt), O.ptr + 2 * int(offO)
         if mask is not None:
-            assert mask.dtype == np.uint8 and mask.shape[0] == B and mask.shape[1] == Lq
-            d.mask, d.ldmask, d.strideMask = mask.ptr, mask.shape[2], mask.shape[1] * mask.shape[2]
+            assert mask.dtype == np.uint8
+            if not explicit:
+                assert mask.shape[0] == B and mask.shape[1] == Lq
+            d.ldmask = mask.shape[-1] if ldmask is None else int(ldmask)
+            d.strideMask = Lq * d.ldmask if strideMask is None else int(strideMask)
+            d.mask = mask.ptr + int(offMask)
         d.scale = float(scale)
         check(self.lib.odise_hip_attention(self.h, C.byref(d)), "attention")
         return O
