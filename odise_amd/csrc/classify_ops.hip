@@ -245,6 +245,67 @@ __device__ __forceinline__ f16 sig_f16(float sg, float v) {
     return v > 0.f ? (h < half ? half : h) : (h > below ? below : h);   // selects, no branch
 }
 
+// ---- what the three forms of the per-pixel pass share: one definition each, so they cannot drift apart ---------------------------------
+// One step of a pixel's walk over the queries: query q (score ks, < 0 = not kept; the caller loads it and keeps it wave-uniform) has logit v at
+// the pixel (ok: the pixel exists).  Returns the fp16 sigmoid for S; for a kept query calls ballot(pos), pos = sigmoid >= 0.5 - the caller counts
+// the query's area its own way, inside the same uniform branch - and moves the panoptic arg-max (first maximum of ks * sigmoid; selects, and an
+// int flag, instead of exec-masked moves).  The arg-max stays in the caller's variables (a struct around them changed the tiled kernel's
+// register allocation); they start as -1.f, -1, 0.
+template <typename Ballot>
+__device__ __forceinline__ f16 pixel_step(float v, float ks, int q, bool ok, float& best, int& best_q, int& best_pos, Ballot&& ballot) {
+    const float sg = post_sigmoid(v);
+    const f16 h = sig_f16(sg, v);
+    const bool pos = sg >= 0.5f;
+    if (ks >= 0.f) {
+        ballot(pos);
+        const float pv = ks * sg;
+        const bool upd = ok & (pv > best);
+        best = upd ? pv : best;
+        best_q = upd ? q : best_q;
+        best_pos = upd ? (int)pos : best_pos;
+    }
+    return h;
+}
+// the ids value of a pixel: arg-max kept query | pos << 16, -1 if nothing kept
+__device__ __forceinline__ int pixel_word(int best_q, int best_pos) { return best_q < 0 ? -1 : (best_q | (best_pos << 16)); }
+// a finished pixel p: its ids word (pixel_word) and the two area counters that follow from it (mask_area, intersection)
+__device__ __forceinline__ void commit_pixel(int word, int* __restrict__ ids, int64_t p, int* hist, int Q) {
+    if (ids) ids[p] = word;
+    if (word >= 0) {
+        atomicAdd(&hist[word & 0xffff], 1);
+        if (word & (1 << 16)) atomicAdd(&hist[2 * Q + (word & 0xffff)], 1);
+    }
+}
+// the block's LDS counters (blocks of 256 threads): zero n of them (the caller's barrier follows) / add the nonzero ones to the global counters
+__device__ __forceinline__ void block_zero(int* a, int n) {
+    for (int i = threadIdx.x; i < n; i += 256) a[i] = 0;
+}
+__device__ __forceinline__ void block_flush(const int* a, int* __restrict__ out, int n) {
+    for (int i = threadIdx.x; i < n; i += 256)
+        if (a[i]) atomicAdd(&out[i], a[i]);
+}
+// instance statistics of one thread's 8 queries over its pixels (column_stats_kernel and the tiled pass's epilogue: the sums are explained there)
+constexpr float kStatUnit = 2048.0f;  // fp16 values from 0.5 up are whole multiples of 2^-11
+struct ColumnStats {
+    unsigned int s[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}, c[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    __device__ __forceinline__ void add(f16x8 t) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float a = (float)t[i];
+            if (a >= 0.5f) { s[i] += (unsigned int)(a * kStatUnit); c[i] += 1u; }
+        }
+    }
+    // into the block's [2][Qpad] LDS sums; v = the thread's group of 8 queries
+    __device__ __forceinline__ void commit(unsigned int* st, int Qpad, int v) const {
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (c[i]) {
+                atomicAdd(&st[v * 8 + i], s[i]);
+                atomicAdd(&st[Qpad + v * 8 + i], c[i]);
+            }
+    }
+};
+
 // thread per output pixel.  kscore[q] = panoptic score of query q if it is kept (label != null, score > threshold) else < 0.
 // S [npix, Qpad] f16 sigmoid (optional); ids [npix] int32 = argmax kept query | (sigmoid>=0.5 ? 1<<16 : 0), -1 if nothing kept;
 // counts [3][Q] int32: mask_area (argmax == q), original_area (sigmoid >= 0.5), intersection.
@@ -253,15 +314,14 @@ __global__ void __launch_bounds__(256) postprocess_pixels_kernel(const f16* __re
                                                                 PostGeom g) {
     extern __shared__ int hist[];  // [3][Q]
     const int Q = g.Q;
-    for (int i = threadIdx.x; i < 3 * Q; i += blockDim.x) hist[i] = 0;
+    block_zero(hist, 3 * Q);
     __syncthreads();
     const int npix = g.oh * g.ow;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     const bool ok = p < npix;
     const int oy = ok ? p / g.ow : 0, ox = ok ? p - oy * g.ow : 0;
     float best = -1.f;
-    int best_q = -1;
-    bool best_pos = false;
+    int best_q = -1, best_pos = 0;
     for (int q0 = 0; q0 < g.Qpad; q0 += 8) {
         f16x8 sv = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -269,59 +329,47 @@ __global__ void __launch_bounds__(256) postprocess_pixels_kernel(const f16* __re
             const int q = q0 + j;
             if (q < Q) {  // uniform branch
                 const float v = ok ? sample_mask(logits + (int64_t)q * g.h4 * g.w4, g, oy, ox) : -1.f;
-                const float sg = post_sigmoid(v);
-                sv[j] = sig_f16(sg, v);
                 const float ks = kscore[q];
-                const bool pos = sg >= 0.5f;
-                if (ks >= 0.f) {
+                sv[j] = pixel_step(v, ks, q, ok, best, best_q, best_pos, [&](bool pos) {
                     const unsigned long long bal = __ballot(ok && pos);
                     if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&hist[Q + q], __popcll(bal));
-                    const float pv = ks * sg;
-                    if (ok && pv > best) { best = pv; best_q = q; best_pos = pos; }
-                }
+                });
             }
         }
         if (S && ok) *reinterpret_cast<f16x8*>(S + (int64_t)p * g.Qpad + q0) = sv;
     }
-    if (ok) {
-        if (ids) ids[p] = best_q < 0 ? -1 : (best_q | (best_pos ? (1 << 16) : 0));
-        if (best_q >= 0) {
-            atomicAdd(&hist[best_q], 1);
-            if (best_pos) atomicAdd(&hist[2 * Q + best_q], 1);
-        }
-    }
+    if (ok) commit_pixel(pixel_word(best_q, best_pos), ids, p, hist, Q);
     __syncthreads();
-    for (int i = threadIdx.x; i < 3 * Q; i += blockDim.x)
-        if (hist[i]) atomicAdd(&counts[i], hist[i]);
+    block_flush(hist, counts, 3 * Q);
 }
 
 // Same outputs as postprocess_pixels_kernel for the common geometry (output size = image size, mask logits at exactly 1/4 of the
 // padded size): the x4 bilinear upsampling has a fixed tap pattern - output column 4c+k reads cells (c-1, c) with t = .625 / .875
 // for k = 0, 1 and (c, c+1) with t = .125 / .375 for k = 2, 3 (indices clamped at the border, which reproduces the clamped source
 // coordinate exactly) - so one thread produces the 4 pixels of a cell column from 2 rows x 3 cells per query: 6 coalesced 2-byte
-// loads per query instead of 16 gathers, the same arithmetic per pixel, identical results.
+// loads per query instead of 16 gathers; the pixel values come from x4_rows / x4_cols / x4_pixel (post_sample.h), whose expressions are
+// sample_mask's for this geometry, the decision from pixel_step: identical results.
 __global__ void __launch_bounds__(256) postprocess_pixels_x4_kernel(const f16* __restrict__ logits, const float* __restrict__ kscore,
                                                                    f16* __restrict__ S, int* __restrict__ ids, int* __restrict__ counts,
                                                                    PostGeom g) {
     extern __shared__ int hist[];  // [3][Q]
     const int Q = g.Q;
-    for (int i = threadIdx.x; i < 3 * Q; i += blockDim.x) hist[i] = 0;
+    block_zero(hist, 3 * Q);
     __syncthreads();
     const int cw = (g.ow + 3) >> 2;  // cell columns per output row
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const bool okt = t < g.oh * cw;
     const int oy = okt ? t / cw : 0, cx = okt ? t - oy * cw : 0;
-    const int cy = oy >> 2, ky = oy & 3;
-    const int ra = max(ky < 2 ? cy - 1 : cy, 0), rb = min(ky < 2 ? cy : cy + 1, g.h4 - 1);
-    const float ty = ky == 0 ? 0.625f : ky == 1 ? 0.875f : ky == 2 ? 0.125f : 0.375f;
-    const int cl = max(cx - 1, 0), cr = min(cx + 1, g.w4 - 1);
+    int ra, rb, cl, cr;
+    float ty;
+    x4_rows(g, oy, ra, rb, ty);
+    x4_cols(g, cx, cl, cr);
     const int oa = ra * g.w4, ob = rb * g.w4;
     bool ok[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) ok[k] = okt && (4 * cx + k) < g.ow;
     float best[4] = {-1.f, -1.f, -1.f, -1.f};
-    int best_q[4] = {-1, -1, -1, -1};
-    bool best_pos[4] = {false, false, false, false};
+    int best_q[4] = {-1, -1, -1, -1}, best_pos[4] = {0, 0, 0, 0};
     const int64_t p0 = (int64_t)oy * g.ow + 4 * cx;
     const int plane = g.h4 * g.w4;
     for (int q0 = 0; q0 < g.Qpad; q0 += 8) {
@@ -338,19 +386,11 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_kernel(const f16* _
                 const float ks = kscore[q];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float tx = k == 0 ? 0.625f : k == 1 ? 0.875f : k == 2 ? 0.125f : 0.375f;
-                    const float v00 = k < 2 ? al : ac, v01 = k < 2 ? ac : ar, v10 = k < 2 ? bl : bc, v11 = k < 2 ? bc : br;
-                    const float top = v00 + tx * (v01 - v00), bot = v10 + tx * (v11 - v10);
-                    const float v = ok[k] ? top + ty * (bot - top) : -1.f;
-                    const float sg = post_sigmoid(v);
-                    sv[k][j] = sig_f16(sg, v);
-                    const bool pos = sg >= 0.5f;
-                    if (ks >= 0.f) {
+                    const float v = ok[k] ? x4_pixel(k, ty, al, ac, ar, bl, bc, br) : -1.f;
+                    sv[k][j] = pixel_step(v, ks, q, ok[k], best[k], best_q[k], best_pos[k], [&](bool pos) {
                         const unsigned long long bal = __ballot(ok[k] && pos);
                         if ((threadIdx.x & 63) == 0 && bal) atomicAdd(&hist[Q + q], __popcll(bal));
-                        const float pv = ks * sg;
-                        if (ok[k] && pv > best[k]) { best[k] = pv; best_q[k] = q; best_pos[k] = pos; }
-                    }
+                    });
                 }
             }
         }
@@ -362,16 +402,9 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_kernel(const f16* _
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-        if (ok[k]) {
-            if (ids) ids[p0 + k] = best_q[k] < 0 ? -1 : (best_q[k] | (best_pos[k] ? (1 << 16) : 0));
-            if (best_q[k] >= 0) {
-                atomicAdd(&hist[best_q[k]], 1);
-                if (best_pos[k]) atomicAdd(&hist[2 * Q + best_q[k]], 1);
-            }
-        }
+        if (ok[k]) commit_pixel(pixel_word(best_q[k], best_pos[k]), ids, p0 + k, hist, Q);
     __syncthreads();
-    for (int i = threadIdx.x; i < 3 * Q; i += blockDim.x)
-        if (hist[i]) atomicAdd(&counts[i], hist[i]);
+    block_flush(hist, counts, 3 * Q);
 }
 
 // ---- tiled form of postprocess_pixels_x4_kernel ------------------------------------------------------------------------------------
@@ -379,13 +412,21 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_kernel(const f16* _
 // writes the pixel-major matrix S as 16-byte pieces of 208-byte rows, 13 separate partial-line stores per pixel: 375 us per 1024^2 image,
 // 0.58 TB/s of its 218 MB (profiles/r02_bench_full_by_shape.txt).  Here a block owns 256 consecutive pixels of one output row (64 cell
 // columns) and ALL queries: the 13 groups of 8 queries are dealt round-robin to the block's four wavefronts (4x the threads of the old
-// form), every thread evaluates its 4 pixels x 8 queries per group with the same arithmetic as before - bit-identical results - and
+// form), every thread evaluates its 4 pixels x 8 queries per group with x4_pixel and pixel_step - bit-identical results - and
 // puts the fp16 sigmoids into an LDS image of the tile's S rows; the tile is then written out as ONE contiguous 53 KB run of the matrix
 // (256 pixels x 208 bytes are adjacent in memory), 16 bytes per lane, whole 128-byte lines.  The panoptic arg-max is finished across the
 // four query slices through LDS (ties to the lowest query, like the sequential walk), the area counters as before.
-constexpr float kStatUnit = 2048.0f;  // instance statistics: fp16 values from 0.5 up are whole multiples of 2^-11 (column_stats_kernel)
 constexpr int PT_PIX = 256;          // pixels of a tile
 constexpr int PT_CELLS = 64;         // cell columns of a tile (one per lane)
+// 8 queries of a pixel row of the LDS image, as two 8-byte halves (the rows are 8-byte aligned: pitch)
+__device__ __forceinline__ f16x8 tile_load8(const char* src) {
+    const f16x4 lo = *reinterpret_cast<const f16x4*>(src), hi = *reinterpret_cast<const f16x4*>(src + 8);
+    return f16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+__device__ __forceinline__ void tile_store8(char* dst, f16x8 v) {
+    *reinterpret_cast<f16x4*>(dst) = f16x4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<f16x4*>(dst + 8) = f16x4{v[4], v[5], v[6], v[7]};
+}
 // Round 6: the semantic head rides in the same kernel (`sem` != nullptr).  sem_seg[c, p] = sum_q P[q, c] sigmoid(mask)[q, p]
 // (maskformer_model.py:280-284) was a GEMM over the pixel-major matrix S this kernel had just written: 218 MB out, 218 MB back in, then 558 MB
 // of scores per 1024^2 picture - 353 us at 1.8 TB/s behind the 204 us pixel pass.  The tile's S rows are still in LDS when the block is done
@@ -406,23 +447,22 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_tiled_kernel(const 
     int* hist = red_q + 4 * PT_PIX;                                         // [3][Q]
     unsigned int* st = reinterpret_cast<unsigned int*>(hist + 3 * Q);       // [2][Qpad] instance statistics of the tile (stats_partial)
     const int tid = threadIdx.x, lane = tid & 63, slice = tid >> 6;
-    for (int i = tid; i < 3 * Q + 2 * Qpad; i += 256) hist[i] = 0;
+    block_zero(hist, 3 * Q + 2 * Qpad);   // hist and st in one sweep
     const int oy = blockIdx.x / tiles_per_row, cx0 = (blockIdx.x - oy * tiles_per_row) * PT_CELLS;
     const int cw = (g.ow + 3) >> 2;
     const int cx = cx0 + lane;
     const bool okt = cx < cw;
     const int cxc = okt ? cx : cw - 1;
-    const int cy = oy >> 2, ky = oy & 3;
-    const int ra = max(ky < 2 ? cy - 1 : cy, 0), rb = min(ky < 2 ? cy : cy + 1, g.h4 - 1);
-    const float ty = ky == 0 ? 0.625f : ky == 1 ? 0.875f : ky == 2 ? 0.125f : 0.375f;
-    const int cl = max(cxc - 1, 0), cr = min(cxc + 1, g.w4 - 1);
+    int ra, rb, cl, cr;
+    float ty;
+    x4_rows(g, oy, ra, rb, ty);
+    x4_cols(g, cxc, cl, cr);
     const int oa = ra * g.w4, ob = rb * g.w4;
     bool ok[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) ok[k] = okt && (4 * cx + k) < g.ow;
     float best[4] = {-1.f, -1.f, -1.f, -1.f};
-    int best_q[4] = {-1, -1, -1, -1};
-    int best_pos[4] = {0, 0, 0, 0};   // int, not bool: selects instead of exec-masked moves
+    int best_q[4] = {-1, -1, -1, -1}, best_pos[4] = {0, 0, 0, 0};
     const int plane = g.h4 * g.w4;
     __syncthreads();   // hist is zero
     for (int q0 = slice * 8; q0 < Qpad; q0 += 32) {
@@ -452,40 +492,21 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_tiled_kernel(const 
                 int npos = 0;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float tx = k == 0 ? 0.625f : k == 1 ? 0.875f : k == 2 ? 0.125f : 0.375f;
-                    const float v00 = k < 2 ? al : ac, v01 = k < 2 ? ac : ar, v10 = k < 2 ? bl : bc, v11 = k < 2 ? bc : br;
-                    const float top = v00 + tx * (v01 - v00), bot = v10 + tx * (v11 - v10);
-                    const float v = ok[k] ? top + ty * (bot - top) : -1.f;
-                    const float sg = post_sigmoid(v);
-                    sv[k][j] = sig_f16(sg, v);
-                    const bool pos = sg >= 0.5f;
-                    if (ks >= 0.f) {   // wave-uniform
-                        npos += __popcll(__ballot(ok[k] & pos));
-                        const float pv = ks * sg;
-                        const bool upd = ok[k] & (pv > best[k]);
-                        best[k] = upd ? pv : best[k];
-                        best_q[k] = upd ? q : best_q[k];
-                        best_pos[k] = upd ? (int)pos : best_pos[k];
-                    }
+                    const float v = ok[k] ? x4_pixel(k, ty, al, ac, ar, bl, bc, br) : -1.f;
+                    sv[k][j] = pixel_step(v, ks, q, ok[k], best[k], best_q[k], best_pos[k], [&](bool pos) { npos += __popcll(__ballot(ok[k] & pos)); });
                 }
                 if (ks >= 0.f && lane == 0 && npos) atomicAdd(&hist[Q + q], npos);
             }
         }
         if (S || (KS > 0 && sem) || stats_partial) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-                char* dst = tile + (size_t)(4 * lane + k) * pitch + q0 * 2;
-                f16x4v lo = {sv[k][0], sv[k][1], sv[k][2], sv[k][3]}, hi = {sv[k][4], sv[k][5], sv[k][6], sv[k][7]};
-                *reinterpret_cast<f16x4v*>(dst) = lo;
-                *reinterpret_cast<f16x4v*>(dst + 8) = hi;
-            }
+            for (int k = 0; k < 4; ++k) tile_store8(tile + (size_t)(4 * lane + k) * pitch + q0 * 2, sv[k]);
         }
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         red_v[slice * PT_PIX + 4 * lane + k] = best[k];
-        red_q[slice * PT_PIX + 4 * lane + k] = best_q[k] < 0 ? -1 : (best_q[k] | (best_pos[k] << 16));
+        red_q[slice * PT_PIX + 4 * lane + k] = pixel_word(best_q[k], best_pos[k]);
     }
     __syncthreads();
     // ---- panoptic arg-max across the four query slices: thread per pixel of the tile
@@ -500,11 +521,7 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_tiled_kernel(const 
                 const int qq = red_q[sl * PT_PIX + tid];
                 if (qq >= 0 && (v > bv || (v == bv && (qq & 0xffff) < (bq & 0xffff)))) { bv = v; bq = qq; }
             }
-            if (ids) ids[(int64_t)oy * g.ow + px] = bq;
-            if (bq >= 0) {
-                atomicAdd(&hist[bq & 0xffff], 1);
-                if (bq & (1 << 16)) atomicAdd(&hist[2 * Q + (bq & 0xffff)], 1);
-            }
+            commit_pixel(bq, ids, (int64_t)oy * g.ow + px, hist, Q);
         }
     }
     // ---- instance statistics of the tile (column_stats_kernel's sums, taken from the LDS image instead of a second pass over S in HBM)
@@ -513,25 +530,9 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_tiled_kernel(const 
         const int v = tid % V, pl = tid / V;
         const int npx = min(PT_PIX, g.ow - 4 * cx0);
         if (pl < PL) {
-            unsigned int s[8], c[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) s[i] = c[i] = 0u;
-            for (int p = pl; p < npx; p += PL) {
-                typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-                const char* src = tile + (size_t)p * pitch + v * 16;
-                const f16x4v lo = *reinterpret_cast<const f16x4v*>(src), hi = *reinterpret_cast<const f16x4v*>(src + 8);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float a = (float)(i < 4 ? lo[i & 3] : hi[i & 3]);
-                    if (a >= 0.5f) { s[i] += (unsigned int)(a * kStatUnit); c[i] += 1u; }
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (c[i]) {
-                    atomicAdd(&st[v * 8 + i], s[i]);
-                    atomicAdd(&st[Qpad + v * 8 + i], c[i]);
-                }
+            ColumnStats acc;
+            for (int p = pl; p < npx; p += PL) acc.add(tile_load8(tile + (size_t)p * pitch + v * 16));
+            acc.commit(st, Qpad, v);
         }
     }
     // ---- the tile's S rows: one contiguous run of the matrix
@@ -542,11 +543,7 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_tiled_kernel(const 
         f16* dst = S + ((int64_t)oy * g.ow + 4 * cx0) * Qpad;
         for (int j = tid; j < nchunks; j += 256) {
             const int pxl = j / cpp, part = j - pxl * cpp;
-            typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-            const char* src = tile + (size_t)pxl * pitch + part * 16;
-            const f16x4v lo = *reinterpret_cast<const f16x4v*>(src), hi = *reinterpret_cast<const f16x4v*>(src + 8);
-            f16x8 o = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-            *reinterpret_cast<f16x8*>(dst + (int64_t)j * 8) = o;
+            *reinterpret_cast<f16x8*>(dst + (int64_t)j * 8) = tile_load8(tile + (size_t)pxl * pitch + part * 16);
         }
     }
     // ---- semantic scores of the tile's pixels from the LDS image (the tile is complete since the barrier above)
@@ -563,12 +560,7 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_tiled_kernel(const 
             for (int ks = 0; ks < KS; ++ks) {
                 const int ko = ks * 16 + hi * 8;
                 pf[ks] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-                if (pok && ko + 8 <= Qpad) {
-                    typedef _Float16 f16x4v __attribute__((ext_vector_type(4)));
-                    const char* src = tile + (size_t)pxl * pitch + ko * 2;
-                    const f16x4v lo = *reinterpret_cast<const f16x4v*>(src), hh = *reinterpret_cast<const f16x4v*>(src + 8);
-                    pf[ks] = f16x8{lo[0], lo[1], lo[2], lo[3], hh[0], hh[1], hh[2], hh[3]};
-                }
+                if (pok && ko + 8 <= Qpad) pf[ks] = tile_load8(tile + (size_t)pxl * pitch + ko * 2);
             }
             float* out = sem + (int64_t)oy * g.ow + px;
             for (int c0 = 0; c0 < K; c0 += 32) {
@@ -592,8 +584,7 @@ __global__ void __launch_bounds__(256) postprocess_pixels_x4_tiled_kernel(const 
         }
     }
     __syncthreads();
-    for (int i = tid; i < 3 * Q; i += 256)
-        if (hist[i]) atomicAdd(&counts[i], hist[i]);
+    block_flush(hist, counts, 3 * Q);
     if (stats_partial)
         for (int i = tid; i < 2 * Qpad; i += 256) stats_partial[(int64_t)blockIdx.x * 2 * Qpad + i] = st[i];
 }
@@ -610,24 +601,10 @@ __global__ void __launch_bounds__(256) column_stats_kernel(const f16* __restrict
     const int p0 = blockIdx.x * pix_per_block, p1 = min(npix, p0 + pix_per_block);
     for (int i = threadIdx.x; i < 2 * Qpad; i += blockDim.x) cs[i] = 0u;
     __syncthreads();
-    unsigned int s[8], c[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s[i] = c[i] = 0u;
     if (pl < PL) {
-        for (int p = p0 + pl; p < p1; p += PL) {
-            const f16x8 t = *reinterpret_cast<const f16x8*>(S + (int64_t)p * Qpad + v * 8);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const float a = (float)t[i];
-                if (a >= 0.5f) { s[i] += (unsigned int)(a * kStatUnit); c[i] += 1u; }
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            if (c[i]) {
-                atomicAdd(&cs[v * 8 + i], s[i]);
-                atomicAdd(&cs[Qpad + v * 8 + i], c[i]);
-            }
+        ColumnStats acc;
+        for (int p = p0 + pl; p < p1; p += PL) acc.add(*reinterpret_cast<const f16x8*>(S + (int64_t)p * Qpad + v * 8));
+        acc.commit(cs, Qpad, v);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < 2 * Qpad; i += blockDim.x) partial[(int64_t)blockIdx.x * 2 * Qpad + i] = cs[i];
@@ -679,10 +656,10 @@ __global__ void __launch_bounds__(256) instance_masks_x4_kernel(const f16* __res
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= g.oh * cw) return;
     const int oy = t / cw, cx = t - oy * cw;
-    int ra, rb;
+    int ra, rb, cl, cr;
     float ty;
     x4_rows(g, oy, ra, rb, ty);
-    const int cl = max(cx - 1, 0), cr = min(cx + 1, g.w4 - 1);
+    x4_cols(g, cx, cl, cr);
     const f16* lr = logits + (int64_t)idx[n] * g.h4 * g.w4;
     const float al = (float)lr[ra * g.w4 + cl], ac = (float)lr[ra * g.w4 + cx], ar = (float)lr[ra * g.w4 + cr];
     const float bl = (float)lr[rb * g.w4 + cl], bc = (float)lr[rb * g.w4 + cx], br = (float)lr[rb * g.w4 + cr];
@@ -1084,15 +1061,16 @@ int launch_classify_rows(odise_hip_ctx* ctx, const float* L1, const float* L2, c
     ODISE_CHECK_HIP(hipGetLastError());
     return ODISE_OK;
 }
+// the exact 4x upsampling the x4 kernels serve: output size = image size, padded size = 4 x the logits' (post_sample.h)
+static bool exact_x4(const PostGeom& g) { return g.oh == g.ih && g.ow == g.iw && g.ph == 4 * g.h4 && g.pw == 4 * g.w4; }
 static size_t tiled_lds(const PostGeom& g) {
     return (size_t)PT_PIX * (g.Qpad * 2 + 8) + 8 * (size_t)PT_PIX * 4 + 3 * (size_t)g.Q * sizeof(int) + 2 * (size_t)g.Qpad * sizeof(unsigned int);
 }
 // true when the pixel pass of this geometry runs its tiled form (an exact 4x upsampling whose tile fits 64 KB of LDS): that form can leave the
 // instance statistics itself (stats_partial: `postprocess_pixels_stat_blocks` block partials for column_fold), so S need not exist for them
-bool postprocess_pixels_tiled(const PostGeom& g) {
-    return g.oh == g.ih && g.ow == g.iw && g.ph == 4 * g.h4 && g.pw == 4 * g.w4 && g_post_generic == 0 && tiled_lds(g) <= 64 * 1024;
-}
-int postprocess_pixels_stat_blocks(const PostGeom& g) { return g.oh * (int)ceil_div((g.ow + 3) / 4, PT_CELLS); }
+bool postprocess_pixels_tiled(const PostGeom& g) { return exact_x4(g) && g_post_generic == 0 && tiled_lds(g) <= 64 * 1024; }
+static int tiles_per_row(const PostGeom& g) { return (int)ceil_div((g.ow + 3) / 4, PT_CELLS); }
+int postprocess_pixels_stat_blocks(const PostGeom& g) { return g.oh * tiles_per_row(g); }
 // ... and the semantic scores too (Qpad <= 112): the caller then passes PT / sem to launch_postprocess_pixels and skips the semantic GEMM
 bool postprocess_pixels_fuses_semantic(const PostGeom& g) { return postprocess_pixels_tiled(g) && g.Qpad <= 112 && g.ow % 32 == 0; }
 int launch_postprocess_pixels(odise_hip_ctx* ctx, const f16* logits, const float* kscore, f16* S, int* ids, int* counts, const PostGeom& g, const f16* PT,
@@ -1100,14 +1078,14 @@ int launch_postprocess_pixels(odise_hip_ctx* ctx, const f16* logits, const float
     const int npix = g.oh * g.ow;
     ODISE_REQUIRE(!sem || (PT && K > 0 && postprocess_pixels_fuses_semantic(g)), "postprocess_pixels: this geometry cannot fuse the semantic head");
     ODISE_REQUIRE(!stats_partial || postprocess_pixels_tiled(g), "postprocess_pixels: this geometry cannot leave the instance statistics");
-    if (g.oh == g.ih && g.ow == g.iw && g.ph == 4 * g.h4 && g.pw == 4 * g.w4 && g_post_generic != 1) {
+    if (exact_x4(g) && g_post_generic != 1) {
         const size_t lds = tiled_lds(g);
         if (g_post_generic != 2 && lds <= 64 * 1024) {   // tiled form (two blocks per CU); odise_hip_post_generic(2) keeps the thread-per-cell-column form
-            const int tiles_per_row = (int)ceil_div((g.ow + 3) / 4, PT_CELLS);
-            if (sem) hipLaunchKernelGGL(postprocess_pixels_x4_tiled_kernel<7>, dim3((unsigned)(g.oh * tiles_per_row)), dim3(256), lds, ctx->stream, logits, kscore, S,
-                                        ids, counts, g, tiles_per_row, PT, sem, K, stats_partial);
-            else hipLaunchKernelGGL(postprocess_pixels_x4_tiled_kernel<0>, dim3((unsigned)(g.oh * tiles_per_row)), dim3(256), lds, ctx->stream, logits, kscore, S, ids,
-                                    counts, g, tiles_per_row, nullptr, nullptr, 0, stats_partial);
+            const dim3 grid((unsigned)postprocess_pixels_stat_blocks(g));
+            if (sem) hipLaunchKernelGGL(postprocess_pixels_x4_tiled_kernel<7>, grid, dim3(256), lds, ctx->stream, logits, kscore, S, ids, counts, g, tiles_per_row(g), PT,
+                                        sem, K, stats_partial);
+            else hipLaunchKernelGGL(postprocess_pixels_x4_tiled_kernel<0>, grid, dim3(256), lds, ctx->stream, logits, kscore, S, ids, counts, g, tiles_per_row(g), nullptr,
+                                    nullptr, 0, stats_partial);
             ODISE_CHECK_HIP(hipGetLastError());
             return ODISE_OK;
         }
@@ -1180,9 +1158,7 @@ int launch_panoptic_write(odise_hip_ctx* ctx, const int* ids, const int* map, in
     return ODISE_OK;
 }
 // the geometries instance_masks_x4_kernel serves (rle.hip samples its pixels with the same taps there)
-bool instance_masks_x4(const PostGeom& g) {
-    return g.oh == g.ih && g.ow == g.iw && g.ph == 4 * g.h4 && g.pw == 4 * g.w4 && g.ow % 4 == 0 && g_post_generic != 1;
-}
+bool instance_masks_x4(const PostGeom& g) { return exact_x4(g) && g.ow % 4 == 0 && g_post_generic != 1; }
 int launch_instance_masks(odise_hip_ctx* ctx, const f16* logits, const int* idx, float* out, int n, const PostGeom& g, const int* n_dev) {
     if (n == 0) return ODISE_OK;
     if (instance_masks_x4(g) && ((uintptr_t)out & 15) == 0) {

@@ -46,7 +46,13 @@ __device__ __forceinline__ void x4_rows(const PostGeom& g, int oy, int& ra, int&
     rb = min(ky < 2 ? cy : cy + 1, g.h4 - 1);
     ty = ky == 0 ? 0.625f : ky == 1 ? 0.875f : ky == 2 ? 0.125f : 0.375f;
 }
-// pixel k of a cell column from its six taps (a* on row ra, b* on row rb; l / c / r = columns cl, cx, cr)
+// the neighbour columns of cell column cx (a lane past the row's last cell column passes the clamped one: every load stays in range)
+__device__ __forceinline__ void x4_cols(const PostGeom& g, int cx, int& cl, int& cr) {
+    cl = max(cx - 1, 0);
+    cr = min(cx + 1, g.w4 - 1);
+}
+// pixel k of a cell column from its six taps (a* on row ra, b* on row rb; l / c / r = columns cl, cx, cr): the value every x4 consumer thresholds -
+// both x4 forms of the per-pixel pass, instance_masks_x4_kernel and rle_pack_x4_kernel
 __device__ __forceinline__ float x4_pixel(int k, float ty, float al, float ac, float ar, float bl, float bc, float br) {
     const float tx = k == 0 ? 0.625f : k == 1 ? 0.875f : k == 2 ? 0.125f : 0.375f;
     const float v00 = k < 2 ? al : ac, v01 = k < 2 ? ac : ar, v10 = k < 2 ? bl : bc, v11 = k < 2 ? bc : br;

@@ -151,7 +151,8 @@ __global__ void __launch_bounds__(256) rle_pack_x4_kernel(const f16* __restrict_
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= G.R * cw) return;
     const int r = t / cw, cx = t - r * cw;
-    const int cl = max(cx - 1, 0), cr = min(cx + 1, g.w4 - 1);
+    int cl, cr;
+    x4_cols(g, cx, cl, cr);
     const f16* lr = logits + (int64_t)idx[i] * g.h4 * g.w4;
     const int y0 = 64 * r, rows = min(64, g.oh - y0);
     unsigned long long v0 = 0ull, v1 = 0ull, v2 = 0ull, v3 = 0ull;
