@@ -938,7 +938,10 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g, WaveAcc<BM, BN,
     // chunk: everything but the 256x320 tile), without GEGLU (its half-width rows leave the lean loop; the block-wide form is ~15 % ahead there).
     // ODISE_GEMM_FLAGS 32768 keeps the block-wide forms everywhere (A/B of whole steps: bench.py --gemm-flags).
     if constexpr (LDSB > 0 && WAVES_M * WAVES_N == 8 && (64 % ((BN / WAVES_N) / 8)) == 0) {
-        if (g.epi.fast && !split && !g.epi.geglu && !g.epi_block && !ODISE_ABLATE(g, 8)) {
+        // (the wave-private form only stores whole 8-column chunks: a block that holds the ragged last chunk of an N % 8 != 0 problem - `fast`
+        // looks at pointers and pitches, not at N - takes the block-wide form, whose scalar tail writes it)
+        const bool whole_chunks = n0 + BN <= g.N || (g.N & 7) == 0;
+        if (g.epi.fast && whole_chunks && !split && !g.epi.geglu && !g.epi_block && !ODISE_ABLATE(g, 8)) {
             gemm_epilogue_wave<BM, BN, WAVES_M, WAVES_N, HALO, STATS, GEGLU_OK, LDSB>(g, acc, smem, m0, n0, zb);
             return;
         }
