@@ -528,6 +528,62 @@ typedef struct {
 } odise_inst_poly_gt;
 int odise_hip_instance_eval_poly(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p);
 
+/* ---- drawing a panoptic result (demo/demo.py:173-199 VisualizationDemo.run_on_image -> detectron2 Visualizer.draw_panoptic_seg) ----
+ * The per-pixel work of that call on the panoptic record as it lies in HBM: the pieces of a segment, where its label goes, and the
+ * coloured picture.  Glyphs and file encoding stay on the host (odise_amd/visualize.py, which also restates the rules below in numpy). */
+/* Connected components of a label map, 8-connectivity.  labels int32 [H,W] (device) -> roots int32 [H,W] (device, must not overlap
+ * labels): roots[p] = the smallest row-major pixel index among the pixels joined to p by 8-neighbour steps over EQUAL labels;
+ * roots[p] = -1 where labels[p] <= 0 (VOID).  A function of the input alone: the same bytes from run to run.  Tiles of 32 x 32 are
+ * labelled in LDS, their borders joined by integer atomic minima in `roots` itself, and a last pass points every pixel at its root; no
+ * scratch.  ODISE_ERR_ARG and nothing written: a null pointer, H or W < 1, H * W > 2^29 - 1.  Asynchronous on the context's stream. */
+int odise_hip_connected_components(odise_hip_ctx* ctx, const int32_t* labels, int H, int W, int32_t* roots);
+/* Where detectron2 puts the labels of a panoptic result (Visualizer.draw_panoptic_seg -> draw_binary_mask / _draw_text_in_mask).
+ * pred_ids / pred_segments are the two parts of the panoptic record, as in odise_pq_desc; in the table the first row of an id counts,
+ * isthing != 0 is a thing, and ids <= 0 of the map are VOID.  Rows of 32 bytes {segment_row, area, x2, y2, x0, y0, x1, y1}: x2 / y2 are
+ * TWICE the median column / row of the pixels the row stands for (np.median(mask.nonzero(), axis=1): the .5 of an even count is exact),
+ * x0..y1 their inclusive bounding box, area their number.
+ *   thing row whose id has a pixel   one anchor over ALL pixels of the segment, in however many pieces it lies.
+ *   stuff row                        nothing if its largest 8-connected component has fewer than small_area pixels; otherwise one anchor
+ *                                    for the largest component (equal areas: the one with the smaller root, i.e. met first in row-major
+ *                                    order) and one for every other component with MORE than large_area pixels.
+ *   a table row without a pixel, a map id without a row: nothing.
+ * Anchors are written in ascending (segment_row, root) order; n_anchors is the total found, at most `cap` rows are written and nothing
+ * is written past them.  detectron2's constants are small_area = 1000, large_area = 120000.  Medians come from per-anchor column and
+ * row histograms and a scan (nothing is sorted); all counting is integer atomics, so the output is the same from run to run.  The
+ * order is found by comparing the anchors of a call with each other: they are few (at most n + H * W / (large_area + 1)).
+ * ODISE_ERR_ARG and nothing written: a null pointer, H or W < 1, H * W > 2^29 - 1, cap < 0.  Scratch comes from the context.
+ * Asynchronous on the context's stream. */
+typedef struct { int32_t segment_row, area, x2, y2, x0, y0, x1, y1; } odise_anchor_row;   /* 32 bytes */
+typedef struct {
+    int H, W;
+    const int32_t* pred_ids;      /* device [H*W] */
+    const int32_t* pred_segments; /* device: n | n rows (id, isthing, category_id); n is read on the device, n <= ODISE_MAX_SEGMENTS */
+    int small_area, large_area;
+    odise_anchor_row* anchors;    /* device [cap] */
+    int cap;
+    int32_t* n_anchors;           /* device [1] */
+} odise_anchor_desc;
+int odise_hip_segment_anchors(odise_hip_ctx* ctx, const odise_anchor_desc* d);
+/* The coloured picture.  image / out uint8 [H,W,3] (device; out == image is allowed, any other overlap is not), colors uint8 [n][3]
+ * (device), one per table row.  Per pixel, in this order of precedence:
+ *   its id is <= 0 or has no row                                          out = image
+ *   a 4-neighbour INSIDE the picture has a different id                    out = edge_rgb
+ *   otherwise, per channel                                                out = (image * (256 - alpha256) + color * alpha256 + 128) >> 8
+ * Integer arithmetic, one pass; buffers of any byte alignment (four pixels per lane as three dwords where image and out are 4-byte
+ * aligned, pixel by pixel otherwise).  ODISE_ERR_ARG and nothing written: a null pointer, H or W < 1, H * W > 2^29 - 1, alpha256
+ * outside 0..256.  Asynchronous on the context's stream. */
+typedef struct {
+    int H, W;
+    const uint8_t* image;
+    const int32_t* pred_ids;      /* as odise_anchor_desc */
+    const int32_t* pred_segments;
+    const uint8_t* colors;
+    int alpha256;                 /* 0 (the picture) .. 256 (the colour) */
+    uint8_t edge_rgb[3];
+    uint8_t* out;
+} odise_overlay_desc;
+int odise_hip_panoptic_overlay(odise_hip_ctx* ctx, const odise_overlay_desc* d);
+
 /* ---- JPEG input -------------------------------------------------------------------------------------------
  * Replaces detectron2 `read_image(file, "RGB")` = PIL.Image.open -> EXIF transpose -> convert("RGB") of the DatasetMapper
  * (configs/common/data/pano_open_d2_eval.py:74-107; demo/demo.py:399) for baseline JPEG files, bit-identical to Pillow /

@@ -108,6 +108,18 @@ class InstPolyGt(C.Structure):
     _fields_ = [("xy", c_void_p), ("poly_offsets", c_void_p), ("gt_polys", c_void_p), ("n_poly", c_int)]
 
 
+class AnchorDesc(C.Structure):
+    """odise_anchor_desc (include/odise_hip.h)."""
+    _fields_ = [("H", c_int), ("W", c_int), ("pred_ids", c_void_p), ("pred_segments", c_void_p), ("small_area", c_int), ("large_area", c_int),
+                ("anchors", c_void_p), ("cap", c_int), ("n_anchors", c_void_p)]
+
+
+class OverlayDesc(C.Structure):
+    """odise_overlay_desc (include/odise_hip.h)."""
+    _fields_ = [("H", c_int), ("W", c_int), ("image", c_void_p), ("pred_ids", c_void_p), ("pred_segments", c_void_p), ("colors", c_void_p),
+                ("alpha256", c_int), ("edge_rgb", C.c_uint8 * 3), ("out", c_void_p)]
+
+
 MAX_SEGMENTS = 100          # ODISE_MAX_SEGMENTS
 COMM_ID_BYTES = 128         # ODISE_COMM_ID_BYTES
 

@@ -89,6 +89,7 @@ extern "C" int odise_hip_destroy(odise_hip_ctx* ctx) {
     odise::jpeg_release(ctx);
     odise::scratch_release(ctx->rle);
     odise::scratch_release(ctx->boundary);
+    odise::scratch_release(ctx->vis);
     odise::pq_release(ctx);
     odise::comm_release(ctx);
     odise::probe_release(ctx);

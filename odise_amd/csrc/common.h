@@ -135,6 +135,7 @@ struct odise_hip_ctx {
     void* launch_log = nullptr;      // std::vector<odise::LaunchRec>* while odise_hip_launch_log is on: (shape, tile, split-K) of every GEMM / conv launch
     odise::DeviceScratch rle;        // rle.hip: odise_hip_rle_encode / odise_hip_instance_rle (bit-packed masks, per-thread scan state, string lengths)
     odise::DeviceScratch boundary;   // eval_ops.hip: odise_hip_label_boundary / odise_hip_semantic_boundary_confusion (byte label maps, their erosions)
+    odise::DeviceScratch vis;        // vis.hip: odise_hip_segment_anchors (roots and areas of the components, the anchor list, the column / row histograms)
     void* pq = nullptr;              // odise::PqScratch* (pq.hip): the pair-count matrix and the ground-truth table staging of odise_hip_panoptic_quality
 };
 

@@ -1,0 +1,141 @@
+"""`python -m odise_amd.demo --input FILE... --output DIR [--vocab "a, b; c"] [--synthetic]`: demo/demo.py on the device path.
+
+A picture is read (JPEG through HipDatasetMapper, anything else through Pillow), resized by ResizeShortestEdge(1024, 2560) on the device,
+run through HipOpenPanopticInference with demo.py's settings (overlap_threshold = 0, alpha / beta = 0.35 / 0.65, demo.py:316-318), and
+its panoptic record - still in HBM - is drawn by HipVisualizer.draw_panoptic_seg and saved with Pillow as DIR/<name>.png.
+
+Weights come from `$ODISE_MODEL_ZOO` through odise_amd/checkpoint.py; `--synthetic` takes random tensors of the real shapes and seeded
+text banks instead (odise_amd/synthetic.py), which draws arbitrary segments but needs no file.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import zlib
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+
+def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
+    ap = argparse.ArgumentParser(prog="python -m odise_amd.demo", description="Panoptic segmentation of pictures, drawn and saved as PNG.")
+    ap.add_argument("--input", nargs="+", required=True, metavar="FILE", help="pictures (JPEG is decoded on the device)")
+    ap.add_argument("--output", required=True, metavar="DIR", help="directory for the drawn pictures")
+    ap.add_argument("--vocab", default="", help='extra classes, demo.py style: "black pickup truck, pickup truck; blue sky, sky"')
+    ap.add_argument("--synthetic", action="store_true", help="random weights of the real shapes and seeded text banks: needs no checkpoint")
+    ap.add_argument("--device", type=int, default=0)
+    return ap.parse_args(argv)
+
+
+def extra_classes(vocab: str) -> List[List[str]]:
+    """demo.py:330-334: classes separated by ';', the synonyms of a class by ','."""
+    return [[s.strip() for s in c.split(",") if s.strip()] for c in vocab.split(";") if c.strip()]
+
+
+def output_path(out_dir: str, file_name: str) -> str:
+    return os.path.join(out_dir, os.path.splitext(os.path.basename(file_name))[0] + ".png")
+
+
+def _palette(n: int, seed: int) -> list:
+    rng = np.random.default_rng(seed)
+    return [tuple(int(v) for v in c) for c in rng.integers(32, 224, (n, 3))]
+
+
+def demo_metadata(labels: List[List[str]], num_things: int) -> dict:
+    """What demo.py builds with MetadataCatalog: the first synonym of a class is its name; things come first."""
+    names = [l[0] for l in labels]
+    return {"thing_classes": names[:num_things], "stuff_classes": names, "thing_colors": _palette(num_things, 1), "stuff_colors": _palette(len(names), 2),
+            "thing_ids": list(range(num_things))}
+
+
+class _SeededText:
+    """--synthetic: stands in for tokenizer + CLIP text tower (no merges file, no weights): a prompt string -> a seeded random row."""
+
+    def __call__(self, strings):
+        return list(strings)
+
+    def build_text_embed(self, strings):
+        return np.stack([np.random.default_rng(zlib.crc32(s.encode())).standard_normal(768) for s in strings]).astype(np.float32)
+
+
+def build_model(ctx, labels: List[List[str]], num_things: int, synthetic: bool):
+    from .pipeline import HipCategoryODISE, HipOpenPanopticInference
+    if synthetic:
+        from .synthetic import synthetic_state
+        hip = HipCategoryODISE(ctx, synthetic_state(), overlap_threshold=0.0)
+        text = _SeededText()
+        hip.attach_text(text, text, train_labels=labels)
+    else:
+        from .checkpoint import assemble_state, load_openai_clip
+        from .text import HipTextEncoder
+        from .tokenizer import SimpleTokenizer
+        hip = HipCategoryODISE(ctx, assemble_state(ctx), overlap_threshold=0.0)
+        hip.attach_text(SimpleTokenizer(), HipTextEncoder(ctx, load_openai_clip("clip://ViT-L-14-336")))
+    hip._alpha, hip._beta = 0.35, 0.65                                   # demo.py:316-318
+    metadata = demo_metadata(labels, num_things)
+    return HipOpenPanopticInference(hip, labels, metadata, semantic_on=False, instance_on=False, panoptic_on=True), metadata
+
+
+def default_labels(extra: List[List[str]]):
+    """(labels, number of things).  With the reference's label files at hand ($ODISE_OPENSEG_LABELS) the COCO panoptic vocabulary of
+    demo.py's `--label COCO`; without them only the classes given with --vocab (demo.py treats those as things and puts them first)."""
+    from .checkpoint import default_train_labels
+    try:
+        coco = default_train_labels()
+    except FileNotFoundError:
+        coco = []
+    labels = extra + coco
+    if not labels:
+        raise SystemExit("no vocabulary: give classes with --vocab or point ODISE_OPENSEG_LABELS at the reference's label files")
+    return labels, len(extra) + (80 if coco else 0)
+
+
+def read_picture(ctx, file_name: str):
+    """-> DeviceArray uint8 [h,w,3]"""
+    from ._lib import UnsupportedInput
+    from .ingest import HipDatasetMapper
+    try:
+        return HipDatasetMapper(ctx, None)({"file_name": file_name})["image"]
+    except UnsupportedInput:
+        from PIL import Image, ImageOps
+        with Image.open(file_name) as im:
+            return ctx.to_device(np.ascontiguousarray(np.asarray(ImageOps.exif_transpose(im).convert("RGB"), np.uint8)))
+
+
+def run_on_image(ctx, model, visualizer, image_dev) -> np.ndarray:
+    """VisualizationDemo.run_on_image (demo.py:173-199) for a picture that is on the device; the result never leaves it before it is drawn."""
+    from ._lib import MAX_SEGMENTS
+    from .ingest import HipDatasetMapper
+    h, w = image_dev.shape[:2]
+    inputs = HipDatasetMapper(ctx, 1024, 2560)._finish({"height": h, "width": w}, image_dev)
+    record = ctx.empty((h * w + 1 + 3 * MAX_SEGMENTS,), np.int32)
+    inner = model.model
+    saved = inner.open_state_dict()
+    inner.load_open_state_dict(model.open_state_dict)
+    try:
+        inner.infer_device([inputs["image"]], 0, [tuple(inputs["image"].shape[:2])], [(h, w)], pan_out=[record])
+    finally:
+        inner.load_open_state_dict(saved)
+    return visualizer.draw_panoptic_seg(image_dev, record, (h, w))
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    args = parse_args(argv)
+    from PIL import Image
+    from .runtime import Context
+    from .visualize import HipVisualizer
+    labels, num_things = default_labels(extra_classes(args.vocab))
+    ctx = Context(args.device)
+    model, metadata = build_model(ctx, labels, num_things, args.synthetic)
+    visualizer = HipVisualizer(ctx, metadata)
+    os.makedirs(args.output, exist_ok=True)
+    for file_name in args.input:
+        picture = run_on_image(ctx, model, visualizer, read_picture(ctx, file_name))
+        Image.fromarray(picture).save(output_path(args.output, file_name))
+        print(f"{file_name} -> {output_path(args.output, file_name)}")
+    ctx.close()
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

@@ -498,6 +498,54 @@ class Context:
         return self.panoptic_quality(flat.view((h, w), np.int32), flat.view((1 + 3 * MAX_SEGMENTS,), np.int32, h * w * 4), gt, gt_segments,
                                      num_categories, stats, flags)
 
+    # ---- drawing a panoptic result (include/odise_hip.h odise_hip_connected_components ..; host restatement: odise_amd/visualize.py) ----
+    def connected_components(self, labels: DeviceArray, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """labels int32 [H,W] -> int32 [H,W]: the smallest row-major index of the pixel's 8-connected component of equal labels,
+        -1 where labels <= 0."""
+        H, W = labels.shape
+        assert labels.dtype == np.int32
+        if out is None:
+            out = self.empty((H, W), np.int32)
+        assert out.dtype == np.int32 and out.shape == (H, W)
+        check(self.lib.odise_hip_connected_components(self.h, _p(labels), H, W, _p(out)), "connected_components")
+        return out
+
+    def segment_anchors(self, pred_ids: DeviceArray, pred_segments: DeviceArray, small_area: int = 1000, large_area: int = 120000,
+                        cap: int = 256, anchors: Optional[DeviceArray] = None, n_anchors: Optional[DeviceArray] = None):
+        """Label anchors of a panoptic result, enqueued: pred_ids int32 [H,W], pred_segments int32 [n | n x (id, isthing, category)]
+        -> (anchors [cap] records of visualize.ANCHOR_DTYPE, n_anchors int32 [1] = all that were found)."""
+        from ._lib import AnchorDesc
+        from .visualize import ANCHOR_DTYPE
+        H, W = pred_ids.shape
+        assert pred_ids.dtype == np.int32 and pred_segments.dtype == np.int32
+        if anchors is None:
+            anchors = self.zeros((int(cap),), ANCHOR_DTYPE)
+        if n_anchors is None:
+            n_anchors = self.zeros((1,), np.int32)
+        assert anchors.dtype == ANCHOR_DTYPE and anchors.shape[0] >= max(int(cap), 0) and n_anchors.dtype == np.int32
+        d = AnchorDesc()
+        d.H, d.W, d.pred_ids, d.pred_segments = H, W, pred_ids.ptr, pred_segments.ptr
+        d.small_area, d.large_area, d.anchors, d.cap, d.n_anchors = int(small_area), int(large_area), anchors.ptr, int(cap), n_anchors.ptr
+        check(self.lib.odise_hip_segment_anchors(self.h, C.byref(d)), "segment_anchors")
+        return anchors, n_anchors
+
+    def panoptic_overlay(self, image: DeviceArray, pred_ids: DeviceArray, pred_segments: DeviceArray, colors: DeviceArray,
+                         alpha256: int = 128, edge_rgb=(0, 0, 0), out: Optional[DeviceArray] = None) -> DeviceArray:
+        """image uint8 [H,W,3] -> out uint8 [H,W,3] (may be `image`): segments blended with colors uint8 [n,3], outlines in edge_rgb."""
+        from ._lib import OverlayDesc
+        H, W = pred_ids.shape
+        assert image.dtype == np.uint8 and image.shape == (H, W, 3), (image.dtype, image.shape)
+        assert pred_ids.dtype == np.int32 and pred_segments.dtype == np.int32 and colors.dtype == np.uint8
+        if out is None:
+            out = self.empty((H, W, 3), np.uint8)
+        assert out.dtype == np.uint8 and out.shape == (H, W, 3)
+        d = OverlayDesc()
+        d.H, d.W, d.image, d.pred_ids, d.pred_segments, d.colors = H, W, image.ptr, pred_ids.ptr, pred_segments.ptr, colors.ptr
+        d.alpha256, d.out = int(alpha256), out.ptr
+        d.edge_rgb[0], d.edge_rgb[1], d.edge_rgb[2] = (int(c) & 255 for c in edge_rgb)
+        check(self.lib.odise_hip_panoptic_overlay(self.h, C.byref(d)), "panoptic_overlay")
+        return out
+
     # ---- COCO RLE of instance masks (segm evaluation; include/odise_hip.h odise_hip_rle_encode / odise_hip_instance_rle) ----------------
     # Default string capacity per mask.  A string has one to seven characters per run and most runs of a real mask take two or three, so
     # 8 KiB holds a mask with ~3000 runs - a blob spanning ~1500 columns; a selection that needs more costs one more pass (the retry).

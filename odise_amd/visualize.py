@@ -1,0 +1,223 @@
+"""Drawing a panoptic result: `VisualizationDemo.run_on_image` (demo/demo.py:173-199) -> detectron2 `Visualizer.draw_panoptic_seg`.
+
+The per-pixel work - the pieces of a segment, where its label goes, the colour blend and the outlines - runs on the device
+(csrc/vis.hip: odise_hip_connected_components / odise_hip_segment_anchors / odise_hip_panoptic_overlay) on the panoptic record as it lies
+in HBM; glyphs are drawn on the host with Pillow.  This module holds
+
+* the numpy restatement of the three rules, written literally: the reference the device is held to (tests/test_gpu_visualize.py), itself
+  pinned to scipy.ndimage.label, np.median and a per-pixel loop (tests/test_visualize_cpu.py);
+* `segment_colors`: which colour a table row gets;
+* `HipVisualizer.draw_panoptic_seg`.
+
+The rules are detectron2's (a stuff label at the median pixel of the segment's largest 8-connected component and of every other
+component above `large_area`, nothing for a segment whose largest component is below `small_area`; a thing label at the median pixel of
+its mask).  NO pixel parity with detectron2's matplotlib rendering is claimed: the rules are its rules, the rasterisation - integer
+blend, one-pixel outlines along 4-neighbour id changes, Pillow's default font - is this project's.
+"""
+from __future__ import annotations
+
+import colorsys
+from typing import Optional, Sequence
+
+import numpy as np
+
+SMALL_AREA = 1000       # detectron2 _SMALL_OBJECT_AREA_THRESH
+LARGE_AREA = 120000     # detectron2 _LARGE_MASK_AREA_THRESH
+
+ANCHOR_DTYPE = np.dtype([("segment_row", np.int32), ("area", np.int32), ("x2", np.int32), ("y2", np.int32),
+                         ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32)])   # odise_anchor_row, 32 bytes
+assert ANCHOR_DTYPE.itemsize == 32
+
+
+# ---- the restatement ------------------------------------------------------------------------------------------------------------------
+def connected_roots(labels) -> np.ndarray:
+    """labels int [H,W] -> int32 [H,W]: the smallest row-major index among the pixels joined to p by 8-neighbour steps over equal
+    labels; -1 where labels <= 0.  A flood fill from every pixel that has no root yet, in row-major order (so the seed is the minimum)."""
+    labels = np.asarray(labels)
+    H, W = labels.shape
+    roots = np.full((H, W), -1, np.int32)
+    for y in range(H):
+        for x in range(W):
+            l = labels[y, x]
+            if l <= 0 or roots[y, x] >= 0:
+                continue
+            seed = y * W + x
+            roots[y, x] = seed
+            stack = [(y, x)]
+            while stack:
+                cy, cx = stack.pop()
+                for ny in range(max(cy - 1, 0), min(cy + 2, H)):
+                    for nx in range(max(cx - 1, 0), min(cx + 2, W)):
+                        if roots[ny, nx] < 0 and labels[ny, nx] == l:
+                            roots[ny, nx] = seed
+                            stack.append((ny, nx))
+    return roots
+
+
+def _table(segments) -> np.ndarray:
+    return np.asarray(segments, np.int64).reshape(-1, 3)
+
+
+def _row_of_id(segments: np.ndarray) -> dict:
+    rows = {}
+    for r, (i, _, _) in enumerate(segments):
+        if i > 0 and int(i) not in rows:          # the first row of an id counts
+            rows[int(i)] = r
+    return rows
+
+
+def _anchor(row: int, mask: np.ndarray) -> tuple:
+    ys, xs = np.nonzero(mask)
+    my, mx = np.median(np.stack([ys, xs]), axis=1)
+    return (row, len(ys), int(round(2 * mx)), int(round(2 * my)), int(xs.min()), int(ys.min()), int(xs.max()), int(ys.max()))
+
+
+def segment_anchors(pred_ids, segments, small_area: int = SMALL_AREA, large_area: int = LARGE_AREA) -> np.ndarray:
+    """pred_ids int [H,W], segments rows (id, isthing, category) -> ANCHOR_DTYPE records in ascending (segment_row, root) order."""
+    pred_ids = np.asarray(pred_ids)
+    segments = _table(segments)
+    rows = _row_of_id(segments)
+    roots = None
+    out = []
+    for r, (i, isthing, _) in enumerate(segments):
+        if rows.get(int(i)) != r:
+            continue
+        mask = pred_ids == i
+        if not mask.any():
+            continue
+        if isthing:
+            out.append(_anchor(r, mask))
+            continue
+        if roots is None:
+            roots = connected_roots(pred_ids)
+        comp, areas = np.unique(roots[mask], return_counts=True)          # ascending root = the order the components are met in
+        largest = int(np.argmax(areas))                                   # the first of equal areas
+        if areas[largest] < small_area:
+            continue
+        for k, c in enumerate(comp):
+            if k == largest or areas[k] > large_area:
+                out.append(_anchor(r, roots == c))
+    return np.array(out, ANCHOR_DTYPE) if out else np.zeros((0,), ANCHOR_DTYPE)
+
+
+def panoptic_overlay(image, pred_ids, segments, colors, alpha256: int = 128, edge_rgb=(0, 0, 0)) -> np.ndarray:
+    """image uint8 [H,W,3] -> uint8 [H,W,3]: pixels of a table row blended with the row's colour, outlined where a 4-neighbour inside
+    the picture has another id; everything else untouched."""
+    image = np.asarray(image, np.uint8)
+    ids = np.asarray(pred_ids).astype(np.int64)
+    segments = _table(segments)
+    colors = np.asarray(colors, np.int64).reshape(-1, 3)
+    assert 0 <= alpha256 <= 256
+    row = np.full(ids.shape, -1, np.int64)
+    for i, r in _row_of_id(segments).items():
+        row[ids == i] = r
+    known = row >= 0
+    edge = np.zeros(ids.shape, bool)
+    edge[:, 1:] |= ids[:, 1:] != ids[:, :-1]
+    edge[:, :-1] |= ids[:, :-1] != ids[:, 1:]
+    edge[1:, :] |= ids[1:, :] != ids[:-1, :]
+    edge[:-1, :] |= ids[:-1, :] != ids[1:, :]
+    blend = (image.astype(np.int64) * (256 - alpha256) + colors[np.where(known, row, 0)] * alpha256 + 128) >> 8 if len(colors) else image
+    out = np.where(known[..., None], blend, image)
+    out = np.where((known & edge)[..., None], np.asarray(edge_rgb, np.int64), out)
+    return out.astype(np.uint8)
+
+
+# ---- colours --------------------------------------------------------------------------------------------------------------------------
+def _meta(metadata, key, default=None):
+    if metadata is None:
+        return default
+    v = metadata.get(key) if isinstance(metadata, dict) else getattr(metadata, key, None)
+    return default if v is None else v
+
+
+def _fallback_color(k: int) -> tuple:
+    r, g, b = colorsys.hsv_to_rgb((k * 0.61803398875) % 1.0, 0.65, 0.95)
+    return int(r * 255), int(g * 255), int(b * 255)
+
+
+def _jitter(color, segment_id: int) -> tuple:
+    """A per-segment-id offset of up to +-24 per channel (detectron2 jitters instance colours randomly; here it is a function of the id)."""
+    x = (int(segment_id) * 2654435761) & 0xFFFFFFFF
+    return tuple(int(min(255, max(0, int(c) + ((x >> (8 * k)) & 0xFF) % 49 - 24))) for k, c in enumerate(color))
+
+
+def segment_colors(segments, metadata=None) -> np.ndarray:
+    """uint8 [n,3], one colour per table row: the metadata's `stuff_colors[category]` for stuff, its `thing_colors[category]` with a
+    deterministic per-segment-id jitter for things; a category the metadata has no colour for gets one from a fixed hue sequence."""
+    segments = _table(segments)
+    stuff, thing = _meta(metadata, "stuff_colors", []), _meta(metadata, "thing_colors", [])
+    out = np.zeros((len(segments), 3), np.uint8)
+    for r, (i, isthing, cat) in enumerate(segments):
+        table = thing if isthing else stuff
+        base = tuple(table[cat]) if 0 <= cat < len(table) else _fallback_color(int(cat))
+        out[r] = _jitter(base, i) if isthing else base
+    return out
+
+
+def segment_names(segments, metadata=None) -> list:
+    segments = _table(segments)
+    stuff, thing = _meta(metadata, "stuff_classes", []), _meta(metadata, "thing_classes", [])
+    names = []
+    for _, isthing, cat in segments:
+        table = thing if isthing and 0 <= cat < len(thing) else stuff
+        names.append(str(table[cat]) if 0 <= cat < len(table) else f"class {int(cat)}")
+    return names
+
+
+def draw_labels(picture: np.ndarray, anchors: np.ndarray, segments, metadata=None) -> np.ndarray:
+    """Class names at the anchors, centred on them (detectron2 centres a thing's label on the mask median when no box is drawn, and a
+    stuff label on its component's): white text on a dark plate, Pillow's default font."""
+    from PIL import Image, ImageDraw, ImageFont
+    names = segment_names(segments, metadata)
+    img = Image.fromarray(np.ascontiguousarray(picture, np.uint8))
+    draw = ImageDraw.Draw(img)
+    font = ImageFont.load_default()
+    for a in anchors:
+        text = names[int(a["segment_row"])]
+        cx, cy = a["x2"] / 2.0, a["y2"] / 2.0
+        l, t, r, b = draw.textbbox((0, 0), text, font=font)
+        x, y = cx - (r - l) / 2.0 - l, cy - (b - t) / 2.0 - t
+        draw.rectangle([x + l - 2, y + t - 1, x + r + 2, y + b + 1], fill=(0, 0, 0))
+        draw.text((x, y), text, fill=(255, 255, 255), font=font)
+    return np.asarray(img)
+
+
+def draw_panoptic_seg(image, pred_ids, segments, metadata=None, alpha256: int = 128, edge_rgb=(0, 0, 0), small_area: int = SMALL_AREA,
+                      large_area: int = LARGE_AREA) -> np.ndarray:
+    """The host path from end to end: what HipVisualizer.draw_panoptic_seg returns, computed by the restatement."""
+    segments = _table(segments)
+    pic = panoptic_overlay(image, pred_ids, segments, segment_colors(segments, metadata), alpha256, edge_rgb)
+    return draw_labels(pic, segment_anchors(pred_ids, segments, small_area, large_area), segments, metadata)
+
+
+class HipVisualizer:
+    """`Visualizer(image, metadata).draw_panoptic_seg(panoptic_seg, segments_info)` for a result that is still on the device.
+
+    No pixel parity with detectron2's matplotlib rendering is claimed: the rules (which pixels belong to a label, where it goes) are
+    its rules; the rasterisation is this project's."""
+
+    def __init__(self, ctx, metadata=None, alpha: float = 0.5, edge_rgb=(0, 0, 0), small_area: int = SMALL_AREA, large_area: int = LARGE_AREA,
+                 max_anchors: int = 256):
+        self.ctx, self.metadata = ctx, metadata
+        self.alpha256 = int(round(alpha * 256))
+        self.edge_rgb, self.small_area, self.large_area, self.max_anchors = tuple(edge_rgb), int(small_area), int(large_area), int(max_anchors)
+
+    def draw_panoptic_seg(self, image_dev, record_dev, hw) -> np.ndarray:
+        """image_dev uint8 [h,w,3] and the panoptic record int32 [h*w | 1 | 3*MAX_SEGMENTS] on the device -> host uint8 [h,w,3].
+        Overlay and anchors on the device, one read-back of the picture and the anchor rows (the table travels first: its rows choose
+        the colours), the names drawn at the anchors."""
+        from ._lib import MAX_SEGMENTS
+        ctx = self.ctx
+        h, w = int(hw[0]), int(hw[1])
+        assert record_dev.dtype == np.int32 and int(np.prod(record_dev.shape)) >= h * w + 1 + 3 * MAX_SEGMENTS, (record_dev.shape, hw)
+        flat = record_dev.view((h * w + 1 + 3 * MAX_SEGMENTS,), np.int32)
+        ids, table = flat.view((h, w), np.int32), flat.view((1 + 3 * MAX_SEGMENTS,), np.int32, h * w * 4)
+        tail = table.numpy()
+        n = min(max(int(tail[0]), 0), MAX_SEGMENTS)
+        segments = tail[1:1 + 3 * n].reshape(n, 3)
+        colors = ctx.to_device(np.ascontiguousarray(segment_colors(segments, self.metadata).reshape(-1, 3)) if n else np.zeros((1, 3), np.uint8))
+        pic = ctx.panoptic_overlay(image_dev, ids, table, colors, self.alpha256, self.edge_rgb)
+        anchors, count = ctx.segment_anchors(ids, table, self.small_area, self.large_area, self.max_anchors)
+        picture, rows, found = pic.numpy(), anchors.numpy(), int(count.numpy()[0])
+        return draw_labels(picture, rows[:min(found, self.max_anchors)], segments, self.metadata)
