@@ -583,6 +583,56 @@ typedef struct {
     uint8_t* out;
 } odise_overlay_desc;
 int odise_hip_panoptic_overlay(odise_hip_ctx* ctx, const odise_overlay_desc* d);
+/* ---- drawing instance and semantic results (the else branch of run_on_image: draw_sem_seg, then draw_instance_predictions) ----
+ * Instance masks overlap, so they are drawn from the bit-packed words the segm evaluators use (exactly the pixels of
+ * odise_hip_instance_rle), not from a label map.  The descriptor follows odise_inst_eval_desc: the detections are the selection of image
+ * b of the last head forward (inst_table / inst_scores / pad / img as there; masks sampled from the mask logits, n read on the device),
+ * or dense `masks` [topk,h,w], for which inst_table (NULL: n = topk) and inst_scores (NULL: no score test) are optional.
+ *   kept       instance i < n is kept iff inst_scores[i] >= min_score and its mask has a pixel.
+ *   anchors    (optional) [topk] rows, one per table index: segment_row = i, area, x2 / y2 = TWICE np.median of the mask's columns / rows
+ *              (detectron2 centres the label there when the instance has no box; the reference's pred_boxes are zeros), x0..y1 the
+ *              bounding box.  A row that is not kept (or i >= n) is {-1, 0, 0, 0, 0, 0, 0, 0}.
+ *   order      (optional) int32 [topk]: the position of instance i in the draw order, -1 when it is not kept.  detectron2 draws the
+ *              largest area first; here: descending area, ties by ascending table index.
+ *   out        (optional) the picture.  Per pixel, starting from c = image and walking the kept instances in draw order, for each
+ *              instance i whose mask holds the pixel: c = edge_colors[i] if a 4-neighbour INSIDE the picture is outside mask i, else per
+ *              channel c = (c * (256 - alpha256) + colors[i] * alpha256 + 128) >> 8.  Pixels in no kept mask keep the image; n = 0
+ *              copies it.  colors / edge_colors uint8 [topk][3] (device), by table index.  out == image is allowed, any other overlap
+ *              is not; buffers of any byte alignment (four pixels of a row as three dwords where they are 4-byte aligned in both).
+ * Column and row histograms come from popcounts and bit tests of the packed words, the order from counting, the picture from tiles of
+ * 64 x 64 pixels whose mask and edge bits are transposed through LDS: integer work without atomics, the same bytes from run to run.
+ * ODISE_ERR_ARG and nothing written: a null required pointer (out needs image, colors and edge_colors; without masks inst_table and
+ * inst_scores; at least one output), h or w < 1, h * w > 2^29 - 1, topk outside 1..100, alpha256 outside 0..256, an out that overlaps
+ * image without being equal to it, the geometry errors of odise_hip_instance_rle.  Scratch comes from the context.  Asynchronous on
+ * the context's stream. */
+typedef struct {
+    int h, w;                       /* size of the picture = output size of the masks */
+    const void* masks; int dtype;   /* dense [topk,h,w] (ODISE_F32 / ODISE_U8), or NULL = from the mask logits of image b of the last head forward: */
+    int b, pad_h, pad_w, img_h, img_w;   /* as odise_hip_instance_rle */
+    const int32_t* inst_table;      /* device [1 + 2*topk]: n | query index | class  (n read on the device) */
+    const float* inst_scores;       /* device [topk] */
+    int topk;                       /* 1..100 */
+    float min_score;
+    const uint8_t* image;           /* device [h,w,3] */
+    const uint8_t* colors;          /* device [topk][3] */
+    const uint8_t* edge_colors;     /* device [topk][3] */
+    int alpha256;                   /* 0 (the picture) .. 256 (the colour) */
+    uint8_t* out;                   /* device [h,w,3], optional */
+    odise_anchor_row* anchors;      /* device [topk], optional */
+    int32_t* order;                 /* device [topk], optional */
+} odise_inst_draw_desc;
+int odise_hip_instance_draw(odise_hip_ctx* ctx, const odise_inst_draw_desc* d);
+/* A semantic result as a panoptic record that odise_hip_segment_anchors and odise_hip_panoptic_overlay draw unchanged (draw_sem_seg).
+ * Input: labels int32 [H,W] (the fused arg-max map) or sem_seg fp32 [K,H,W] (arg-max over the planes, ties to the lower class, as
+ * odise_hip_semantic_confusion takes it); exactly one of the two.  record int32 [H*W | 1 | 3*ODISE_MAX_SEGMENTS] (device, must not
+ * overlap the input): ids, n, n rows (id, 0, category) with id = category + 1, the rest of the table zero.  Rows in descending pixel
+ * count, ties by the smaller category (the order draw_sem_seg draws in); of more than ODISE_MAX_SEGMENTS present classes the first
+ * ODISE_MAX_SEGMENTS are kept.  A label outside [0, K) and a class without a row get id 0.  Every row is stuff, so
+ * odise_hip_segment_anchors applies draw_sem_seg's rule: a label at the largest component and at every component above large_area, none
+ * if the largest is below small_area.  Counting is a per-block LDS histogram added with integer atomics, the order is found by counting.
+ * ODISE_ERR_ARG and nothing written: a null pointer or both inputs, H or W < 1, H * W > 2^29 - 1, K outside 1..12288.  Scratch comes
+ * from the context.  Asynchronous on the context's stream. */
+int odise_hip_semantic_record(odise_hip_ctx* ctx, const int32_t* labels, const float* sem_seg, int K, int H, int W, int32_t* record);
 
 /* ---- JPEG input -------------------------------------------------------------------------------------------
  * Replaces detectron2 `read_image(file, "RGB")` = PIL.Image.open -> EXIF transpose -> convert("RGB") of the DatasetMapper

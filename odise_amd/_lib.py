@@ -120,6 +120,14 @@ class OverlayDesc(C.Structure):
                 ("alpha256", c_int), ("edge_rgb", C.c_uint8 * 3), ("out", c_void_p)]
 
 
+class InstDrawDesc(C.Structure):
+    """odise_inst_draw_desc (include/odise_hip.h)."""
+    _fields_ = [("h", c_int), ("w", c_int), ("masks", c_void_p), ("dtype", c_int), ("b", c_int), ("pad_h", c_int), ("pad_w", c_int),
+                ("img_h", c_int), ("img_w", c_int), ("inst_table", c_void_p), ("inst_scores", c_void_p), ("topk", c_int),
+                ("min_score", c_float), ("image", c_void_p), ("colors", c_void_p), ("edge_colors", c_void_p), ("alpha256", c_int),
+                ("out", c_void_p), ("anchors", c_void_p), ("order", c_void_p)]
+
+
 MAX_SEGMENTS = 100          # ODISE_MAX_SEGMENTS
 COMM_ID_BYTES = 128         # ODISE_COMM_ID_BYTES
 

@@ -138,17 +138,6 @@ __global__ void __launch_bounds__(256) u8_hwc_to_f32_chw_pad_kernel(const uint8_
     dst[idx] = (y < H && x < W) ? (float)src[((int64_t)y * W + x) * C + c] * scale : 0.f;
 }
 
-// first-maximum argmax over the K planes of pixel p (torch.argmax semantics for distinct values; ties -> lowest class)
-__device__ __forceinline__ int argmax_first(const float* __restrict__ sem, int K, int64_t npix, int64_t p) {
-    float best = sem[p];
-    int bi = 0;
-    for (int k = 1; k < K; ++k) {
-        const float v = sem[(int64_t)k * npix + p];
-        if (v > best) { best = v; bi = k; }
-    }
-    return bi;
-}
-
 // ---- Boundary IoU counters ------------------------------------------------------------------------------------------------------------------
 // A byte label map is [H][Pd] dwords, Pd = ceil(W / 4), byte x & 3 of dword x >> 2; the bytes past W in a row's last dword are never
 // initialised: every dword read masks them (`tail`).  Two maps (prediction, ground truth) lie back to back and share a launch (blockIdx.y).

@@ -1,4 +1,5 @@
-// lds_hist.h — the evaluators' per-block counting histogram (eval_ops.hip, pq.hip).
+// lds_hist.h — the evaluators' per-block counting histogram (eval_ops.hip, pq.hip, vis_inst.hip) and the arg-max over class planes that
+// feeds it (eval_ops.hip, vis_inst.hip).
 //
 // A block counts `n` cells in the dynamic LDS of its launch and adds the non-zero ones to the global matrix with integer atomics when it is
 // done (deterministic: integer addition commutes); a matrix of more than kLdsHistCells cells is counted in global memory directly.  Which of
@@ -44,5 +45,16 @@ struct LdsHist {
                 if (const unsigned c = cells()[i]) add_global(i, c);
     }
 };
+
+// first-maximum argmax over the K planes of pixel p (torch.argmax semantics for distinct values; ties -> lowest class)
+__device__ __forceinline__ int argmax_first(const float* __restrict__ sem, int K, int64_t npix, int64_t p) {
+    float best = sem[p];
+    int bi = 0;
+    for (int k = 1; k < K; ++k) {
+        const float v = sem[(int64_t)k * npix + p];
+        if (v > best) { best = v; bi = k; }
+    }
+    return bi;
+}
 
 }  // namespace odise

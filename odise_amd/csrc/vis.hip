@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "vis_scan.h"   // vis_scan_middle, vis_check_size: shared with vis_inst.hip
 
 namespace odise {
 
@@ -305,37 +306,15 @@ __global__ void __launch_bounds__(kVisThreads) vis_hist_kernel(const int* __rest
 }
 
 // One wave per (anchor, axis): the two middle elements of the sorted coordinates (twice the median is their sum) and the first / last
-// occupied bin, by an inclusive scan over the histogram, 64 bins at a time.
+// occupied bin, by the scan of vis_scan.h.
 __global__ void __launch_bounds__(64) vis_median_kernel(const VisState* __restrict__ st, const int* __restrict__ hist, int H, int W, int hcap, int cap,
                                                        odise_anchor_row* __restrict__ anchors) {
     const int a = blockIdx.x >> 1, axis = blockIdx.x & 1, lane = threadIdx.x;
     if (a >= st->count || a >= hcap || a >= cap) return;
     const int nb = axis ? H : W;
     const int* h = hist + (int64_t)a * ((int64_t)W + H) + (axis ? W : 0);
-    const int N = anchors[a].area, k1 = (N - 1) >> 1, k2 = N >> 1;
-    int m1 = -1, m2 = -1, lo = INT32_MAX, hi = -1, run = 0;
-    for (int b0 = 0; b0 < nb; b0 += 64) {
-        const int i = b0 + lane, c = i < nb ? h[i] : 0;
-        int inc = c;
-        for (int d = 1; d < 64; d <<= 1) {
-            const int up = __shfl_up(inc, d);
-            if (lane >= d) inc += up;
-        }
-        const int cum = run + inc, exc = cum - c;
-        if (c > 0) {
-            if (exc <= k1 && k1 < cum) m1 = i;
-            if (exc <= k2 && k2 < cum) m2 = i;
-            lo = min(lo, i);
-            hi = max(hi, i);
-        }
-        run = __shfl(cum, 63);
-    }
-    for (int d = 32; d; d >>= 1) {
-        m1 = max(m1, __shfl_xor(m1, d));
-        m2 = max(m2, __shfl_xor(m2, d));
-        lo = min(lo, __shfl_xor(lo, d));
-        hi = max(hi, __shfl_xor(hi, d));
-    }
+    int m1, m2, lo, hi;
+    vis_scan_middle(h, nb, anchors[a].area, lane, m1, m2, lo, hi);   // vis_scan.h
     if (lane == 0) {
         if (axis) { anchors[a].y2 = m1 + m2; anchors[a].y0 = lo; anchors[a].y1 = hi; }
         else { anchors[a].x2 = m1 + m2; anchors[a].x0 = lo; anchors[a].x1 = hi; }
@@ -407,11 +386,6 @@ __global__ void __launch_bounds__(kVisThreads) overlay_kernel(const uint8_t* ima
         const unsigned o = overlay_pixel(S, L, ids, H, W, p, x, y, in, alpha, edge);
         out[3 * i] = (uint8_t)o; out[3 * i + 1] = (uint8_t)(o >> 8); out[3 * i + 2] = (uint8_t)(o >> 16);
     }
-}
-
-static int vis_check_size(const char* who, int H, int W) {
-    ODISE_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= INT32_MAX / 4, "%s: bad size %dx%d", who, H, W);
-    return ODISE_OK;
 }
 
 }  // namespace odise

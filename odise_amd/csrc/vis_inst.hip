@@ -1,0 +1,403 @@
+// vis_inst.hip — drawing instance and semantic results: the else branch of VisualizationDemo.run_on_image (demo/demo.py:173-199),
+// detectron2 draw_instance_predictions / draw_sem_seg (odise_hip_instance_draw / odise_hip_semantic_record; host restatement:
+// odise_amd/visualize.py).
+//
+// Instances overlap, so there is no label map: the masks are the bit-packed words of rle_pack.h ([n][w][R], word (x, r) = rows
+// 64 r .. 64 r + 63 of column x), packed from the mask logits with the taps of odise_hip_instance_rle or from dense masks.
+//
+//   inst_col_kernel      count of column x = the popcounts of its R words
+//   inst_row_kernel      a wave per (mask, r), lane = bit: count of row 64 r + lane = the columns whose word has the bit.  A lane loads
+//                        the word of its own column and the wave walks the 64 loaded words by readlane.  No atomics in either.
+//   inst_anchor_kernel   a wave per (mask, axis): area = the sum of the histogram, kept = in the table, score >= min_score and area > 0,
+//                        then the scan of vis_scan.h for twice the median and the bounding box
+//   inst_order_kernel    draw order = rank by (area descending, index ascending) among the kept, by counting; list[rank] = index
+//   inst_overlay_kernel  one block per tile of 64 columns x 64 rows (one word row).  The kept masks are taken in draw order, kDrawChunk
+//                        at a time: a thread fetches the words of four neighbouring columns of one mask (with the bits above and below
+//                        and the columns left and right), works out which pixels have a 4-neighbour outside the mask, and leaves in LDS
+//                        one dword per (mask, 4 rows, 4 columns): 16 mask bits and 16 edge bits.  That is the transpose: in the pixel
+//                        phase a thread owns 4 x 4 pixels - four consecutive pixels of four rows, kept in registers over the whole walk -
+//                        and reads one conflict-free dword per mask, which it skips when its mask bits are zero.  A row of four pixels
+//                        travels as three dwords where its 12 bytes are 4-byte aligned in both pictures, byte by byte otherwise.
+//
+// The semantic record: a per-block LDS histogram of the labels (lds_hist.h; the arg-max of semantic_confusion_kernel for a score
+// tensor), the rank of every present class by counting, and one pass that turns labels into ids.
+#include <algorithm>
+
+#include "lds_hist.h"
+#include "rle_pack.h"
+#include "vis_scan.h"
+
+namespace odise {
+
+constexpr int kInstDrawMax = 100;          // topk limit (the instance head keeps at most 100 per picture)
+constexpr int kDrawThreads = 256;
+constexpr int kDrawChunk = 50;             // masks staged at a time
+constexpr int kDrawStride = 256 + 16;      // dwords per staged mask: 16 row groups x 16 column groups, + 16 so that the 32 lanes of a
+                                           // staging write (two masks) fall on 32 different banks
+constexpr int kSemMaxClasses = kLdsHistCells;
+
+struct InstDrawState {
+    int area[kInstDrawMax];                // pixels of a kept instance, 0 when it is not kept
+    int list[kInstDrawMax];                // list[k] = the instance drawn k-th
+    int n_kept;
+    int pad[3];
+};
+
+__device__ __forceinline__ int inst_count(const int* __restrict__ table, int topk) {
+    if (!table) return topk;
+    const int n = table[0];
+    return n < 0 ? 0 : (n > topk ? topk : n);
+}
+
+__global__ void __launch_bounds__(kDrawThreads) inst_col_kernel(const unsigned long long* __restrict__ words, RleGrid G, const int* __restrict__ table,
+                                                               int topk, int* __restrict__ colhist) {
+    const int i = blockIdx.y;
+    if (i >= inst_count(table, topk)) return;
+    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (x >= G.w) return;
+    const unsigned long long* c = words + (int64_t)i * G.nw + x * G.R;
+    int s = 0;
+    for (int r = 0; r < G.R; ++r) s += __popcll(c[r]);
+    colhist[(int64_t)i * G.w + x] = s;
+}
+
+__global__ void __launch_bounds__(64) inst_row_kernel(const unsigned long long* __restrict__ words, RleGrid G, const int* __restrict__ table, int topk,
+                                                     int* __restrict__ rowhist) {
+    const int i = blockIdx.y, r = blockIdx.x, lane = threadIdx.x;
+    if (i >= inst_count(table, topk)) return;
+    const unsigned long long* wd = words + (int64_t)i * G.nw + r;
+    int cnt = 0;
+    for (int x0 = 0; x0 < G.w; x0 += 64) {
+        const int x = x0 + lane;
+        const unsigned long long v = x < G.w ? wd[(int64_t)x * G.R] : 0ull;
+        const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+#pragma unroll
+        for (int j = 0; j < 64; ++j) {
+            const unsigned lj = (unsigned)__builtin_amdgcn_readlane(lo, j), hj = (unsigned)__builtin_amdgcn_readlane(hi, j);
+            cnt += (int)(((lane < 32 ? lj : hj) >> (lane & 31)) & 1u);
+        }
+    }
+    const int y = 64 * r + lane;
+    if (y < G.h) rowhist[(int64_t)i * G.h + y] = cnt;
+}
+
+// axes = 1: areas only (nothing is scanned, `anchors` is null); axes = 2: a wave per axis.  The x wave owns segment_row, area and the
+// x fields of a row (and all of a row that is not kept), the y wave the y fields.
+__global__ void __launch_bounds__(64) inst_anchor_kernel(const int* __restrict__ colhist, const int* __restrict__ rowhist, int H, int W,
+                                                        const int* __restrict__ table, const float* __restrict__ scores, int topk, float min_score,
+                                                        int axes, InstDrawState* __restrict__ st, odise_anchor_row* __restrict__ anchors) {
+    const int i = blockIdx.x / axes, axis = blockIdx.x - i * axes, lane = threadIdx.x;
+    const int nb = axis ? H : W;
+    const int* h = axis ? rowhist + (int64_t)i * H : colhist + (int64_t)i * W;
+    int N = 0;
+    if (i < inst_count(table, topk)) {
+        for (int b0 = 0; b0 < nb; b0 += 64) N += b0 + lane < nb ? h[b0 + lane] : 0;
+        for (int d = 32; d; d >>= 1) N += __shfl_xor(N, d);
+    }
+    const bool kept = N > 0 && (!scores || scores[i] >= min_score);
+    if (!kept) {
+        if (lane == 0 && axis == 0) {
+            st->area[i] = 0;
+            if (anchors) {
+                odise_anchor_row r;
+                r.segment_row = -1; r.area = 0; r.x2 = 0; r.y2 = 0; r.x0 = 0; r.y0 = 0; r.x1 = 0; r.y1 = 0;
+                anchors[i] = r;
+            }
+        }
+        return;
+    }
+    if (lane == 0 && axis == 0) st->area[i] = N;
+    if (!anchors) return;
+    int m1, m2, lo, hi;
+    vis_scan_middle(h, nb, N, lane, m1, m2, lo, hi);
+    if (lane == 0) {
+        if (axis) { anchors[i].y2 = m1 + m2; anchors[i].y0 = lo; anchors[i].y1 = hi; }
+        else { anchors[i].segment_row = i; anchors[i].area = N; anchors[i].x2 = m1 + m2; anchors[i].x0 = lo; anchors[i].x1 = hi; }
+    }
+}
+
+__global__ void __launch_bounds__(128) inst_order_kernel(InstDrawState* __restrict__ st, int topk, int* __restrict__ order) {
+    __shared__ int a[kInstDrawMax];
+    const int t = threadIdx.x;
+    if (t < topk) a[t] = st->area[t];
+    __syncthreads();
+    if (t < topk) {
+        int rank = -1;
+        if (a[t] > 0) {
+            rank = 0;
+            for (int j = 0; j < topk; ++j) rank += (a[j] > a[t] || (a[j] == a[t] && j < t)) ? 1 : 0;
+            st->list[rank] = t;
+        }
+        if (order) order[t] = rank;
+    }
+    if (t == 0) {
+        int n = 0;
+        for (int j = 0; j < topk; ++j) n += a[j] > 0 ? 1 : 0;
+        st->n_kept = n;
+    }
+}
+
+__device__ __forceinline__ unsigned draw_blend(unsigned v, unsigned ia, unsigned crb, unsigned cg) {
+    // red and blue in one multiply: a channel's v * ia + c * a + 128 <= 255 * 256 + 128 stays inside its 16 bits
+    const unsigned rb = (((v & 0xff00ffu) * ia + crb) >> 8) & 0xff00ffu;
+    const unsigned g = (((v >> 8) & 0xffu) * ia + cg) >> 8;
+    return rb | (g << 8);
+}
+
+// image == out is safe: a thread reads its own 16 pixels before it writes them and no other thread reads them.
+__global__ void __launch_bounds__(kDrawThreads) inst_overlay_kernel(const unsigned long long* __restrict__ words, RleGrid G, int ntx,
+                                                                   const InstDrawState* __restrict__ st, const uint8_t* image,
+                                                                   const uint8_t* __restrict__ colors, const uint8_t* __restrict__ edge_colors,
+                                                                   int alpha, uint8_t* out) {
+    __shared__ unsigned sl[kDrawChunk * kDrawStride];
+    __shared__ unsigned s_crb[kDrawChunk], s_cg[kDrawChunk], s_edge[kDrawChunk];
+    const int t = threadIdx.x, H = G.h, W = G.w;
+    const int r = blockIdx.x / ntx, x0 = (blockIdx.x - r * ntx) * 64;
+    const int xq = t & 15, rg = t >> 4;
+    const int px_x = x0 + 4 * xq, px_y = 64 * r + 4 * rg;
+    const unsigned ia = (unsigned)(256 - alpha);
+
+    unsigned px[4][4];
+    bool vec[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int y = px_y + j;
+        const int64_t off = 3 * ((int64_t)y * W + px_x);
+        vec[j] = y < H && px_x + 3 < W && ((((uintptr_t)image + off) | ((uintptr_t)out + off)) & 3) == 0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) px[j][c] = 0u;
+        if (vec[j]) {
+            const unsigned* src = (const unsigned*)(image + off);   // the 12 bytes of four pixels inside the row
+            const unsigned d0 = src[0], d1 = src[1], d2 = src[2];
+            px[j][0] = d0 & 0xffffffu; px[j][1] = (d0 >> 24) | ((d1 & 0xffffu) << 8); px[j][2] = (d1 >> 16) | ((d2 & 0xffu) << 16); px[j][3] = d2 >> 8;
+        } else if (y < H) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (px_x + c < W) {
+                    const uint8_t* s = image + off + 3 * c;
+                    px[j][c] = (unsigned)s[0] | ((unsigned)s[1] << 8) | ((unsigned)s[2] << 16);
+                }
+        }
+    }
+
+    const int n_kept = min(max(st->n_kept, 0), kInstDrawMax);
+    const int rows = min(64, H - 64 * r);
+    const unsigned long long padbits = rows == 64 ? 0ull : ~0ull << rows;   // rows past the picture count as inside the mask: no edge there
+    for (int k0 = 0; k0 < n_kept; k0 += kDrawChunk) {
+        const int nk = min(kDrawChunk, n_kept - k0);
+        __syncthreads();                                                     // the previous chunk has been read
+        if (t < nk) {
+            const int i = st->list[k0 + t];
+            const unsigned c = (unsigned)colors[3 * i] | ((unsigned)colors[3 * i + 1] << 8) | ((unsigned)colors[3 * i + 2] << 16);
+            s_crb[t] = (c & 0xff00ffu) * (unsigned)alpha + 0x800080u;
+            s_cg[t] = ((c >> 8) & 0xffu) * (unsigned)alpha + 128u;
+            s_edge[t] = (unsigned)edge_colors[3 * i] | ((unsigned)edge_colors[3 * i + 1] << 8) | ((unsigned)edge_colors[3 * i + 2] << 16);
+        }
+        for (int it = t; it < nk * 16; it += kDrawThreads) {                // item = (mask k, four columns q)
+            const int k = it >> 4, q = it & 15, xa = x0 + 4 * q;
+            const int i = st->list[k0 + k];
+            const unsigned long long* wm = words + (int64_t)i * G.nw + r;   // word (x, r) = wm[x * R]
+            unsigned long long m[6];                                        // columns xa - 1 .. xa + 4; outside the picture: inside the mask
+#pragma unroll
+            for (int c = 0; c < 6; ++c) {
+                const int x = xa - 1 + c;
+                m[c] = (x >= 0 && x < W) ? wm[(int64_t)x * G.R] : ~0ull;
+            }
+            unsigned long long mm[4], ee[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                const int x = xa + c;
+                mm[c] = 0ull; ee[c] = 0ull;
+                if (x < W) {
+                    const unsigned long long v = m[c + 1];
+                    const unsigned long long above = r > 0 ? wm[(int64_t)x * G.R - 1] >> 63 : 1ull;
+                    const unsigned long long below = r < G.R - 1 ? wm[(int64_t)x * G.R + 1] & 1ull : 1ull;
+                    const unsigned long long up = (v << 1) | above, down = ((v | padbits) >> 1) | (below << 63);
+                    mm[c] = v;
+                    ee[c] = v & ~(up & down & m[c] & m[c + 2]);
+                }
+            }
+            unsigned* dst = sl + k * kDrawStride + q;
+#pragma unroll
+            for (int g = 0; g < 16; ++g) {
+                unsigned d = 0u;
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    d |= ((unsigned)(mm[c] >> (4 * g)) & 0xfu) << (4 * c) | ((unsigned)(ee[c] >> (4 * g)) & 0xfu) << (16 + 4 * c);
+                dst[g * 16] = d;
+            }
+        }
+        __syncthreads();
+        for (int k = 0; k < nk; ++k) {
+            const unsigned s = sl[k * kDrawStride + t];                     // t = rg * 16 + xq
+            if ((s & 0xffffu) == 0u) continue;
+            const unsigned crb = s_crb[k], cg = s_cg[k], edge = s_edge[k];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const int bit = 4 * c + j;
+                    if ((s >> bit) & 1u) px[j][c] = ((s >> (16 + bit)) & 1u) ? edge : draw_blend(px[j][c], ia, crb, cg);
+                }
+        }
+    }
+
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int y = px_y + j;
+        const int64_t off = 3 * ((int64_t)y * W + px_x);
+        if (vec[j]) {
+            unsigned* dst = (unsigned*)(out + off);
+            dst[0] = px[j][0] | (px[j][1] << 24);
+            dst[1] = (px[j][1] >> 8) | (px[j][2] << 16);
+            dst[2] = (px[j][2] >> 16) | (px[j][3] << 8);
+        } else if (y < H) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+                if (px_x + c < W) {
+                    uint8_t* o = out + off + 3 * c;
+                    o[0] = (uint8_t)px[j][c]; o[1] = (uint8_t)(px[j][c] >> 8); o[2] = (uint8_t)(px[j][c] >> 16);
+                }
+        }
+    }
+}
+
+// ---- the semantic record ----------------------------------------------------------------------------------------------------------
+
+// counts[l] += 1 for every label in [0, K).  kSem: the label is the first-maximum arg-max over the K planes and is left in ids[p].
+template <bool kSem>
+__global__ void __launch_bounds__(256) sem_count_kernel(const int* __restrict__ labels, const float* __restrict__ sem, int K, int npix,
+                                                       unsigned* __restrict__ counts, int* __restrict__ ids) {
+    const LdsHist<unsigned> Hh(counts, K, K <= kLdsHistCells);
+    Hh.clear();
+    Hh.sync();
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+        int l;
+        if (kSem) { l = argmax_first(sem, K, npix, p); ids[p] = l; }
+        else l = labels[p];
+        if ((unsigned)l < (unsigned)K) Hh.add(l, 1u);
+    }
+    Hh.sync();
+    Hh.flush();
+}
+
+// One block.  The row of a present class = the classes with a larger count, or an equal count and a smaller index.  map[c] = its id.
+__global__ void __launch_bounds__(1024) sem_rank_kernel(const unsigned* __restrict__ counts, int K, int* __restrict__ map, int* __restrict__ table) {
+    __shared__ int present;
+    if (threadIdx.x == 0) present = 0;
+    __syncthreads();
+    for (int c = threadIdx.x; c < K; c += blockDim.x) {
+        const unsigned cnt = counts[c];
+        int id = 0;
+        if (cnt > 0u) {
+            int rank = 0;
+            for (int j = 0; j < K; ++j) {
+                const unsigned v = counts[j];
+                rank += (v > cnt || (v == cnt && j < c)) ? 1 : 0;
+            }
+            if (rank < ODISE_MAX_SEGMENTS) {
+                id = c + 1;
+                table[1 + 3 * rank] = id; table[2 + 3 * rank] = 0; table[3 + 3 * rank] = c;
+            }
+            atomicAdd(&present, 1);
+        }
+        map[c] = id;
+    }
+    __syncthreads();
+    const int n = min(present, ODISE_MAX_SEGMENTS);
+    if (threadIdx.x == 0) table[0] = n;
+    for (int i = 3 * n + threadIdx.x; i < 3 * ODISE_MAX_SEGMENTS; i += blockDim.x) table[1 + i] = 0;
+}
+
+template <bool kSem>
+__global__ void __launch_bounds__(256) sem_ids_kernel(const int* __restrict__ labels, const int* __restrict__ map, int K, int npix, int* __restrict__ ids) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+        const int l = kSem ? ids[p] : labels[p];
+        ids[p] = (unsigned)l < (unsigned)K ? map[l] : 0;
+    }
+}
+
+}  // namespace odise
+
+using namespace odise;
+
+extern "C" int odise_hip_instance_draw(odise_hip_ctx* ctx, const odise_inst_draw_desc* d) {
+    ODISE_REQUIRE(ctx && d, "instance_draw: null argument");
+    ODISE_REQUIRE(d->masks || (d->inst_table && d->inst_scores), "instance_draw: the selection of the last head forward needs inst_table and inst_scores");
+    ODISE_REQUIRE(!d->out || (d->image && d->colors && d->edge_colors), "instance_draw: an output picture needs image, colors and edge_colors");
+    ODISE_REQUIRE(d->out || d->anchors || d->order, "instance_draw: no output");
+    ODISE_TRY(vis_check_size("instance_draw", d->h, d->w));
+    ODISE_REQUIRE(d->topk >= 1 && d->topk <= kInstDrawMax, "instance_draw: topk %d (1..%d)", d->topk, kInstDrawMax);
+    ODISE_REQUIRE(d->alpha256 >= 0 && d->alpha256 <= 256, "instance_draw: alpha256 %d outside 0..256", d->alpha256);
+    ODISE_REQUIRE(!d->masks || d->dtype == ODISE_F32 || d->dtype == ODISE_U8, "instance_draw: dtype %d (ODISE_F32 or ODISE_U8)", d->dtype);
+    ODISE_REQUIRE((((uintptr_t)d->inst_table | (uintptr_t)d->inst_scores | (uintptr_t)d->anchors | (uintptr_t)d->order) & 3) == 0,
+                  "instance_draw: int32 / float buffers must be 4-byte aligned");
+    const int H = d->h, W = d->w, topk = d->topk;
+    if (d->out && d->out != d->image) {
+        const uintptr_t a = (uintptr_t)d->image, b = (uintptr_t)d->out, nb = (uintptr_t)3 * H * W;
+        ODISE_REQUIRE(a + nb <= b || b + nb <= a, "instance_draw: out overlaps image without being equal to it");
+    }
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    PostGeom g;
+    const f16* logits = nullptr;
+    if (!d->masks) ODISE_TRY(rle_instance_geom(ctx, "instance_draw", d->b, d->pad_h, d->pad_w, d->img_h, d->img_w, H, W, &g, &logits));
+    const RleGrid G = rle_grid(H, W);
+    const size_t col_b = (size_t)round_up((int64_t)topk * W * 4, 16), row_b = d->anchors ? (size_t)round_up((int64_t)topk * H * 4, 16) : 0;
+    RleScratch s;
+    ODISE_TRY(rle_scratch(ctx, topk, G, &s, sizeof(InstDrawState) + col_b + row_b));
+    InstDrawState* st = (InstDrawState*)s.extra;
+    int* colhist = (int*)((char*)s.extra + sizeof(InstDrawState));
+    int* rowhist = (int*)((char*)colhist + col_b);
+    const int* table = (const int*)d->inst_table;
+    if (d->masks) ODISE_TRY(rle_pack_dense(ctx, d->masks, d->dtype, topk, G, s.words));
+    else ODISE_TRY(rle_pack_logits(ctx, logits, table, topk, g, G, s.words));
+    hipLaunchKernelGGL(inst_col_kernel, dim3((unsigned)ceil_div(W, kDrawThreads), (unsigned)topk), dim3(kDrawThreads), 0, ctx->stream,
+                       (const unsigned long long*)s.words, G, table, topk, colhist);
+    ODISE_CHECK_HIP(hipGetLastError());
+    if (d->anchors) {
+        hipLaunchKernelGGL(inst_row_kernel, dim3((unsigned)G.R, (unsigned)topk), dim3(64), 0, ctx->stream, (const unsigned long long*)s.words, G, table,
+                           topk, rowhist);
+        ODISE_CHECK_HIP(hipGetLastError());
+    }
+    const int axes = d->anchors ? 2 : 1;
+    hipLaunchKernelGGL(inst_anchor_kernel, dim3((unsigned)(axes * topk)), dim3(64), 0, ctx->stream, (const int*)colhist, (const int*)rowhist, H, W, table,
+                       d->inst_scores, topk, d->min_score, axes, st, d->anchors);
+    ODISE_CHECK_HIP(hipGetLastError());
+    if (d->order || d->out) {
+        hipLaunchKernelGGL(inst_order_kernel, dim3(1), dim3(128), 0, ctx->stream, st, topk, (int*)d->order);
+        ODISE_CHECK_HIP(hipGetLastError());
+    }
+    if (d->out) {
+        const int ntx = (int)ceil_div(W, 64);
+        hipLaunchKernelGGL(inst_overlay_kernel, dim3((unsigned)((int64_t)ntx * G.R)), dim3(kDrawThreads), 0, ctx->stream,
+                           (const unsigned long long*)s.words, G, ntx, (const InstDrawState*)st, d->image, d->colors, d->edge_colors, d->alpha256, d->out);
+        ODISE_CHECK_HIP(hipGetLastError());
+    }
+    return ODISE_OK;
+}
+
+extern "C" int odise_hip_semantic_record(odise_hip_ctx* ctx, const int32_t* labels, const float* sem_seg, int K, int H, int W, int32_t* record) {
+    ODISE_REQUIRE(ctx, "semantic_record: null context");
+    ODISE_REQUIRE((labels != nullptr) != (sem_seg != nullptr) && record, "semantic_record: one of labels / sem_seg, and a record");
+    ODISE_TRY(vis_check_size("semantic_record", H, W));
+    ODISE_REQUIRE(K >= 1 && K <= kSemMaxClasses, "semantic_record: %d classes (1..%d)", K, kSemMaxClasses);
+    ODISE_REQUIRE((((uintptr_t)labels | (uintptr_t)sem_seg | (uintptr_t)record) & 3) == 0, "semantic_record: buffers must be 4-byte aligned");
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    const int npix = H * W;
+    const size_t kb = (size_t)round_up((int64_t)K * 4, 16);
+    ODISE_TRY(scratch_reserve(ctx->vis, 2 * kb, 8, drain_streams(ctx->stream), "semantic_record"));
+    unsigned* counts = (unsigned*)ctx->vis.ptr;
+    int* map = (int*)((char*)ctx->vis.ptr + kb);
+    int* ids = (int*)record;
+    ODISE_CHECK_HIP(hipMemsetAsync(counts, 0, kb, ctx->stream));
+    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(npix, 256), 8 * ctx->cu_count));
+    if (sem_seg) hipLaunchKernelGGL(sem_count_kernel<true>, dim3(blocks), dim3(256), lds_hist_bytes(K), ctx->stream, (const int*)nullptr, sem_seg, K, npix, counts, ids);
+    else hipLaunchKernelGGL(sem_count_kernel<false>, dim3(blocks), dim3(256), lds_hist_bytes(K), ctx->stream, (const int*)labels, (const float*)nullptr, K, npix, counts, ids);
+    ODISE_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(sem_rank_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned*)counts, K, map, ids + npix);
+    ODISE_CHECK_HIP(hipGetLastError());
+    if (sem_seg) hipLaunchKernelGGL(sem_ids_kernel<true>, dim3(blocks), dim3(256), 0, ctx->stream, (const int*)nullptr, (const int*)map, K, npix, ids);
+    else hipLaunchKernelGGL(sem_ids_kernel<false>, dim3(blocks), dim3(256), 0, ctx->stream, (const int*)labels, (const int*)map, K, npix, ids);
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}

@@ -1,8 +1,13 @@
-"""`python -m odise_amd.demo --input FILE... --output DIR [--vocab "a, b; c"] [--synthetic]`: demo/demo.py on the device path.
+"""`python -m odise_amd.demo --input FILE... --output DIR [--vocab "a, b; c"] [--synthetic] [--task panoptic|semantic|instance]`:
+demo/demo.py on the device path.
 
 A picture is read (JPEG through HipDatasetMapper, anything else through Pillow), resized by ResizeShortestEdge(1024, 2560) on the device,
 run through HipOpenPanopticInference with demo.py's settings (overlap_threshold = 0, alpha / beta = 0.35 / 0.65, demo.py:316-318), and
 its panoptic record - still in HBM - is drawn by HipVisualizer.draw_panoptic_seg and saved with Pillow as DIR/<name>.png.
+
+`--task semantic` / `--task instance` take the other branch of run_on_image: the wrapper is built with that head on (and panoptic off), and
+the semantic map (HipVisualizer.draw_sem_seg), then the instance selection (draw_instance_predictions, scores below
+`--confidence-threshold` left out) are drawn, the instances on top.
 
 Weights come from `$ODISE_MODEL_ZOO` through odise_amd/checkpoint.py; `--synthetic` takes random tensors of the real shapes and seeded
 text banks instead (odise_amd/synthetic.py), which draws arbitrary segments but needs no file.
@@ -24,6 +29,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--vocab", default="", help='extra classes, demo.py style: "black pickup truck, pickup truck; blue sky, sky"')
     ap.add_argument("--synthetic", action="store_true", help="random weights of the real shapes and seeded text banks: needs no checkpoint")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--task", choices=("panoptic", "semantic", "instance"), default="panoptic",
+                    help="which head is on and drawn (semantic-only vocabularies, or the instance masks segm AP scores)")
+    ap.add_argument("--confidence-threshold", type=float, default=0.5, help="--task instance: instances below this score are not drawn")
     return ap.parse_args(argv)
 
 
@@ -58,7 +66,7 @@ class _SeededText:
         return np.stack([np.random.default_rng(zlib.crc32(s.encode())).standard_normal(768) for s in strings]).astype(np.float32)
 
 
-def build_model(ctx, labels: List[List[str]], num_things: int, synthetic: bool):
+def build_model(ctx, labels: List[List[str]], num_things: int, synthetic: bool, task: str = "panoptic"):
     from .pipeline import HipCategoryODISE, HipOpenPanopticInference
     if synthetic:
         from .synthetic import synthetic_state
@@ -73,7 +81,8 @@ def build_model(ctx, labels: List[List[str]], num_things: int, synthetic: bool):
         hip.attach_text(SimpleTokenizer(), HipTextEncoder(ctx, load_openai_clip("clip://ViT-L-14-336")))
     hip._alpha, hip._beta = 0.35, 0.65                                   # demo.py:316-318
     metadata = demo_metadata(labels, num_things)
-    return HipOpenPanopticInference(hip, labels, metadata, semantic_on=False, instance_on=False, panoptic_on=True), metadata
+    return HipOpenPanopticInference(hip, labels, metadata, semantic_on=task == "semantic", instance_on=task == "instance",
+                                    panoptic_on=task == "panoptic"), metadata
 
 
 def default_labels(extra: List[List[str]]):
@@ -102,21 +111,39 @@ def read_picture(ctx, file_name: str):
             return ctx.to_device(np.ascontiguousarray(np.asarray(ImageOps.exif_transpose(im).convert("RGB"), np.uint8)))
 
 
-def run_on_image(ctx, model, visualizer, image_dev) -> np.ndarray:
+def run_on_image(ctx, model, visualizer, image_dev, task: str = "panoptic", confidence_threshold: float = 0.5) -> np.ndarray:
     """VisualizationDemo.run_on_image (demo.py:173-199) for a picture that is on the device; the result never leaves it before it is drawn."""
     from ._lib import MAX_SEGMENTS
     from .ingest import HipDatasetMapper
     h, w = image_dev.shape[:2]
     inputs = HipDatasetMapper(ctx, 1024, 2560)._finish({"height": h, "width": w}, image_dev)
-    record = ctx.empty((h * w + 1 + 3 * MAX_SEGMENTS,), np.int32)
+    record = ctx.empty((h * w + 1 + 3 * MAX_SEGMENTS,), np.int32) if task == "panoptic" else None
     inner = model.model
     saved = inner.open_state_dict()
     inner.load_open_state_dict(model.open_state_dict)
+    keep, rle, amax = inner.keep_instance_selection, inner.instance_rle, inner.semantic_argmax
+    if task == "instance":
+        inner.keep_instance_selection, inner.instance_rle = True, True       # the selection stays on the device; no dense mask tensor
+    if task == "semantic":
+        inner.semantic_argmax = True                                         # the fused arg-max map; no [K,h,w] tensor
     try:
-        inner.infer_device([inputs["image"]], 0, [tuple(inputs["image"].shape[:2])], [(h, w)], pan_out=[record])
+        results = inner.infer_device([inputs["image"]], 0, [tuple(inputs["image"].shape[:2])], [(h, w)], pan_out=[record] if record is not None else None)
     finally:
         inner.load_open_state_dict(saved)
-    return visualizer.draw_panoptic_seg(image_dev, record, (h, w))
+        inner.keep_instance_selection, inner.instance_rle, inner.semantic_argmax = keep, rle, amax
+    if task == "panoptic":
+        return visualizer.draw_panoptic_seg(image_dev, record, (h, w))
+    picture = image_dev                                                      # the else branch: semantic, then instances on top
+    if "sem_seg" in results[0] or "sem_seg_argmax" in results[0]:
+        sem = results[0].get("sem_seg_argmax", results[0].get("sem_seg"))
+        picture = ctx.to_device(visualizer.draw_sem_seg(picture, sem, inner.num_classes))
+    if task == "instance":
+        sel = inner.last_selection
+        topk = sel["topk"]
+        picture = visualizer.draw_instance_predictions(picture, 0, sel["inst_table"].view((1 + 2 * topk,), np.int32),
+                                                       sel["inst_scores"].view((topk,), np.float32), topk, sel["pad_hw"], sel["img_hw"][0],
+                                                       sel["out_hw"][0], min_score=confidence_threshold)
+    return picture if isinstance(picture, np.ndarray) else picture.numpy()
 
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
@@ -126,11 +153,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     from .visualize import HipVisualizer
     labels, num_things = default_labels(extra_classes(args.vocab))
     ctx = Context(args.device)
-    model, metadata = build_model(ctx, labels, num_things, args.synthetic)
+    model, metadata = build_model(ctx, labels, num_things, args.synthetic, args.task)
     visualizer = HipVisualizer(ctx, metadata)
     os.makedirs(args.output, exist_ok=True)
     for file_name in args.input:
-        picture = run_on_image(ctx, model, visualizer, read_picture(ctx, file_name))
+        picture = run_on_image(ctx, model, visualizer, read_picture(ctx, file_name), args.task, args.confidence_threshold)
         Image.fromarray(picture).save(output_path(args.output, file_name))
         print(f"{file_name} -> {output_path(args.output, file_name)}")
     ctx.close()

@@ -546,6 +546,59 @@ class Context:
         check(self.lib.odise_hip_panoptic_overlay(self.h, C.byref(d)), "panoptic_overlay")
         return out
 
+    # ---- drawing instance and semantic results (include/odise_hip.h odise_hip_instance_draw / odise_hip_semantic_record) ----------------
+    def instance_draw(self, out_hw, topk: int, table_row=None, scores_row=None, masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0),
+                      img_hw=(0, 0), min_score: float = 0.0, image: Optional[DeviceArray] = None, colors: Optional[DeviceArray] = None,
+                      edge_colors: Optional[DeviceArray] = None, alpha256: int = 128, want=("out", "anchors", "order"), out=None, anchors=None,
+                      order=None) -> dict:
+        """Enqueue odise_hip_instance_draw.  Detections as in `instance_eval`: the selection table_row [1 + 2 topk] / scores_row [topk]
+        of image b of the last head forward, or dense `masks` [topk, h, w] (table_row / scores_row then optional).  `want` names the
+        outputs; buffers given for them are used, others are allocated -> {"out": uint8 [h,w,3], "anchors": visualize.ANCHOR_DTYPE
+        [topk], "order": int32 [topk]} (the ones asked for)."""
+        from ._lib import InstDrawDesc
+        from .visualize import ANCHOR_DTYPE
+        h, w, topk = int(out_hw[0]), int(out_hw[1]), int(topk)
+        d = InstDrawDesc()
+        d.h, d.w, d.topk, d.min_score, d.alpha256 = h, w, topk, float(min_score), int(alpha256)
+        if masks is not None:
+            assert tuple(masks.shape) == (topk, h, w), (masks.shape, topk, out_hw)
+            d.masks, d.dtype = masks.ptr, (F32 if masks.dtype == np.float32 else U8)
+        d.b, d.pad_h, d.pad_w, d.img_h, d.img_w = int(b), int(pad_hw[0]), int(pad_hw[1]), int(img_hw[0]), int(img_hw[1])
+        ptr = lambda a: a.ptr if isinstance(a, DeviceArray) else a
+        d.inst_table, d.inst_scores = ptr(table_row), ptr(scores_row)
+        res = {}
+        if "out" in want:
+            assert image is not None and image.dtype == np.uint8 and tuple(image.shape) == (h, w, 3), "instance_draw: image uint8 [h,w,3]"
+            res["out"] = out if out is not None else self.empty((h, w, 3), np.uint8)
+            d.image, d.colors, d.edge_colors, d.out = image.ptr, ptr(colors), ptr(edge_colors), res["out"].ptr
+        if "anchors" in want:
+            res["anchors"] = anchors if anchors is not None else self.empty((topk,), ANCHOR_DTYPE)
+            d.anchors = res["anchors"].ptr
+        if "order" in want:
+            res["order"] = order if order is not None else self.empty((topk,), np.int32)
+            d.order = res["order"].ptr
+        check(self.lib.odise_hip_instance_draw(self.h, C.byref(d)), "instance_draw")
+        return res
+
+    def semantic_record(self, labels_or_sem_seg: DeviceArray, K: Optional[int] = None, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """labels int32 [H,W] (needs K) or sem_seg float32 [K,H,W] -> the panoptic record int32 [H*W + 1 + 3*MAX_SEGMENTS] of the semantic
+        result (ids = category + 1, rows (id, 0, category) by descending pixel count), enqueued."""
+        from ._lib import MAX_SEGMENTS
+        a = labels_or_sem_seg
+        if a.dtype == np.float32:
+            assert len(a.shape) == 3 and (K is None or int(K) == a.shape[0]), (a.shape, K)
+            K, H, W = a.shape
+            labels, sem = None, a
+        else:
+            assert a.dtype == np.int32 and len(a.shape) == 2 and K is not None, (a.dtype, a.shape, K)
+            H, W = a.shape
+            labels, sem = a, None
+        if out is None:
+            out = self.empty((H * W + 1 + 3 * MAX_SEGMENTS,), np.int32)
+        assert out.dtype == np.int32 and int(np.prod(out.shape)) >= H * W + 1 + 3 * MAX_SEGMENTS
+        check(self.lib.odise_hip_semantic_record(self.h, _p(labels), _p(sem), int(K), H, W, _p(out)), "semantic_record")
+        return out
+
     # ---- COCO RLE of instance masks (segm evaluation; include/odise_hip.h odise_hip_rle_encode / odise_hip_instance_rle) ----------------
     # Default string capacity per mask.  A string has one to seven characters per run and most runs of a real mask take two or three, so
     # 8 KiB holds a mask with ~3000 runs - a blob spanning ~1500 columns; a selection that needs more costs one more pass (the retry).

@@ -123,6 +123,85 @@ def panoptic_overlay(image, pred_ids, segments, colors, alpha256: int = 128, edg
     return out.astype(np.uint8)
 
 
+# ---- the restatement: instances and semantic results (csrc/vis_inst.hip) ----------------------------------------------------------------
+def _kept(masks, scores, min_score) -> np.ndarray:
+    """bool [n]: score >= min_score (float32, as the device compares) and a pixel in the mask; no scores: every non-empty mask."""
+    masks = np.asarray(masks) != 0
+    kept = masks.reshape(len(masks), -1).any(axis=1) if len(masks) else np.zeros(0, bool)
+    if scores is not None:
+        kept &= np.asarray(scores, np.float32)[:len(masks)] >= np.float32(min_score)
+    return kept
+
+
+def instance_anchors(masks, scores=None, min_score: float = 0.0, topk: Optional[int] = None) -> np.ndarray:
+    """masks [n,H,W] (nonzero = 1) -> ANCHOR_DTYPE [topk], one row per table index: (i, area, twice the median column / row, bounding
+    box) of a kept instance, (-1, 0, ..) otherwise and past n."""
+    masks = np.asarray(masks) != 0
+    topk = len(masks) if topk is None else int(topk)
+    out = np.zeros(topk, ANCHOR_DTYPE)
+    out["segment_row"] = -1
+    for i, k in enumerate(_kept(masks, scores, min_score)):
+        if k:
+            out[i] = _anchor(i, masks[i])
+    return out
+
+
+def instance_order(masks, scores=None, min_score: float = 0.0, topk: Optional[int] = None) -> np.ndarray:
+    """int32 [topk]: the position of instance i in the draw order (descending area, ties by ascending index), -1 when it is not kept."""
+    masks = np.asarray(masks) != 0
+    topk = len(masks) if topk is None else int(topk)
+    kept = _kept(masks, scores, min_score)
+    area = masks.reshape(len(masks), -1).sum(axis=1) if len(masks) else np.zeros(0, np.int64)
+    out = np.full(topk, -1, np.int32)
+    for rank, i in enumerate(sorted((i for i in range(len(masks)) if kept[i]), key=lambda i: (-int(area[i]), i))):
+        out[i] = rank
+    return out
+
+
+def instance_overlay(image, masks, colors, edge_colors, alpha256: int = 128, scores=None, min_score: float = 0.0) -> np.ndarray:
+    """image uint8 [H,W,3] -> uint8 [H,W,3]: the kept instances in draw order, one over the other; a pixel of a mask with a 4-neighbour
+    inside the picture that is outside the mask takes the instance's edge colour, any other pixel of the mask is blended with its colour."""
+    out = np.asarray(image, np.uint8).astype(np.int64)
+    masks = np.asarray(masks) != 0
+    colors, edge_colors = np.asarray(colors, np.int64).reshape(-1, 3), np.asarray(edge_colors, np.int64).reshape(-1, 3)
+    assert 0 <= alpha256 <= 256
+    order = instance_order(masks, scores, min_score)
+    for i in sorted((i for i in range(len(masks)) if order[i] >= 0), key=lambda i: order[i]):
+        m = masks[i]
+        edge = np.zeros(m.shape, bool)
+        edge[:, 1:] |= ~m[:, :-1]
+        edge[:, :-1] |= ~m[:, 1:]
+        edge[1:, :] |= ~m[:-1, :]
+        edge[:-1, :] |= ~m[1:, :]
+        blend = (out * (256 - alpha256) + colors[i] * alpha256 + 128) >> 8
+        out = np.where((m & ~edge)[..., None], blend, out)
+        out = np.where((m & edge)[..., None], edge_colors[i], out)
+    return out.astype(np.uint8)
+
+
+def semantic_record(labels, K: int, max_segments: Optional[int] = None) -> np.ndarray:
+    """labels int [H,W] -> int32 [H*W + 1 + 3*MAX_SEGMENTS]: ids | n | rows (id, 0, category), id = category + 1, rows by descending
+    pixel count (ties: the smaller category), at most MAX_SEGMENTS of them; a label outside [0, K) or without a row has id 0."""
+    from ._lib import MAX_SEGMENTS
+    cap = MAX_SEGMENTS if max_segments is None else int(max_segments)
+    labels = np.asarray(labels).astype(np.int64)
+    counts = np.bincount(labels[(labels >= 0) & (labels < K)].reshape(-1), minlength=K)
+    rows = sorted((c for c in range(K) if counts[c] > 0), key=lambda c: (-int(counts[c]), c))[:cap]
+    ids = np.zeros(labels.shape, np.int32)
+    table = np.zeros(1 + 3 * cap, np.int32)
+    table[0] = len(rows)
+    for r, c in enumerate(rows):
+        ids[labels == c] = c + 1
+        table[1 + 3 * r:4 + 3 * r] = (c + 1, 0, c)
+    return np.concatenate([ids.reshape(-1), table])
+
+
+def sem_labels(labels_or_sem_seg) -> np.ndarray:
+    """int labels [H,W] as they are; scores [K,H,W] -> their arg-max (the first maximum, as np.argmax and the device take it)."""
+    a = np.asarray(labels_or_sem_seg)
+    return a.argmax(axis=0).astype(np.int32) if a.ndim == 3 else a
+
+
 # ---- colours --------------------------------------------------------------------------------------------------------------------------
 def _meta(metadata, key, default=None):
     if metadata is None:
@@ -155,6 +234,30 @@ def segment_colors(segments, metadata=None) -> np.ndarray:
     return out
 
 
+def instance_colors(classes, metadata=None) -> np.ndarray:
+    """uint8 [n,3], by table index: the metadata's `thing_colors[class]` (or the fixed hue sequence) with the `_jitter` of the index."""
+    thing = _meta(metadata, "thing_colors", [])
+    out = np.zeros((len(classes), 3), np.uint8)
+    for i, cat in enumerate(classes):
+        cat = int(cat)
+        out[i] = _jitter(tuple(thing[cat]) if 0 <= cat < len(thing) else _fallback_color(cat), i)
+    return out
+
+
+def instance_edge_colors(colors) -> np.ndarray:
+    """uint8 [n,3]: the outline of a mask colour - the colour at 3/10 of its brightness when it is light (channel sum >= 384), moved
+    7/10 of the way to white when it is dark."""
+    c = np.asarray(colors, np.int64).reshape(-1, 3)
+    light = c.sum(axis=1, keepdims=True) >= 384
+    return np.where(light, c * 3 // 10, 255 - (255 - c) * 3 // 10).astype(np.uint8)
+
+
+def instance_texts(classes, scores, metadata=None) -> list:
+    """detectron2 _create_text_labels: "<class> <score in percent>%"."""
+    thing = _meta(metadata, "thing_classes", [])
+    return [f"{thing[int(c)] if 0 <= int(c) < len(thing) else f'class {int(c)}'} {float(s) * 100:.0f}%" for c, s in zip(classes, scores)]
+
+
 def segment_names(segments, metadata=None) -> list:
     segments = _table(segments)
     stuff, thing = _meta(metadata, "stuff_classes", []), _meta(metadata, "thing_classes", [])
@@ -168,13 +271,17 @@ def segment_names(segments, metadata=None) -> list:
 def draw_labels(picture: np.ndarray, anchors: np.ndarray, segments, metadata=None) -> np.ndarray:
     """Class names at the anchors, centred on them (detectron2 centres a thing's label on the mask median when no box is drawn, and a
     stuff label on its component's): white text on a dark plate, Pillow's default font."""
+    return draw_texts(picture, anchors, segment_names(segments, metadata))
+
+
+def draw_texts(picture: np.ndarray, anchors: np.ndarray, texts: Sequence[str]) -> np.ndarray:
+    """texts[segment_row] centred on every anchor: white on a dark plate, Pillow's default font."""
     from PIL import Image, ImageDraw, ImageFont
-    names = segment_names(segments, metadata)
     img = Image.fromarray(np.ascontiguousarray(picture, np.uint8))
     draw = ImageDraw.Draw(img)
     font = ImageFont.load_default()
     for a in anchors:
-        text = names[int(a["segment_row"])]
+        text = texts[int(a["segment_row"])]
         cx, cy = a["x2"] / 2.0, a["y2"] / 2.0
         l, t, r, b = draw.textbbox((0, 0), text, font=font)
         x, y = cx - (r - l) / 2.0 - l, cy - (b - t) / 2.0 - t
@@ -189,6 +296,28 @@ def draw_panoptic_seg(image, pred_ids, segments, metadata=None, alpha256: int = 
     segments = _table(segments)
     pic = panoptic_overlay(image, pred_ids, segments, segment_colors(segments, metadata), alpha256, edge_rgb)
     return draw_labels(pic, segment_anchors(pred_ids, segments, small_area, large_area), segments, metadata)
+
+
+def draw_sem_seg(image, labels_or_sem_seg, K: int, metadata=None, alpha256: int = 128, edge_rgb=(0, 0, 0), small_area: int = SMALL_AREA,
+                 large_area: int = LARGE_AREA) -> np.ndarray:
+    """The host twin of HipVisualizer.draw_sem_seg: the semantic record drawn as a panoptic result whose rows are all stuff."""
+    from ._lib import MAX_SEGMENTS
+    labels = sem_labels(labels_or_sem_seg)
+    rec = semantic_record(labels, K)
+    npix = labels.size
+    n = int(rec[npix])
+    return draw_panoptic_seg(image, rec[:npix].reshape(labels.shape), rec[npix + 1:npix + 1 + 3 * n].reshape(n, 3), metadata, alpha256, edge_rgb,
+                             small_area, large_area)
+
+
+def draw_instance_predictions(image, masks, classes, scores, metadata=None, alpha256: int = 128, min_score: float = 0.0) -> np.ndarray:
+    """The host twin of HipVisualizer.draw_instance_predictions: masks [n,H,W], classes / scores [n]."""
+    colors = instance_colors(classes, metadata)
+    pic = instance_overlay(image, masks, colors, instance_edge_colors(colors), alpha256, scores, min_score)
+    anchors = instance_anchors(masks, scores, min_score)
+    order = instance_order(masks, scores, min_score)
+    kept = sorted((i for i in range(len(anchors)) if order[i] >= 0), key=lambda i: order[i])
+    return draw_texts(pic, anchors[kept], instance_texts(classes, scores, metadata))
 
 
 class HipVisualizer:
@@ -221,3 +350,28 @@ class HipVisualizer:
         anchors, count = ctx.segment_anchors(ids, table, self.small_area, self.large_area, self.max_anchors)
         picture, rows, found = pic.numpy(), anchors.numpy(), int(count.numpy()[0])
         return draw_labels(picture, rows[:min(found, self.max_anchors)], segments, self.metadata)
+
+
+    def draw_sem_seg(self, image_dev, labels_or_sem_seg, K: Optional[int] = None) -> np.ndarray:
+        """`draw_sem_seg(predictions["sem_seg"].argmax(0))`: labels int32 [h,w] (the fused arg-max map; needs K) or sem_seg float32
+        [K,h,w] on the device -> host uint8 [h,w,3].  odise_hip_semantic_record turns the result into a record of stuff rows, which is
+        drawn as a panoptic one."""
+        h, w = labels_or_sem_seg.shape[-2:]
+        return self.draw_panoptic_seg(image_dev, self.ctx.semantic_record(labels_or_sem_seg, K), (h, w))
+
+    def draw_instance_predictions(self, image_dev, b, table_row, scores_row, topk, pad_hw, img_hw, out_hw, min_score: float = 0.0) -> np.ndarray:
+        """`draw_instance_predictions(predictions["instances"])` for the selection of image b of the last head forward, as it lies on the
+        device (table_row int32 [1 + 2 topk], scores_row float32 [topk]) -> host uint8 [h,w,3].  The table and the scores travel first
+        (their classes choose colours and texts), the masks never do: overlay, anchors and order on the device, one read-back, then
+        "<class> <score>%" at the anchors, in draw order."""
+        ctx, topk = self.ctx, int(topk)
+        table, scores = table_row.numpy().reshape(-1), scores_row.numpy().reshape(-1)
+        n = min(max(int(table[0]), 0), topk)
+        classes = table[1 + topk:1 + topk + n]
+        colors = np.zeros((topk, 3), np.uint8)
+        colors[:n] = instance_colors(classes, self.metadata)
+        res = ctx.instance_draw(out_hw, topk, table_row, scores_row, b=b, pad_hw=pad_hw, img_hw=img_hw, min_score=min_score, image=image_dev,
+                                colors=ctx.to_device(colors), edge_colors=ctx.to_device(instance_edge_colors(colors)), alpha256=self.alpha256)
+        picture, anchors, order = res["out"].numpy(), res["anchors"].numpy(), res["order"].numpy()
+        kept = sorted((i for i in range(n) if order[i] >= 0), key=lambda i: order[i])
+        return draw_texts(picture, anchors[kept], instance_texts(classes, scores[:n], self.metadata))
