@@ -527,6 +527,43 @@ typedef struct {
     int n_poly;
 } odise_inst_poly_gt;
 int odise_hip_instance_eval_poly(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p);
+/* COCOeval.accumulate for iouType "segm" on the rows of odise_hip_instance_eval as they lie on the device: maxDets (1, 10, 100), the four
+ * area ranges, the ten IoU thresholds and the caller's table of recall thresholds; byte for byte what odise_amd/instance_eval.py
+ * accumulate returns for the same rows.
+ * The rows come in blocks: block b is rows[b] = odise_inst_eval_row [slots[b] * topk] and counts[b] = int32 [slots[b]]; slot s holds one
+ * picture's rows in descending score, only its first counts[b][s] (clamped to 0..topk) exist.  Arrival order is block, slot, position.
+ *   rank      the position of a row among the rows of its category in its slot, in slot order; maxDet m keeps the rows with rank < m.
+ *   order     per category: score descending (every finite value and +-inf as -score orders them, -0 ties with +0), then `image`
+ *             ascending, then arrival order.  That is the host's stable sort on `image` followed by argsort(-score, kind="mergesort")
+ *             as long as no two slots share an image number (the host function merges such slots into one picture; this call does not).
+ *   cells     per category k with npig[k][a] > 0, maxDet m, range a, threshold t, over the kept rows in that order: tp / fp = the inclusive
+ *             counts of matched & ~ignored / ~matched & ~ignored at bit 10 a + t; rc = tp / npig[k][a], pr = tp / (fp + tp + 2^-52), IEEE
+ *             double divisions; pr is replaced by its right-to-left running maximum; precision[t][r][k][a][m] = pr at the first row with
+ *             rc >= rec_thrs[r], 0 without one; recall[t][k][a][m] = the last rc, 0 without rows.  Where npig[k][a] <= 0 every cell of
+ *             (k, a) is -1.  Both outputs are written completely.  rec_thrs must ascend (COCO's np.linspace(0, 1, 101) does; pass that
+ *             table, i / 100.0 is not the same numbers).
+ * flags (OR-ed in): 1 = a row's category outside [0, num_categories), 2 = a NaN score.  A call that raises one fills both outputs with
+ * -1; such rows are set aside before anything is indexed by them, no access leaves a buffer.
+ * Limits (ODISE_ERR_ARG and nothing written otherwise): sum of slots[b] * topk <= 2^24, num_categories 1..65535, topk 1..100,
+ * n_rec 1..101, no null pointer.  n_blocks = 0, slots[b] = 0 and counts of 0 are valid.
+ * The sort is a stable LSD radix sort of the library's own (csrc/radix_sort.h); counts are integers and the maximum is exact, so the
+ * bytes are the same from run to run.  Scratch comes from the context (56 bytes per row of capacity).  Asynchronous on the context's
+ * stream; the host arrays are read before the call returns. */
+typedef struct {
+    int n_blocks;
+    const odise_inst_eval_row* const* rows;   /* HOST [n_blocks] of device pointers */
+    const int32_t* const* counts;             /* HOST [n_blocks] of device pointers */
+    const int32_t* slots;                     /* HOST [n_blocks] */
+    int topk;                                 /* rows per slot */
+    int num_categories;                       /* K */
+    const int64_t* npig;                      /* device [K][4]: non-ignored ground truths per (category, range) */
+    const double* rec_thrs;                   /* device [n_rec], ascending */
+    int n_rec;                                /* R */
+    double* precision;                        /* device [10][R][K][4][3] */
+    double* recall;                           /* device [10][K][4][3] */
+    int32_t* flags;                           /* device [1] */
+} odise_inst_accum_desc;
+int odise_hip_instance_accumulate(odise_hip_ctx* ctx, const odise_inst_accum_desc* d);
 
 /* ---- drawing a panoptic result (demo/demo.py:173-199 VisualizationDemo.run_on_image -> detectron2 Visualizer.draw_panoptic_seg) ----
  * The per-pixel work of that call on the panoptic record as it lies in HBM: the pieces of a segment, where its label goes, and the

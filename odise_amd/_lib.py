@@ -108,6 +108,12 @@ class InstPolyGt(C.Structure):
     _fields_ = [("xy", c_void_p), ("poly_offsets", c_void_p), ("gt_polys", c_void_p), ("n_poly", c_int)]
 
 
+class InstAccumDesc(C.Structure):
+    """odise_inst_accum_desc (include/odise_hip.h)."""
+    _fields_ = [("n_blocks", c_int), ("rows", c_void_p), ("counts", c_void_p), ("slots", c_void_p), ("topk", c_int), ("num_categories", c_int),
+                ("npig", c_void_p), ("rec_thrs", c_void_p), ("n_rec", c_int), ("precision", c_void_p), ("recall", c_void_p), ("flags", c_void_p)]
+
+
 class AnchorDesc(C.Structure):
     """odise_anchor_desc (include/odise_hip.h)."""
     _fields_ = [("H", c_int), ("W", c_int), ("pred_ids", c_void_p), ("pred_segments", c_void_p), ("small_area", c_int), ("large_area", c_int),

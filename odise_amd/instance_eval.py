@@ -243,6 +243,25 @@ def accumulate(rows, npig_ka, K: int):
     return precision, recall
 
 
+# odise_hip_instance_accumulate (csrc/inst_accum.hip): `accumulate` on the device
+ACCUM_FLAG_BAD_CLASS, ACCUM_FLAG_NAN_SCORE = 1, 2
+ACCUM_FLAG_NAMES = {ACCUM_FLAG_BAD_CLASS: "a row's category is outside [0, num_categories)", ACCUM_FLAG_NAN_SCORE: "a row's score is NaN"}
+
+
+def accumulate_flag_names(flags: int) -> list:
+    return [name for bit, name in ACCUM_FLAG_NAMES.items() if flags & bit]
+
+
+def score_sort_key(scores) -> np.ndarray:
+    """uint32 keys whose ascending order is the descending order of float32 scores, as `-score` orders them: -0 ties with +0, +inf comes
+    first, equal scores (and only those) have equal keys.  The key the device sort uses (csrc/inst_accum.hip score_key); NaN has no
+    place in it."""
+    s = np.ascontiguousarray(scores, np.float32).reshape(-1)
+    u = np.where(s == 0, np.float32(0), s).view(np.uint32)
+    u = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000))
+    return ~u
+
+
 def _mean_valid(s: np.ndarray) -> float:
     s = s[s > -1]
     return float(np.mean(s)) if s.size else -1.0

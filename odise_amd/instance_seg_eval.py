@@ -1,7 +1,8 @@
 """InstanceSegEvaluator / COCOEvaluator(tasks=("segm",)) (odise/evaluation/d2_evaluator.py:29,104) on the device: `process` enqueues one
 `odise_hip_instance_eval` per picture on the instance selection of `odise_hip_infer` - the masks are sampled from the mask logits, matched
-against the ground truth and reduced to one 32-byte row per detection, no RLE string and no JSON - and `evaluate` reads the rows back
-once, gathers them across ranks and does COCOeval.accumulate / summarize on the host (odise_amd/instance_eval.py).
+against the ground truth and reduced to one 32-byte row per detection, no RLE string and no JSON - and `evaluate` runs
+COCOeval.accumulate on the device too (`odise_hip_instance_accumulate`: on one rank the rows never leave it; across ranks they are
+gathered on the host first and go up again as one block), which leaves the host summarize / results (odise_amd/instance_eval.py).
 
 Ground truth is what COCO's instance annotations hold: polygons (rasterised on the device, pycocotools' annToRLE bit for bit) for the
 objects, RLE (compressed or uncompressed) for the crowds, mixed freely in one picture."""
@@ -13,7 +14,7 @@ import numpy as np
 
 from . import distributed as D
 from . import instance_eval as IE
-from .runtime import Context, DeviceArray
+from .runtime import Context, DeviceArray, InstanceAccumulateError
 
 
 class HipInstanceSegEvaluator:
@@ -34,7 +35,7 @@ class HipInstanceSegEvaluator:
     def reset(self) -> None:
         from ._lib import check
         check(self.ctx.lib.odise_hip_memset(self.ctx.h, self.flags.ptr, 0, 4), "memset")
-        self._chunks, self._pictures = [], 0
+        self._chunks, self._pictures, self._images = [], 0, []
         self._npig = np.zeros((self.K, 4), np.int64)
 
     def _slot(self):
@@ -60,6 +61,7 @@ class HipInstanceSegEvaluator:
         self._npig += IE.npig(table, self.K)
         gt = self.ctx.instance_gt_to_device(table, runs, offsets, *((xy, poly_offsets, gt_polys) if len(poly_offsets) > 1 else ()))
         rows, n_rows = self._slot()
+        self._images.append(int(image_index))
         self.ctx.instance_eval(out_hw, inst_table_row, inst_scores_row, self.topk, gt, self.K, int(image_index), rows, n_rows, self.flags,
                                masks=pred_masks, b=b, pad_hw=pad_hw, img_hw=img_hw)
 
@@ -81,18 +83,52 @@ class HipInstanceSegEvaluator:
             out += [host[i, :n[i]] for i in range(used)]
         return np.concatenate(out) if out else np.zeros(0, IE.ROW_DTYPE)
 
-    def evaluate(self) -> dict:
+    @staticmethod
+    def slots_of(rows: np.ndarray, topk: int):
+        """Compact rows (every picture's rows back to back) -> (rows [slots * topk], counts int32 [slots]), a slot per run of one `image`
+        number, or None when an image number comes back after another one or a run is longer than topk: pictures that the host function
+        would merge."""
+        rows = np.asarray(rows, IE.ROW_DTYPE).reshape(-1)
+        first = np.flatnonzero(np.r_[True, rows["image"][1:] != rows["image"][:-1]]) if len(rows) else np.zeros(0, np.int64)
+        counts = np.diff(np.r_[first, len(rows)]).astype(np.int32)
+        if len(np.unique(rows["image"][first])) != len(first) or (counts > topk).any():
+            return None
+        out = np.zeros((len(first), topk), IE.ROW_DTYPE)
+        out[np.repeat(np.arange(len(first)), counts), np.arange(len(rows)) - np.repeat(first, counts)] = rows
+        return out.reshape(-1), counts
+
+    def evaluate(self, accumulate_on: str = "device") -> dict:
+        """accumulate_on: "device" = odise_hip_instance_accumulate, "host" = instance_eval.accumulate; the results are bit-identical.  When an
+        image number was given twice the host path is taken whatever was asked: the host function merges such pictures and the device
+        order is not defined for them."""
         import torch
         import torch.distributed as dist
-        rows, flags, npig = self.rows(), int(self.flags.numpy()[0]), self._npig
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        assert accumulate_on in ("device", "host"), accumulate_on
+        many = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        flags, npig = int(self.flags.numpy()[0]), self._npig
+        blocks = None
+        if many:
+            rows = self.rows()
             parts = [None] * dist.get_world_size()
             dist.all_gather_object(parts, (rows, flags))
             rows = np.concatenate([p[0] for p in parts])
             for p in parts:
                 flags |= int(p[1])                                           # every rank raises when any rank saw a flag
             npig = D.sum_confusion(torch.from_numpy(npig.copy())).numpy()
+            if accumulate_on == "device" and not flags:
+                block = self.slots_of(rows, self.topk)                       # the same decision on every rank: it is made on the gathered rows
+                blocks = [block] if block is not None else None
+        elif accumulate_on == "device" and len(set(self._images)) == len(self._images):
+            blocks = self._chunks                                            # as they lie
         if flags:
             raise RuntimeError("instance evaluation: malformed input(s): " + "; ".join(IE.flag_names(flags)))
-        self.precision, self.recall = IE.accumulate(rows, npig, self.K)
+        if blocks is not None:
+            try:
+                self.precision, self.recall = self.ctx.instance_accumulate(blocks, npig, self.K, self.topk)
+            except InstanceAccumulateError as e:
+                if e.flags != IE.ACCUM_FLAG_NAN_SCORE:
+                    raise
+                blocks = None                                                # a NaN score: the device sort has no place for it, numpy's has
+        if blocks is None:
+            self.precision, self.recall = IE.accumulate(rows if many else self.rows(), npig, self.K)
         return IE.results(self.precision, self.recall, self.class_names)

@@ -69,6 +69,15 @@ class DeviceArray:
         return self
 
 
+class InstanceAccumulateError(RuntimeError):
+    """`Context.instance_accumulate` raised a flag (instance_eval.ACCUM_FLAG_NAMES); .precision / .recall are what the device wrote."""
+
+    def __init__(self, flags: int, precision: np.ndarray, recall: np.ndarray):
+        from .instance_eval import accumulate_flag_names
+        super().__init__("instance accumulate: malformed input(s): " + "; ".join(accumulate_flag_names(flags)))
+        self.flags, self.precision, self.recall = flags, precision, recall
+
+
 def _p(a: Optional[DeviceArray]):
     return C.c_void_p(a.ptr) if a is not None else C.c_void_p(None)
 
@@ -736,6 +745,56 @@ class Context:
             check(self.lib.odise_hip_instance_eval_poly(self.h, C.byref(d), C.byref(p)), "instance_eval_poly")
         else:
             check(self.lib.odise_hip_instance_eval(self.h, C.byref(d)), "instance_eval")
+
+    def instance_accumulate(self, blocks, npig, num_categories: int, topk: int, rec_thrs=None):
+        """COCOeval.accumulate on the device (odise_hip_instance_accumulate; host restatement: instance_eval.accumulate, which this
+        equals byte for byte).  blocks: a sequence of (rows, counts) - `rows` a DeviceArray of instance_eval.ROW_DTYPE [slots * topk],
+        `counts` a DeviceArray int32 [slots], as the evaluator keeps them - or of host arrays of those shapes, which are uploaded; no two
+        slots may share an `image` number.  npig int64 [K, 4] (host or device); rec_thrs: instance_eval.REC_THRS unless given.
+        -> (precision float64 [10, R, K, 4, 3], recall float64 [10, K, 4, 3]) after ONE read-back, which is the only wait.  A flag raises
+        `InstanceAccumulateError` (its .flags, .precision and .recall hold what the device wrote: -1 everywhere)."""
+        from ._lib import InstAccumDesc
+        from . import instance_eval as IE
+        K, topk = int(num_categories), int(topk)
+        thr = np.ascontiguousarray(IE.REC_THRS if rec_thrs is None else rec_thrs, np.float64).reshape(-1)
+        R = thr.size
+        dev = []
+        for rows, counts in blocks:
+            if not isinstance(rows, DeviceArray):
+                rows = self.to_device(np.ascontiguousarray(rows, IE.ROW_DTYPE).reshape(-1))
+            if not isinstance(counts, DeviceArray):
+                counts = self.to_device(np.ascontiguousarray(counts, np.int32).reshape(-1))
+            slots = int(np.prod(counts.shape, dtype=np.int64))
+            assert rows.dtype == IE.ROW_DTYPE and counts.dtype == np.int32 and int(np.prod(rows.shape, dtype=np.int64)) == slots * topk, \
+                (rows.shape, rows.dtype, counts.shape, counts.dtype, topk)
+            dev.append((rows, counts, slots))
+        nb = len(dev)
+        row_ptrs = (C.c_void_p * max(nb, 1))(*[r.ptr for r, _, _ in dev])
+        count_ptrs = (C.c_void_p * max(nb, 1))(*[c.ptr for _, c, _ in dev])
+        slots = (C.c_int32 * max(nb, 1))(*[s for _, _, s in dev])
+        if not isinstance(npig, DeviceArray):
+            npig = np.ascontiguousarray(npig, np.int64)
+            assert npig.shape == (K, 4), (npig.shape, K)
+            # one upload: npig | rec_thrs
+            up = self.to_device(np.concatenate([npig.reshape(-1).view(np.uint8), thr.view(np.uint8)]))
+            npig_d, thr_d = up.view((K, 4), np.int64), up.view((R,), np.float64, K * 32)
+        else:
+            npig_d, thr_d = npig, self.to_device(thr)
+        n_p, n_r = 10 * R * K * 12, 10 * K * 12
+        out = self.empty((n_p + n_r + 1,), np.float64)              # precision | recall | flags: one read-back
+        flags = out.view((1,), np.int32, (n_p + n_r) * 8)
+        check(self.lib.odise_hip_memset(self.h, flags.ptr, 0, 8), "memset")
+        d = InstAccumDesc()
+        d.n_blocks, d.rows, d.counts, d.slots = nb, C.addressof(row_ptrs), C.addressof(count_ptrs), C.addressof(slots)
+        d.topk, d.num_categories, d.npig, d.rec_thrs, d.n_rec = topk, K, npig_d.ptr, thr_d.ptr, R
+        d.precision, d.recall, d.flags = out.ptr, out.ptr + n_p * 8, flags.ptr
+        check(self.lib.odise_hip_instance_accumulate(self.h, C.byref(d)), "instance_accumulate")
+        host = out.numpy()
+        precision, recall = host[:n_p].reshape(10, R, K, 4, 3), host[n_p:n_p + n_r].reshape(10, K, 4, 3)
+        f = int(host[n_p + n_r:].view(np.int32)[0])
+        if f:
+            raise InstanceAccumulateError(f, precision, recall)
+        return precision, recall
 
 
     def jpeg_decode(self, data: bytes, apply_orientation: bool = True, out: Optional[DeviceArray] = None) -> DeviceArray:
