@@ -670,6 +670,45 @@ int odise_hip_instance_draw(odise_hip_ctx* ctx, const odise_inst_draw_desc* d);
  * ODISE_ERR_ARG and nothing written: a null pointer or both inputs, H or W < 1, H * W > 2^29 - 1, K outside 1..12288.  Scratch comes
  * from the context.  Asynchronous on the context's stream. */
 int odise_hip_semantic_record(odise_hip_ctx* ctx, const int32_t* labels, const float* sem_seg, int K, int H, int W, int32_t* record);
+/* ---- a thing keeps its colour from frame to frame (demo/demo.py:201-243 run_on_video -> detectron2 VideoVisualizer._assign_colors) ----
+ * The mask-IoU path of that rule on panoptic records as they lie in HBM (host restatement: odise_amd/video.py ColorTracker).
+ *   instances   of a frame: the table rows with isthing != 0 that are the first row of their id, have an id > 0 and own a pixel of
+ *               pred_ids, in table-row order; (label = category, mask, area, ttl = the tracker's ttl).
+ *   live list   ordered, empty at the start; after a frame: that frame's instances in their order, then the surviving old ones in theirs.
+ *   iou         of live row o and new instance j: inter / (area_o + area_j - inter) as the double division of the two integers, 0 where
+ *               the categories differ.
+ *   matching    every live row takes j = the FIRST maximum of its iou row.  If that iou > 0.5 (strict) and o is the smallest list position
+ *               among the rows that chose j this way, j takes o's colour and o leaves the list; every other live row loses one ttl and
+ *               stays iff ttl > 0 (also a row whose j went to an earlier row, whatever its second-best is).
+ *   colours     new instances without a colour take pool[counter % n_pool], counter += 1, in instance order; the counter lives on.
+ * colors is in/out: only the rows of this frame's instances are written.  The tracker keeps what it needs (a byte map per retained frame:
+ * 0 = no instance, 1 + table row; a live row can only come from the last ttl <= 8 frames), so the record may be reused as soon as the call
+ * has returned; all of its memory (8 byte maps, a pair-count matrix of 8 x 101 x 101 int32, 800 live rows) is allocated by
+ * odise_hip_track_create and released by odise_hip_track_destroy.  Two launches per frame, no synchronisation: one sweep over the pixels
+ * counts (old index, new index) pairs of every retained frame that still has a live row in the per-block LDS histogram (in the matrix
+ * directly when the frames' tables together need more than 12288 cells) and writes the new byte map in place of the oldest; one block
+ * matches, colours and compacts the list.  Integer atomics only: the same bytes from run to run.
+ * ODISE_ERR_ARG and nothing written: a null required pointer, H or W < 1, H * W > 2^29 - 1, ttl outside 1..8, n_pool < 1, a negative cap,
+ * live without n_live, a descriptor whose H / W are not the tracker's.  Asynchronous on the context's stream. */
+typedef struct odise_track odise_track;
+int odise_hip_track_create(odise_hip_ctx* ctx, int H, int W, int ttl, const uint8_t* pool_rgb /* HOST [n_pool][3] */, int n_pool, odise_track** out);
+int odise_hip_track_reset(odise_hip_ctx* ctx, odise_track* track);     /* empties the live list and the counter */
+int odise_hip_track_destroy(odise_hip_ctx* ctx, odise_track* track);   /* waits for the stream */
+typedef struct { int32_t frame, id, category, area, ttl, rgb /* r | g << 8 | b << 16 */, pad0, pad1; } odise_track_row;   /* 32 bytes; pads are 0 */
+typedef struct {
+    odise_track* track;
+    int H, W;                     /* must be the tracker's */
+    const int32_t* pred_ids;      /* device [H*W], as odise_overlay_desc (read 16 bytes at a time when so aligned, pixel by pixel otherwise) */
+    const int32_t* pred_segments; /* device: n | n rows (id, isthing, category_id); n is read on the device, n <= ODISE_MAX_SEGMENTS */
+    uint8_t* colors;              /* device [ODISE_MAX_SEGMENTS][3], in/out */
+    odise_track_row* live;        /* optional, device [live_cap]: the live list AFTER the frame, in list order; nothing past live_cap rows */
+    int live_cap;
+    int32_t* n_live;              /* device [1], required with live: the length of the list (not clipped to live_cap) */
+    double* iou;                  /* optional, device [iou_cap][ODISE_MAX_SEGMENTS]: iou[o * ODISE_MAX_SEGMENTS + j] of live row o of the
+                                     list BEFORE the frame and this frame's instance j; other cells are left alone */
+    int iou_cap;
+} odise_track_desc;
+int odise_hip_track_frame(odise_hip_ctx* ctx, const odise_track_desc* d);
 
 /* ---- JPEG input -------------------------------------------------------------------------------------------
  * Replaces detectron2 `read_image(file, "RGB")` = PIL.Image.open -> EXIF transpose -> convert("RGB") of the DatasetMapper

@@ -134,6 +134,12 @@ class InstDrawDesc(C.Structure):
                 ("out", c_void_p), ("anchors", c_void_p), ("order", c_void_p)]
 
 
+class TrackDesc(C.Structure):
+    """odise_track_desc (include/odise_hip.h)."""
+    _fields_ = [("track", c_void_p), ("H", c_int), ("W", c_int), ("pred_ids", c_void_p), ("pred_segments", c_void_p), ("colors", c_void_p),
+                ("live", c_void_p), ("live_cap", c_int), ("n_live", c_void_p), ("iou", c_void_p), ("iou_cap", c_int)]
+
+
 MAX_SEGMENTS = 100          # ODISE_MAX_SEGMENTS
 COMM_ID_BYTES = 128         # ODISE_COMM_ID_BYTES
 

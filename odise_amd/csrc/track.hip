@@ -1,0 +1,440 @@
+// track.hip — a thing keeps its colour from frame to frame (odise_hip_track_*; detectron2 VideoVisualizer._assign_colors, mask-IoU path).
+//
+// The tracker owns a ring of kTrackRing byte maps (0 = no instance, 1 + table row of the frame's record), the live list (at most
+// kTrackRing x ODISE_MAX_SEGMENTS rows: a row can only come from the last ttl <= 8 frames) and a pair-count matrix that is zero between
+// calls.  Two launches per frame, no synchronisation (host restatement: odise_amd/video.py):
+//
+//   track_pixel_kernel   one sweep over the pixels.  Four pixels per lane and step: the new map as one 16-byte load, every retained map
+//                        that still has a live row as one dword.  The new ids become 1 + table row through the table held in LDS (a lane
+//                        keeps its last translation).  One (rows_old + 1) x (n + 1) matrix per retained map, laid end to end, is counted in
+//                        the per-block histogram (lds_hist.h); a lane counts a run of equal pairs per map in a register.  The new byte map
+//                        goes where the oldest lay: a pixel's old byte is read by the lane that overwrites it, before it does.
+//   track_match_kernel   one block, a thread per live row: new areas (column sums), the first-maximum arg-max of every live row, the
+//                        winner of a new instance = the smallest list position among the rows that chose it (atomicMin in LDS), colours,
+//                        then the list compacted by a block scan behind the new instances, and the matrix zeroed again.
+#include <algorithm>
+
+#include "common.h"
+#include "lds_hist.h"
+#include "vis_scan.h"
+
+namespace odise {
+
+constexpr int kTrackRing = 8;                                            // retained frames = the largest ttl
+constexpr int kTrackSlots = ODISE_MAX_SEGMENTS + 1;                      // 0 = no instance, 1 + table row
+constexpr int kTrackLiveCap = kTrackRing * ODISE_MAX_SEGMENTS;
+constexpr int kTrackMatrixCells = kTrackRing * kTrackSlots * kTrackSlots;
+constexpr int kTrackMatchThreads = 1024;                                 // >= kTrackLiveCap: a thread per live row
+static_assert(kTrackMatchThreads >= kTrackLiveCap, "a thread per live row");
+
+struct TrackState {   // device
+    int frame, counter, n_live, pad;         // frames since the reset, pool counter (kept modulo n_pool), rows of `live`
+    int slot_rows[kTrackRing];               // table rows of the frame a ring slot holds
+    odise_track_row live[kTrackLiveCap];
+    int live_row[kTrackLiveCap];             // table row of a live instance in its own frame: its byte in that frame's map, minus one
+};
+
+}  // namespace odise
+
+struct odise_track {
+    int H = 0, W = 0, ttl = 0, n_pool = 0;
+    int64_t map_stride = 0;                  // bytes between ring maps (npix rounded up to 16)
+    odise::TrackState* state = nullptr;
+    uint8_t* maps = nullptr;                 // [kTrackRing][map_stride]
+    int* matrix = nullptr;                   // [kTrackMatrixCells], zero between calls
+    uint8_t* pool = nullptr;                 // [n_pool][3]
+};
+
+namespace odise {
+
+// The matrices of a frame: one per retained map that still has a live row, (rows + 1) x (n + 1) cells each, laid end to end; with no live
+// row at all a single 1 x (n + 1) matrix without a map (the new areas are column sums of the first matrix).
+struct TrackLayout {
+    int n, passes, cells;
+    int slot[kTrackRing];      // ring slot of a pass, -1 = no map
+    int off[kTrackRing];       // first cell of its matrix
+    int pass_of[kTrackRing];   // ring slot -> pass, -1 = not retained
+};
+
+__device__ __forceinline__ int track_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+// tab[i] = id of table row i when the row can be an instance (a thing, id > 0, the first row of its id), else 0.  Whole block; no barrier.
+__device__ __forceinline__ void track_load_table(const int* __restrict__ seg, int n, int* tab) {
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int id = seg[1 + 3 * i];
+        bool first = id > 0 && seg[2 + 3 * i] != 0;
+        for (int r = 0; r < i && first; ++r) first = seg[1 + 3 * r] != id;
+        tab[i] = first ? id : 0;
+    }
+}
+
+// Whole block: `active` is scratch, `L` the result; both are published by the barriers in here.
+__device__ __forceinline__ void track_layout(const TrackState* __restrict__ st, int n, int* active, TrackLayout* L) {
+    if (threadIdx.x < kTrackRing) active[threadIdx.x] = 0;
+    __syncthreads();
+    const int n_live = track_clamp(st->n_live, kTrackLiveCap);
+    for (int r = threadIdx.x; r < n_live; r += blockDim.x) active[st->live[r].frame & (kTrackRing - 1)] = 1;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int passes = 0, cells = 0;
+        for (int s = 0; s < kTrackRing; ++s) {
+            L->pass_of[s] = -1;
+            if (!active[s]) continue;
+            L->pass_of[s] = passes;
+            L->slot[passes] = s;
+            L->off[passes] = cells;
+            cells += (track_clamp(st->slot_rows[s], ODISE_MAX_SEGMENTS) + 1) * (n + 1);
+            ++passes;
+        }
+        if (!passes) { L->slot[0] = -1; L->off[0] = 0; cells = n + 1; passes = 1; }
+        for (int k = passes; k < kTrackRing; ++k) { L->slot[k] = -1; L->off[k] = 0; }
+        L->n = n; L->passes = passes; L->cells = cells;   // <= kTrackRing * kTrackSlots * kTrackSlots
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ int track_find(const int* tab, int n, int id) {
+    if (id <= 0) return 0;
+    for (int r = 0; r < n; ++r)
+        if (tab[r] == id) return r + 1;
+    return 0;
+}
+
+struct TrackLane {
+    int last_id, last_j;                       // the lane's last translation
+    int cell[kTrackRing], run[kTrackRing];     // per pass: the pair being counted and its length so far (registers: the loops are unrolled)
+};
+
+template <bool LDS>
+__device__ __forceinline__ void track_flush_run(int cell, int run, const LdsHist<int>& H) {
+    if (run && (unsigned)cell < (unsigned)H.n) {   // a byte of a retained map is at most that frame's row count: always inside
+        if (LDS) H.add_lds(cell, (unsigned)run);
+        else H.add_global(cell, (unsigned)run);
+    }
+}
+
+template <bool LDS>
+__device__ __forceinline__ void track_count(TrackLane& T, int k, int cell, const LdsHist<int>& H) {
+    if (cell == T.cell[k]) { ++T.run[k]; return; }
+    track_flush_run<LDS>(T.cell[k], T.run[k], H);
+    T.cell[k] = cell;
+    T.run[k] = 1;
+}
+
+__device__ __forceinline__ int track_translate(TrackLane& T, const int* tab, int n, int id) {
+    if (id != T.last_id) { T.last_id = id; T.last_j = track_find(tab, n, id); }
+    return T.last_j;
+}
+
+// four pixels of group q (bytes 4 q .. 4 q + 3 of every map; the maps are 16-byte aligned)
+template <bool LDS>
+__device__ __forceinline__ void track_group(TrackLane& T, const TrackLayout& L, uint8_t* maps, int64_t map_stride, int new_slot, int64_t q,
+                                            int j0, int j1, int j2, int j3, const LdsHist<int>& H) {
+    const int w = L.n + 1;
+#pragma unroll
+    for (int k = 0; k < kTrackRing; ++k) {
+        if (k >= L.passes) break;
+        const int s = L.slot[k];
+        const unsigned o = s >= 0 ? ((const unsigned*)(maps + (int64_t)s * map_stride))[q] : 0u;
+        const int base = L.off[k];
+        const int o0 = (int)(o & 255u), o1 = (int)((o >> 8) & 255u), o2 = (int)((o >> 16) & 255u), o3 = (int)(o >> 24);
+        if (o0 | j0) track_count<LDS>(T, k, base + o0 * w + j0, H);   // the (nothing, nothing) pair is not needed
+        if (o1 | j1) track_count<LDS>(T, k, base + o1 * w + j1, H);
+        if (o2 | j2) track_count<LDS>(T, k, base + o2 * w + j2, H);
+        if (o3 | j3) track_count<LDS>(T, k, base + o3 * w + j3, H);
+    }
+    ((unsigned*)(maps + (int64_t)new_slot * map_stride))[q] = (unsigned)j0 | ((unsigned)j1 << 8) | ((unsigned)j2 << 16) | ((unsigned)j3 << 24);
+}
+
+template <bool LDS>
+__device__ __forceinline__ void track_pixel(TrackLane& T, const TrackLayout& L, uint8_t* maps, int64_t map_stride, int new_slot, int64_t i, int j,
+                                            const LdsHist<int>& H) {
+    const int w = L.n + 1;
+#pragma unroll
+    for (int k = 0; k < kTrackRing; ++k) {
+        if (k >= L.passes) break;
+        const int s = L.slot[k];
+        const int o = s >= 0 ? (int)maps[(int64_t)s * map_stride + i] : 0;
+        if (o | j) track_count<LDS>(T, k, L.off[k] + o * w + j, H);
+    }
+    maps[(int64_t)new_slot * map_stride + i] = (uint8_t)j;
+}
+
+// matrix += the pair counts of the frame; maps[frame & 7] = the frame's byte map.  vec != 0: pred is 16-byte aligned (groups of four pixels
+// are read whole; the last npix & 3 pixels and an unaligned map are read pixel by pixel).  lds_cells = cells of the dynamic LDS histogram.
+// A pixel is read and written by one lane only, and its old bytes are read before its new byte is stored (maps is not __restrict__).
+__global__ void __launch_bounds__(256) track_pixel_kernel(const int* __restrict__ pred, const int* __restrict__ pred_segments,
+                                                         const TrackState* __restrict__ st, uint8_t* maps, int64_t map_stride, int npix, int vec,
+                                                         int lds_cells, int* __restrict__ matrix) {
+    __shared__ int tab[ODISE_MAX_SEGMENTS];
+    __shared__ int active[kTrackRing];
+    __shared__ TrackLayout L;
+    const int n = track_clamp(pred_segments[0], ODISE_MAX_SEGMENTS);
+    track_load_table(pred_segments, n, tab);
+    track_layout(st, n, active, &L);
+    const LdsHist<int> H(matrix, L.cells, L.cells <= lds_cells);
+    H.clear();
+    __syncthreads();
+
+    const int new_slot = st->frame & (kTrackRing - 1);
+    TrackLane T;
+    T.last_id = 0; T.last_j = 0;
+#pragma unroll
+    for (int k = 0; k < kTrackRing; ++k) { T.cell[k] = 0; T.run[k] = 0; }
+    const int groups = npix >> 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    if (vec) {
+        for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += stride) {
+            const int4 p = ((const int4*)pred)[q];
+            const int j0 = track_translate(T, tab, n, p.x), j1 = track_translate(T, tab, n, p.y);
+            const int j2 = track_translate(T, tab, n, p.z), j3 = track_translate(T, tab, n, p.w);
+            if (H.lds) track_group<true>(T, L, maps, map_stride, new_slot, q, j0, j1, j2, j3, H);
+            else track_group<false>(T, L, maps, map_stride, new_slot, q, j0, j1, j2, j3, H);
+        }
+    }
+    for (int64_t i = (vec ? (int64_t)groups * 4 : 0) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride) {
+        const int j = track_translate(T, tab, n, pred[i]);
+        if (H.lds) track_pixel<true>(T, L, maps, map_stride, new_slot, i, j, H);
+        else track_pixel<false>(T, L, maps, map_stride, new_slot, i, j, H);
+    }
+#pragma unroll
+    for (int k = 0; k < kTrackRing; ++k) {
+        if (H.lds) track_flush_run<true>(T.cell[k], T.run[k], H);
+        else track_flush_run<false>(T.cell[k], T.run[k], H);
+    }
+    __syncthreads();
+    H.flush();
+}
+
+// One block of kTrackMatchThreads.  matrix: the pair counts of the frame (zeroed on return); st: the tracker before the frame -> after it.
+__global__ void __launch_bounds__(kTrackMatchThreads) track_match_kernel(int* __restrict__ matrix, const int* __restrict__ pred_segments,
+                                                                        TrackState* __restrict__ st, const uint8_t* __restrict__ pool, int n_pool,
+                                                                        int ttl, uint8_t* __restrict__ colors, odise_track_row* __restrict__ live_out,
+                                                                        int live_cap, int* __restrict__ n_live_out, double* __restrict__ iou_out,
+                                                                        int iou_cap) {
+    __shared__ int tab[ODISE_MAX_SEGMENTS], cat[ODISE_MAX_SEGMENTS], area[ODISE_MAX_SEGMENTS];
+    __shared__ int rank[ODISE_MAX_SEGMENTS];      // position of a row among the frame's instances, -1 = no instance
+    __shared__ int winner[ODISE_MAX_SEGMENTS];    // smallest list position of the live rows that chose the instance
+    __shared__ int urank[ODISE_MAX_SEGMENTS];     // position among the instances that take a new colour
+    __shared__ int rgb[ODISE_MAX_SEGMENTS];
+    __shared__ int active[kTrackRing];
+    __shared__ TrackLayout L;
+    __shared__ int wave_sum[kTrackMatchThreads / 64];
+    __shared__ int n_inst, n_new;
+    const int tid = threadIdx.x;
+    const int n = track_clamp(pred_segments[0], ODISE_MAX_SEGMENTS);
+    const int n_live = track_clamp(st->n_live, kTrackLiveCap), frame = st->frame, counter = st->counter;
+    track_load_table(pred_segments, n, tab);
+    track_layout(st, n, active, &L);   // its barriers also order the reads of st->frame / n_live / counter above before anything is written
+    const int w = n + 1;
+
+    // the frame's instances: candidates that own a pixel (area = column sum of the first matrix, whose rows cover every pixel of the map)
+    if (tid < n) {
+        int a = 0;
+        if (tab[tid]) {
+            const int rows = L.slot[0] >= 0 ? track_clamp(st->slot_rows[L.slot[0]], ODISE_MAX_SEGMENTS) + 1 : 1;
+            for (int o = 0; o < rows; ++o) a += matrix[L.off[0] + o * w + tid + 1];
+        }
+        area[tid] = a;
+        cat[tid] = pred_segments[3 + 3 * tid];
+        winner[tid] = INT32_MAX;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int c = 0;
+        for (int j = 0; j < n; ++j) rank[j] = area[j] > 0 ? c++ : -1;
+        n_inst = c;
+    }
+    __syncthreads();
+
+    // a thread per live row: its iou row, the first maximum
+    odise_track_row row = {};
+    int my_row = 0, choice = -1;
+    if (tid < n_live) {
+        row = st->live[tid];
+        my_row = st->live_row[tid];
+        const int k = L.pass_of[row.frame & (kTrackRing - 1)];
+        const int* m = matrix + L.off[k < 0 ? 0 : k] + (my_row + 1) * w;
+        double best = 0.0;
+        for (int j = 0; j < n; ++j) {
+            if (rank[j] < 0) continue;
+            double iou = 0.0;
+            if (k >= 0 && cat[j] == row.category) {
+                const int inter = m[j + 1];
+                iou = (double)inter / (double)((int64_t)row.area + area[j] - inter);
+            }
+            if (iou_out && tid < iou_cap) iou_out[(int64_t)tid * ODISE_MAX_SEGMENTS + rank[j]] = iou;
+            if (iou > best) { best = iou; choice = j; }
+        }
+        if (best > 0.5) atomicMin(&winner[choice], tid);
+        else choice = -1;
+    }
+    __syncthreads();
+    if (tid < n && rank[tid] >= 0 && winner[tid] != INT32_MAX) rgb[tid] = st->live[winner[tid]].rgb;   // read before the list is rewritten
+    if (tid == 0) {
+        int u = 0;
+        for (int j = 0; j < n; ++j) urank[j] = (rank[j] >= 0 && winner[j] == INT32_MAX) ? u++ : -1;
+        n_new = u;
+    }
+    __syncthreads();
+    if (tid < n && rank[tid] >= 0) {
+        if (urank[tid] >= 0) {
+            const uint8_t* c = pool + 3 * ((counter + urank[tid]) % n_pool);
+            rgb[tid] = (int)c[0] | ((int)c[1] << 8) | ((int)c[2] << 16);
+        }
+        colors[3 * tid] = (uint8_t)(rgb[tid] & 255);
+        colors[3 * tid + 1] = (uint8_t)((rgb[tid] >> 8) & 255);
+        colors[3 * tid + 2] = (uint8_t)((rgb[tid] >> 16) & 255);
+    }
+
+    // the survivors keep their order behind the new instances: an exclusive block scan of the keep flags
+    const bool matched = choice >= 0 && winner[choice] == tid;
+    const int keep = (tid < n_live && !matched && row.ttl - 1 > 0) ? 1 : 0;
+    const int lane = tid & 63, wave = tid >> 6;
+    int inc = keep;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int up = __shfl_up(inc, d);
+        if (lane >= d) inc += up;
+    }
+    if (lane == 63) wave_sum[wave] = inc;
+    __syncthreads();   // also: every thread holds its row and the winners' colours are read, the list may be rewritten
+    int before = 0, kept = 0;
+    for (int v = 0; v < kTrackMatchThreads / 64; ++v) {
+        const int s = wave_sum[v];
+        if (v < wave) before += s;
+        kept += s;
+    }
+    const int total = min(n_inst + kept, kTrackLiveCap);
+    if (keep) {
+        const int pos = n_inst + before + inc - 1;
+        if (pos < kTrackLiveCap) {
+            row.ttl -= 1;
+            st->live[pos] = row;
+            st->live_row[pos] = my_row;
+            if (live_out && pos < live_cap) live_out[pos] = row;
+        }
+    }
+    if (tid < n && rank[tid] >= 0) {
+        odise_track_row r;
+        r.frame = frame; r.id = tab[tid]; r.category = cat[tid]; r.area = area[tid]; r.ttl = ttl; r.rgb = rgb[tid]; r.pad0 = 0; r.pad1 = 0;
+        const int pos = rank[tid];
+        st->live[pos] = r;
+        st->live_row[pos] = tid;
+        if (live_out && pos < live_cap) live_out[pos] = r;
+    }
+    if (tid == 0) {
+        st->n_live = total;
+        st->frame = frame + 1;
+        st->counter = (counter + n_new) % n_pool;
+        st->slot_rows[frame & (kTrackRing - 1)] = n;
+        if (n_live_out) n_live_out[0] = total;
+    }
+    for (int i = tid; i < L.cells; i += kTrackMatchThreads) matrix[i] = 0;
+}
+
+static void track_free(odise_track* t) {
+    if (t->state) (void)hipFree(t->state);
+    if (t->maps) (void)hipFree(t->maps);
+    if (t->matrix) (void)hipFree(t->matrix);
+    if (t->pool) (void)hipFree(t->pool);
+    delete t;
+}
+
+static int track_clear(odise_hip_ctx* ctx, odise_track* t) {
+    ODISE_CHECK_HIP(hipMemsetAsync(t->state, 0, sizeof(TrackState), ctx->stream));
+    ODISE_CHECK_HIP(hipMemsetAsync(t->matrix, 0, (size_t)kTrackMatrixCells * sizeof(int), ctx->stream));
+    return ODISE_OK;
+}
+
+// everything that can be refused is refused before anything is enqueued
+static int track_check_args(const odise_track_desc* d) {
+    ODISE_REQUIRE(d, "track_frame: null descriptor");
+    ODISE_REQUIRE(d->track && d->pred_ids && d->pred_segments && d->colors, "track_frame: null pointer");
+    ODISE_TRY(vis_check_size("track_frame", d->H, d->W));
+    ODISE_REQUIRE(d->H == d->track->H && d->W == d->track->W, "track_frame: a %dx%d frame for a tracker of %dx%d", d->H, d->W, d->track->H,
+                  d->track->W);
+    ODISE_REQUIRE(d->live_cap >= 0 && d->iou_cap >= 0, "track_frame: negative cap (live_cap %d, iou_cap %d)", d->live_cap, d->iou_cap);
+    ODISE_REQUIRE(!d->live || d->n_live, "track_frame: live without n_live");
+    ODISE_REQUIRE(((uintptr_t)d->pred_ids & 3) == 0 && ((uintptr_t)d->pred_segments & 3) == 0 && ((uintptr_t)d->live & 3) == 0 &&
+                      ((uintptr_t)d->n_live & 3) == 0 && ((uintptr_t)d->iou & 7) == 0,
+                  "track_frame: int32 buffers must be 4-byte aligned, iou 8-byte aligned");
+    return ODISE_OK;
+}
+
+}  // namespace odise
+
+using namespace odise;
+
+extern "C" int odise_hip_track_create(odise_hip_ctx* ctx, int H, int W, int ttl, const uint8_t* pool_rgb, int n_pool, odise_track** out) {
+    ODISE_REQUIRE(ctx, "track_create: null context");
+    ODISE_REQUIRE(out && pool_rgb, "track_create: null pointer");
+    ODISE_TRY(vis_check_size("track_create", H, W));
+    ODISE_REQUIRE(ttl >= 1 && ttl <= kTrackRing, "track_create: ttl %d outside 1..%d", ttl, kTrackRing);
+    ODISE_REQUIRE(n_pool >= 1 && n_pool <= (1 << 20), "track_create: n_pool %d outside 1..2^20", n_pool);
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    odise_track* t = new odise_track();
+    t->H = H; t->W = W; t->ttl = ttl; t->n_pool = n_pool;
+    t->map_stride = round_up((int64_t)H * W, 16);
+    const size_t bytes = sizeof(TrackState) + (size_t)kTrackRing * t->map_stride + (size_t)kTrackMatrixCells * sizeof(int) + (size_t)n_pool * 3;
+    const bool ok = hipMalloc((void**)&t->state, sizeof(TrackState)) == hipSuccess &&
+                    hipMalloc((void**)&t->maps, (size_t)kTrackRing * t->map_stride) == hipSuccess &&
+                    hipMalloc((void**)&t->matrix, (size_t)kTrackMatrixCells * sizeof(int)) == hipSuccess &&
+                    hipMalloc((void**)&t->pool, (size_t)n_pool * 3) == hipSuccess;
+    if (!ok) {
+        (void)hipGetLastError();
+        track_free(t);
+        set_error("track_create: could not allocate %zu bytes", bytes);
+        return ODISE_ERR_NOMEM;
+    }
+    int rc = ODISE_OK;
+    if (hipMemcpy(t->pool, pool_rgb, (size_t)n_pool * 3, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("track_create: copying the colour pool failed");
+        rc = ODISE_ERR_HIP;
+    }
+    if (rc == ODISE_OK) rc = track_clear(ctx, t);
+    if (rc != ODISE_OK) {
+        (void)hipGetLastError();
+        track_free(t);
+        return rc;
+    }
+    *out = t;
+    return ODISE_OK;
+}
+
+extern "C" int odise_hip_track_reset(odise_hip_ctx* ctx, odise_track* track) {
+    ODISE_REQUIRE(ctx, "track_reset: null context");
+    ODISE_REQUIRE(track, "track_reset: null tracker");
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    return track_clear(ctx, track);
+}
+
+extern "C" int odise_hip_track_destroy(odise_hip_ctx* ctx, odise_track* track) {
+    ODISE_REQUIRE(ctx, "track_destroy: null context");
+    ODISE_REQUIRE(track, "track_destroy: null tracker");
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // frames in flight read its memory
+    track_free(track);
+    return ODISE_OK;
+}
+
+extern "C" int odise_hip_track_frame(odise_hip_ctx* ctx, const odise_track_desc* d) {
+    ODISE_REQUIRE(ctx, "track_frame: null context");
+    ODISE_TRY(track_check_args(d));
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    odise_track* t = d->track;
+    const int npix = d->H * d->W;
+    const int vec = ((uintptr_t)d->pred_ids & 15) == 0;
+    const int lds_cells = kLdsHistCells;   // the tables are read on the device: room for the most the histogram holds
+    const int blocks = (int)std::min<int64_t>(ceil_div(ceil_div(npix, 4), 256), 8 * ctx->cu_count);
+    hipLaunchKernelGGL(track_pixel_kernel, dim3(blocks), dim3(256), lds_hist_bytes(lds_cells), ctx->stream, (const int*)d->pred_ids,
+                       (const int*)d->pred_segments, (const TrackState*)t->state, t->maps, t->map_stride, npix, vec, lds_cells, t->matrix);
+    ODISE_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(track_match_kernel, dim3(1), dim3(kTrackMatchThreads), 0, ctx->stream, t->matrix, (const int*)d->pred_segments, t->state,
+                       (const uint8_t*)t->pool, t->n_pool, t->ttl, d->colors, d->live, d->live_cap, (int*)d->n_live, d->iou, d->iou_cap);
+    const hipError_t launched = hipGetLastError();
+    if (launched != hipSuccess) {   // the pixel pass has counted and nothing will clear its counts
+        (void)hipMemsetAsync(t->matrix, 0, (size_t)kTrackMatrixCells * sizeof(int), ctx->stream);
+        ODISE_CHECK_HIP(launched);
+    }
+    return ODISE_OK;
+}

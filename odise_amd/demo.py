@@ -1,4 +1,4 @@
-"""`python -m odise_amd.demo --input FILE... --output DIR [--vocab "a, b; c"] [--synthetic] [--task panoptic|semantic|instance]`:
+"""`python -m odise_amd.demo (--input FILE... | --video-input SRC [--ttl N]) --output DIR [--vocab "a, b; c"] [--synthetic] [--task panoptic|semantic|instance]`:
 demo/demo.py on the device path.
 
 A picture is read (JPEG through HipDatasetMapper, anything else through Pillow), resized by ResizeShortestEdge(1024, 2560) on the device,
@@ -8,6 +8,12 @@ its panoptic record - still in HBM - is drawn by HipVisualizer.draw_panoptic_seg
 `--task semantic` / `--task instance` take the other branch of run_on_image: the wrapper is built with that head on (and panoptic off), and
 the semantic map (HipVisualizer.draw_sem_seg), then the instance selection (draw_instance_predictions, scores below
 `--confidence-threshold` left out) are drawn, the instances on top.
+
+`--video-input SRC` takes run_on_video (demo.py:201-243) instead: SRC is a directory of frames (read in sorted name order) or a multi-frame
+file Pillow opens (no container decoding); every frame goes through the same model call and is drawn by
+HipVideoVisualizer.draw_panoptic_seg_predictions, which keeps a thing's colour from frame to frame (`--ttl` frames of memory), and saved as
+DIR/frame_%06d.png - or, when `--output` ends in .gif, all frames as one animated GIF.  `--task semantic` draws every frame on its own;
+`--task instance` is refused (the reference tracks pred_boxes there, which are all zeros on this model).
 
 Weights come from `$ODISE_MODEL_ZOO` through odise_amd/checkpoint.py; `--synthetic` takes random tensors of the real shapes and seeded
 text banks instead (odise_amd/synthetic.py), which draws arbitrary segments but needs no file.
@@ -24,15 +30,23 @@ import numpy as np
 
 def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap = argparse.ArgumentParser(prog="python -m odise_amd.demo", description="Panoptic segmentation of pictures, drawn and saved as PNG.")
-    ap.add_argument("--input", nargs="+", required=True, metavar="FILE", help="pictures (JPEG is decoded on the device)")
-    ap.add_argument("--output", required=True, metavar="DIR", help="directory for the drawn pictures")
+    src = ap.add_mutually_exclusive_group(required=True)
+    src.add_argument("--input", nargs="+", metavar="FILE", help="pictures (JPEG is decoded on the device)")
+    src.add_argument("--video-input", metavar="SRC", help="a directory of frames (sorted by name) or a multi-frame file Pillow opens")
+    ap.add_argument("--output", required=True, metavar="DIR", help="directory for the drawn pictures (--video-input: or a .gif file)")
+    ap.add_argument("--ttl", type=int, default=8, help="--video-input: frames an unseen thing keeps its colour for (1..8)")
     ap.add_argument("--vocab", default="", help='extra classes, demo.py style: "black pickup truck, pickup truck; blue sky, sky"')
     ap.add_argument("--synthetic", action="store_true", help="random weights of the real shapes and seeded text banks: needs no checkpoint")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--task", choices=("panoptic", "semantic", "instance"), default="panoptic",
                     help="which head is on and drawn (semantic-only vocabularies, or the instance masks segm AP scores)")
     ap.add_argument("--confidence-threshold", type=float, default=0.5, help="--task instance: instances below this score are not drawn")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.video_input is not None and args.task == "instance":
+        ap.error("--task instance with --video-input: the reference tracks pred_boxes there, which are all zeros on this model")
+    if not 1 <= args.ttl <= 8:
+        ap.error(f"--ttl {args.ttl} outside 1..8")
+    return args
 
 
 def extra_classes(vocab: str) -> List[List[str]]:
@@ -111,7 +125,37 @@ def read_picture(ctx, file_name: str):
             return ctx.to_device(np.ascontiguousarray(np.asarray(ImageOps.exif_transpose(im).convert("RGB"), np.uint8)))
 
 
-def run_on_image(ctx, model, visualizer, image_dev, task: str = "panoptic", confidence_threshold: float = 0.5) -> np.ndarray:
+def video_frames(src: str) -> list:
+    """[(name, loader)] of --video-input: the files of a directory in sorted name order (loader(ctx) = read_picture), or the frames of
+    a multi-frame file as Pillow's ImageSequence yields them (name = "<file>#<index>")."""
+    if os.path.isdir(src):
+        names = sorted(f for f in os.listdir(src) if os.path.isfile(os.path.join(src, f)))
+        return [(os.path.join(src, f), (lambda ctx, p=os.path.join(src, f): read_picture(ctx, p))) for f in names]
+    from PIL import Image, ImageSequence
+    with Image.open(src) as im:
+        frames = [np.ascontiguousarray(np.asarray(f.convert("RGB"), np.uint8)) for f in ImageSequence.Iterator(im)]
+    return [(f"{src}#{k}", (lambda ctx, a=a: ctx.to_device(a))) for k, a in enumerate(frames)]
+
+
+def frame_path(out_dir: str, index: int) -> str:
+    return os.path.join(out_dir, "frame_%06d.png" % index)
+
+
+def run_on_video(ctx, model, visualizer, frames, task: str = "panoptic"):
+    """VisualizationDemo.run_on_video (demo.py:201-243): yields the drawn frames.  visualizer: a HipVideoVisualizer (panoptic: its
+    tracker colours the things; semantic: every frame on its own).  A frame of another size than the first is refused by name."""
+    size = None
+    for name, load in frames:
+        image_dev = load(ctx)
+        hw = tuple(image_dev.shape[:2])
+        size = size or hw
+        if hw != size:
+            raise SystemExit(f"{name}: a {hw[0]}x{hw[1]} frame in a video of {size[0]}x{size[1]}")
+        yield run_on_image(ctx, model, visualizer, image_dev, task, video=True)
+
+
+def run_on_image(ctx, model, visualizer, image_dev, task: str = "panoptic", confidence_threshold: float = 0.5,
+                 video: bool = False) -> np.ndarray:
     """VisualizationDemo.run_on_image (demo.py:173-199) for a picture that is on the device; the result never leaves it before it is drawn."""
     from ._lib import MAX_SEGMENTS
     from .ingest import HipDatasetMapper
@@ -132,7 +176,8 @@ def run_on_image(ctx, model, visualizer, image_dev, task: str = "panoptic", conf
         inner.load_open_state_dict(saved)
         inner.keep_instance_selection, inner.instance_rle, inner.semantic_argmax = keep, rle, amax
     if task == "panoptic":
-        return visualizer.draw_panoptic_seg(image_dev, record, (h, w))
+        draw = visualizer.draw_panoptic_seg_predictions if video else visualizer.draw_panoptic_seg
+        return draw(image_dev, record, (h, w))
     picture = image_dev                                                      # the else branch: semantic, then instances on top
     if "sem_seg" in results[0] or "sem_seg_argmax" in results[0]:
         sem = results[0].get("sem_seg_argmax", results[0].get("sem_seg"))
@@ -150,10 +195,28 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     args = parse_args(argv)
     from PIL import Image
     from .runtime import Context
-    from .visualize import HipVisualizer
+    from .visualize import HipVideoVisualizer, HipVisualizer
     labels, num_things = default_labels(extra_classes(args.vocab))
     ctx = Context(args.device)
     model, metadata = build_model(ctx, labels, num_things, args.synthetic, args.task)
+    if args.video_input is not None:
+        visualizer = HipVideoVisualizer(ctx, metadata, ttl=args.ttl)
+        drawn = run_on_video(ctx, model, visualizer, video_frames(args.video_input), args.task)
+        if args.output.lower().endswith(".gif"):
+            os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
+            pictures = [Image.fromarray(p) for p in drawn]
+            if not pictures:
+                raise SystemExit(f"{args.video_input}: no frames")
+            pictures[0].save(args.output, save_all=True, append_images=pictures[1:], duration=100, loop=0)
+            print(f"{args.video_input} -> {args.output} ({len(pictures)} frames)")
+        else:
+            os.makedirs(args.output, exist_ok=True)
+            for k, picture in enumerate(drawn):
+                Image.fromarray(picture).save(frame_path(args.output, k))
+                print(f"{args.video_input} frame {k} -> {frame_path(args.output, k)}")
+        visualizer.close()
+        ctx.close()
+        return 0
     visualizer = HipVisualizer(ctx, metadata)
     os.makedirs(args.output, exist_ok=True)
     for file_name in args.input:

@@ -555,6 +555,37 @@ class Context:
         check(self.lib.odise_hip_panoptic_overlay(self.h, C.byref(d)), "panoptic_overlay")
         return out
 
+    # ---- colours of things across frames (include/odise_hip.h odise_hip_track_*; host restatement: odise_amd/video.py) -------------------
+    def track_create(self, hw, ttl: int = 8, pool=None) -> "Tracker":
+        """A tracker for frames of hw = (H, W): pool uint8 [P,3] on the host (video.default_pool() when None)."""
+        return Tracker(self, hw, ttl, pool)
+
+    def track_frame(self, tracker: "Tracker", pred_ids: DeviceArray, pred_segments: DeviceArray, colors: DeviceArray,
+                    live: Optional[DeviceArray] = None, n_live: Optional[DeviceArray] = None, iou: Optional[DeviceArray] = None,
+                    live_cap: Optional[int] = None, iou_cap: Optional[int] = None) -> DeviceArray:
+        """One frame, enqueued: pred_ids int32 [H,W] and pred_segments int32 [n | n x (id, isthing, category)] (the two parts of a panoptic
+        record), colors uint8 [MAX_SEGMENTS,3] in/out (the rows of the frame's instances are rewritten).  Optional dumps: live [cap]
+        records of video.TRACK_ROW_DTYPE with n_live int32 [1], iou float64 [cap, MAX_SEGMENTS]."""
+        from ._lib import MAX_SEGMENTS, TrackDesc
+        from .video import TRACK_ROW_DTYPE
+        H, W = pred_ids.shape
+        assert pred_ids.dtype == np.int32 and pred_segments.dtype == np.int32
+        assert colors.dtype == np.uint8 and colors.nbytes >= 3 * MAX_SEGMENTS, (colors.dtype, colors.shape)
+        d = TrackDesc()
+        d.track, d.H, d.W, d.pred_ids, d.pred_segments, d.colors = tracker.handle, H, W, pred_ids.ptr, pred_segments.ptr, colors.ptr
+        if live is not None:
+            assert live.dtype == TRACK_ROW_DTYPE and (n_live is None or n_live.dtype == np.int32)
+            d.live, d.live_cap = live.ptr, live.shape[0] if live_cap is None else int(live_cap)
+            assert d.live_cap <= live.shape[0]
+        if n_live is not None:
+            d.n_live = n_live.ptr
+        if iou is not None:
+            assert iou.dtype == np.float64 and len(iou.shape) == 2 and iou.shape[1] == MAX_SEGMENTS, (iou.dtype, iou.shape)
+            d.iou, d.iou_cap = iou.ptr, iou.shape[0] if iou_cap is None else int(iou_cap)
+            assert d.iou_cap <= iou.shape[0]
+        check(self.lib.odise_hip_track_frame(self.h, C.byref(d)), "track_frame")
+        return colors
+
     # ---- drawing instance and semantic results (include/odise_hip.h odise_hip_instance_draw / odise_hip_semantic_record) ----------------
     def instance_draw(self, out_hw, topk: int, table_row=None, scores_row=None, masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0),
                       img_hw=(0, 0), min_score: float = 0.0, image: Optional[DeviceArray] = None, colors: Optional[DeviceArray] = None,
@@ -810,6 +841,33 @@ class Context:
         check(self.lib.odise_hip_jpeg_decode(self.h, buf, C.c_int64(len(data)), _p(out), C.c_int64(out.nbytes), int(bool(apply_orientation)),
                                              C.byref(h), C.byref(w)), "jpeg_decode")
         return out.view((h.value, w.value, 3)) if out.shape != (h.value, w.value, 3) else out
+
+
+class Tracker:
+    """odise_track (include/odise_hip.h): the library's tracker object for frames of one size; `close()` (or collection) releases it."""
+
+    def __init__(self, ctx: Context, hw, ttl: int = 8, pool=None):
+        from .video import default_pool
+        pool = default_pool() if pool is None else np.ascontiguousarray(np.asarray(pool, np.uint8).reshape(-1, 3))
+        self.ctx, self.hw, self.ttl, self.pool = ctx, (int(hw[0]), int(hw[1])), int(ttl), pool
+        h = C.c_void_p()
+        check(ctx.lib.odise_hip_track_create(ctx.h, self.hw[0], self.hw[1], self.ttl, pool.ctypes.data_as(C.c_void_p), len(pool), C.byref(h)),
+              "track_create")
+        self.handle = h.value
+
+    def reset(self) -> None:
+        check(self.ctx.lib.odise_hip_track_reset(self.ctx.h, C.c_void_p(self.handle)), "track_reset")
+
+    def close(self) -> None:
+        if self.handle and self.ctx.h:
+            self.ctx.lib.odise_hip_track_destroy(self.ctx.h, C.c_void_p(self.handle))
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class RlePending:

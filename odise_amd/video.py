@@ -1,0 +1,142 @@
+"""A thing keeps its colour from frame to frame: `VisualizationDemo.run_on_video` (demo/demo.py:201-243) -> detectron2
+`VideoVisualizer.draw_panoptic_seg_predictions` -> `_assign_colors`, the mask-IoU path.
+
+This module holds the numpy restatement of the rule - the reference the device tracker (csrc/track.hip: odise_hip_track_frame) is held to
+byte for byte (tests/test_gpu_track.py), itself pinned to a literal sequential formulation (tests/test_track_cpu.py) - and the host twin
+of `HipVideoVisualizer.draw_panoptic_seg_predictions`.
+
+The rule (include/odise_hip.h states it in full): the instances of a frame are the thing rows that are the first row of their id, have an
+id > 0 and own a pixel, in table-row order.  Every live instance takes the first maximum of its IoU row against them (0 where the
+categories differ); if that IoU is above 0.5 and no earlier live instance chose the same new one, the new instance inherits its colour and
+the old one leaves the list, otherwise the old one loses one ttl and stays while ttl > 0.  New instances without a colour take the next
+one of a fixed pool (detectron2 draws a random one).  The live list is the frame's instances, then the surviving old ones, in order.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from .visualize import (LARGE_AREA, SMALL_AREA, _fallback_color, _row_of_id, _table, draw_labels, panoptic_overlay, segment_anchors,
+                        segment_colors)
+
+TRACK_ROW_DTYPE = np.dtype([("frame", np.int32), ("id", np.int32), ("category", np.int32), ("area", np.int32), ("ttl", np.int32),
+                            ("rgb", np.int32), ("pad0", np.int32), ("pad1", np.int32)])   # odise_track_row, 32 bytes
+assert TRACK_ROW_DTYPE.itemsize == 32
+MAX_TTL = 8                 # retained frames of the device tracker
+POOL_COLORS = 74            # detectron2 VideoVisualizer max_num_instances
+
+
+def default_pool(n: int = POOL_COLORS) -> np.ndarray:
+    return np.array([_fallback_color(k) for k in range(n)], np.uint8).reshape(n, 3)
+
+
+def frame_instances(pred_ids, segments) -> list:
+    """[(table row, id, category, bool mask)] of a frame, in table-row order."""
+    pred_ids = np.asarray(pred_ids)
+    segments = _table(segments)
+    rows = _row_of_id(segments)
+    out = []
+    for r, (i, isthing, cat) in enumerate(segments):
+        if not isthing or rows.get(int(i)) != r:
+            continue
+        mask = pred_ids == i
+        if mask.any():
+            out.append((r, int(i), int(cat), mask))
+    return out
+
+
+def pack_rgb(c) -> int:
+    return int(c[0]) | (int(c[1]) << 8) | (int(c[2]) << 16)
+
+
+def match_winners(iou) -> tuple:
+    """iou float64 [live, new] -> (choice, winner), the order-free form of the matching that the device runs: choice[o] = the first
+    maximum of row o when it is above 0.5, else -1; winner[j] = the smallest o with choice[o] == j.  Live row o is matched iff
+    winner[choice[o]] == o - exactly the rows the sequential walk matches, since a row is refused there only when an earlier row took
+    its choice."""
+    iou = np.asarray(iou, np.float64)
+    choice = [int(np.argmax(row)) if row.size and row.max() > 0.5 else -1 for row in iou]
+    winner = {}
+    for o, j in enumerate(choice):
+        if j >= 0 and j not in winner:
+            winner[j] = o
+    return choice, winner
+
+
+class ColorTracker:
+    """`assign(pred_ids, segments, colors) -> colors` per frame.  `live` is the list after the last frame (dicts with frame, id, category,
+    area, ttl, rgb, mask), `last_iou` the float64 [live before the frame, instances of the frame] matrix of the last frame."""
+
+    def __init__(self, ttl: int = MAX_TTL, pool=None):
+        if not 1 <= int(ttl) <= MAX_TTL:
+            raise ValueError(f"ttl {ttl} outside 1..{MAX_TTL}")
+        self.ttl = int(ttl)
+        self.pool = default_pool() if pool is None else np.ascontiguousarray(np.asarray(pool, np.uint8).reshape(-1, 3))
+        if len(self.pool) < 1:
+            raise ValueError("an empty colour pool")
+        self.reset()
+
+    def reset(self) -> None:
+        self.live, self.counter, self.frame, self.hw = [], 0, 0, None
+        self.last_iou = np.zeros((0, 0), np.float64)
+
+    def live_rows(self) -> np.ndarray:
+        out = np.zeros(len(self.live), TRACK_ROW_DTYPE)
+        for k, o in enumerate(self.live):
+            out[k] = (o["frame"], o["id"], o["category"], o["area"], o["ttl"], o["rgb"], 0, 0)
+        return out
+
+    def assign(self, pred_ids, segments, colors: Optional[np.ndarray] = None) -> np.ndarray:
+        """pred_ids int [H,W], segments rows (id, isthing, category), colors uint8 [n,3] (what the rows have so far; zeros when not
+        given) -> uint8 [n,3]: the rows of the frame's instances recoloured, every other row as it came."""
+        pred_ids = np.asarray(pred_ids)
+        segments = _table(segments)
+        if self.hw is None:
+            self.hw = tuple(pred_ids.shape)
+        if tuple(pred_ids.shape) != self.hw:
+            raise ValueError(f"a {pred_ids.shape} frame for a tracker of {self.hw}")
+        out = np.zeros((len(segments), 3), np.uint8) if colors is None else np.array(colors, np.uint8).reshape(len(segments), 3)
+        new = frame_instances(pred_ids, segments)
+        area = [int(m.sum()) for _, _, _, m in new]
+        iou = np.zeros((len(self.live), len(new)), np.float64)
+        for a, o in enumerate(self.live):
+            for b, (_, _, cat, mask) in enumerate(new):
+                if cat == o["category"]:
+                    inter = int((o["mask"] & mask).sum())
+                    iou[a, b] = np.float64(inter) / np.float64(o["area"] + area[b] - inter)
+        self.last_iou = iou
+        choice, winner = match_winners(iou)
+        rgb = [None] * len(new)
+        for b, a in winner.items():
+            rgb[b] = self.live[a]["rgb"]
+        survivors = []
+        for a, o in enumerate(self.live):
+            if choice[a] >= 0 and winner[choice[a]] == a:
+                continue
+            o["ttl"] -= 1
+            if o["ttl"] > 0:
+                survivors.append(o)
+        for b in range(len(new)):
+            if rgb[b] is None:
+                rgb[b] = pack_rgb(self.pool[self.counter % len(self.pool)])
+                self.counter += 1
+        fresh = []
+        for b, (r, i, cat, mask) in enumerate(new):
+            out[r] = (rgb[b] & 255, (rgb[b] >> 8) & 255, (rgb[b] >> 16) & 255)
+            fresh.append({"frame": self.frame, "id": i, "category": cat, "area": area[b], "ttl": self.ttl, "rgb": rgb[b], "mask": mask.copy()})
+        self.live = fresh + survivors
+        self.frame += 1
+        return out
+
+
+def draw_panoptic_seg_predictions(image, pred_ids, segments, tracker: ColorTracker, metadata=None, alpha256: int = 128, edge_rgb=(0, 0, 0),
+                                  small_area: int = SMALL_AREA, large_area: int = LARGE_AREA, labels: bool = True) -> np.ndarray:
+    """`draw_panoptic_seg` with the tracker's colours for things: what HipVideoVisualizer.draw_panoptic_seg_predictions returns, computed
+    by the restatement (labels=False: the picture before the names are drawn)."""
+    segments = _table(segments)
+    colors = tracker.assign(pred_ids, segments, segment_colors(segments, metadata))
+    pic = panoptic_overlay(image, pred_ids, segments, colors, alpha256, edge_rgb)
+    if not labels:
+        return pic
+    return draw_labels(pic, segment_anchors(pred_ids, segments, small_area, large_area), segments, metadata)

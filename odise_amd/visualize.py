@@ -375,3 +375,49 @@ class HipVisualizer:
         picture, anchors, order = res["out"].numpy(), res["anchors"].numpy(), res["order"].numpy()
         kept = sorted((i for i in range(n) if order[i] >= 0), key=lambda i: order[i])
         return draw_texts(picture, anchors[kept], instance_texts(classes, scores[:n], self.metadata))
+
+
+class HipVideoVisualizer(HipVisualizer):
+    """detectron2 `VideoVisualizer(metadata)` for results that are still on the device: `draw_panoptic_seg_predictions` per frame, with
+    the colours of things carried from frame to frame by the library's tracker (odise_hip_track_frame; the rule: odise_amd/video.py).
+    `draw_sem_seg` is HipVisualizer's per-picture call: semantic maps are not tracked."""
+
+    def __init__(self, ctx, metadata=None, ttl: int = 8, pool=None, **kwargs):
+        super().__init__(ctx, metadata, **kwargs)
+        self.ttl, self.pool, self.tracker = int(ttl), pool, None
+
+    def reset(self) -> None:
+        if self.tracker is not None:
+            self.tracker.reset()
+
+    def close(self) -> None:
+        if self.tracker is not None:
+            self.tracker.close()
+            self.tracker = None
+
+    def draw_panoptic_seg_predictions(self, frame_dev, record_dev, hw, labels: bool = True) -> np.ndarray:
+        """frame_dev uint8 [h,w,3] and the frame's panoptic record on the device -> host uint8 [h,w,3] (labels=False: before the names
+        are drawn).  The table travels first (its rows choose the stuff colours and the names); the map never does: the tracker, the
+        overlay and the anchors read it where it lies.  The tracker is made at the first frame's size; another size is an error."""
+        from ._lib import MAX_SEGMENTS
+        ctx = self.ctx
+        h, w = int(hw[0]), int(hw[1])
+        assert record_dev.dtype == np.int32 and int(np.prod(record_dev.shape)) >= h * w + 1 + 3 * MAX_SEGMENTS, (record_dev.shape, hw)
+        if self.tracker is None:
+            self.tracker = ctx.track_create((h, w), self.ttl, self.pool)
+        if self.tracker.hw != (h, w):
+            raise ValueError(f"a {h}x{w} frame for a tracker of {self.tracker.hw[0]}x{self.tracker.hw[1]}")
+        flat = record_dev.view((h * w + 1 + 3 * MAX_SEGMENTS,), np.int32)
+        ids, table = flat.view((h, w), np.int32), flat.view((1 + 3 * MAX_SEGMENTS,), np.int32, h * w * 4)
+        tail = table.numpy()
+        n = min(max(int(tail[0]), 0), MAX_SEGMENTS)
+        segments = tail[1:1 + 3 * n].reshape(n, 3)
+        host_colors = np.zeros((MAX_SEGMENTS, 3), np.uint8)
+        host_colors[:n] = segment_colors(segments, self.metadata)
+        colors = ctx.track_frame(self.tracker, ids, table, ctx.to_device(host_colors))
+        pic = ctx.panoptic_overlay(frame_dev, ids, table, colors, self.alpha256, self.edge_rgb)
+        if not labels:
+            return pic.numpy()
+        anchors, count = ctx.segment_anchors(ids, table, self.small_area, self.large_area, self.max_anchors)
+        picture, rows, found = pic.numpy(), anchors.numpy(), int(count.numpy()[0])
+        return draw_labels(picture, rows[:min(found, self.max_anchors)], segments, self.metadata)
