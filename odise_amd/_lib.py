@@ -10,6 +10,8 @@ import ctypes as C
 import os
 import re
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ODISE_HIP_LIB") or os.path.join(HERE, "lib", "libodise_hip.so")  # env: developer A/B builds
 HEADER_PATH = os.path.join(HERE, "..", "include", "odise_hip.h")
@@ -142,6 +144,20 @@ class TrackDesc(C.Structure):
 
 MAX_SEGMENTS = 100          # ODISE_MAX_SEGMENTS
 COMM_ID_BYTES = 128         # ODISE_COMM_ID_BYTES
+RECORD_TABLE_LEN = 1 + 3 * MAX_SEGMENTS   # the tail of a panoptic record: n | rows (id, isthing, category)
+
+
+def record_len(h: int, w: int) -> int:
+    """int32 elements of the panoptic record of an h x w picture: ids [h*w] | table [RECORD_TABLE_LEN]."""
+    return int(h) * int(w) + RECORD_TABLE_LEN
+
+
+def split_record(record, hw):
+    """A device record of at least record_len(h, w) int32 -> its two views (ids [h,w], table [RECORD_TABLE_LEN]); nothing is copied."""
+    h, w = int(hw[0]), int(hw[1])
+    assert record.dtype == np.int32 and int(np.prod(record.shape)) >= record_len(h, w), (record.shape, hw)
+    flat = record.view((record_len(h, w),), np.int32)
+    return flat.view((h, w), np.int32), flat.view((RECORD_TABLE_LEN,), np.int32, h * w * 4)
 
 
 class UnsupportedInput(RuntimeError):

@@ -11,6 +11,7 @@
 //   column_stats / panoptic_write / instance_masks
 #include "engine.h"
 #include "post_sample.h"
+#include "record.h"
 
 namespace odise {
 
@@ -754,18 +755,14 @@ __global__ void panoptic_decide_kernel(const int* __restrict__ cnt, const float*
             }
             ++current;
             mp[q] = current;
-            if (table) {
-                table[1 + 3 * n] = current;
-                table[2 + 3 * n] = thing ? 1 : 0;
-                table[3 + 3 * n] = cls;
-            }
+            if (table) record_set_row(table, n, current, thing ? 1 : 0, cls);
             ++n;
         }
     }
     if (table) {
         const int m = n < max_segments ? n : max_segments;
         table[0] = m;
-        for (int i = m; i < max_segments; ++i) table[1 + 3 * i] = table[2 + 3 * i] = table[3 + 3 * i] = 0;
+        record_zero_rows(table, m, max_segments, 0, 1);   // this thread alone
     }
 }
 

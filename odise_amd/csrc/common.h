@@ -140,6 +140,12 @@ struct odise_hip_ctx {
 };
 
 namespace odise {
+// blocks of a grid-stride kernel over `items`: enough to cover them, at most eight per compute unit, at least one
+static inline int grid_blocks(const odise_hip_ctx* ctx, int64_t items, int threads) {
+    const int64_t need = ceil_div(items, threads), most = 8 * (int64_t)ctx->cu_count;
+    return (int)(need < 1 ? 1 : (need > most ? most : need));
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a PER-DEVICE property of a kernel: remember it per (kernel instantiation, device), not per
 // process, and let any number of host threads race to set it (the call is idempotent; the bit is published after it succeeded).
 struct LdsAttrOnce {

@@ -1,5 +1,6 @@
-// lds_hist.h — the evaluators' per-block counting histogram (eval_ops.hip, pq.hip, vis_inst.hip) and the arg-max over class planes that
-// feeds it (eval_ops.hip, vis_inst.hip).
+// lds_hist.h — the per-block counting histogram (eval_ops.hip, pq.hip, track.hip, vis_inst.hip), the run of equal cells that a lane counts
+// in a register before it touches the histogram (pq.hip, track.hip), and the arg-max over class planes that feeds it (eval_ops.hip,
+// vis_inst.hip).
 //
 // A block counts `n` cells in the dynamic LDS of its launch and adds the non-zero ones to the global matrix with integer atomics when it is
 // done (deterministic: integer addition commutes); a matrix of more than kLdsHistCells cells is counted in global memory directly.  Which of
@@ -43,6 +44,27 @@ struct LdsHist {
         if (lds)
             for (int i = threadIdx.x; i < n; i += blockDim.x)
                 if (const unsigned c = cells()[i]) add_global(i, c);
+    }
+};
+
+// A run of equal cells counted in a register and added to the histogram when the cell changes.  LDS = H.lds, decided once per kernel: the
+// pixel loop is a template over it.  The bounds guard is for track.hip, whose cells come from bytes of retained maps (a byte is at most that
+// frame's row count: always inside); in pq.hip a cell is below H.n by construction and the guard costs one compare per change of pair.
+struct HistRun {
+    int cell = 0, run = 0;
+    template <bool LDS, class Cell>
+    __device__ __forceinline__ void flush(const LdsHist<Cell>& H) const {
+        if (run && (unsigned)cell < (unsigned)H.n) {
+            if (LDS) H.add_lds(cell, (unsigned)run);
+            else H.add_global(cell, (unsigned)run);
+        }
+    }
+    template <bool LDS, class Cell>
+    __device__ __forceinline__ void count(int c, const LdsHist<Cell>& H) {
+        if (c == cell) { ++run; return; }
+        flush<LDS>(H);
+        cell = c;
+        run = 1;
     }
 };
 

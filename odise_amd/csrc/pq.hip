@@ -18,6 +18,8 @@
 
 #include "common.h"
 #include "lds_hist.h"
+#include "record.h"
+#include "rgb.h"
 
 namespace odise {
 
@@ -36,38 +38,62 @@ struct PqScratch {
     int next = 0;
 };
 
-__device__ __forceinline__ int pq_clamp_n(int n) { return n < 0 ? 0 : (n > ODISE_MAX_SEGMENTS ? ODISE_MAX_SEGMENTS : n); }
-
-// slot of `id` in a table of `rows` ids with stride `stride` ints: 0 = VOID, 1 + first row holding it, rows + 1 = absent
-__device__ __forceinline__ int pq_find_slot(const int* ids, int stride, int rows, int id) {
+// slot of `id` in a table of `rows` ids: 0 = VOID (id 0 only: a negative id is looked up), 1 + first row holding it, rows + 1 = absent
+__device__ __forceinline__ int pq_find_slot(const int* ids, int rows, int id) {
     if (id == 0) return 0;
-    for (int r = 0; r < rows; ++r)
-        if (ids[r * stride] == id) return r + 1;
-    return rows + 1;
+    const int r = record_find(ids, rows, id);
+    return r < 0 ? rows + 1 : r + 1;
 }
 
+struct PqTables {   // the two id tables in LDS
+    const int* gt_ids;
+    int n_gt;
+    const int* pred_ids;
+    int n;
+};
+
 struct PqLane {
-    int last_gid, last_gslot, last_pid, last_pslot;   // the lane's last translations
-    int cell, run;                                    // the pair being counted and its length so far
+    RecordMemo gt, pred;   // the lane's last translations
+    HistRun pair;          // the pair being counted and its length so far
 };
 
 template <bool LDS>
-__device__ __forceinline__ void pq_flush_run(PqLane& L, const LdsHist<int>& H) {
-    if (L.run) {
-        if (LDS) H.add_lds(L.cell, (unsigned)L.run);
-        else H.add_global(L.cell, (unsigned)L.run);
-    }
+__device__ __forceinline__ void pq_count(PqLane& L, int gid, int pid, const PqTables& T, const LdsHist<int>& H) {
+    const int gslot = record_memo(L.gt, gid, [&](int id) { return pq_find_slot(T.gt_ids, T.n_gt, id); });
+    const int pslot = record_memo(L.pred, pid, [&](int id) { return pq_find_slot(T.pred_ids, T.n, id); });
+    L.pair.count<LDS>(gslot * (T.n + 2) + pslot, H);   // < (n_gt + 2) * (n + 2) <= kPqMatrixCells
 }
 
+// the pixels of the block, and the runs the lanes still hold
 template <bool LDS>
-__device__ __forceinline__ void pq_count(PqLane& L, int gid, int pid, const int* gt_ids, int n_gt, const int* pred_ids_tab, int n, const LdsHist<int>& H) {
-    if (gid != L.last_gid) { L.last_gid = gid; L.last_gslot = pq_find_slot(gt_ids, 1, n_gt, gid); }
-    if (pid != L.last_pid) { L.last_pid = pid; L.last_pslot = pq_find_slot(pred_ids_tab, 1, n, pid); }
-    const int cell = L.last_gslot * (n + 2) + L.last_pslot;   // < (n_gt + 2) * (n + 2) <= kPqMatrixCells
-    if (cell == L.cell) { ++L.run; return; }
-    pq_flush_run<LDS>(L, H);
-    L.cell = cell;
-    L.run = 1;
+__device__ __forceinline__ void pq_pixels(const int* __restrict__ pred, const void* __restrict__ gt, int gt_layout, int npix, int vec, const PqTables& T,
+                                          const LdsHist<int>& H) {
+    PqLane L = {{0, 0}, {0, 0}, {}};   // VOID -> slot 0 holds for both tables
+    const uint8_t* gt8 = (const uint8_t*)gt;
+    const int* gt32 = (const int*)gt;
+    const int groups = npix >> 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    if (vec) {
+        for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += stride) {
+            const int4 p = ((const int4*)pred)[q];
+            unsigned g[4];
+            if (gt_layout == 0) {
+                const unsigned* d = (const unsigned*)gt + 3 * q;   // bytes 12 q .. 12 q + 11 < 3 npix
+                rgb4_unpack(d[0], d[1], d[2], g);
+            } else {
+                const uint4 v = ((const uint4*)gt)[q];
+                g[0] = v.x; g[1] = v.y; g[2] = v.z; g[3] = v.w;
+            }
+            pq_count<LDS>(L, (int)g[0], p.x, T, H);
+            pq_count<LDS>(L, (int)g[1], p.y, T, H);
+            pq_count<LDS>(L, (int)g[2], p.z, T, H);
+            pq_count<LDS>(L, (int)g[3], p.w, T, H);
+        }
+    }
+    // pixel by pixel: everything when the buffers are not aligned, else the last npix & 3 pixels
+    for (int64_t i = (vec ? (int64_t)groups * 4 : 0) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride)
+        pq_count<LDS>(L, gt_layout == 0 ? (int)rgb_load(gt8 + 3 * i) : gt32[i], pred[i], T, H);
+    L.pair.flush<LDS>(H);
 }
 
 // matrix[(n_gt + 2) x (n + 2)] += pair counts of the picture.  vec != 0: pred 16-byte aligned and gt dword aligned (groups of 4 pixels are
@@ -77,60 +103,16 @@ __global__ void __launch_bounds__(256) pq_pixel_kernel(const int* __restrict__ p
                                                       int* __restrict__ matrix) {
     __shared__ int gt_ids[kPqMaxGt];
     __shared__ int pred_tab[ODISE_MAX_SEGMENTS];
-    const int n = pq_clamp_n(pred_segments[0]);
+    const int n = record_rows(pred_segments);
     const int cells = (n_gt + 2) * (n + 2);
     const LdsHist<int> H(matrix, cells, cells <= lds_cells);
     for (int i = threadIdx.x; i < n_gt; i += blockDim.x) gt_ids[i] = gt_table[4 * i];
-    for (int i = threadIdx.x; i < n; i += blockDim.x) pred_tab[i] = pred_segments[1 + 3 * i];
+    record_load(pred_segments, n, pred_tab);
+    const PqTables T = {gt_ids, n_gt, pred_tab, n};
     H.clear();
     __syncthreads();
-
-    PqLane L;
-    L.last_gid = 0; L.last_gslot = 0; L.last_pid = 0; L.last_pslot = 0;   // VOID -> slot 0 holds for both tables
-    L.cell = 0; L.run = 0;
-    const uint8_t* gt8 = (const uint8_t*)gt;
-    const int* gt32 = (const int*)gt;
-    const int groups = npix >> 2;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    if (vec) {
-        for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += stride) {
-            const int4 p = ((const int4*)pred)[q];
-            int g0, g1, g2, g3;
-            if (gt_layout == 0) {
-                const unsigned* d = (const unsigned*)gt + 3 * q;   // bytes 12 q .. 12 q + 11 < 3 npix
-                const unsigned d0 = d[0], d1 = d[1], d2 = d[2];
-                g0 = (int)(d0 & 0xffffffu);
-                g1 = (int)((d0 >> 24) | ((d1 & 0xffffu) << 8));
-                g2 = (int)((d1 >> 16) | ((d2 & 0xffu) << 16));
-                g3 = (int)(d2 >> 8);
-            } else {
-                const int4 g = ((const int4*)gt)[q];
-                g0 = g.x; g1 = g.y; g2 = g.z; g3 = g.w;
-            }
-            if (H.lds) {
-                pq_count<true>(L, g0, p.x, gt_ids, n_gt, pred_tab, n, H);
-                pq_count<true>(L, g1, p.y, gt_ids, n_gt, pred_tab, n, H);
-                pq_count<true>(L, g2, p.z, gt_ids, n_gt, pred_tab, n, H);
-                pq_count<true>(L, g3, p.w, gt_ids, n_gt, pred_tab, n, H);
-            } else {
-                pq_count<false>(L, g0, p.x, gt_ids, n_gt, pred_tab, n, H);
-                pq_count<false>(L, g1, p.y, gt_ids, n_gt, pred_tab, n, H);
-                pq_count<false>(L, g2, p.z, gt_ids, n_gt, pred_tab, n, H);
-                pq_count<false>(L, g3, p.w, gt_ids, n_gt, pred_tab, n, H);
-            }
-        }
-    }
-    // pixel by pixel: everything when the buffers are not aligned, else the last npix & 3 pixels
-    for (int64_t i = (vec ? (int64_t)groups * 4 : 0) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride) {
-        const int pid = pred[i];
-        int gid;
-        if (gt_layout == 0) gid = (int)gt8[3 * i] | ((int)gt8[3 * i + 1] << 8) | ((int)gt8[3 * i + 2] << 16);
-        else gid = gt32[i];
-        if (H.lds) pq_count<true>(L, gid, pid, gt_ids, n_gt, pred_tab, n, H);
-        else pq_count<false>(L, gid, pid, gt_ids, n_gt, pred_tab, n, H);
-    }
-    if (H.lds) pq_flush_run<true>(L, H);
-    else pq_flush_run<false>(L, H);
+    if (H.lds) pq_pixels<true>(pred, gt, gt_layout, npix, vec, T, H);
+    else pq_pixels<false>(pred, gt, gt_layout, npix, vec, T, H);
     __syncthreads();
     H.flush();
 }
@@ -156,14 +138,14 @@ __global__ void __launch_bounds__(kPqMatchThreads) pq_match_kernel(int* __restri
     __shared__ int p_area[kPqPredSlots], p_void[kPqPredSlots];
     __shared__ int bad;
     const int tid = threadIdx.x, nt = blockDim.x;
-    const int n = pq_clamp_n(pred_segments[0]);
+    const int n = record_rows(pred_segments);
     const int W = n + 2, cells = (n_gt + 2) * W;
     if (tid == 0) bad = 0;
     for (int i = tid; i < n_gt; i += nt) {
         g_id[i] = gt_table[4 * i]; g_cat[i] = gt_table[4 * i + 1]; g_crowd[i] = gt_table[4 * i + 2]; g_area[i] = gt_table[4 * i + 3];
         g_cnt[i] = 0; g_first[i] = -1; g_iou[i] = 0.0;
     }
-    for (int i = tid; i < n; i += nt) { p_id[i] = pred_segments[1 + 3 * i]; p_cat[i] = pred_segments[3 + 3 * i]; p_matched[i] = 0; }
+    for (int i = tid; i < n; i += nt) { p_id[i] = record_id(pred_segments, i); p_cat[i] = record_category(pred_segments, i); p_matched[i] = 0; }
     for (int p = tid; p < W; p += nt) {               // pred areas = column sums
         int a = 0;
         for (int g = 0; g < n_gt + 2; ++g) a += matrix[g * W + p];
@@ -327,7 +309,7 @@ extern "C" int odise_hip_panoptic_quality(odise_hip_ctx* ctx, const odise_pq_des
     const int npix = d->H * d->W;
     const int vec = ((uintptr_t)d->pred_ids & 15) == 0 && ((uintptr_t)d->gt & (d->gt_layout == 0 ? 3 : 15)) == 0;
     const int lds_cells = std::min((d->n_gt + 2) * kPqPredSlots, kLdsHistCells);   // n is read on the device: room for the most it can be
-    const int blocks = (int)std::min<int64_t>(ceil_div(ceil_div(npix, 4), 256), 8 * ctx->cu_count);
+    const int blocks = grid_blocks(ctx, ceil_div(npix, 4), 256);
     hipLaunchKernelGGL(pq_pixel_kernel, dim3(blocks), dim3(256), (size_t)lds_cells * sizeof(unsigned), ctx->stream, (const int*)d->pred_ids,
                        (const int*)d->pred_segments, d->gt, d->gt_layout, (const int*)s->gt_table, d->n_gt, npix, vec, lds_cells, s->matrix);
     ODISE_CHECK_HIP(hipGetLastError());

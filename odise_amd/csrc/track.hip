@@ -16,6 +16,8 @@
 
 #include "common.h"
 #include "lds_hist.h"
+#include "record.h"
+#include "rgb.h"
 #include "vis_scan.h"
 
 namespace odise {
@@ -60,12 +62,11 @@ __device__ __forceinline__ int track_clamp(int v, int hi) { return v < 0 ? 0 : (
 
 // tab[i] = id of table row i when the row can be an instance (a thing, id > 0, the first row of its id), else 0.  Whole block; no barrier.
 __device__ __forceinline__ void track_load_table(const int* __restrict__ seg, int n, int* tab) {
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-        const int id = seg[1 + 3 * i];
-        bool first = id > 0 && seg[2 + 3 * i] != 0;
-        for (int r = 0; r < i && first; ++r) first = seg[1 + 3 * r] != id;
-        tab[i] = first ? id : 0;
-    }
+    record_load(seg, n, tab, nullptr, kRecordIsThing, [seg](int i, int id) {
+        bool first = id > 0 && record_isthing(seg, i) != 0;
+        for (int r = 0; r < i && first; ++r) first = record_id(seg, r) != id;
+        return first ? id : 0;
+    });
 }
 
 // Whole block: `active` is scratch, `L` the result; both are published by the barriers in here.
@@ -93,37 +94,16 @@ __device__ __forceinline__ void track_layout(const TrackState* __restrict__ st, 
     __syncthreads();
 }
 
-__device__ __forceinline__ int track_find(const int* tab, int n, int id) {
-    if (id <= 0) return 0;
-    for (int r = 0; r < n; ++r)
-        if (tab[r] == id) return r + 1;
-    return 0;
-}
+// 1 + the row of the filtered table that holds `id`; 0 = no instance (id <= 0, or no such row)
+__device__ __forceinline__ int track_find(const int* tab, int n, int id) { return id <= 0 ? 0 : record_find(tab, n, id) + 1; }
 
 struct TrackLane {
-    int last_id, last_j;                       // the lane's last translation
-    int cell[kTrackRing], run[kTrackRing];     // per pass: the pair being counted and its length so far (registers: the loops are unrolled)
+    RecordMemo last;             // the lane's last translation
+    HistRun pair[kTrackRing];    // per pass: the pair being counted and its length so far (registers: the loops are unrolled)
 };
 
-template <bool LDS>
-__device__ __forceinline__ void track_flush_run(int cell, int run, const LdsHist<int>& H) {
-    if (run && (unsigned)cell < (unsigned)H.n) {   // a byte of a retained map is at most that frame's row count: always inside
-        if (LDS) H.add_lds(cell, (unsigned)run);
-        else H.add_global(cell, (unsigned)run);
-    }
-}
-
-template <bool LDS>
-__device__ __forceinline__ void track_count(TrackLane& T, int k, int cell, const LdsHist<int>& H) {
-    if (cell == T.cell[k]) { ++T.run[k]; return; }
-    track_flush_run<LDS>(T.cell[k], T.run[k], H);
-    T.cell[k] = cell;
-    T.run[k] = 1;
-}
-
 __device__ __forceinline__ int track_translate(TrackLane& T, const int* tab, int n, int id) {
-    if (id != T.last_id) { T.last_id = id; T.last_j = track_find(tab, n, id); }
-    return T.last_j;
+    return record_memo(T.last, id, [&](int v) { return track_find(tab, n, v); });
 }
 
 // four pixels of group q (bytes 4 q .. 4 q + 3 of every map; the maps are 16-byte aligned)
@@ -138,10 +118,10 @@ __device__ __forceinline__ void track_group(TrackLane& T, const TrackLayout& L, 
         const unsigned o = s >= 0 ? ((const unsigned*)(maps + (int64_t)s * map_stride))[q] : 0u;
         const int base = L.off[k];
         const int o0 = (int)(o & 255u), o1 = (int)((o >> 8) & 255u), o2 = (int)((o >> 16) & 255u), o3 = (int)(o >> 24);
-        if (o0 | j0) track_count<LDS>(T, k, base + o0 * w + j0, H);   // the (nothing, nothing) pair is not needed
-        if (o1 | j1) track_count<LDS>(T, k, base + o1 * w + j1, H);
-        if (o2 | j2) track_count<LDS>(T, k, base + o2 * w + j2, H);
-        if (o3 | j3) track_count<LDS>(T, k, base + o3 * w + j3, H);
+        if (o0 | j0) T.pair[k].count<LDS>(base + o0 * w + j0, H);   // the (nothing, nothing) pair is not needed
+        if (o1 | j1) T.pair[k].count<LDS>(base + o1 * w + j1, H);
+        if (o2 | j2) T.pair[k].count<LDS>(base + o2 * w + j2, H);
+        if (o3 | j3) T.pair[k].count<LDS>(base + o3 * w + j3, H);
     }
     ((unsigned*)(maps + (int64_t)new_slot * map_stride))[q] = (unsigned)j0 | ((unsigned)j1 << 8) | ((unsigned)j2 << 16) | ((unsigned)j3 << 24);
 }
@@ -155,9 +135,30 @@ __device__ __forceinline__ void track_pixel(TrackLane& T, const TrackLayout& L, 
         if (k >= L.passes) break;
         const int s = L.slot[k];
         const int o = s >= 0 ? (int)maps[(int64_t)s * map_stride + i] : 0;
-        if (o | j) track_count<LDS>(T, k, L.off[k] + o * w + j, H);
+        if (o | j) T.pair[k].count<LDS>(L.off[k] + o * w + j, H);
     }
     maps[(int64_t)new_slot * map_stride + i] = (uint8_t)j;
+}
+
+// the pixels of the block, and the runs the lanes still hold
+template <bool LDS>
+__device__ __forceinline__ void track_pixels(const int* __restrict__ pred, const int* tab, int n, const TrackLayout& L, uint8_t* maps, int64_t map_stride,
+                                             int new_slot, int npix, int vec, const LdsHist<int>& H) {
+    TrackLane T = {{0, 0}, {}};   // VOID is no instance
+    const int groups = npix >> 2;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    if (vec) {
+        for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += stride) {
+            const int4 p = ((const int4*)pred)[q];
+            const int j0 = track_translate(T, tab, n, p.x), j1 = track_translate(T, tab, n, p.y);
+            const int j2 = track_translate(T, tab, n, p.z), j3 = track_translate(T, tab, n, p.w);
+            track_group<LDS>(T, L, maps, map_stride, new_slot, q, j0, j1, j2, j3, H);
+        }
+    }
+    for (int64_t i = (vec ? (int64_t)groups * 4 : 0) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride)
+        track_pixel<LDS>(T, L, maps, map_stride, new_slot, i, track_translate(T, tab, n, pred[i]), H);
+#pragma unroll
+    for (int k = 0; k < kTrackRing; ++k) T.pair[k].flush<LDS>(H);
 }
 
 // matrix += the pair counts of the frame; maps[frame & 7] = the frame's byte map.  vec != 0: pred is 16-byte aligned (groups of four pixels
@@ -169,39 +170,15 @@ __global__ void __launch_bounds__(256) track_pixel_kernel(const int* __restrict_
     __shared__ int tab[ODISE_MAX_SEGMENTS];
     __shared__ int active[kTrackRing];
     __shared__ TrackLayout L;
-    const int n = track_clamp(pred_segments[0], ODISE_MAX_SEGMENTS);
+    const int n = record_rows(pred_segments);
     track_load_table(pred_segments, n, tab);
     track_layout(st, n, active, &L);
     const LdsHist<int> H(matrix, L.cells, L.cells <= lds_cells);
     H.clear();
     __syncthreads();
-
     const int new_slot = st->frame & (kTrackRing - 1);
-    TrackLane T;
-    T.last_id = 0; T.last_j = 0;
-#pragma unroll
-    for (int k = 0; k < kTrackRing; ++k) { T.cell[k] = 0; T.run[k] = 0; }
-    const int groups = npix >> 2;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    if (vec) {
-        for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += stride) {
-            const int4 p = ((const int4*)pred)[q];
-            const int j0 = track_translate(T, tab, n, p.x), j1 = track_translate(T, tab, n, p.y);
-            const int j2 = track_translate(T, tab, n, p.z), j3 = track_translate(T, tab, n, p.w);
-            if (H.lds) track_group<true>(T, L, maps, map_stride, new_slot, q, j0, j1, j2, j3, H);
-            else track_group<false>(T, L, maps, map_stride, new_slot, q, j0, j1, j2, j3, H);
-        }
-    }
-    for (int64_t i = (vec ? (int64_t)groups * 4 : 0) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride) {
-        const int j = track_translate(T, tab, n, pred[i]);
-        if (H.lds) track_pixel<true>(T, L, maps, map_stride, new_slot, i, j, H);
-        else track_pixel<false>(T, L, maps, map_stride, new_slot, i, j, H);
-    }
-#pragma unroll
-    for (int k = 0; k < kTrackRing; ++k) {
-        if (H.lds) track_flush_run<true>(T.cell[k], T.run[k], H);
-        else track_flush_run<false>(T.cell[k], T.run[k], H);
-    }
+    if (H.lds) track_pixels<true>(pred, tab, n, L, maps, map_stride, new_slot, npix, vec, H);
+    else track_pixels<false>(pred, tab, n, L, maps, map_stride, new_slot, npix, vec, H);
     __syncthreads();
     H.flush();
 }
@@ -222,7 +199,7 @@ __global__ void __launch_bounds__(kTrackMatchThreads) track_match_kernel(int* __
     __shared__ int wave_sum[kTrackMatchThreads / 64];
     __shared__ int n_inst, n_new;
     const int tid = threadIdx.x;
-    const int n = track_clamp(pred_segments[0], ODISE_MAX_SEGMENTS);
+    const int n = record_rows(pred_segments);
     const int n_live = track_clamp(st->n_live, kTrackLiveCap), frame = st->frame, counter = st->counter;
     track_load_table(pred_segments, n, tab);
     track_layout(st, n, active, &L);   // its barriers also order the reads of st->frame / n_live / counter above before anything is written
@@ -236,7 +213,7 @@ __global__ void __launch_bounds__(kTrackMatchThreads) track_match_kernel(int* __
             for (int o = 0; o < rows; ++o) a += matrix[L.off[0] + o * w + tid + 1];
         }
         area[tid] = a;
-        cat[tid] = pred_segments[3 + 3 * tid];
+        cat[tid] = record_category(pred_segments, tid);
         winner[tid] = INT32_MAX;
     }
     __syncthreads();
@@ -278,13 +255,8 @@ __global__ void __launch_bounds__(kTrackMatchThreads) track_match_kernel(int* __
     }
     __syncthreads();
     if (tid < n && rank[tid] >= 0) {
-        if (urank[tid] >= 0) {
-            const uint8_t* c = pool + 3 * ((counter + urank[tid]) % n_pool);
-            rgb[tid] = (int)c[0] | ((int)c[1] << 8) | ((int)c[2] << 16);
-        }
-        colors[3 * tid] = (uint8_t)(rgb[tid] & 255);
-        colors[3 * tid + 1] = (uint8_t)((rgb[tid] >> 8) & 255);
-        colors[3 * tid + 2] = (uint8_t)((rgb[tid] >> 16) & 255);
+        if (urank[tid] >= 0) rgb[tid] = (int)rgb_load(pool + 3 * ((counter + urank[tid]) % n_pool));
+        rgb_store(colors + 3 * tid, (unsigned)rgb[tid]);
     }
 
     // the survivors keep their order behind the new instances: an exclusive block scan of the keep flags
@@ -425,7 +397,7 @@ extern "C" int odise_hip_track_frame(odise_hip_ctx* ctx, const odise_track_desc*
     const int npix = d->H * d->W;
     const int vec = ((uintptr_t)d->pred_ids & 15) == 0;
     const int lds_cells = kLdsHistCells;   // the tables are read on the device: room for the most the histogram holds
-    const int blocks = (int)std::min<int64_t>(ceil_div(ceil_div(npix, 4), 256), 8 * ctx->cu_count);
+    const int blocks = grid_blocks(ctx, ceil_div(npix, 4), 256);
     hipLaunchKernelGGL(track_pixel_kernel, dim3(blocks), dim3(256), lds_hist_bytes(lds_cells), ctx->stream, (const int*)d->pred_ids,
                        (const int*)d->pred_segments, (const TrackState*)t->state, t->maps, t->map_stride, npix, vec, lds_cells, t->matrix);
     ODISE_CHECK_HIP(hipGetLastError());

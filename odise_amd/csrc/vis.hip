@@ -22,15 +22,15 @@
 #include <algorithm>
 
 #include "common.h"
-#include "vis_scan.h"   // vis_scan_middle, vis_check_size: shared with vis_inst.hip
+#include "record.h"     // the table of the record: rows, loader, search, a lane's last translation
+#include "rgb.h"        // packed pixels and the blend: shared with vis_inst.hip
+#include "vis_scan.h"   // vis_scan_middle, vis_anchor_row, vis_check_size: shared with vis_inst.hip
 
 namespace odise {
 
 constexpr int kCcTile = 32;                       // tile side
 constexpr int kCcTilePix = kCcTile * kCcTile;
 constexpr int kVisThreads = 256;
-
-__device__ __forceinline__ int vis_clamp_n(int n) { return n < 0 ? 0 : (n > ODISE_MAX_SEGMENTS ? ODISE_MAX_SEGMENTS : n); }
 
 template <bool LDS>
 __device__ __forceinline__ int cc_load(const int* p) {
@@ -137,17 +137,15 @@ __global__ void __launch_bounds__(kVisThreads) cc_flatten_kernel(int npix, int* 
     }
 }
 
-static int vis_blocks(odise_hip_ctx* ctx, int64_t items) { return (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(items, kVisThreads), 8 * ctx->cu_count)); }
-
 static int cc_enqueue(odise_hip_ctx* ctx, const int* labels, int H, int W, int* roots) {
     const int ntx = (int)ceil_div(W, kCcTile), nty = (int)ceil_div(H, kCcTile);
     hipLaunchKernelGGL(cc_tile_kernel, dim3(ntx * nty), dim3(kVisThreads), 0, ctx->stream, labels, H, W, ntx, roots);
     ODISE_CHECK_HIP(hipGetLastError());
     const int64_t n_vert = (int64_t)(ntx - 1) * H, n_all = n_vert + (int64_t)(nty - 1) * W;
     if (n_all > 0) {
-        hipLaunchKernelGGL(cc_merge_kernel, dim3(vis_blocks(ctx, n_all)), dim3(kVisThreads), 0, ctx->stream, labels, H, W, n_vert, n_all, roots);
+        hipLaunchKernelGGL(cc_merge_kernel, dim3(grid_blocks(ctx, n_all, kVisThreads)), dim3(kVisThreads), 0, ctx->stream, labels, H, W, n_vert, n_all, roots);
         ODISE_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(cc_flatten_kernel, dim3(vis_blocks(ctx, (int64_t)H * W)), dim3(kVisThreads), 0, ctx->stream, H * W, roots);
+        hipLaunchKernelGGL(cc_flatten_kernel, dim3(grid_blocks(ctx, (int64_t)H * W, kVisThreads)), dim3(kVisThreads), 0, ctx->stream, H * W, roots);
         ODISE_CHECK_HIP(hipGetLastError());
     }
     return ODISE_OK;
@@ -164,25 +162,13 @@ struct VisState {                                        // zeroed at the start 
 };
 static_assert(sizeof(VisState) % 16 == 0, "the state is cleared together with the histograms behind it");
 
-struct VisTable {
+struct VisTable {   // the n rows of the record, by record_load
     int id[ODISE_MAX_SEGMENTS];
     int thing[ODISE_MAX_SEGMENTS];
-    int n;
 };
 
-__device__ __forceinline__ void vis_load_table(VisTable& T, const int* __restrict__ seg) {   // followed by the caller's __syncthreads()
-    const int n = vis_clamp_n(seg[0]);
-    for (int i = threadIdx.x; i < n; i += blockDim.x) { T.id[i] = seg[1 + 3 * i]; T.thing[i] = seg[2 + 3 * i]; }
-    if (threadIdx.x == 0) T.n = n;
-}
-
 // the first row that holds `id`; -1 for VOID (id <= 0) and for an id without a row
-__device__ __forceinline__ int vis_row(const VisTable& T, int id) {
-    if (id <= 0) return -1;
-    for (int r = 0; r < T.n; ++r)
-        if (T.id[r] == id) return r;
-    return -1;
-}
+__device__ __forceinline__ int vis_row(const VisTable& T, int n, int id) { return id <= 0 ? -1 : record_find(T.id, n, id); }
 
 // area[root] = pixels of the component.  A wave whose 64 pixels lie in one component adds once.
 __global__ void __launch_bounds__(kVisThreads) vis_area_kernel(const int* __restrict__ roots, int npix, int* __restrict__ area) {
@@ -203,12 +189,13 @@ __global__ void __launch_bounds__(kVisThreads) vis_area_kernel(const int* __rest
 __global__ void __launch_bounds__(kVisThreads) vis_root_kernel(const int* __restrict__ ids, const int* __restrict__ seg, const int* __restrict__ roots,
                                                               const int* __restrict__ area, int npix, VisState* __restrict__ st) {
     __shared__ VisTable T;
-    vis_load_table(T, seg);
+    const int n = record_rows(seg);
+    record_load(seg, n, T.id, T.thing);
     __syncthreads();
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += stride) {
         if (roots[p] != (int)p) continue;
-        const int s = vis_row(T, ids[p]);
+        const int s = vis_row(T, n, ids[p]);
         if (s < 0) continue;
         if (T.thing[s]) atomicAdd(&st->seg_area[s], area[p]);
         else atomicMax(&st->best[s], ((unsigned long long)(unsigned)area[p] << 32) | (unsigned)(0x7fffffff - (int)p));
@@ -220,14 +207,15 @@ __global__ void __launch_bounds__(kVisThreads) vis_select_kernel(const int* __re
                                                                 const int* __restrict__ area, int npix, int small_area, int large_area,
                                                                 VisState* __restrict__ st, int4* __restrict__ list, int list_cap) {
     __shared__ VisTable T;
-    vis_load_table(T, seg);
+    const int n = record_rows(seg);
+    record_load(seg, n, T.id, T.thing);
     __syncthreads();
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x, total = (int64_t)npix + T.n;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, total = (int64_t)npix + n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
         int4 e;
         if (i < npix) {
             if (roots[i] != (int)i) continue;
-            const int s = vis_row(T, ids[i]);
+            const int s = vis_row(T, n, ids[i]);
             if (s < 0 || T.thing[s]) continue;
             const unsigned long long b = st->best[s];
             const int best_area = (int)(b >> 32), best_root = 0x7fffffff - (int)(unsigned)b;
@@ -259,13 +247,9 @@ __global__ void __launch_bounds__(kVisThreads) vis_rank_kernel(const int* __rest
             const int4 f = list[j];
             rank += ((((unsigned long long)(unsigned)f.x << 32) | (unsigned)f.y) < key) ? 1 : 0;
         }
-        if (seg[2 + 3 * e.x]) st->thing_anchor[e.x] = rank + 1;
+        if (record_isthing(seg, e.x)) st->thing_anchor[e.x] = rank + 1;
         else area[e.y] = ~rank;
-        if (rank < cap) {
-            odise_anchor_row r;
-            r.segment_row = e.x; r.area = e.z; r.x2 = 0; r.y2 = 0; r.x0 = 0; r.y0 = 0; r.x1 = 0; r.y1 = 0;
-            anchors[rank] = r;
-        }
+        if (rank < cap) anchors[rank] = vis_anchor_row(e.x, e.z);
     }
     if (blockIdx.x == 0 && threadIdx.x == 0) *n_anchors = cnt;
 }
@@ -276,19 +260,19 @@ __global__ void __launch_bounds__(kVisThreads) vis_hist_kernel(const int* __rest
                                                               const int* __restrict__ area, const VisState* __restrict__ st, int H, int W, int hcap,
                                                               int* __restrict__ hist) {
     __shared__ VisTable T;
-    vis_load_table(T, seg);
+    const int n = record_rows(seg);
+    record_load(seg, n, T.id, T.thing);
     __syncthreads();
     const int lane = threadIdx.x & 63, npix = H * W;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, bins = (int64_t)W + H;
-    int last_id = 0, last_row = -1;
+    RecordMemo M = {0, -1};   // VOID has no row
     for (int64_t base = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63); base < npix; base += stride) {   // wave-uniform
         const int64_t p = base + lane;
         int a = -1, x = 0, y = -1;
         if (p < npix) {
-            const int id = ids[p];
-            if (id != last_id) { last_id = id; last_row = vis_row(T, id); }
-            if (last_row >= 0) {
-                if (T.thing[last_row]) a = st->thing_anchor[last_row] - 1;
+            const int row = record_memo(M, ids[p], [&](int id) { return vis_row(T, n, id); });
+            if (row >= 0) {
+                if (T.thing[row]) a = st->thing_anchor[row] - 1;
                 else { const int v = area[roots[p]]; a = v < 0 ? ~v : -1; }
                 if (a >= hcap) a = -1;
             }
@@ -328,25 +312,17 @@ static int64_t vis_list_cap(int64_t npix, int large_area) { return ODISE_MAX_SEG
 
 struct OverlayTable {
     VisTable T;
-    uint8_t color[3 * ODISE_MAX_SEGMENTS];
+    unsigned crb[ODISE_MAX_SEGMENTS], cg[ODISE_MAX_SEGMENTS];   // the colour of a row as blend_rgb takes it
 };
 
-struct OverlayLane { int last_id, last_row; };
-
 // the pixel p = y * W + x with the bytes `in` (r | g << 8 | b << 16)
-__device__ __forceinline__ unsigned overlay_pixel(const OverlayTable& S, OverlayLane& L, const int* __restrict__ ids, int H, int W, int p, int x, int y,
-                                                  unsigned in, int alpha, unsigned edge) {
+__device__ __forceinline__ unsigned overlay_pixel(const OverlayTable& S, int n, RecordMemo& M, const int* __restrict__ ids, int H, int W, int p, int x,
+                                                  int y, unsigned in, int alpha, unsigned edge) {
     const int id = ids[p];
-    if (id != L.last_id) { L.last_id = id; L.last_row = vis_row(S.T, id); }
-    const int s = L.last_row;
+    const int s = record_memo(M, id, [&](int v) { return vis_row(S.T, n, v); });
     if (s < 0) return in;
     if ((x > 0 && ids[p - 1] != id) || (x < W - 1 && ids[p + 1] != id) || (y > 0 && ids[p - W] != id) || (y < H - 1 && ids[p + W] != id)) return edge;
-    unsigned o = 0;
-    for (int c = 0; c < 3; ++c) {
-        const unsigned v = (in >> (8 * c)) & 0xffu;
-        o |= ((v * (unsigned)(256 - alpha) + (unsigned)S.color[3 * s + c] * (unsigned)alpha + 128u) >> 8) << (8 * c);   // <= 255
-    }
-    return o;
+    return blend_rgb(in, (unsigned)(256 - alpha), S.crb[s], S.cg[s]);
 }
 
 // vec != 0: image and out are 4-byte aligned and groups of four pixels travel as three dwords.  A lane reads its own pixels before it
@@ -355,36 +331,28 @@ __global__ void __launch_bounds__(kVisThreads) overlay_kernel(const uint8_t* ima
                                                              const uint8_t* __restrict__ colors, int H, int W, int alpha, unsigned edge, int vec,
                                                              uint8_t* out) {
     __shared__ OverlayTable S;
-    vis_load_table(S.T, seg);
-    {
-        const int n = vis_clamp_n(seg[0]);
-        for (int i = threadIdx.x; i < 3 * n; i += blockDim.x) S.color[i] = colors[i];
-    }
+    const int n = record_rows(seg);
+    record_load(seg, n, S.T.id, S.T.thing);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) blend_color(rgb_load(colors + 3 * i), (unsigned)alpha, S.crb[i], S.cg[i]);
     __syncthreads();
-    OverlayLane L;
-    L.last_id = 0; L.last_row = -1;
+    RecordMemo M = {0, -1};   // VOID has no row
     const int npix = H * W, groups = vec ? npix >> 2 : 0;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < groups; q += stride) {
         const unsigned* src = (const unsigned*)image + 3 * q;    // bytes 12 q .. 12 q + 11 < 3 npix
-        const unsigned d0 = src[0], d1 = src[1], d2 = src[2];
-        unsigned px[4] = {d0 & 0xffffffu, (d0 >> 24) | ((d1 & 0xffffu) << 8), (d1 >> 16) | ((d2 & 0xffu) << 16), d2 >> 8};
+        unsigned px[4];
+        rgb4_unpack(src[0], src[1], src[2], px);
         const int p0 = (int)(4 * q);
         int y = p0 / W, x = p0 - y * W;
         for (int k = 0; k < 4; ++k) {
-            px[k] = overlay_pixel(S, L, ids, H, W, p0 + k, x, y, px[k], alpha, edge);
+            px[k] = overlay_pixel(S, n, M, ids, H, W, p0 + k, x, y, px[k], alpha, edge);
             if (++x == W) { x = 0; ++y; }
         }
-        unsigned* dst = (unsigned*)out + 3 * q;
-        dst[0] = px[0] | (px[1] << 24);
-        dst[1] = (px[1] >> 8) | (px[2] << 16);
-        dst[2] = (px[2] >> 16) | (px[3] << 8);
+        rgb4_pack(px, (unsigned*)out + 3 * q);
     }
     for (int64_t i = (int64_t)groups * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += stride) {
         const int p = (int)i, y = p / W, x = p - y * W;
-        const unsigned in = (unsigned)image[3 * i] | ((unsigned)image[3 * i + 1] << 8) | ((unsigned)image[3 * i + 2] << 16);
-        const unsigned o = overlay_pixel(S, L, ids, H, W, p, x, y, in, alpha, edge);
-        out[3 * i] = (uint8_t)o; out[3 * i + 1] = (uint8_t)(o >> 8); out[3 * i + 2] = (uint8_t)(o >> 16);
+        rgb_store(out + 3 * i, overlay_pixel(S, n, M, ids, H, W, p, x, y, rgb_load(image + 3 * i), alpha, edge));
     }
 }
 
@@ -428,15 +396,15 @@ extern "C" int odise_hip_segment_anchors(odise_hip_ctx* ctx, const odise_anchor_
     const int* seg = (const int*)d->pred_segments;
     ODISE_CHECK_HIP(hipMemsetAsync(base, 0, clear_b, ctx->stream));
     ODISE_TRY(cc_enqueue(ctx, ids, H, W, roots));
-    const int pb = vis_blocks(ctx, npix);
+    const int pb = grid_blocks(ctx, npix, kVisThreads);
     hipLaunchKernelGGL(vis_area_kernel, dim3(pb), dim3(kVisThreads), 0, ctx->stream, (const int*)roots, npix, area);
     ODISE_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(vis_root_kernel, dim3(pb), dim3(kVisThreads), 0, ctx->stream, ids, seg, (const int*)roots, (const int*)area, npix, st);
     ODISE_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(vis_select_kernel, dim3(vis_blocks(ctx, (int64_t)npix + ODISE_MAX_SEGMENTS)), dim3(kVisThreads), 0, ctx->stream, ids, seg,
+    hipLaunchKernelGGL(vis_select_kernel, dim3(grid_blocks(ctx, (int64_t)npix + ODISE_MAX_SEGMENTS, kVisThreads)), dim3(kVisThreads), 0, ctx->stream, ids, seg,
                        (const int*)roots, (const int*)area, npix, d->small_area, d->large_area, st, list, list_cap);
     ODISE_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(vis_rank_kernel, dim3(vis_blocks(ctx, list_cap)), dim3(kVisThreads), 0, ctx->stream, seg, st, (const int4*)list, list_cap, area,
+    hipLaunchKernelGGL(vis_rank_kernel, dim3(grid_blocks(ctx, list_cap, kVisThreads)), dim3(kVisThreads), 0, ctx->stream, seg, st, (const int4*)list, list_cap, area,
                        d->anchors, d->cap, (int*)d->n_anchors);
     ODISE_CHECK_HIP(hipGetLastError());
     if (hcap > 0) {
@@ -461,7 +429,7 @@ extern "C" int odise_hip_panoptic_overlay(odise_hip_ctx* ctx, const odise_overla
     const int npix = d->H * d->W;
     const int vec = (((uintptr_t)d->image | (uintptr_t)d->out) & 3) == 0;
     const unsigned edge = (unsigned)d->edge_rgb[0] | ((unsigned)d->edge_rgb[1] << 8) | ((unsigned)d->edge_rgb[2] << 16);
-    hipLaunchKernelGGL(overlay_kernel, dim3(vis_blocks(ctx, ceil_div(npix, 4))), dim3(kVisThreads), 0, ctx->stream, (const uint8_t*)d->image,
+    hipLaunchKernelGGL(overlay_kernel, dim3(grid_blocks(ctx, ceil_div(npix, 4), kVisThreads)), dim3(kVisThreads), 0, ctx->stream, (const uint8_t*)d->image,
                        (const int*)d->pred_ids, (const int*)d->pred_segments, (const uint8_t*)d->colors, d->H, d->W, d->alpha256, edge, vec,
                        (uint8_t*)d->out);
     ODISE_CHECK_HIP(hipGetLastError());

@@ -24,6 +24,8 @@
 #include <algorithm>
 
 #include "lds_hist.h"
+#include "record.h"
+#include "rgb.h"
 #include "rle_pack.h"
 #include "vis_scan.h"
 
@@ -98,11 +100,7 @@ __global__ void __launch_bounds__(64) inst_anchor_kernel(const int* __restrict__
     if (!kept) {
         if (lane == 0 && axis == 0) {
             st->area[i] = 0;
-            if (anchors) {
-                odise_anchor_row r;
-                r.segment_row = -1; r.area = 0; r.x2 = 0; r.y2 = 0; r.x0 = 0; r.y0 = 0; r.x1 = 0; r.y1 = 0;
-                anchors[i] = r;
-            }
+            if (anchors) anchors[i] = vis_anchor_row(-1, 0);
         }
         return;
     }
@@ -137,13 +135,6 @@ __global__ void __launch_bounds__(128) inst_order_kernel(InstDrawState* __restri
     }
 }
 
-__device__ __forceinline__ unsigned draw_blend(unsigned v, unsigned ia, unsigned crb, unsigned cg) {
-    // red and blue in one multiply: a channel's v * ia + c * a + 128 <= 255 * 256 + 128 stays inside its 16 bits
-    const unsigned rb = (((v & 0xff00ffu) * ia + crb) >> 8) & 0xff00ffu;
-    const unsigned g = (((v >> 8) & 0xffu) * ia + cg) >> 8;
-    return rb | (g << 8);
-}
-
 // image == out is safe: a thread reads its own 16 pixels before it writes them and no other thread reads them.
 __global__ void __launch_bounds__(kDrawThreads) inst_overlay_kernel(const unsigned long long* __restrict__ words, RleGrid G, int ntx,
                                                                    const InstDrawState* __restrict__ st, const uint8_t* image,
@@ -168,15 +159,11 @@ __global__ void __launch_bounds__(kDrawThreads) inst_overlay_kernel(const unsign
         for (int c = 0; c < 4; ++c) px[j][c] = 0u;
         if (vec[j]) {
             const unsigned* src = (const unsigned*)(image + off);   // the 12 bytes of four pixels inside the row
-            const unsigned d0 = src[0], d1 = src[1], d2 = src[2];
-            px[j][0] = d0 & 0xffffffu; px[j][1] = (d0 >> 24) | ((d1 & 0xffffu) << 8); px[j][2] = (d1 >> 16) | ((d2 & 0xffu) << 16); px[j][3] = d2 >> 8;
+            rgb4_unpack(src[0], src[1], src[2], px[j]);
         } else if (y < H) {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                if (px_x + c < W) {
-                    const uint8_t* s = image + off + 3 * c;
-                    px[j][c] = (unsigned)s[0] | ((unsigned)s[1] << 8) | ((unsigned)s[2] << 16);
-                }
+                if (px_x + c < W) px[j][c] = rgb_load(image + off + 3 * c);
         }
     }
 
@@ -188,10 +175,8 @@ __global__ void __launch_bounds__(kDrawThreads) inst_overlay_kernel(const unsign
         __syncthreads();                                                     // the previous chunk has been read
         if (t < nk) {
             const int i = st->list[k0 + t];
-            const unsigned c = (unsigned)colors[3 * i] | ((unsigned)colors[3 * i + 1] << 8) | ((unsigned)colors[3 * i + 2] << 16);
-            s_crb[t] = (c & 0xff00ffu) * (unsigned)alpha + 0x800080u;
-            s_cg[t] = ((c >> 8) & 0xffu) * (unsigned)alpha + 128u;
-            s_edge[t] = (unsigned)edge_colors[3 * i] | ((unsigned)edge_colors[3 * i + 1] << 8) | ((unsigned)edge_colors[3 * i + 2] << 16);
+            blend_color(rgb_load(colors + 3 * i), (unsigned)alpha, s_crb[t], s_cg[t]);
+            s_edge[t] = rgb_load(edge_colors + 3 * i);
         }
         for (int it = t; it < nk * 16; it += kDrawThreads) {                // item = (mask k, four columns q)
             const int k = it >> 4, q = it & 15, xa = x0 + 4 * q;
@@ -237,7 +222,7 @@ __global__ void __launch_bounds__(kDrawThreads) inst_overlay_kernel(const unsign
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const int bit = 4 * c + j;
-                    if ((s >> bit) & 1u) px[j][c] = ((s >> (16 + bit)) & 1u) ? edge : draw_blend(px[j][c], ia, crb, cg);
+                    if ((s >> bit) & 1u) px[j][c] = ((s >> (16 + bit)) & 1u) ? edge : blend_rgb(px[j][c], ia, crb, cg);
                 }
         }
     }
@@ -247,17 +232,11 @@ __global__ void __launch_bounds__(kDrawThreads) inst_overlay_kernel(const unsign
         const int y = px_y + j;
         const int64_t off = 3 * ((int64_t)y * W + px_x);
         if (vec[j]) {
-            unsigned* dst = (unsigned*)(out + off);
-            dst[0] = px[j][0] | (px[j][1] << 24);
-            dst[1] = (px[j][1] >> 8) | (px[j][2] << 16);
-            dst[2] = (px[j][2] >> 16) | (px[j][3] << 8);
+            rgb4_pack(px[j], (unsigned*)(out + off));
         } else if (y < H) {
 #pragma unroll
             for (int c = 0; c < 4; ++c)
-                if (px_x + c < W) {
-                    uint8_t* o = out + off + 3 * c;
-                    o[0] = (uint8_t)px[j][c]; o[1] = (uint8_t)(px[j][c] >> 8); o[2] = (uint8_t)(px[j][c] >> 16);
-                }
+                if (px_x + c < W) rgb_store(out + off + 3 * c, px[j][c]);
         }
     }
 }
@@ -297,7 +276,7 @@ __global__ void __launch_bounds__(1024) sem_rank_kernel(const unsigned* __restri
             }
             if (rank < ODISE_MAX_SEGMENTS) {
                 id = c + 1;
-                table[1 + 3 * rank] = id; table[2 + 3 * rank] = 0; table[3 + 3 * rank] = c;
+                record_set_row(table, rank, id, 0, c);
             }
             atomicAdd(&present, 1);
         }
@@ -306,7 +285,7 @@ __global__ void __launch_bounds__(1024) sem_rank_kernel(const unsigned* __restri
     __syncthreads();
     const int n = min(present, ODISE_MAX_SEGMENTS);
     if (threadIdx.x == 0) table[0] = n;
-    for (int i = 3 * n + threadIdx.x; i < 3 * ODISE_MAX_SEGMENTS; i += blockDim.x) table[1 + i] = 0;
+    record_zero_rows(table, n, ODISE_MAX_SEGMENTS, threadIdx.x, blockDim.x);
 }
 
 template <bool kSem>
@@ -390,7 +369,7 @@ extern "C" int odise_hip_semantic_record(odise_hip_ctx* ctx, const int32_t* labe
     int* map = (int*)((char*)ctx->vis.ptr + kb);
     int* ids = (int*)record;
     ODISE_CHECK_HIP(hipMemsetAsync(counts, 0, kb, ctx->stream));
-    const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>(ceil_div(npix, 256), 8 * ctx->cu_count));
+    const int blocks = grid_blocks(ctx, npix, 256);
     if (sem_seg) hipLaunchKernelGGL(sem_count_kernel<true>, dim3(blocks), dim3(256), lds_hist_bytes(K), ctx->stream, (const int*)nullptr, sem_seg, K, npix, counts, ids);
     else hipLaunchKernelGGL(sem_count_kernel<false>, dim3(blocks), dim3(256), lds_hist_bytes(K), ctx->stream, (const int*)labels, (const float*)nullptr, K, npix, counts, ids);
     ODISE_CHECK_HIP(hipGetLastError());

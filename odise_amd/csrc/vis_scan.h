@@ -36,6 +36,13 @@ __device__ __forceinline__ void vis_scan_middle(const int* __restrict__ h, int n
     }
 }
 
+// an anchor row before its coordinates are scanned
+__device__ __forceinline__ odise_anchor_row vis_anchor_row(int segment_row, int area) {
+    odise_anchor_row r;
+    r.segment_row = segment_row; r.area = area; r.x2 = 0; r.y2 = 0; r.x0 = 0; r.y0 = 0; r.x1 = 0; r.y1 = 0;
+    return r;
+}
+
 static inline int vis_check_size(const char* who, int H, int W) {
     ODISE_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= INT32_MAX / 4, "%s: bad size %dx%d", who, H, W);
     return ODISE_OK;

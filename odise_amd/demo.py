@@ -157,11 +157,11 @@ def run_on_video(ctx, model, visualizer, frames, task: str = "panoptic"):
 def run_on_image(ctx, model, visualizer, image_dev, task: str = "panoptic", confidence_threshold: float = 0.5,
                  video: bool = False) -> np.ndarray:
     """VisualizationDemo.run_on_image (demo.py:173-199) for a picture that is on the device; the result never leaves it before it is drawn."""
-    from ._lib import MAX_SEGMENTS
+    from ._lib import record_len
     from .ingest import HipDatasetMapper
     h, w = image_dev.shape[:2]
     inputs = HipDatasetMapper(ctx, 1024, 2560)._finish({"height": h, "width": w}, image_dev)
-    record = ctx.empty((h * w + 1 + 3 * MAX_SEGMENTS,), np.int32) if task == "panoptic" else None
+    record = ctx.empty((record_len(h, w),), np.int32) if task == "panoptic" else None
     inner = model.model
     saved = inner.open_state_dict()
     inner.load_open_state_dict(model.open_state_dict)

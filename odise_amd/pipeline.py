@@ -266,7 +266,7 @@ class HipCategoryODISE(HipODISE):
         """Pooled output buffers of `n` images + a PostDesc pointing at them (B / pad / img_hw / mask_cls are left to the caller).
         `alloc(tag, shape, dtype) -> DeviceArray` (optional) provides the LARGE per-image outputs instead of the pool - the drop-in model hands
         out views of torch tensors on its own device, so the library writes the reference's result tensors in place (no copy at the edge)."""
-        from ._lib import MAX_SEGMENTS, PostDesc
+        from ._lib import PostDesc, record_len
         K, topk = self.num_classes, int(self.test_topk_per_image)
         d = PostDesc()
         keep = []                                                          # ctypes arrays must outlive the call
@@ -288,7 +288,7 @@ class HipCategoryODISE(HipODISE):
                 if ext is not None:                                        # caller-owned record (this rank's slice of the gather buffer)
                     bufs["pan"][i], bufs["pan_ext"][i] = ext, True
                 else:
-                    bufs["pan"][i] = big(f"pan{i}", (oh * ow + 1 + 3 * MAX_SEGMENTS,), np.int32)
+                    bufs["pan"][i] = big(f"pan{i}", (record_len(oh, ow),), np.int32)
             if self.instance_on and not self.instance_rle:
                 bufs["masks"][i] = big(f"masks{i}", (topk, oh, ow), np.float32)
 
@@ -337,7 +337,7 @@ class HipCategoryODISE(HipODISE):
 
     def _collect(self, bufs, out_sizes, to_host: bool) -> list:
         """Read the small tables back (one synchronisation) and assemble the reference's result dicts."""
-        from ._lib import MAX_SEGMENTS
+        from ._lib import split_record
         n, topk = len(out_sizes), int(self.test_topk_per_image)
         results = [dict() for _ in range(n)]
         itable = bufs["itable"].numpy() if self.instance_on else None
@@ -353,9 +353,9 @@ class HipCategoryODISE(HipODISE):
                 if bufs["pan_ext"][i]:
                     r["panoptic_seg"] = (None, None)                       # the record lives in the caller's buffer (decode with distributed.unpack_record)
                 else:
-                    tail = rec.view((1 + 3 * MAX_SEGMENTS,), np.int32, oh * ow * 4).numpy()
+                    seg, table = split_record(rec, (oh, ow))
+                    tail = table.numpy()
                     info = [{"id": int(a), "isthing": bool(b), "category_id": int(c)} for a, b, c in tail[1:1 + 3 * int(tail[0])].reshape(-1, 3)]
-                    seg = rec.view((oh, ow), np.int32)
                     r["panoptic_seg"] = (seg.numpy() if to_host else seg, info)
             if self.instance_on and self.instance_rle:
                 cnt = int(itable[i, 0])

@@ -500,12 +500,9 @@ class Context:
                                 stats: Optional[DeviceArray] = None, flags: Optional[DeviceArray] = None):
         """`panoptic_quality` of a panoptic record int32 [h*w | 1 | 3*MAX_SEGMENTS] as odise_hip_infer / postprocess_batch leave it on the
         device (also a row of the exchange buffer): the map and the table are two offsets into it, nothing travels to the host."""
-        from ._lib import MAX_SEGMENTS
-        h, w = int(hw[0]), int(hw[1])
-        assert record.dtype == np.int32 and int(np.prod(record.shape)) >= h * w + 1 + 3 * MAX_SEGMENTS, (record.shape, hw)
-        flat = record.view((h * w + 1 + 3 * MAX_SEGMENTS,), np.int32)
-        return self.panoptic_quality(flat.view((h, w), np.int32), flat.view((1 + 3 * MAX_SEGMENTS,), np.int32, h * w * 4), gt, gt_segments,
-                                     num_categories, stats, flags)
+        from ._lib import split_record
+        ids, table = split_record(record, hw)
+        return self.panoptic_quality(ids, table, gt, gt_segments, num_categories, stats, flags)
 
     # ---- drawing a panoptic result (include/odise_hip.h odise_hip_connected_components ..; host restatement: odise_amd/visualize.py) ----
     def connected_components(self, labels: DeviceArray, out: Optional[DeviceArray] = None) -> DeviceArray:
@@ -623,7 +620,7 @@ class Context:
     def semantic_record(self, labels_or_sem_seg: DeviceArray, K: Optional[int] = None, out: Optional[DeviceArray] = None) -> DeviceArray:
         """labels int32 [H,W] (needs K) or sem_seg float32 [K,H,W] -> the panoptic record int32 [H*W + 1 + 3*MAX_SEGMENTS] of the semantic
         result (ids = category + 1, rows (id, 0, category) by descending pixel count), enqueued."""
-        from ._lib import MAX_SEGMENTS
+        from ._lib import record_len
         a = labels_or_sem_seg
         if a.dtype == np.float32:
             assert len(a.shape) == 3 and (K is None or int(K) == a.shape[0]), (a.shape, K)
@@ -634,8 +631,8 @@ class Context:
             H, W = a.shape
             labels, sem = a, None
         if out is None:
-            out = self.empty((H * W + 1 + 3 * MAX_SEGMENTS,), np.int32)
-        assert out.dtype == np.int32 and int(np.prod(out.shape)) >= H * W + 1 + 3 * MAX_SEGMENTS
+            out = self.empty((record_len(H, W),), np.int32)
+        assert out.dtype == np.int32 and int(np.prod(out.shape)) >= record_len(H, W)
         check(self.lib.odise_hip_semantic_record(self.h, _p(labels), _p(sem), int(K), H, W, _p(out)), "semantic_record")
         return out
 

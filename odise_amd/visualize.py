@@ -336,12 +336,9 @@ class HipVisualizer:
         """image_dev uint8 [h,w,3] and the panoptic record int32 [h*w | 1 | 3*MAX_SEGMENTS] on the device -> host uint8 [h,w,3].
         Overlay and anchors on the device, one read-back of the picture and the anchor rows (the table travels first: its rows choose
         the colours), the names drawn at the anchors."""
-        from ._lib import MAX_SEGMENTS
+        from ._lib import MAX_SEGMENTS, split_record
         ctx = self.ctx
-        h, w = int(hw[0]), int(hw[1])
-        assert record_dev.dtype == np.int32 and int(np.prod(record_dev.shape)) >= h * w + 1 + 3 * MAX_SEGMENTS, (record_dev.shape, hw)
-        flat = record_dev.view((h * w + 1 + 3 * MAX_SEGMENTS,), np.int32)
-        ids, table = flat.view((h, w), np.int32), flat.view((1 + 3 * MAX_SEGMENTS,), np.int32, h * w * 4)
+        ids, table = split_record(record_dev, hw)
         tail = table.numpy()
         n = min(max(int(tail[0]), 0), MAX_SEGMENTS)
         segments = tail[1:1 + 3 * n].reshape(n, 3)
@@ -399,16 +396,14 @@ class HipVideoVisualizer(HipVisualizer):
         """frame_dev uint8 [h,w,3] and the frame's panoptic record on the device -> host uint8 [h,w,3] (labels=False: before the names
         are drawn).  The table travels first (its rows choose the stuff colours and the names); the map never does: the tracker, the
         overlay and the anchors read it where it lies.  The tracker is made at the first frame's size; another size is an error."""
-        from ._lib import MAX_SEGMENTS
+        from ._lib import MAX_SEGMENTS, split_record
         ctx = self.ctx
         h, w = int(hw[0]), int(hw[1])
-        assert record_dev.dtype == np.int32 and int(np.prod(record_dev.shape)) >= h * w + 1 + 3 * MAX_SEGMENTS, (record_dev.shape, hw)
+        ids, table = split_record(record_dev, hw)   # checks the size before a tracker is made
         if self.tracker is None:
             self.tracker = ctx.track_create((h, w), self.ttl, self.pool)
         if self.tracker.hw != (h, w):
             raise ValueError(f"a {h}x{w} frame for a tracker of {self.tracker.hw[0]}x{self.tracker.hw[1]}")
-        flat = record_dev.view((h * w + 1 + 3 * MAX_SEGMENTS,), np.int32)
-        ids, table = flat.view((h, w), np.int32), flat.view((1 + 3 * MAX_SEGMENTS,), np.int32, h * w * 4)
         tail = table.numpy()
         n = min(max(int(tail[0]), 0), MAX_SEGMENTS)
         segments = tail[1:1 + 3 * n].reshape(n, 3)

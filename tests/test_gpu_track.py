@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import track_cases as TC
+from record_helpers import upload_record
 from odise_amd import video as VD
 from odise_amd import visualize as V
 from odise_amd._lib import MAX_SEGMENTS, TrackDesc
@@ -25,13 +26,6 @@ def record_of(ids, tab):
     rec[ids.size] = len(tab)
     rec[ids.size + 1:ids.size + 1 + 3 * len(tab)] = tab.reshape(-1)
     return rec
-
-
-def upload_record(ctx, ids, tab, unaligned=False):
-    """-> (buffer, ids [H,W], table): two views of one device record; unaligned: it starts one int32 past a 16-byte boundary."""
-    off = 4 if unaligned else 0
-    buf = ctx.to_device(np.concatenate([np.full(off // 4, -7, np.int32), record_of(ids, tab)]))
-    return buf, buf.view(ids.shape, np.int32, off), buf.view((1 + 3 * MAX_SEGMENTS,), np.int32, off + ids.size * 4)
 
 
 def live_guard(cap):
@@ -55,7 +49,7 @@ def run_sequence(ctx, case, tracker, unaligned=False, clobber=False, live_cap=No
     """Every frame checked against the restatement -> the bytes the device wrote, per frame."""
     got = []
     for t, ((ids, tab), want) in enumerate(zip(case.frames, TC.expected(case))):
-        buf, ids_dev, table_dev = upload_record(ctx, ids, tab, unaligned)
+        buf, ids_dev, table_dev = upload_record(ctx, record_of(ids, tab), ids.shape, unaligned)
         colors = ctx.to_device(TC.prefill())
         cap = len(want["live"]) if live_cap is None else live_cap
         live, n_live = ctx.to_device(live_guard(cap)), ctx.to_device(np.full(1, -9, np.int32))
@@ -141,7 +135,7 @@ def test_frames_without_the_optional_outputs(ctx):
     trk = ctx.track_create(case.hw, case.ttl, case.pool)
     try:
         for (ids, tab), want in zip(case.frames, TC.expected(case)):
-            _, ids_dev, table_dev = upload_record(ctx, ids, tab)
+            _, ids_dev, table_dev = upload_record(ctx, record_of(ids, tab), ids.shape)
             colors = ctx.track_frame(trk, ids_dev, table_dev, ctx.to_device(TC.prefill()))
             assert colors.numpy().tobytes() == want["colors"].tobytes()
     finally:
@@ -165,7 +159,7 @@ def test_bad_arguments_are_refused_and_nothing_is_written(ctx):
     trk = ctx.track_create(case.hw, case.ttl, case.pool)
     try:
         (ids, tab) = case.frames[0]
-        _, ids_dev, table_dev = upload_record(ctx, ids, tab)
+        _, ids_dev, table_dev = upload_record(ctx, record_of(ids, tab), ids.shape)
         colors = ctx.to_device(TC.prefill())
         live, n_live = ctx.to_device(live_guard(4)), ctx.to_device(np.full(1, -9, np.int32))
         iou_fill = np.full((4, MAX_SEGMENTS), -7.0, np.float64)

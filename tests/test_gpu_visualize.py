@@ -8,6 +8,7 @@ import pytest
 
 from odise_amd import visualize as V
 from odise_amd._lib import MAX_SEGMENTS, AnchorDesc, OverlayDesc
+from record_helpers import upload_record
 from vis_cases import cases, hand_cases
 
 pytestmark = pytest.mark.gpu
@@ -16,17 +17,8 @@ CASES = cases()
 GUARD = 3          # anchor rows behind `cap` that must stay as they were
 
 
-def upload_record(ctx, case, unaligned=False):
-    """-> (ids [H,W], table) as two views of one device record; unaligned: the record starts one int32 past a 16-byte boundary."""
-    rec = case.record()
-    h, w = case.hw
-    off = 4 if unaligned else 0
-    buf = ctx.to_device(np.concatenate([np.full(off // 4, -7, np.int32), rec]))
-    return buf.view((h, w), np.int32, off), buf.view((1 + 3 * MAX_SEGMENTS,), np.int32, off + h * w * 4)
-
-
 def device_anchors(ctx, case, cap=64, unaligned=False):
-    ids, table = upload_record(ctx, case, unaligned)
+    _, ids, table = upload_record(ctx, case.record(), case.hw, unaligned)
     rows = []
     for _ in range(2):
         guard = np.zeros(cap + GUARD, V.ANCHOR_DTYPE)
@@ -91,7 +83,7 @@ def test_anchors_of_a_record_that_is_not_16_byte_aligned(ctx):
 
 
 def device_overlay(ctx, case, alpha256=128, edge=(255, 255, 255), in_place=False, unaligned=False):
-    ids, table = upload_record(ctx, case, unaligned)
+    _, ids, table = upload_record(ctx, case.record(), case.hw, unaligned)
     h, w = case.hw
     image, colors = case.image(), ctx.to_device(case.colors())
     off = 1 if unaligned else 0
@@ -130,7 +122,7 @@ def test_overlay_options(ctx, alpha256, in_place, unaligned):
 def test_bad_arguments_are_refused_and_nothing_is_written(ctx):
     case = CASES["thresholds"]
     h, w = case.hw
-    ids, table = upload_record(ctx, case)
+    _, ids, table = upload_record(ctx, case.record(), case.hw)
     lib = ctx.lib
     roots = ctx.to_device(np.full((h, w), -9, np.int32))
     assert lib.odise_hip_connected_components(ctx.h, None, h, w, roots.ptr) == -1

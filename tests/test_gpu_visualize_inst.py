@@ -9,6 +9,7 @@ import pytest
 from odise_amd import coco_rle
 from odise_amd import visualize as V
 from odise_amd._lib import MAX_SEGMENTS, U8, InstDrawDesc
+from record_helpers import upload_record
 from vis_inst_cases import cases, hand_cases, sem_cases
 
 pytestmark = pytest.mark.gpu
@@ -145,8 +146,7 @@ def test_semantic_record_from_labels_and_from_scores(ctx, name):
     assert got[0].tobytes() == want.tobytes() and got[1].tobytes() == got[0].tobytes()
     # the record draws through the two existing calls as the restatement draws it
     h, w = case.hw
-    rec = ctx.to_device(case.record())
-    ids, table = rec.view((h, w), np.int32), rec.view((1 + 3 * MAX_SEGMENTS,), np.int32, h * w * 4)
+    _, ids, table = upload_record(ctx, case.record(), case.hw)
     n = int(case.record()[h * w])
     rows = case.record()[h * w + 1:h * w + 1 + 3 * n].reshape(n, 3)
     anchors, count = ctx.segment_anchors(ids, table, case.small_area, case.large_area, 256)

@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from odise_amd import video as VD  # noqa: E402
-from odise_amd._lib import MAX_SEGMENTS  # noqa: E402
+from odise_amd._lib import MAX_SEGMENTS, record_len, split_record  # noqa: E402
 from odise_amd.runtime import Context  # noqa: E402
 
 THINGS, STUFF, WARMUP, PERIOD = 20, 10, 8, 9
@@ -45,7 +45,7 @@ def frame(h, w, t, turning):
 
 
 def record(ids, table):
-    rec = np.zeros(ids.size + 1 + 3 * MAX_SEGMENTS, np.int32)
+    rec = np.zeros(record_len(*ids.shape), np.int32)
     rec[:ids.size], rec[ids.size] = ids.reshape(-1), len(table)
     rec[ids.size + 1:ids.size + 1 + table.size] = table.reshape(-1)
     return rec
@@ -63,7 +63,7 @@ def tracked(ctx, h, w, reps, turning):
     """-> (ms per frame, live rows when the timing starts); the warm-up frames are checked against the restatement."""
     frames = [frame(h, w, t, turning) for t in range(PERIOD if turning else 2)]     # the timed calls cycle through these
     recs = [ctx.to_device(record(*f)) for f in frames]
-    views = [(r.view((h, w), np.int32), r.view((1 + 3 * MAX_SEGMENTS,), np.int32, h * w * 4)) for r in recs]
+    views = [split_record(r, (h, w)) for r in recs]
     tracker, host = ctx.track_create((h, w)), VD.ColorTracker()
     colors, n_live = ctx.zeros((MAX_SEGMENTS, 3), np.uint8), ctx.zeros((1,), np.int32)
     live = ctx.zeros((8 * MAX_SEGMENTS,), VD.TRACK_ROW_DTYPE)

@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from odise_amd import visualize as V  # noqa: E402
-from odise_amd._lib import MAX_SEGMENTS  # noqa: E402
+from odise_amd._lib import RECORD_TABLE_LEN, split_record  # noqa: E402
 from odise_amd.runtime import Context  # noqa: E402
 
 
@@ -82,11 +82,11 @@ def device_ms(ctx, fn, reps):
 
 def one_size(ctx, h, w, reps):
     ids, segments = smooth_map(h, w)
-    table = np.zeros(1 + 3 * MAX_SEGMENTS, np.int32)
+    table = np.zeros(RECORD_TABLE_LEN, np.int32)
     table[0] = len(segments)
     table[1:1 + 3 * len(segments)] = np.asarray(segments, np.int32).reshape(-1)
     rec = ctx.to_device(np.concatenate([ids.reshape(-1), table]))
-    d_ids, d_table = rec.view((h, w), np.int32), rec.view(table.shape, np.int32, h * w * 4)
+    d_ids, d_table = split_record(rec, (h, w))
     small, large = V.SMALL_AREA, 30000              # 30000: some "other" components qualify at these sizes
     roots = ctx.empty((h, w), np.int32)
     ctx.connected_components(d_ids, roots)
