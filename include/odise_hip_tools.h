@@ -56,9 +56,14 @@ int odise_hip_gemm_debug(int flags);
 int odise_hip_post_generic(int on);
 /* force the tile of the semantic GEMM [K, pixels] = P^T S^T (A/B of the 256-row rule in odise_hip_postprocess_batch); -1 = the rule */
 int odise_hip_sem_tile(int tile);
-/* GroupNorm (csrc/norm.hip): chunks of the statistics pass per image = compute units * chunk_factor / images (default 2; 0 keeps the current value; a NEGATIVE value sets instead the row count from which LayerNorm takes 8 rows per wavefront to its magnitude);
- * fold_in_apply != 0 (default): with <= 64 chunks per image the apply kernel folds the partials itself and gn_finalize_kernel does not run */
-int odise_hip_gn_tuning(int chunk_factor, int fold_in_apply);
+/* GroupNorm (csrc/norm.hip): chunks of the statistics pass per image = compute units * chunk_factor / images (default 2).  A value >= 1 sets the
+ * factor, anything else leaves it.  Another factor is another summation order of the same statistics (tools/head_reroll.py asks what that moves) */
+int odise_hip_gn_tuning(int chunk_factor);
+/* odise_hip_layer_norm with the second output the pixel decoder and the masked decoder take from the same kernel: y2 [rows,C] f16 =
+ * y + table[row % P] (table f32 [P,C]) from the rounded y, the bits odise_hip_add_vec_table(y, NULL, table) writes.  y2 = NULL: no second output;
+ * otherwise C <= 256, a table and P >= 1 are required (ODISE_ERR_ARG and nothing launched).  tests/test_gpu_norm_bits.py holds the identity */
+int odise_hip_layer_norm_table(odise_hip_ctx* ctx, const void* x, void* y, const float* gamma, const float* beta, int rows, int C, float eps, void* y2,
+                               const float* table, int P);
 /* 1: the pixel decoder's MSDeformAttn layers as msda_prepare_kernel + the native-op kernel (the round 1-5 form) instead of the fused gather (A/B, bit-compare) */
 int odise_hip_msda_unfused(int on);
 /* the pixel decoder's MSDeformAttn on raw projections: value f16 [B, Lq, M, 32], off f32 [B*Lq, M*12*2], aw f32 [B*Lq, M*12] (3 levels hs3 x ws3, 4 points),

@@ -26,7 +26,7 @@ scale = np.abs(ref).max()
 for msda_unfused in (0, 1):
     for chunks in (2, 8):
         ctx.lib.odise_hip_msda_unfused(msda_unfused)
-        ctx.lib.odise_hip_gn_tuning(chunks, 1 if chunks == 2 else 0)
+        ctx.lib.odise_hip_gn_tuning(chunks)
         got = hip.head(feats)
         err = np.abs(got["pred_masks"][0] - ref) / scale
         q = err.reshape(100, -1).max(1)
@@ -36,4 +36,4 @@ for msda_unfused in (0, 1):
               f"median query {np.median(q):.2e}, p99.9 of all pixels {np.quantile(err.reshape(-1)[::7], 0.999):.2e}, of the regular queries {np.quantile(err[reg].reshape(-1)[::7], 0.999):.2e}, "
               f"mask_embed {me:.2e}", flush=True)
 ctx.lib.odise_hip_msda_unfused(0)
-ctx.lib.odise_hip_gn_tuning(2, 1)
+ctx.lib.odise_hip_gn_tuning(2)
