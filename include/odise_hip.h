@@ -396,6 +396,43 @@ int odise_hip_label_boundary(odise_hip_ctx* ctx, const int* labels, int K, int H
  * Neither is cleared.  radius <= 0: the formula.  K > 254 is ODISE_ERR_ARG (the evaluator computes no Boundary IoU there) and writes nothing. */
 int odise_hip_semantic_boundary_confusion(odise_hip_ctx* ctx, const float* sem_seg, const int* gt, int K, int H, int W, int radius,
                                           int64_t* conf, int64_t* b_conf);
+/* One WHOLE SemSegEvaluator.process step of a picture (d2_evaluator.py:63 -> detectron2 SemSegEvaluator.process), from the prediction as
+ * it lies in HBM: the counters above and the per-class COCO RLE strings of sem_seg_predictions.json (encode_json_sem_seg: for every label
+ * of np.unique(pred), mask.encode of (pred == label)).  Host restatement: odise_amd/semseg_eval.py.
+ * Prediction, exactly one of: labels int32 [H,W] (the fused arg-max map, sem_argmax of odise_post_desc), or sem_seg fp32 [K,H,W], whose
+ * first-maximum arg-max (ties to the lower class, as odise_hip_semantic_confusion takes it) is taken ONCE into scratch; every later
+ * stage reads labels.
+ * Counting (conf and / or b_conf non-NULL; needs gt int32 [H,W], a gt outside [0,K] counts in column K): conf int64 [(K+1)^2] += exactly
+ * what odise_hip_semantic_confusion adds, b_conf += exactly what odise_hip_semantic_boundary_confusion adds (radius <= 0: the formula);
+ * rows are the prediction.  A non-NULL b_conf with K > 254 is ODISE_ERR_ARG.
+ * Per-class RLE (offsets non-NULL; then classes and n_classes are required): classes int32 [max_classes] = the classes present in
+ * ASCENDING order (np.unique's), -1 past the count; n_classes int32 [1] = how many are present, also when that exceeds max_classes (then
+ * the first max_classes are encoded); rle / capacity / offsets int64 [max_classes+1] / area int64 [max_classes] (optional) as
+ * odise_hip_rle_encode: offsets always complete, nothing written past capacity, strings written only when offsets[max_classes] <=
+ * capacity, entries past the count are empty strings of area 0.  String i is byte-identical to
+ * mask.encode(np.asfortranarray((pred == classes[i]).astype(np.uint8)))["counts"].
+ * flags int32 [1], OR-ed: 1 = a label outside [0,K) in `labels`; that pixel is counted in neither matrix's class rows (in the boundary
+ * maps it stands as K, as odise_hip_label_boundary takes it) and is a zero in every class mask.
+ * ODISE_ERR_ARG and nothing written: a null or doubled prediction, null flags, counting outputs without gt, neither counting nor RLE
+ * asked for, H or W < 1, H * W > 2^29 - 1, K outside 1..12288, max_classes outside 1..65535 (with RLE), a negative capacity or one
+ * without a buffer.  Scratch comes from the context's growable buffers.  Asynchronous on the context's stream. */
+typedef struct {
+    int K, H, W;
+    const int32_t* labels;        /* device [H,W], or NULL */
+    const float* sem_seg;         /* device [K,H,W], or NULL */
+    const int32_t* gt;            /* device [H,W]; NULL = no counting */
+    int radius;
+    int64_t* conf;                /* device [(K+1)^2], optional */
+    int64_t* b_conf;              /* device [(K+1)^2], optional */
+    int max_classes;              /* 1..65535 */
+    int32_t* classes;             /* device [max_classes] */
+    int32_t* n_classes;           /* device [1] */
+    void* rle; int64_t capacity;  /* device bytes */
+    int64_t* offsets;             /* device [max_classes + 1]; NULL = no RLE */
+    int64_t* area;                /* device [max_classes], optional */
+    int32_t* flags;               /* device [1] */
+} odise_semseg_eval_desc;
+int odise_hip_semantic_eval(odise_hip_ctx* ctx, const odise_semseg_eval_desc* d);
 /* hist int32 [na*nb] += count of (a[p], b[p]) pairs with 0 <= a < na, 0 <= b < nb (segment-index co-occurrence of PQ matching) */
 int odise_hip_pair_histogram(odise_hip_ctx* ctx, const int* a, const int* b, int npix, int na, int nb, int* hist);
 /* One picture of COCOPanopticEvaluator's metric (d2_evaluator.py:49 -> panopticapi pq_compute_single_core) without the PNG round trip:

@@ -97,6 +97,13 @@ class PqDesc(C.Structure):
                 ("gt_segments", c_void_p), ("n_gt", c_int), ("num_categories", c_int), ("stats", c_void_p), ("flags", c_void_p)]
 
 
+class SemSegEvalDesc(C.Structure):
+    """odise_semseg_eval_desc (include/odise_hip.h)."""
+    _fields_ = [("K", c_int), ("H", c_int), ("W", c_int), ("labels", c_void_p), ("sem_seg", c_void_p), ("gt", c_void_p), ("radius", c_int),
+                ("conf", c_void_p), ("b_conf", c_void_p), ("max_classes", c_int), ("classes", c_void_p), ("n_classes", c_void_p),
+                ("rle", c_void_p), ("capacity", c_int64), ("offsets", c_void_p), ("area", c_void_p), ("flags", c_void_p)]
+
+
 class InstEvalDesc(C.Structure):
     """odise_inst_eval_desc (include/odise_hip.h)."""
     _fields_ = [("h", c_int), ("w", c_int), ("masks", c_void_p), ("dtype", c_int), ("b", c_int), ("pad_h", c_int), ("pad_w", c_int),

@@ -12,6 +12,9 @@
 //                                  d2_evaluator.py:49): co-occurrence counts of (ground-truth segment, predicted segment) indices of
 //                                  pre-indexed maps.  The evaluator's whole per-picture step - ids to slots, counts, matching, the add
 //                                  into (iou, tp, fp, fn) - is odise_hip_panoptic_quality in pq.hip.
+//   odise_hip_semantic_eval        the whole SemSegEvaluator.process step from the prediction as it lies in HBM - the int32 label map of the
+//                                  fused arg-max, or the score tensor with the arg-max taken once into scratch: both matrices below and the
+//                                  per-class COCO RLE strings of sem_seg_predictions.json (sem_rle.hip).
 //   odise_hip_label_boundary / odise_hip_semantic_boundary_confusion
 //                                  the second per-pixel job of SemSegEvaluator.process (K < 255, OpenCV importable): prediction and ground
 //                                  truth both go through _mask_to_boundary - a 3x3 grey-scale erosion behind a zero ring, repeated
@@ -34,10 +37,12 @@
 
 #include "common.h"
 #include "lds_hist.h"
+#include "rle_pack.h"   // sem_rle.hip: the per-class strings of odise_hip_semantic_eval
 
 namespace odise {
 
 constexpr int kPrecisionBits = 32 - 8 - 2;
+constexpr int64_t kSemEvalMaxPixels = (1ll << 29) - 1;   // odise_hip_semantic_eval: per picture, as odise_hip_panoptic_quality
 
 struct ResampleCoeffs {
     std::vector<int> bounds;  // [out][2] (xmin, count)
@@ -208,6 +213,46 @@ __global__ void __launch_bounds__(256) semantic_confusion_kernel(const float* __
     }
     H.sync();
     H.flush();
+}
+
+// odise_hip_semantic_eval: per pixel the label - the arg-max, taken here once and kept in lab_out (kSem), or the caller's map - and, with a
+// ground truth, what semantic_confusion_kernel counts of it: (label, gt) in conf (optional) and the two byte maps (kMaps).  A label
+// outside [0, K) (possible only in a caller's map) raises flag 1, is counted in no cell and stands as K in the byte map.
+template <bool kSem, bool kMaps>
+__global__ void __launch_bounds__(256) semantic_eval_kernel(const float* __restrict__ sem, const int* __restrict__ labels, const int* __restrict__ gt, int K,
+                                                           LabelGrid G, unsigned long long* __restrict__ conf, unsigned* __restrict__ maps,
+                                                           int* __restrict__ lab_out, int* __restrict__ flags) {
+    const int64_t npix = (int64_t)G.H * G.W;
+    const int n = (K + 1) * (K + 1);
+    const bool count = conf != nullptr;
+    const LdsHist<unsigned long long> H(conf, n, count && n <= kLdsHistCells);
+    H.clear();
+    H.sync();
+    bool bad = false;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+        int l;
+        bool in = true;
+        if (kSem) {
+            l = argmax_first(sem, K, npix, p);
+            if (lab_out) lab_out[p] = l;   // only the strings read it
+        } else {
+            l = labels[p];
+            in = (unsigned)l < (unsigned)K;
+            bad |= !in;
+        }
+        if (gt) {
+            int g = gt[p];
+            g = (g < 0 || g > K) ? K : g;
+            if (kMaps) {
+                store_label(maps, p, G, in ? l : K);
+                store_label(maps + (int64_t)G.H * G.Pd, p, G, g);
+            }
+            if (count && in) H.add(l * (K + 1) + g, 1u);
+        }
+    }
+    H.sync();
+    H.flush();
+    if (!kSem && bad) atomicOr(flags, 1);
 }
 
 // dst = per-byte minimum of taps.n copies of src shifted by taps.off pixels along the rows (vertical == 0) or the columns; 0 outside
@@ -452,6 +497,61 @@ extern "C" int odise_hip_semantic_boundary_confusion(odise_hip_ctx* ctx, const f
     blocks = (int)std::min<int64_t>(ceil_div(b.per_map, 256), 4 * ctx->cu_count);
     hipLaunchKernelGGL(boundary_confusion_kernel, dim3(blocks), dim3(256), lds, ctx->stream, b.m, b.e, K, b.G, (unsigned long long*)b_conf);
     ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}
+
+extern "C" int odise_hip_semantic_eval(odise_hip_ctx* ctx, const odise_semseg_eval_desc* d) {
+    ODISE_REQUIRE(ctx && d, "semantic_eval: null argument");
+    ODISE_REQUIRE((d->labels != nullptr) != (d->sem_seg != nullptr), "semantic_eval: exactly one of labels / sem_seg");
+    ODISE_REQUIRE(d->flags, "semantic_eval: null flags");
+    const int K = d->K, H = d->H, W = d->W;
+    const bool counting = d->conf || d->b_conf, strings = d->offsets != nullptr;
+    ODISE_REQUIRE(counting || strings, "semantic_eval: nothing to do (no conf, no b_conf, no offsets)");
+    ODISE_REQUIRE(!counting || d->gt, "semantic_eval: counting needs a ground truth");
+    ODISE_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= kSemEvalMaxPixels, "semantic_eval: picture size %dx%d out of range", H, W);
+    ODISE_REQUIRE(K >= 1 && K <= kLdsHistCells, "semantic_eval: %d classes (1..%d)", K, kLdsHistCells);
+    if (d->b_conf) ODISE_TRY(boundary_args("semantic_eval", K, H, W));
+    if (strings) {
+        ODISE_REQUIRE(d->classes && d->n_classes, "semantic_eval: the strings need classes and n_classes");
+        ODISE_REQUIRE(d->max_classes >= 1 && d->max_classes <= 65535, "semantic_eval: max_classes %d (1..65535)", d->max_classes);
+        ODISE_REQUIRE(d->capacity >= 0 && (d->rle || d->capacity == 0), "semantic_eval: capacity %lld without an output buffer", (long long)d->capacity);
+    }
+    ODISE_REQUIRE((((uintptr_t)d->labels | (uintptr_t)d->sem_seg | (uintptr_t)d->gt | (uintptr_t)d->classes | (uintptr_t)d->n_classes | (uintptr_t)d->flags) & 3) == 0 &&
+                      (((uintptr_t)d->conf | (uintptr_t)d->b_conf | (uintptr_t)d->offsets | (uintptr_t)d->area) & 7) == 0,
+                  "semantic_eval: int32 / float buffers must be 4-byte aligned, int64 buffers 8-byte aligned");
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    const RleGrid RG = rle_grid(H, W);
+    const int nmask = strings ? std::min(d->max_classes, K) : 0;
+    SemRleScratch s{};
+    if (strings) ODISE_TRY(sem_rle_scratch(ctx, nmask, RG, K, d->sem_seg != nullptr, &s));   // count only: no label map is kept
+    BoundaryMaps b{};
+    if (d->b_conf) ODISE_TRY(boundary_maps(ctx, H, W, 2, &b));
+    else { b.G.H = H; b.G.W = W; }
+    const int* labels = d->sem_seg ? s.labels : d->labels;
+    if (d->sem_seg || counting) {   // with a caller's map and no ground truth the labels are first read by the RLE passes
+        const size_t lds = d->conf ? lds_hist_bytes((K + 1) * (K + 1)) : 0;
+        const dim3 grid((unsigned)std::min<int64_t>(ceil_div((int64_t)H * W, 256), 4 * ctx->cu_count));
+        unsigned long long* conf = (unsigned long long*)d->conf;
+        const int* gt = counting ? d->gt : nullptr;
+        if (d->sem_seg && d->b_conf)
+            hipLaunchKernelGGL((semantic_eval_kernel<true, true>), grid, dim3(256), lds, ctx->stream, d->sem_seg, (const int*)nullptr, gt, K, b.G, conf, b.m, s.labels, d->flags);
+        else if (d->sem_seg)
+            hipLaunchKernelGGL((semantic_eval_kernel<true, false>), grid, dim3(256), lds, ctx->stream, d->sem_seg, (const int*)nullptr, gt, K, b.G, conf, b.m, s.labels, d->flags);
+        else if (d->b_conf)
+            hipLaunchKernelGGL((semantic_eval_kernel<false, true>), grid, dim3(256), lds, ctx->stream, (const float*)nullptr, d->labels, gt, K, b.G, conf, b.m, (int*)nullptr, d->flags);
+        else
+            hipLaunchKernelGGL((semantic_eval_kernel<false, false>), grid, dim3(256), lds, ctx->stream, (const float*)nullptr, d->labels, gt, K, b.G, conf, b.m, (int*)nullptr, d->flags);
+        ODISE_CHECK_HIP(hipGetLastError());
+    }
+    if (d->b_conf) {
+        ODISE_TRY(erode_maps(ctx, &b, 2, d->radius > 0 ? d->radius : boundary_radius(H, W)));
+        const int blocks = (int)std::min<int64_t>(ceil_div(b.per_map, 256), 4 * ctx->cu_count);
+        hipLaunchKernelGGL(boundary_confusion_kernel, dim3(blocks), dim3(256), lds_hist_bytes((K + 1) * (K + 1)), ctx->stream, b.m, b.e, K, b.G,
+                           (unsigned long long*)d->b_conf);
+        ODISE_CHECK_HIP(hipGetLastError());
+    }
+    if (strings)
+        ODISE_TRY(sem_rle_encode(ctx, s, RG, labels, K, nmask, d->max_classes, d->classes, d->n_classes, d->rle, d->capacity, d->offsets, d->area, d->flags));
     return ODISE_OK;
 }
 

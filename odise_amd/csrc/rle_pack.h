@@ -1,4 +1,5 @@
-// rle_pack.h — what rle.hip (COCO RLE strings), inst_eval.hip (mask IoU and segm matching) and poly.hip (polygon rasterisation) share: the
+// rle_pack.h — what rle.hip (COCO RLE strings), inst_eval.hip (mask IoU and segm matching), poly.hip (polygon rasterisation) and sem_rle.hip
+// (per-class strings of a label map) share: the
 // bit-packed mask layout, the block scan, the launchers of the pack kernels and the string passes (defined in rle.hip, compiled once) and
 // the launcher of the polygon kernel (poly.hip).
 //   word (x, r) of a mask holds pixels (64 r .. 64 r + 63, x), bit k = row 64 r + k, stored [n][w][R], R = ceil(h / 64): the words of a
@@ -75,5 +76,22 @@ int rle_finish(odise_hip_ctx* ctx, const RleScratch& s, const RleGrid& G, int n,
 // they are).  run_offsets (optional, [n_ann + 1]): an annotation with polygons AND a non-empty range here raises flag 4.  Flag 8: a bad polygon.
 int poly_fill_words(odise_hip_ctx* ctx, const double* xy, const int64_t* poly_offsets, const int32_t* ann_polys, int n_ann, int n_poly,
                     const RleGrid& G, unsigned long long* words, unsigned long long* toggle, bool fill_empty, const int64_t* run_offsets, int* flag);
+
+// Per-class strings of a semantic label map (sem_rle.hip; the RLE half of odise_hip_semantic_eval in eval_ops.hip).  The scratch is the
+// context's RLE scratch for nmask masks (0 = no strings wanted) with, behind it, an int32 [h * w] label map of the call's own
+// (own_labels: the arg-max of a score tensor is taken once, into it), the class counts [K], the class -> slot table [K] and the number of
+// masks encoded.
+struct SemRleScratch {
+    RleScratch rle;
+    int* labels;
+    unsigned* counts;
+    unsigned short* slot;
+    int* n_enc;
+};
+int sem_rle_scratch(odise_hip_ctx* ctx, int nmask, const RleGrid& G, int K, bool own_labels, SemRleScratch* s);
+// classes [max_classes] (ascending, -1 past the count), n_classes [1] (all present classes), the strings of the first nmask =
+// min(max_classes, K) at most, offsets [max_classes + 1], area [max_classes] (optional); flag 1 = a label outside [0, K)
+int sem_rle_encode(odise_hip_ctx* ctx, const SemRleScratch& s, const RleGrid& G, const int* labels, int K, int nmask, int max_classes, int* classes,
+                   int* n_classes, void* rle, int64_t capacity, int64_t* offsets, int64_t* area, int* flags);
 
 }  // namespace odise

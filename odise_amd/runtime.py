@@ -458,6 +458,45 @@ class Context:
               "semantic_boundary_confusion")
         return conf, b_conf
 
+    # ---- the whole SemSegEvaluator.process step (include/odise_hip.h odise_hip_semantic_eval; host restatement: odise_amd/semseg_eval.py) ----
+    def semantic_eval_async(self, pred: DeviceArray, K: Optional[int] = None, gt: Optional[DeviceArray] = None, conf: Optional[DeviceArray] = None,
+                            b_conf: Optional[DeviceArray] = None, flags: Optional[DeviceArray] = None, radius: int = 0, rle: bool = True,
+                            max_classes: Optional[int] = None, capacity: Optional[int] = None, bufs=None) -> "SemSegPending":
+        """Enqueue one SemSegEvaluator.process step: pred = labels int32 [H,W] (needs K) or sem_seg float32 [K,H,W]; gt int32 [H,W] with the
+        ignore label already mapped to K.  conf / b_conf int64 [(K+1),(K+1)] are added to (with a gt and neither given, a fresh zeroed conf
+        is counted; b_conf only when given), flags int32 [1] is OR-ed into (a fresh zeroed one when none is given).  rle: also the per-class
+        COCO RLE strings, at most max_classes (default MAX_SEGMENTS) of them at first; `SemSegPending.result()` enqueues the call again when
+        the strings did not fit the capacity or more classes are present - it reads `pred` again, so `pred` must hold the picture until
+        `settle()` or `result()` has run (call `settle()` before a pooled buffer is handed on).  bufs =(bytes uint8 [capacity], meta int32 [1 + max_classes],
+        offsets-and-area int64 [2 max_classes + 1]) device arrays to use instead of fresh ones (a retry still allocates its own)."""
+        if pred.dtype == np.float32:
+            assert len(pred.shape) == 3 and (K is None or int(K) == pred.shape[0]), (pred.shape, K)
+            K, H, W = pred.shape
+        else:
+            assert pred.dtype == np.int32 and len(pred.shape) == 2 and K is not None, (pred.dtype, pred.shape, K)
+            H, W = pred.shape
+        K = int(K)
+        assert gt is None or (gt.dtype == np.int32 and tuple(gt.shape) == (H, W)), "gt must be int32 [H,W]"
+        if gt is not None and conf is None and b_conf is None:
+            conf = self.zeros((K + 1, K + 1), np.int64)
+        for m in (conf, b_conf):
+            assert m is None or (m.dtype == np.int64 and int(np.prod(m.shape)) == (K + 1) * (K + 1)), "conf / b_conf must be int64 [(K+1),(K+1)]"
+        if flags is None:
+            flags = self.zeros((1,), np.int32)
+        assert flags.dtype == np.int32
+        return SemSegPending(self, pred, K, (H, W), gt, conf, b_conf, flags, int(radius), bool(rle), max_classes, capacity, bufs)
+
+    @staticmethod
+    def sem_rle_bytes(hw) -> int:
+        """Default string capacity of a picture's semantic RLE, all classes together.  The classes partition the picture, so the strings
+        hold two runs (one to three characters each for a smooth map) per change of label along the columns, whatever the number of
+        classes: a byte per four pixels covers a change every ~16 pixels of every column; a busier map costs the retry."""
+        return max(4096, int(hw[0]) * int(hw[1]) // 4)
+
+    def semantic_eval(self, pred: DeviceArray, K: Optional[int] = None, gt: Optional[DeviceArray] = None, **kw):
+        """`semantic_eval_async(...).result()`: (classes int32 [n], RLE dicts [n], area int64 [n]) of the classes present, ascending."""
+        return self.semantic_eval_async(pred, K, gt, **kw).result()
+
     def pair_histogram(self, a: DeviceArray, b: DeviceArray, na: int, nb: int, hist: Optional[DeviceArray] = None) -> DeviceArray:
         npix = int(np.prod(a.shape))
         if hist is None:
@@ -901,6 +940,94 @@ class RlePending:
             k = int(np.count_nonzero(np.diff(off)))
             rles, area = rles[:k], area[:k]
         return rles, area
+
+
+class SemSegPending:
+    """An enqueued `odise_hip_semantic_eval` call.  The matrices are counted by the first launch only, and the ground truth is let
+    go of right after it.  `settle()` reads n_classes and the offsets back (one synchronisation) and enqueues the RLE part again -
+    without the counters - at most twice: with max_classes = n_classes when more classes are present than were asked for, and with
+    exactly offsets[-1] bytes when the strings did not fit.  A retry READS `pred` AGAIN (from a score tensor it takes the whole K-plane
+    arg-max again, about the cost of the first call: the labels of the first launch lay in the context's shared scratch and are gone), so
+    `settle()` must run while `pred` still holds the picture; after it `pred` is let go of and `result()` reads only buffers of this
+    object.  `result()` settles first when nobody has: then the caller keeps `pred` untouched until `result()`."""
+
+    def __init__(self, ctx: Context, pred, K, hw, gt, conf, b_conf, flags, radius, rle, max_classes, capacity, bufs=None):
+        from ._lib import MAX_SEGMENTS
+        self.ctx, self.pred, self.K, self.hw, self.conf, self.b_conf, self.flags, self.radius = ctx, pred, K, hw, conf, b_conf, flags, radius
+        self.rle = rle
+        self.max_classes = int(max_classes) if max_classes is not None else MAX_SEGMENTS
+        self.capacity = int(capacity) if capacity is not None else Context.sem_rle_bytes(hw)
+        self.launches = 0
+        self._settled = None
+        if rle and bufs is not None:
+            self.buf, self.meta, self.off = bufs
+            assert self.buf.nbytes >= self.capacity and self.meta.nbytes >= 4 * (1 + self.max_classes) and self.off.nbytes >= 8 * (2 * self.max_classes + 1)
+        elif rle:
+            self._alloc()
+        counting = gt is not None and (conf is not None or b_conf is not None)
+        self._launch(gt if counting else None)
+        if not rle:
+            self.pred = None
+
+    def _alloc(self):
+        n = self.max_classes
+        self.buf = self.ctx.empty((max(self.capacity, 1),), np.uint8)
+        self.meta = self.ctx.empty((1 + n,), np.int32)              # n_classes | classes
+        self.off = self.ctx.empty((2 * n + 1,), np.int64)           # offsets [n + 1] | area [n]
+
+    def _launch(self, gt=None):
+        """gt None: the strings alone (a retry)."""
+        from ._lib import SemSegEvalDesc
+        d = SemSegEvalDesc()
+        d.K, d.H, d.W, d.radius = self.K, self.hw[0], self.hw[1], self.radius
+        if self.pred.dtype == np.float32:
+            d.sem_seg = self.pred.ptr
+        else:
+            d.labels = self.pred.ptr
+        d.flags = self.flags.ptr
+        if gt is not None:
+            d.gt = gt.ptr
+            d.conf = self.conf.ptr if self.conf is not None else None
+            d.b_conf = self.b_conf.ptr if self.b_conf is not None else None
+        if self.rle:
+            n = self.max_classes
+            d.max_classes, d.n_classes, d.classes = n, self.meta.ptr, self.meta.ptr + 4
+            d.rle, d.capacity, d.offsets, d.area = self.buf.ptr, self.capacity, self.off.ptr, self.off.ptr + 8 * (n + 1)
+        check(self.ctx.lib.odise_hip_semantic_eval(self.ctx.h, C.byref(d)), "semantic_eval")
+        self.launches += 1
+
+    def settle(self) -> "SemSegPending":
+        """Read n_classes and the offsets, enqueue the retries the picture needs (they read `pred`), let go of `pred`."""
+        if self._settled is not None or not self.rle:
+            return self
+        meta = self.meta.view((1 + self.max_classes,), np.int32).numpy()
+        if int(meta[0]) > self.max_classes:                           # more classes present than asked for: once more for all of them
+            self.max_classes = int(meta[0])
+            self._alloc()
+            self._launch()
+            meta = self.meta.numpy()
+        n = int(meta[0])
+        assert n <= self.max_classes, (n, self.max_classes)
+        off = self.off.view((2 * self.max_classes + 1,), np.int64).numpy()
+        total = int(off[self.max_classes])
+        if total > self.capacity:                                     # nothing was written: once more with the exact size
+            self.capacity = total
+            self.buf = self.ctx.empty((total,), np.uint8)
+            self._launch()
+            off = self.off.numpy()
+            assert int(off[self.max_classes]) == total, (int(off[self.max_classes]), total)
+        self._settled = (meta[1:1 + n].copy(), off[:n + 1].copy(), off[self.max_classes + 1:self.max_classes + 1 + n].copy())
+        self.pred = self.meta = self.off = None                       # the strings in self.buf are all that is still to be read
+        return self
+
+    def result(self):
+        if not self.rle:
+            return np.zeros(0, np.int32), [], np.zeros(0, np.int64)
+        classes, off, area = self.settle()._settled
+        total = int(off[-1])
+        raw = self.buf.view((total,), np.uint8).numpy().tobytes() if total else b""
+        rles = [{"size": [int(self.hw[0]), int(self.hw[1])], "counts": raw[off[i]:off[i + 1]].decode("ascii")} for i in range(len(classes))]
+        return classes, rles, area
 
 
 def _jpeg_info_struct(info: dict):
