@@ -747,6 +747,31 @@ typedef struct {
 } odise_track_desc;
 int odise_hip_track_frame(odise_hip_ctx* ctx, const odise_track_desc* d);
 
+/* ---- test-time augmentation of the semantic head (Mask2Former SemanticSegmentorWithTTA: several short-edge sizes, each also mirrored,
+ * sem_seg averaged at the original size) ------------------------------------------------------------------------------------------
+ * sem_seg = P^T sigmoid(masks) is linear in the (query, pixel) probabilities, so the mean over A views is one product over the views' query
+ * sets laid end to end, and its arg-max never needs [K, h, w].  The handle owns S_cat f16 [out_h*out_w, max_views*Qpad] and PT_cat f16
+ * [K, max_views*Qpad] (Qpad = Q rounded up to 8); they outlive the odise_hip_infer calls of the views.
+ *   create    ODISE_ERR_ARG: a null pointer, out_h*out_w >= 2^30, K outside 1..65536, Q outside 1..304, max_views outside 1..64, or buffers
+ *             larger than the free device memory; ODISE_ERR_NOMEM if the allocation fails all the same.
+ *   add_view  image b of the context's current mask logits (odise_hip_head_forward / odise_hip_infer / odise_hip_set_head_masks) and that
+ *             image's mask_cls_b (device fp32 [Q, K+1] log-probabilities) become the next view: its S bits are what the post-processing
+ *             pixel pass writes for (pad, img, out = the handle's size), sampled at column out_w-1-x when hflip; its PT bits those of
+ *             odise_hip_postprocess_batch.  One launch, asynchronous.  ODISE_ERR_ARG and the handle unchanged: a view beyond max_views, a
+ *             vocabulary size or query count that is not the handle's, b out of range, img larger than pad, pad other than 4 x the logit grid.
+ *   finish    sem_seg (optional, device fp32 [K, out_h, out_w]) = the sum over the views divided by their number in fp32; sem_argmax
+ *             (optional, device int32 [out_h*out_w]) = first maximum of the sums.  With one unmirrored view sem_argmax is bit-identical to
+ *             odise_post_desc's.  ODISE_ERR_ARG: no view added, or neither output.  The views stay; reset starts the next picture.
+ *   destroy   waits for the stream. */
+typedef struct odise_tta odise_tta;
+int odise_hip_tta_create(odise_hip_ctx* ctx, int out_h, int out_w, int K, int Q, int max_views, odise_tta** out);
+int odise_hip_tta_reset(odise_hip_ctx* ctx, odise_tta* tta);
+int odise_hip_tta_destroy(odise_hip_ctx* ctx, odise_tta* tta);
+int odise_hip_tta_add_view(odise_hip_ctx* ctx, odise_tta* tta, int b, const float* mask_cls_b, int pad_h, int pad_w, int img_h, int img_w, int hflip);
+int odise_hip_tta_finish(odise_hip_ctx* ctx, odise_tta* tta, float* sem_seg, int32_t* sem_argmax);
+/* dst uint8 [H,W,C] = src mirrored left to right (HFlipTransform on the resized picture); src != dst, H*W*C < 2^31.  Asynchronous. */
+int odise_hip_hflip_u8_hwc(odise_hip_ctx* ctx, const void* src, void* dst, int H, int W, int C);
+
 /* ---- JPEG input -------------------------------------------------------------------------------------------
  * Replaces detectron2 `read_image(file, "RGB")` = PIL.Image.open -> EXIF transpose -> convert("RGB") of the DatasetMapper
  * (configs/common/data/pano_open_d2_eval.py:74-107; demo/demo.py:399) for baseline JPEG files, bit-identical to Pillow /

@@ -21,6 +21,10 @@ int odise_hip_lds_rate(odise_hip_ctx* ctx, int variant, int rounds, int blocks, 
  * M, N multiples of 256, K a multiple of 128.  variant: bit 0 = no s_setprio, bit 1 = wave groups in lockstep */
 int odise_hip_gemm8p(odise_hip_ctx* ctx, const void* A, const void* W, void* C, int M, int N, int K, int variant);
 
+/* tta.hip: the single-view semantic_argmax_kernel on the operands of a one-view odise_tta handle, the yardstick odise_hip_tta_finish is
+ * timed against on the same bits (tools/tta_bench.py) */
+int odise_hip_lab_tta_single_argmax(odise_hip_ctx* ctx, odise_tta* tta, int32_t* sem_argmax);
+
 #ifdef __cplusplus
 }
 #endif

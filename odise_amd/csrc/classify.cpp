@@ -84,6 +84,8 @@ void classify_destroy(ModelStore* ms) {
     ms->classify = nullptr;
 }
 
+int classify_num_classes(ModelStore* ms) { return ms->classify && ms->classify->has_vocab ? ms->classify->K : 0; }
+
 static int classify_build(odise_hip_ctx* ctx) {
     ModelStore* ms = store_of(ctx);
     classify_destroy(ms);

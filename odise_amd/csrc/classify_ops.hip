@@ -229,22 +229,7 @@ __global__ void __launch_bounds__(256) classify_rows_kernel(const float* __restr
     if (tid == 0) orow[K] = logf(pn + 1e-8f);
 }
 
-// sigmoid of the per-pixel pass: v_exp_f32 + v_rcp_f32 (1 ulp each) instead of the library expf and the IEEE division (~20 VALU
-// instructions less per pixel and query, of ~70); the result is rounded to fp16 for S and compared against 0.5 for the panoptic flag, both far
-// coarser.  All three forms of the pass (generic, x4, tiled) share it, so they stay bit-identical to each other.
-__device__ __forceinline__ float post_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-
-// fp16 sigmoid for the pixel-major matrix S.  The instance head counts a pixel as inside the mask iff its LOGIT is positive
-// (maskformer_model.py:371 `mask_pred > 0`) and averages sigmoid over exactly those pixels (:376-377); sigmoid(v) for |v| < ~1e-3 rounds to
-// 0.5 in fp16 on either side of zero, so a non-positive logit never gets more than the last fp16 value below 0.5 (and a positive one never less
-// than 0.5): `S >= 0.5` then reproduces `logit > 0` exactly, and no value moves by more than one fp16 step of its own size - the semantic
-// scores, which read the same matrix, keep the 2^-11 relative error of a plain rounding.  (Lifting the positive side to the next value ABOVE
-// 0.5 instead cost those pixels 2^-10: tests/test_gpu_postprocess.py, generic geometry.)
-__device__ __forceinline__ f16 sig_f16(float sg, float v) {
-    const f16 h = (f16)sg;
-    const f16 half = (f16)0.5f, below = (f16)0.499755859375f;
-    return v > 0.f ? (h < half ? half : h) : (h > below ? below : h);   // selects, no branch
-}
+// post_sigmoid / sig_f16 (the sigmoid of the per-pixel pass and its fp16 rounding for S): post_sample.h, shared with tta.hip
 
 // ---- what the three forms of the per-pixel pass share: one definition each, so they cannot drift apart ---------------------------------
 // One step of a pixel's walk over the queries: query q (score ks, < 0 = not kept; the caller loads it and keeps it wave-uniform) has logit v at
@@ -694,18 +679,12 @@ __global__ void __launch_bounds__(256) post_decide_kernel(const float* __restric
     }
     for (int q = blockIdx.y * 4 + wave; q < Q; q += 4 * gridDim.y) {   // one wavefront per query (grid.y = Q / 4: a single block per image took 71 us on the serial tail)
         const float* row = mc + (int64_t)q * (K + 1);
-        float m = -INFINITY;
-        for (int k = lane; k <= K; k += 64) m = fmaxf(m, row[k]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        float ssum = 0.f;
-        for (int k = lane; k <= K; k += 64) ssum += expf(row[k] - m);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) ssum += __shfl_xor(ssum, o);
+        float m, ssum;
+        wave_softmax_stats(row, K, lane, m, ssum);
         float best = -1.f;
         int best_k = 0x7fffffff;
         for (int k = lane; k <= K; k += 64) {
-            const float pr = expf(row[k] - m) / ssum;
+            const float pr = softmax_prob(row[k], m, ssum);
             if (k < K) {
                 if (semT) semT[(int64_t)b * semT_stride + (int64_t)k * Qpad + q] = (f16)pr;
                 if (probs) probs[(int64_t)b * probs_stride + (int64_t)q * K + k] = pr;

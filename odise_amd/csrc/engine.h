@@ -341,6 +341,7 @@ struct HeadOutputs {
     const float* class_logits;  // [B, Q, 2] learned (object, no-object) logits of the caption variant's class_embed, or nullptr
 };
 int head_outputs(ModelStore* ms, HeadOutputs* out);
+int classify_num_classes(ModelStore* ms);   // classify.cpp: K of the current vocabulary, 0 without one (tta.hip)
 void maskgen_invalidate_outputs(ModelStore* ms);   // the arena was reallocated: outputs of earlier backbone / head calls are gone
 
 // gemm.hip / norm.hip internals used by Exec

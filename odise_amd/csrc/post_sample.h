@@ -1,5 +1,5 @@
 // post_sample.h — the mask-logit resampling of the post-processing stage (odise.py:326-331 + sem_seg_postprocess), shared by the kernels that
-// threshold it: classify_ops.hip (per-pixel pass, instance masks) and rle.hip (COCO RLE of the instance masks).  One definition, so every
+// threshold it: classify_ops.hip (per-pixel pass, instance masks), rle.hip (COCO RLE of the instance masks) and tta.hip (the views' sigmoid matrices).  One definition, so every
 // consumer sees the same bits.
 #pragma once
 #include "engine.h"
@@ -59,5 +59,37 @@ __device__ __forceinline__ float x4_pixel(int k, float ty, float al, float ac, f
     const float top = v00 + tx * (v01 - v00), bot = v10 + tx * (v11 - v10);
     return top + ty * (bot - top);
 }
+
+// sigmoid of the per-pixel pass: v_exp_f32 + v_rcp_f32 (1 ulp each) instead of the library expf and the IEEE division (~20 VALU
+// instructions less per pixel and query, of ~70); the result is rounded to fp16 for S and compared against 0.5 for the panoptic flag, both far
+// coarser.  All three forms of the pass (generic, x4, tiled) share it, so they stay bit-identical to each other.
+__device__ __forceinline__ float post_sigmoid(float v) { return __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
+
+// fp16 sigmoid for the pixel-major matrix S.  The instance head counts a pixel as inside the mask iff its LOGIT is positive
+// (maskformer_model.py:371 `mask_pred > 0`) and averages sigmoid over exactly those pixels (:376-377); sigmoid(v) for |v| < ~1e-3 rounds to
+// 0.5 in fp16 on either side of zero, so a non-positive logit never gets more than the last fp16 value below 0.5 (and a positive one never less
+// than 0.5): `S >= 0.5` then reproduces `logit > 0` exactly, and no value moves by more than one fp16 step of its own size - the semantic
+// scores, which read the same matrix, keep the 2^-11 relative error of a plain rounding.  (Lifting the positive side to the next value ABOVE
+// 0.5 instead cost those pixels 2^-10: tests/test_gpu_postprocess.py, generic geometry.)
+__device__ __forceinline__ f16 sig_f16(float sg, float v) {
+    const f16 h = (f16)sg;
+    const f16 half = (f16)0.5f, below = (f16)0.499755859375f;
+    return v > 0.f ? (h < half ? half : h) : (h > below ? below : h);   // selects, no branch
+}
+
+// F.softmax over one query's K + 1 log-probabilities (maskformer_model.py:287) by one wavefront: the row's maximum and the sum of the
+// exponentials in every lane, then softmax_prob per entry.  post_decide_kernel (semT, the A operand of the semantic product) and
+// tta_view_kernel (a view's columns of PT_cat) share it, so both hold the same fp16 bits.
+__device__ __forceinline__ void wave_softmax_stats(const float* __restrict__ row, int K, int lane, float& m, float& ssum) {
+    m = -INFINITY;
+    for (int k = lane; k <= K; k += 64) m = fmaxf(m, row[k]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    ssum = 0.f;
+    for (int k = lane; k <= K; k += 64) ssum += expf(row[k] - m);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ssum += __shfl_xor(ssum, o);
+}
+__device__ __forceinline__ float softmax_prob(float x, float m, float ssum) { return expf(x - m) / ssum; }
 
 }  // namespace odise

@@ -1,4 +1,4 @@
-"""`python -m odise_amd.demo (--input FILE... | --video-input SRC [--ttl N]) --output DIR [--vocab "a, b; c"] [--synthetic] [--task panoptic|semantic|instance]`:
+"""`python -m odise_amd.demo (--input FILE... | --video-input SRC [--ttl N]) --output DIR [--vocab "a, b; c"] [--synthetic] [--task panoptic|semantic|instance] [--tta 768,1024,1280 [--no-tta-flip]]`:
 demo/demo.py on the device path.
 
 A picture is read (JPEG through HipDatasetMapper, anything else through Pillow), resized by ResizeShortestEdge(1024, 2560) on the device,
@@ -8,6 +8,9 @@ its panoptic record - still in HBM - is drawn by HipVisualizer.draw_panoptic_seg
 `--task semantic` / `--task instance` take the other branch of run_on_image: the wrapper is built with that head on (and panoptic off), and
 the semantic map (HipVisualizer.draw_sem_seg), then the instance selection (draw_instance_predictions, scores below
 `--confidence-threshold` left out) are drawn, the instances on top.
+
+`--task semantic --tta 768,1024,1280` averages the semantic scores over the picture at these short-edge sizes, each also mirrored unless
+`--no-tta-flip` (odise_amd/tta.py HipSemanticTTA: Mask2Former's SemanticSegmentorWithTTA), and draws the arg-max of the mean.
 
 `--video-input SRC` takes run_on_video (demo.py:201-243) instead: SRC is a directory of frames (read in sorted name order) or a multi-frame
 file Pillow opens (no container decoding); every frame goes through the same model call and is drawn by
@@ -41,7 +44,23 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--task", choices=("panoptic", "semantic", "instance"), default="panoptic",
                     help="which head is on and drawn (semantic-only vocabularies, or the instance masks segm AP scores)")
     ap.add_argument("--confidence-threshold", type=float, default=0.5, help="--task instance: instances below this score are not drawn")
+    ap.add_argument("--tta", default=None, metavar="SIZES", help="--task semantic: average the semantic scores over these short-edge sizes "
+                    '("768,1024,1280"), each also mirrored (multi-scale / flip test-time augmentation)')
+    ap.add_argument("--no-tta-flip", action="store_true", help="--tta: the sizes only, no mirrored views")
     args = ap.parse_args(argv)
+    if args.tta is not None:
+        if args.task != "semantic":
+            ap.error(f"--tta with --task {args.task}: test-time augmentation exists for the semantic head only")
+        try:
+            args.tta = tuple(int(v) for v in args.tta.split(","))
+        except ValueError:
+            ap.error(f"--tta {args.tta!r}: comma-separated short-edge sizes expected")
+        if not args.tta or min(args.tta) < 1:
+            ap.error("--tta: sizes must be positive")
+        if args.video_input is not None:
+            ap.error("--tta with --video-input: test-time augmentation runs on single pictures")
+    elif args.no_tta_flip:
+        ap.error("--no-tta-flip without --tta")
     if args.video_input is not None and args.task == "instance":
         ap.error("--task instance with --video-input: the reference tracks pred_boxes there, which are all zeros on this model")
     if not 1 <= args.ttl <= 8:
@@ -155,7 +174,7 @@ def run_on_video(ctx, model, visualizer, frames, task: str = "panoptic"):
 
 
 def run_on_image(ctx, model, visualizer, image_dev, task: str = "panoptic", confidence_threshold: float = 0.5,
-                 video: bool = False) -> np.ndarray:
+                 video: bool = False, tta=None) -> np.ndarray:
     """VisualizationDemo.run_on_image (demo.py:173-199) for a picture that is on the device; the result never leaves it before it is drawn."""
     from ._lib import record_len
     from .ingest import HipDatasetMapper
@@ -171,7 +190,11 @@ def run_on_image(ctx, model, visualizer, image_dev, task: str = "panoptic", conf
     if task == "semantic":
         inner.semantic_argmax = True                                         # the fused arg-max map; no [K,h,w] tensor
     try:
-        results = inner.infer_device([inputs["image"]], 0, [tuple(inputs["image"].shape[:2])], [(h, w)], pan_out=[record] if record is not None else None)
+        if tta is not None:                                                  # HipSemanticTTA over `model`: its own views of the picture
+            results = tta.forward([{"image": image_dev, "height": h, "width": w}], to_host=False)
+        else:
+            results = inner.infer_device([inputs["image"]], 0, [tuple(inputs["image"].shape[:2])], [(h, w)],
+                                         pan_out=[record] if record is not None else None)
     finally:
         inner.load_open_state_dict(saved)
         inner.keep_instance_selection, inner.instance_rle, inner.semantic_argmax = keep, rle, amax
@@ -219,10 +242,16 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         return 0
     visualizer = HipVisualizer(ctx, metadata)
     os.makedirs(args.output, exist_ok=True)
+    tta = None
+    if args.tta is not None:
+        from .tta import HipSemanticTTA
+        tta = HipSemanticTTA(model, args.tta, 2560, flip=not args.no_tta_flip)
     for file_name in args.input:
-        picture = run_on_image(ctx, model, visualizer, read_picture(ctx, file_name), args.task, args.confidence_threshold)
+        picture = run_on_image(ctx, model, visualizer, read_picture(ctx, file_name), args.task, args.confidence_threshold, tta=tta)
         Image.fromarray(picture).save(output_path(args.output, file_name))
         print(f"{file_name} -> {output_path(args.output, file_name)}")
+    if tta is not None:
+        tta.close()
     ctx.close()
     return 0
 

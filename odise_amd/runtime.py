@@ -591,6 +591,21 @@ class Context:
         check(self.lib.odise_hip_panoptic_overlay(self.h, C.byref(d)), "panoptic_overlay")
         return out
 
+    # ---- test-time augmentation of the semantic head (include/odise_hip.h odise_hip_tta_*; driver: odise_amd/tta.py) -----------------------
+    def tta_create(self, out_hw, K: int, Q: int, max_views: int) -> "SemanticTTA":
+        """A handle that sums up to `max_views` views of a picture whose result has out_hw = (H, W), K classes, Q queries."""
+        return SemanticTTA(self, out_hw, K, Q, max_views)
+
+    def hflip_u8_hwc(self, img: DeviceArray, out: Optional[DeviceArray] = None) -> DeviceArray:
+        """uint8 [H,W,C] mirrored left to right (HFlipTransform on the resized picture)."""
+        H, W, Cc = img.shape
+        assert img.dtype == np.uint8
+        if out is None:
+            out = self.empty((H, W, Cc), np.uint8)
+        assert out.nbytes == H * W * Cc
+        check(self.lib.odise_hip_hflip_u8_hwc(self.h, _p(img), _p(out), H, W, Cc), "hflip_u8_hwc")
+        return out
+
     # ---- colours of things across frames (include/odise_hip.h odise_hip_track_*; host restatement: odise_amd/video.py) -------------------
     def track_create(self, hw, ttl: int = 8, pool=None) -> "Tracker":
         """A tracker for frames of hw = (H, W): pool uint8 [P,3] on the host (video.default_pool() when None)."""
@@ -897,6 +912,41 @@ class Tracker:
     def close(self) -> None:
         if self.handle and self.ctx.h:
             self.ctx.lib.odise_hip_track_destroy(self.ctx.h, C.c_void_p(self.handle))
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SemanticTTA:
+    """odise_tta (include/odise_hip.h): the views of one picture laid end to end for one semantic product; `close()` (or collection)
+    releases the device buffers (S_cat: out_h * out_w * max_views * Qpad fp16)."""
+
+    def __init__(self, ctx: Context, out_hw, K: int, Q: int, max_views: int):
+        self.ctx, self.hw, self.K, self.Q, self.max_views = ctx, (int(out_hw[0]), int(out_hw[1])), int(K), int(Q), int(max_views)
+        self.handle = None
+        h = C.c_void_p()
+        check(ctx.lib.odise_hip_tta_create(ctx.h, self.hw[0], self.hw[1], self.K, self.Q, self.max_views, C.byref(h)), "tta_create")
+        self.handle = h.value
+
+    def reset(self) -> None:
+        check(self.ctx.lib.odise_hip_tta_reset(self.ctx.h, C.c_void_p(self.handle)), "tta_reset")
+
+    def add_view(self, b: int, mask_cls_b, pad_hw, img_hw, hflip: bool = False) -> None:
+        """Image b of the context's current mask logits + its log-probabilities (DeviceArray fp32 [Q, K+1], or a device pointer)."""
+        check(self.ctx.lib.odise_hip_tta_add_view(self.ctx.h, C.c_void_p(self.handle), int(b), mask_cls_b, int(pad_hw[0]), int(pad_hw[1]),
+                                                  int(img_hw[0]), int(img_hw[1]), int(bool(hflip))), "tta_add_view")
+
+    def finish(self, sem_seg: Optional[DeviceArray] = None, sem_argmax: Optional[DeviceArray] = None) -> None:
+        """sem_seg fp32 [K,H,W] = mean over the views; sem_argmax int32 [H,W] = first maximum of their sum.  Either or both."""
+        check(self.ctx.lib.odise_hip_tta_finish(self.ctx.h, C.c_void_p(self.handle), _p(sem_seg), _p(sem_argmax)), "tta_finish")
+
+    def close(self) -> None:
+        if self.handle and self.ctx.h:
+            self.ctx.lib.odise_hip_tta_destroy(self.ctx.h, C.c_void_p(self.handle))
         self.handle = None
 
     def __del__(self):
