@@ -202,11 +202,7 @@ extern "C" int odise_hip_set_vocabulary(odise_hip_ctx* ctx, const float* cat_tex
     if (rc == ODISE_OK) rc = up(seg.data(), seg.size() * sizeof(int), (void**)&bk.seg);
     if (rc == ODISE_OK) rc = up(overlap, (size_t)K * sizeof(int), (void**)&bk.ovl);
     if (rc == ODISE_OK) {
-        odise_gemm_desc d;
-        memset(&d, 0, sizeof(d));
-        d.M = K_tot + 1; d.N = c->pdim; d.K = dim;
-        d.A = d_in; d.lda = dim; d.W = c->text_proj.w; d.ldw = dim;
-        d.C = d_proj; d.ldc = c->pdim; d.c_dtype = ODISE_F32; d.bias_n = c->text_proj.b; d.alpha = 1.f; d.batch = 1;
+        const odise_gemm_desc d = gemm_linear(d_in, K_tot + 1, c->text_proj, d_proj, ODISE_F32);
         rc = odise_hip_gemm(ctx, &d);
     }
     if (rc == ODISE_OK) rc = launch_l2_normalize_f32(ctx, d_proj, bk.T1, K_tot + 1, c->pdim);
@@ -279,22 +275,17 @@ static int classify_impl(odise_hip_ctx* ctx, const float* image, int B, int H, i
     const int Q = ho.Q;
     const int64_t MQ = (int64_t)B * Q;
     // ---- category logits: cos(mask_embed, text_proj(text bank)) --------------------------------------------------------
-    f16* me_n = (f16*)ex.alloc_bytes((size_t)MQ * ho.C * 2);
-    float* L1 = (float*)ex.alloc_bytes((size_t)MQ * (c->Ktot + 1) * 4);
-    float* L2 = (float*)ex.alloc_bytes((size_t)MQ * c->Ktot * 4);
-    f16* ce = (f16*)ex.alloc_bytes((size_t)MQ * c->dim * 2);
-    f16* ce_n = (f16*)ex.alloc_bytes((size_t)MQ * c->dim * 2);
+    f16* me_n = ex.buf<f16>((size_t)MQ * ho.C);
+    float* L1 = ex.buf<float>((size_t)MQ * (c->Ktot + 1));
+    float* L2 = ex.buf<float>((size_t)MQ * c->Ktot);
+    f16* ce = ex.buf<f16>((size_t)MQ * c->dim);
+    f16* ce_n = ex.buf<f16>((size_t)MQ * c->dim);
     const int64_t ldm = round_up(T, 8);
-    uint8_t* tmask = (uint8_t*)ex.alloc_bytes((size_t)B * (T + Q) * ldm);
-    if (!me_n || !L1 || !L2 || !ce || !ce_n || !tmask) return ODISE_ERR_NOMEM;
+    uint8_t* tmask = ex.buf<uint8_t>((size_t)B * (T + Q) * ldm);
+    ODISE_TRY(ex.ok());
     ODISE_REQUIRE(ho.C == c->pdim, "classify: mask_embed dim %d != text_proj out %d", ho.C, c->pdim);
     ODISE_TRY(launch_l2_normalize_f16(ctx, ho.mask_embed, me_n, MQ, ho.C));
-    odise_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.M = (int)MQ; d.N = c->Ktot + 1; d.K = ho.C;
-    d.A = me_n; d.lda = ho.C; d.W = c->T1; d.ldw = ho.C;
-    d.C = L1; d.ldc = c->Ktot + 1; d.c_dtype = ODISE_F32; d.alpha = 1.f; d.batch = 1;
-    ODISE_TRY(ex.gemm(d));
+    ODISE_TRY(ex.linear_f32(me_n, MQ, LinW{c->T1, nullptr, ho.C, c->Ktot + 1}, L1));
     // ---- MaskCLIP (clip.py:325-338): image and masks bilinearly resized to 336^2 -----------------------------------------
     ODISE_TRY(launch_maskclip_token_mask(ctx, ho.pred_masks, tmask, B, Q, ho.h4, ho.w4, S, patch, T, ldm));
     stage_mark(ctx, "classify: text logits + MaskCLIP inputs");
@@ -302,11 +293,7 @@ static int classify_impl(odise_hip_ctx* ctx, const float* image, int B, int H, i
     stage_mark(ctx, "classify: MaskCLIP tower done");
     if (clip_embed_out) ODISE_TRY(odise_hip_cast_f16_to_f32(ctx, ce, clip_embed_out, (size_t)MQ * c->dim));
     ODISE_TRY(launch_l2_normalize_f16(ctx, ce, ce_n, MQ, c->dim));
-    memset(&d, 0, sizeof(d));
-    d.M = (int)MQ; d.N = c->Ktot; d.K = c->dim;
-    d.A = ce_n; d.lda = c->dim; d.W = c->T2; d.ldw = c->dim;
-    d.C = L2; d.ldc = c->Ktot; d.c_dtype = ODISE_F32; d.alpha = 1.f; d.batch = 1;
-    ODISE_TRY(ex.gemm(d));
+    ODISE_TRY(ex.linear_f32(ce_n, MQ, LinW{c->T2, nullptr, c->dim, c->Ktot}, L2));
     // ---- ensemble + null merge -----------------------------------------------------------------------------------------------
     if (c->caption && !ho.class_logits) {
         set_error("classify: word_head weights were loaded but the decoder has no class_embed (not a CaptionODISE checkpoint)");
@@ -348,32 +335,27 @@ extern "C" int odise_hip_postprocess_pixels(odise_hip_ctx* ctx, int b, const flo
     if (counts) ODISE_CHECK_HIP(hipMemsetAsync(counts, 0, 3 * (size_t)ho.Q * sizeof(int), ctx->stream));
     int* cnt = counts;
     if (!cnt) {
-        cnt = (int*)ex.alloc_bytes(3 * (size_t)ho.Q * sizeof(int));
-        if (!cnt) return ODISE_ERR_NOMEM;
+        cnt = ex.buf<int>(3 * (size_t)ho.Q);
+        ODISE_TRY(ex.ok());
         ODISE_CHECK_HIP(hipMemsetAsync(cnt, 0, 3 * (size_t)ho.Q * sizeof(int), ctx->stream));
     }
     const f16* logits = ho.pred_masks + (size_t)b * ho.Q * ho.h4 * ho.w4;
     ODISE_TRY(launch_postprocess_pixels(ctx, logits, kscore, S, ids, cnt, g));
     if (sem_seg && semT) {
         // sem_seg[c, p] = sum_q softmax(mask_cls)[q, c] * sigmoid(mask)[q, p]   (maskformer_model.py:280-284) as an MFMA GEMM
-        f16* A = (f16*)ex.alloc_bytes((size_t)K * g.Qpad * 2);
-        if (!A) return ODISE_ERR_NOMEM;
+        f16* A = ex.buf<f16>((size_t)K * g.Qpad);
+        ODISE_TRY(ex.ok());
         ODISE_CHECK_HIP(hipMemsetAsync(A, 0, (size_t)K * g.Qpad * 2, ctx->stream));
         // semT fp32 [K, Q] -> fp16 [K, Qpad] (row pitch change via 2D copy is not possible with a dtype change: cast row-wise)
-        f16* tmp = (f16*)ex.alloc_bytes((size_t)K * ho.Q * 2);
-        if (!tmp) return ODISE_ERR_NOMEM;
+        f16* tmp = ex.buf<f16>((size_t)K * ho.Q);
+        ODISE_TRY(ex.ok());
         ODISE_TRY(odise_hip_cast_f32_to_f16(ctx, semT, tmp, (size_t)K * ho.Q));
         ODISE_CHECK_HIP(hipMemcpy2DAsync(A, (size_t)g.Qpad * 2, tmp, (size_t)ho.Q * 2, (size_t)ho.Q * 2, K, hipMemcpyDeviceToDevice, ctx->stream));
-        odise_gemm_desc d;
-        memset(&d, 0, sizeof(d));
-        d.M = K; d.N = npix; d.K = g.Qpad;
-        d.A = A; d.lda = g.Qpad; d.W = S; d.ldw = g.Qpad;
-        d.C = sem_seg; d.ldc = npix; d.c_dtype = ODISE_F32; d.alpha = 1.f; d.batch = 1;
-        ODISE_TRY(ex.gemm(d));
+        ODISE_TRY(ex.linear_f32(A, K, LinW{S, nullptr, g.Qpad, npix}, sem_seg));   // the pixel-major S [npix, Qpad] is the "weight"
     }
     if (inst_stats) {
-        unsigned int* partial = (unsigned int*)ex.alloc_bytes((size_t)512 * 2 * g.Qpad * 4);
-        if (!partial) return ODISE_ERR_NOMEM;
+        unsigned int* partial = ex.buf<unsigned int>((size_t)512 * 2 * g.Qpad);
+        ODISE_TRY(ex.ok());
         ODISE_TRY(launch_column_stats(ctx, S, partial, inst_stats, npix, g.Qpad));
     }
     return ODISE_OK;
@@ -420,10 +402,10 @@ extern "C" int odise_hip_maskclip_embed(odise_hip_ctx* ctx, const float* image, 
     Exec ex{ctx, ms};
     ArenaScope scope(ms->arena);
     const int64_t MQ = (int64_t)B * Q, ldm = round_up(T, 8);
-    f16* logits16 = (f16*)ex.alloc_bytes((size_t)MQ * h * w * 2);
-    f16* ce = (f16*)ex.alloc_bytes((size_t)MQ * cdim * 2);
-    uint8_t* tmask = (uint8_t*)ex.alloc_bytes((size_t)B * (T + Q) * ldm);
-    if (!logits16 || !ce || !tmask) return ODISE_ERR_NOMEM;
+    f16* logits16 = ex.buf<f16>((size_t)MQ * h * w);
+    f16* ce = ex.buf<f16>((size_t)MQ * cdim);
+    uint8_t* tmask = ex.buf<uint8_t>((size_t)B * (T + Q) * ldm);
+    ODISE_TRY(ex.ok());
     ODISE_TRY(odise_hip_cast_f32_to_f16(ctx, pred_masks, logits16, (size_t)MQ * h * w));
     ODISE_TRY(launch_maskclip_token_mask(ctx, logits16, tmask, B, Q, h, w, S, patch, T, ldm));
     ODISE_TRY(maskclip_tower(ex, image, B, H, W, S, T, Q, tmask, ldm, ce, false));
@@ -574,11 +556,7 @@ extern "C" int odise_hip_postprocess_batch(odise_hip_ctx* ctx, const odise_post_
             side_pending = true;
         }
         if (sem && !fused_sem) {   // sem_seg[c, p] = sum_q softmax(mask_cls)[q, c] * sigmoid(mask)[q, p]  (maskformer_model.py:280-284) as an MFMA GEMM
-            odise_gemm_desc gd;
-            memset(&gd, 0, sizeof(gd));
-            gd.M = K; gd.N = npix; gd.K = Qpad;
-            gd.A = semT + (size_t)b * K * Qpad; gd.lda = Qpad; gd.W = S; gd.ldw = Qpad;
-            gd.C = sem; gd.ldc = npix; gd.c_dtype = ODISE_F32; gd.alpha = 1.f; gd.batch = 1;
+            const odise_gemm_desc gd = gemm_linear(semT + (size_t)b * K * Qpad, K, LinW{S, nullptr, Qpad, npix}, sem, ODISE_F32);   // S [npix, Qpad] is the "weight"
             // HBM-bound (K = Qpad ~ 104): per pixel 208 B of S in, 4 B x K out.  The cost model, fitted on MFMA-bound shapes, picks 64-row tiles
             // and every row tile re-reads the 218 MB matrix S (3x at K = 133); a 256-row tile covers up to 256 classes per pass over S - its
             // idle MFMA rows cost nothing here (measured: tools/post_bench.py).

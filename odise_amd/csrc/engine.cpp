@@ -247,19 +247,6 @@ int Exec::alloc_gn_stats(Act& a) {
     return a.gn_part ? ODISE_OK : ODISE_ERR_NOMEM;
 }
 
-int Exec::linear(const f16* x, int64_t M, const LinW& w, f16* y, int act, const f16* residual, bool geglu) {
-    odise_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.M = (int)M; d.N = w.out; d.K = w.in;
-    d.A = x; d.lda = w.in;
-    d.W = w.w; d.ldw = w.in;
-    d.C = y; d.ldc = geglu ? w.out / 2 : w.out; d.c_dtype = ODISE_F16;
-    d.bias_n = w.b;
-    d.residual = residual; d.ldr = d.ldc;
-    d.act = act; d.geglu = geglu ? 1 : 0; d.alpha = 1.f; d.batch = 1;
-    return gemm(d);
-}
-
 int Exec::group_norm(const Act& x, const NormW& w, Act& y, float eps, int act) {
     if (!y.p) ODISE_TRY(alloc(y, x.n, x.h, x.w, x.c));
     if (x.gn_part && x.gn_blocks > 0)  // the conv that wrote x already reduced it per channel and row block

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "common.h"
+#include "stage_desc.h"
 
 namespace odise {
 
@@ -175,20 +176,35 @@ struct Packer {
 struct Exec {
     odise_hip_ctx* ctx;
     ModelStore* ms;
+    int status = ODISE_OK;   // sticky: the first arena exhaustion of buf() (alloc_bytes has set the message)
     int alloc(Act& a, int n, int h, int w, int c);
     int alloc_gn_stats(Act& a);  // reserve the statistics buffer of an (already shaped) activation that a conv is about to write
     void* alloc_bytes(size_t bytes);
+    // `count` elements from the arena; a function takes its buffers one after the other and checks ok() once before it launches anything
+    template <class T>
+    T* buf(size_t count) {
+        T* p = (T*)alloc_bytes(count * sizeof(T));
+        if (!p) status = ODISE_ERR_NOMEM;
+        return p;
+    }
+    int ok() const { return status; }
 
     int conv(const Act& x, const ConvW& w, Act& y, int stride = 1, int pad = -1, bool upsample = false, const Act* residual = nullptr,
              const float* per_image_add = nullptr, int64_t pia_ld = 0, int act = ODISE_ACT_NONE, int pad_t = -1, int pad_l = -1,
              int oh = -1, int ow = -1);
-    // y[M, out] = act(x[M,in] W^T + b) (+ residual)
-    int linear(const f16* x, int64_t M, const LinW& w, f16* y, int act = ODISE_ACT_NONE, const f16* residual = nullptr,
-               bool geglu = false);
     int group_norm(const Act& x, const NormW& w, Act& y, float eps, int act);
     int layer_norm(const f16* x, f16* y, int64_t rows, const NormW& w, float eps);
-    int gemm(const odise_gemm_desc& d);
+    int gemm(const odise_gemm_desc& d);        // counts the MACs of every GEMM / attention below
     int attention(const odise_attn_desc& d);
+    // y[M, out] = act(x[M,in] W^T + b) (+ residual); linear_f32: the same into fp32
+    int linear(const f16* x, int64_t M, const LinW& w, f16* y, int act = ODISE_ACT_NONE, const f16* residual = nullptr, bool geglu = false) {
+        return gemm(gemm_linear(x, M, w, y, ODISE_F16, act, residual, geglu));
+    }
+    int linear_f32(const f16* x, int64_t M, const LinW& w, float* y) { return gemm(gemm_linear(x, M, w, y, ODISE_F32)); }
+    // V^T[b] = Wv x[b]^T + bias_m -> [B, out, ldvt]
+    int vt(const LinW& v, const float* bias_m, const f16* x, int B, int64_t L, int64_t ldvt, f16* out) {
+        return gemm(gemm_vt(v, bias_m, x, B, L, ldvt, out));
+    }
 };
 
 

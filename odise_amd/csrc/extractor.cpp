@@ -378,34 +378,18 @@ static int run_vae_attn(Exec& ex, const VaeAttn& w, const Act& x, Act& out) {
     ODISE_TRY(ex.group_norm(x, w.norm, t, 1e-6f, ODISE_ACT_NONE));
     const int64_t ldv = round_up(HW, 8);
     ODISE_REQUIRE(HW % 8 == 0, "vae attention: H*W=%lld must be a multiple of 8", (long long)HW);
-    f16* qk = (f16*)ex.alloc_bytes((size_t)M * 2 * C * 2);
-    f16* vt = (f16*)ex.alloc_bytes((size_t)x.n * C * ldv * 2);
-    f16* S = (f16*)ex.alloc_bytes((size_t)x.n * HW * ldv * 2);
-    f16* o = (f16*)ex.alloc_bytes((size_t)M * C * 2);
-    if (!qk || !vt || !S || !o) return ODISE_ERR_NOMEM;
+    f16* qk = ex.buf<f16>((size_t)M * 2 * C);
+    f16* vt = ex.buf<f16>((size_t)x.n * C * ldv);
+    f16* S = ex.buf<f16>((size_t)x.n * HW * ldv);
+    f16* o = ex.buf<f16>((size_t)M * C);
+    ODISE_TRY(ex.ok());
     ODISE_TRY(ex.linear(t.p, M, w.qk, qk));
-    odise_gemm_desc d;
-    memset(&d, 0, sizeof(d));  // V^T[b] = Wv n[b]^T + bv (bias along rows)
-    d.M = C; d.N = (int)HW; d.K = C;
-    d.A = w.v.w; d.lda = C; d.W = t.p; d.ldw = C; d.strideW = HW * C;
-    d.C = vt; d.ldc = ldv; d.strideC = (int64_t)C * ldv; d.c_dtype = ODISE_F16;
-    d.bias_m = w.v_bias; d.alpha = 1.f; d.batch = x.n;
-    ODISE_TRY(ex.gemm(d));
-    memset(&d, 0, sizeof(d));  // S[b] = q[b] k[b]^T * C^-0.5
-    d.M = (int)HW; d.N = (int)HW; d.K = C;
-    d.A = qk; d.lda = 2 * C; d.strideA = HW * 2 * C;
-    d.W = qk + C; d.ldw = 2 * C; d.strideW = HW * 2 * C;
-    d.C = S; d.ldc = ldv; d.strideC = HW * ldv; d.c_dtype = ODISE_F16;
-    d.alpha = 1.0f / sqrtf((float)C); d.batch = x.n;
-    ODISE_TRY(ex.gemm(d));
+    ODISE_TRY(ex.vt(w.v, w.v_bias, t.p, x.n, HW, ldv, vt));  // V^T[b] = Wv n[b]^T + bv (bias along rows)
+    // S[b] = q[b] k[b]^T * C^-0.5
+    ODISE_TRY(ex.gemm(gemm_batched_nt(qk, 2 * C, HW * 2 * C, qk + C, 2 * C, HW * 2 * C, S, ldv, HW * ldv, HW, HW, C, x.n, ODISE_F16, 1.0f / sqrtf((float)C))));
     ODISE_TRY(launch_softmax_rows(ex.ctx, S, S, (int64_t)x.n * HW, (int)HW, ldv, 1.0f));
-    memset(&d, 0, sizeof(d));  // o[b] = P[b] v[b]  (W operand = V^T)
-    d.M = (int)HW; d.N = C; d.K = (int)HW;
-    d.A = S; d.lda = ldv; d.strideA = HW * ldv;
-    d.W = vt; d.ldw = ldv; d.strideW = (int64_t)C * ldv;
-    d.C = o; d.ldc = C; d.strideC = HW * C; d.c_dtype = ODISE_F16;
-    d.alpha = 1.f; d.batch = x.n;
-    ODISE_TRY(ex.gemm(d));
+    // o[b] = P[b] v[b]  (W operand = V^T)
+    ODISE_TRY(ex.gemm(gemm_batched_nt(S, ldv, HW * ldv, vt, ldv, (int64_t)C * ldv, o, C, HW * C, HW, C, HW, x.n)));
     ODISE_TRY(ex.linear(o, M, w.proj, out.p, ODISE_ACT_NONE, x.p));
     ex.ms->arena.release(mk);
     return ODISE_OK;
@@ -435,14 +419,14 @@ int clip_tower(Exec& ex, const Act& img, int extra, const uint8_t* mask, int64_t
     const int64_t ldvt = kv ? kv->ldvt : M;
     const int Bk = kv ? kv_images : 0;   // leading images that only leave keys and values
     ODISE_REQUIRE(!kv || (extra == 0 && Bk >= 1 && Bk <= B && kv->B == Bk && kv->TP == TP), "clip_tower: key / value store laid out for another batch");
-    f16* x = (f16*)ex.alloc_bytes((size_t)M * Wd * 2);
-    f16* x2 = (f16*)ex.alloc_bytes((size_t)M * Wd * 2);
-    f16* n = (f16*)ex.alloc_bytes((size_t)M * Wd * 2);
-    f16* qk = kv ? kv->qk : (f16*)ex.alloc_bytes((size_t)M * 2 * Wd * 2);
-    f16* vt = kv ? kv->vt : (f16*)ex.alloc_bytes((size_t)Wd * ldvt * 2);
-    f16* att = (f16*)ex.alloc_bytes((size_t)M * Wd * 2);
-    f16* hid = (f16*)ex.alloc_bytes((size_t)M * 4 * Wd * 2);
-    if (!x || !x2 || !n || !qk || !vt || !att || !hid) return ODISE_ERR_NOMEM;
+    f16* x = ex.buf<f16>((size_t)M * Wd);
+    f16* x2 = ex.buf<f16>((size_t)M * Wd);
+    f16* n = ex.buf<f16>((size_t)M * Wd);
+    f16* qk = kv ? kv->qk : ex.buf<f16>((size_t)M * 2 * Wd);
+    f16* vt = kv ? kv->vt : ex.buf<f16>((size_t)Wd * ldvt);
+    f16* att = ex.buf<f16>((size_t)M * Wd);
+    f16* hid = ex.buf<f16>((size_t)M * 4 * Wd);
+    ODISE_TRY(ex.ok());
     if (TP > TA) ODISE_CHECK_HIP(hipMemsetAsync(att, 0, (size_t)M * Wd * 2, ex.ctx->stream));  // the attention never writes the tail rows: keep them finite
     ODISE_TRY(launch_clip_assemble(ex.ctx, patches.p, e->clip_cls, e->clip_pos, n, B, T, extra, TP, Wd));
     ODISE_TRY(ex.layer_norm(n, x, M, e->clip_ln_pre, 1e-5f));
@@ -460,21 +444,18 @@ int clip_tower(Exec& ex, const Act& img, int extra, const uint8_t* mask, int64_t
     const int P = Wd / kLnPartCols;
     float *part_a = nullptr, *part_b = nullptr, *fin = nullptr;
     if (fold) {
-        part_a = (float*)ex.alloc_bytes((size_t)M * P * 2 * sizeof(float));
-        part_b = (float*)ex.alloc_bytes((size_t)M * P * 2 * sizeof(float));
-        fin = (float*)ex.alloc_bytes((size_t)M * 2 * sizeof(float));
-        if (!part_a || !part_b || !fin) return ODISE_ERR_NOMEM;
+        part_a = ex.buf<float>((size_t)M * P * 2);
+        part_b = ex.buf<float>((size_t)M * P * 2);
+        fin = ex.buf<float>((size_t)M * 2);
+        ODISE_TRY(ex.ok());
     }
-    auto lin = [&](const f16* a, const LinW& w, f16* y, int act, const f16* residual, const LnEpi& ln) -> int {
-        odise_gemm_desc d;
-        memset(&d, 0, sizeof(d));
-        d.M = (int)M; d.N = w.out; d.K = w.in;
-        d.A = a; d.lda = w.in; d.W = w.w; d.ldw = w.in;
-        d.C = y; d.ldc = w.out; d.c_dtype = ODISE_F16;
-        d.bias_n = w.b; d.residual = residual; d.ldr = w.out;
-        d.act = act; d.alpha = 1.f; d.batch = 1;
+    // the folded GEMMs bypass Exec::gemm: they count their MACs here
+    auto gemm_folded = [&](const odise_gemm_desc& d, const LnEpi& ln) -> int {
         ex.ms->macs += (double)d.M * d.N * d.K;
         return gemm_ln(ex.ctx, &d, ln);
+    };
+    auto lin = [&](const f16* a, const LinW& w, f16* y, int act, const f16* residual, const LnEpi& ln) -> int {
+        return gemm_folded(gemm_linear(a, M, w, y, ODISE_F16, act, residual), ln);
     };
     bool first = true;
     int layer = 0;
@@ -486,45 +467,31 @@ int clip_tower(Exec& ex, const Act& img, int extra, const uint8_t* mask, int64_t
             vt = kv->vt + (size_t)layer * kv->vt_stride;
             ++layer;
         }
-        odise_gemm_desc d;
-        memset(&d, 0, sizeof(d));
-        d.M = Wd; d.N = (int)M; d.K = Wd;  // V^T of every image side by side (only its first T columns are ever read: the image tokens)
-        d.lda = Wd; d.ldw = Wd;
-        d.C = vt; d.ldc = ldvt; d.c_dtype = ODISE_F16;
-        d.alpha = 1.f; d.batch = 1;
+        // V^T of every image side by side, one GEMM (only its first T columns per image are ever read: the image tokens)
         if (folded1) {
             LnEpi l1;
             l1.part = part_b; l1.P = P; l1.inv_c = 1.f / (float)Wd; l1.eps = 1e-5f; l1.colsum = b.qk_cs; l1.final_out = fin;
             ODISE_TRY(lin(x, b.qk_f, qk, ODISE_ACT_NONE, nullptr, l1));
             LnEpi lv;   // swapped operands: the normalised tokens are the rows of W, (r1, rstd) finished by the q|k GEMM above
             lv.fin = fin; lv.rowsum = b.v_cs;
-            d.A = b.v_f.w; d.W = x; d.bias_m = b.v_f_bias;
-            ex.ms->macs += (double)d.M * d.N * d.K;
-            ODISE_TRY(gemm_ln(ex.ctx, &d, lv));
+            ODISE_TRY(gemm_folded(gemm_vt(b.v_f, b.v_f_bias, x, M, ldvt, vt), lv));
         } else {
             ODISE_TRY(ex.layer_norm(x, n, M, b.ln1, 1e-5f));
             ODISE_TRY(ex.linear(n, M, b.qk, qk));
-            d.A = b.v.w; d.W = n; d.bias_m = b.v_bias;
-            ODISE_TRY(ex.gemm(d));
+            ODISE_TRY(ex.gemm(gemm_vt(b.v, b.v_bias, n, M, ldvt, vt)));
         }
         const bool last = &b == &e->clip_blocks.back();
         if (kv && last && Bk == B) {
             ex.ms->arena.release(mk);
             return ODISE_OK;
         }
-        odise_attn_desc a;
-        memset(&a, 0, sizeof(a));
         // The plain tower's result is ln_post(x[:, 0]) (clip.py:196-206): of the LAST block only the class token's row is ever read, so its
         // attention has one query per image and its out-proj / MLP run on B rows instead of B x 577 (dead work of the reference is not executed:
         // no output bit depends on the other 576 rows; -0.3 ms on the step's critical lane)
         const bool cls_only = extra == 0 && last;
-        a.B = B; a.H = heads; a.Lq = cls_only ? 1 : TA; a.Lk = T; a.D = D;
-        a.Q = qk; a.ldq = 2 * Wd; a.strideQ = (int64_t)TP * 2 * Wd;
-        a.K = qk + Wd; a.ldk = 2 * Wd; a.strideK = (int64_t)TP * 2 * Wd;
-        a.Vt = vt; a.ldvt = ldvt; a.strideVt = TP;
-        a.O = att; a.ldo = Wd; a.strideO = (int64_t)TP * Wd;
-        if (extra > 0) { a.mask = mask; a.ldmask = ldm; a.strideMask = (int64_t)TA * ldm; }
-        a.scale = 1.0f / sqrtf((float)D);
+        attn_desc a(B, heads, cls_only ? 1 : TA, T, D);
+        a.qk_fused(qk, 2 * Wd, (int64_t)TP * 2 * Wd).vt(vt, ldvt, TP).o(att, Wd, (int64_t)TP * Wd);
+        if (extra > 0) a.mask(mask, ldm, (int64_t)TA * ldm);
         if (Bk > 0 && Bk < B) {
             // pictures and crops as two launches: the crops keep the grid the K / V^T-resident kernel wants ((head, image) pairs in whole rounds
             // of the chip, attn.hip attn_kvres_ok), the few pictures take the tiled kernel; in the last block the pictures are done
@@ -542,25 +509,20 @@ int clip_tower(Exec& ex, const Act& img, int extra, const uint8_t* mask, int64_t
         if (cls_only) {
             const int Bc = B - Bk;   // the images that have an output
             const size_t skip = (size_t)Bk * TP * Wd;
-            f16* x2c = (f16*)ex.alloc_bytes((size_t)Bc * Wd * 2);
-            f16* nc = (f16*)ex.alloc_bytes((size_t)Bc * Wd * 2);
-            f16* hc = (f16*)ex.alloc_bytes((size_t)Bc * 4 * Wd * 2);
-            f16* xc = (f16*)ex.alloc_bytes((size_t)Bc * Wd * 2);
-            if (!x2c || !nc || !hc || !xc) return ODISE_ERR_NOMEM;
-            memset(&d, 0, sizeof(d));   // x2[cls] = x[cls] + attn[cls] Wo^T + bo: the row stride TP*Wd picks token 0 of every image
-            d.M = Bc; d.N = Wd; d.K = Wd;
-            d.A = att + skip; d.lda = (int64_t)TP * Wd; d.W = b.out.w; d.ldw = Wd;
-            d.C = x2c; d.ldc = Wd; d.c_dtype = ODISE_F16; d.bias_n = b.out.b;
-            d.residual = x + skip; d.ldr = (int64_t)TP * Wd; d.alpha = 1.f; d.batch = 1;
+            f16* x2c = ex.buf<f16>((size_t)Bc * Wd);
+            f16* nc = ex.buf<f16>((size_t)Bc * Wd);
+            f16* hc = ex.buf<f16>((size_t)Bc * 4 * Wd);
+            f16* xc = ex.buf<f16>((size_t)Bc * Wd);
+            ODISE_TRY(ex.ok());
+            // x2[cls] = x[cls] + attn[cls] Wo^T + bo: the row stride TP*Wd picks token 0 of every image
+            odise_gemm_desc d = gemm_linear(att + skip, Bc, b.out, x2c, ODISE_F16, ODISE_ACT_NONE, x + skip);
+            d.lda = d.ldr = (int64_t)TP * Wd;
             ODISE_TRY(ex.gemm(d));
             ODISE_TRY(ex.layer_norm(x2c, nc, Bc, b.ln2, 1e-5f));
             ODISE_TRY(ex.linear(nc, Bc, b.fc, hc, ODISE_ACT_QUICKGELU));
             ODISE_TRY(ex.linear(hc, Bc, b.proj, xc, ODISE_ACT_NONE, x2c));
             ODISE_TRY(ex.layer_norm(xc, nc, Bc, e->clip_ln_post, 1e-5f));
-            memset(&d, 0, sizeof(d));
-            d.M = Bc; d.N = e->clip_out; d.K = Wd; d.A = nc; d.lda = Wd; d.W = e->clip_proj.w; d.ldw = Wd;
-            d.C = out; d.ldc = e->clip_out; d.c_dtype = ODISE_F16; d.alpha = 1.f; d.batch = 1;
-            ODISE_TRY(ex.gemm(d));
+            ODISE_TRY(ex.linear(nc, Bc, e->clip_proj, out));
             ex.ms->arena.release(mk);
             return ODISE_OK;
         }
@@ -580,17 +542,14 @@ int clip_tower(Exec& ex, const Act& img, int extra, const uint8_t* mask, int64_t
         }
     }
     ODISE_TRY(ex.layer_norm(x, n, M, e->clip_ln_post, 1e-5f));
-    odise_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.N = e->clip_out; d.K = Wd; d.W = e->clip_proj.w; d.ldw = Wd;
-    d.C = out; d.ldc = e->clip_out; d.c_dtype = ODISE_F16; d.alpha = 1.f;
     if (extra == 0) {  // class token of every image: row stride TP*Wd picks token 0
-        d.M = B; d.A = n; d.lda = (int64_t)TP * Wd; d.batch = 1;
+        odise_gemm_desc d = gemm_linear(n, B, e->clip_proj, out);
+        d.lda = (int64_t)TP * Wd;
+        ODISE_TRY(ex.gemm(d));
     } else {           // the mask tokens of image b are rows T .. T+extra-1 of its block
-        d.M = extra; d.A = n + (size_t)T * Wd; d.lda = Wd; d.strideA = (int64_t)TP * Wd;
-        d.strideC = (int64_t)extra * e->clip_out; d.batch = B;
+        ODISE_TRY(ex.gemm(gemm_batched_nt(n + (size_t)T * Wd, Wd, (int64_t)TP * Wd, e->clip_proj.w, Wd, 0, out, e->clip_out, (int64_t)extra * e->clip_out, extra,
+                                          e->clip_out, Wd, B)));
     }
-    ODISE_TRY(ex.gemm(d));
     ex.ms->arena.release(mk);
     return ODISE_OK;
 }
@@ -647,13 +606,13 @@ int maskclip_mask_pass(Exec& ex, int Q, const uint8_t* mask, int64_t ldm, int64_
     ODISE_REQUIRE(kv.buf.ptr && kv.layers == (int)e->clip_blocks.size() && kv.width == Wd, "maskclip: the image-token pass has not run for this tower");
     const int64_t M = (int64_t)B * Q;
     const size_t mk = ex.ms->arena.mark();
-    f16* x = (f16*)ex.alloc_bytes((size_t)M * Wd * 2);
-    f16* x2 = (f16*)ex.alloc_bytes((size_t)M * Wd * 2);
-    f16* n = (f16*)ex.alloc_bytes((size_t)M * Wd * 2);
-    f16* q = (f16*)ex.alloc_bytes((size_t)M * Wd * 2);
-    f16* att = (f16*)ex.alloc_bytes((size_t)M * Wd * 2);
-    f16* hid = (f16*)ex.alloc_bytes((size_t)M * 4 * Wd * 2);
-    if (!x || !x2 || !n || !q || !att || !hid) return ODISE_ERR_NOMEM;
+    f16* x = ex.buf<f16>((size_t)M * Wd);
+    f16* x2 = ex.buf<f16>((size_t)M * Wd);
+    f16* n = ex.buf<f16>((size_t)M * Wd);
+    f16* q = ex.buf<f16>((size_t)M * Wd);
+    f16* att = ex.buf<f16>((size_t)M * Wd);
+    f16* hid = ex.buf<f16>((size_t)M * 4 * Wd);
+    ODISE_TRY(ex.ok());
     ODISE_TRY(launch_broadcast_rows(ex.ctx, kv.cls, x, Wd, (int)M));
     int layer = 0;
     for (const ClipBlock& b : e->clip_blocks) {
@@ -661,16 +620,8 @@ int maskclip_mask_pass(Exec& ex, int Q, const uint8_t* mask, int64_t ldm, int64_
         LinW wq = b.qk;   // the query rows of the fused q|k projection
         wq.out = Wd;
         ODISE_TRY(ex.linear(n, M, wq, q));
-        odise_attn_desc a;
-        memset(&a, 0, sizeof(a));
-        a.B = B; a.H = heads; a.Lq = Q; a.Lk = T; a.D = D;
-        a.Q = q; a.ldq = Wd; a.strideQ = (int64_t)Q * Wd;
-        a.K = kv.qk + (size_t)layer * kv.qk_stride + Wd; a.ldk = 2 * Wd; a.strideK = (int64_t)TP * 2 * Wd;
-        a.Vt = kv.vt + (size_t)layer * kv.vt_stride; a.ldvt = kv.ldvt; a.strideVt = TP;
-        a.O = att; a.ldo = Wd; a.strideO = (int64_t)Q * Wd;
-        a.mask = mask; a.ldmask = ldm; a.strideMask = stride_mask;
-        a.scale = 1.0f / sqrtf((float)D);
-        ODISE_TRY(ex.attention(a));
+        ODISE_TRY(ex.attention(attn_desc(B, heads, Q, T, D).q(q, Wd, (int64_t)Q * Wd).k(kv.qk + (size_t)layer * kv.qk_stride + Wd, 2 * Wd, (int64_t)TP * 2 * Wd)
+                                   .vt(kv.vt + (size_t)layer * kv.vt_stride, kv.ldvt, TP).o(att, Wd, (int64_t)Q * Wd).mask(mask, ldm, stride_mask)));
         ODISE_TRY(ex.linear(att, M, b.out, x2, ODISE_ACT_NONE, x));          // x2 = x + attn
         ODISE_TRY(ex.layer_norm(x2, n, M, b.ln2, 1e-5f));
         ODISE_TRY(ex.linear(n, M, b.fc, hid, ODISE_ACT_QUICKGELU));
@@ -678,11 +629,7 @@ int maskclip_mask_pass(Exec& ex, int Q, const uint8_t* mask, int64_t ldm, int64_
         ++layer;
     }
     ODISE_TRY(ex.layer_norm(x, n, M, e->clip_ln_post, 1e-5f));
-    odise_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.M = (int)M; d.N = e->clip_out; d.K = Wd; d.A = n; d.lda = Wd; d.W = e->clip_proj.w; d.ldw = Wd;
-    d.C = out; d.ldc = e->clip_out; d.c_dtype = ODISE_F16; d.alpha = 1.f; d.batch = 1;
-    ODISE_TRY(ex.gemm(d));
+    ODISE_TRY(ex.linear(n, M, e->clip_proj, out));
     ex.ms->arena.release(mk);
     return ODISE_OK;
 }
@@ -882,24 +829,15 @@ int extractor_launch(odise_hip_ctx* ctx, ModelStore* ms, const float* image, int
     float* cond_inputs = nullptr;
     float* cond_emb = nullptr;
     auto conditioning = [&]() -> int {
-        f16* prefix16 = (f16*)ex.alloc_bytes((size_t)B * e->clip_out * 2);
-        float* proj = (float*)ex.alloc_bytes((size_t)B * e->ctx_dim * 4);
-        cond_inputs = (float*)ex.alloc_bytes((size_t)B * 77 * e->ctx_dim * 4);
-        cond_emb = (float*)ex.alloc_bytes((size_t)B * e->ted * 4);
-        if (!prefix16 || !proj || !cond_inputs || !cond_emb) return ODISE_ERR_NOMEM;
+        f16* prefix16 = ex.buf<f16>((size_t)B * e->clip_out);
+        float* proj = ex.buf<float>((size_t)B * e->ctx_dim);
+        cond_inputs = ex.buf<float>((size_t)B * 77 * e->ctx_dim);
+        cond_emb = ex.buf<float>((size_t)B * e->ted);
+        ODISE_TRY(ex.ok());
         ODISE_TRY(run_clip(ex, e, image, B, H, W, prefix16));
-        odise_gemm_desc d;
-        memset(&d, 0, sizeof(d));
-        d.M = B; d.N = e->ctx_dim; d.K = e->cap_proj.in;
-        d.A = prefix16; d.lda = e->cap_proj.in; d.W = e->cap_proj.w; d.ldw = e->cap_proj.in;
-        d.C = proj; d.ldc = e->ctx_dim; d.c_dtype = ODISE_F32; d.bias_n = e->cap_proj.b; d.alpha = 1.f; d.batch = 1;
-        ODISE_TRY(ex.gemm(d));
+        ODISE_TRY(ex.linear_f32(prefix16, B, e->cap_proj, proj));
         ODISE_TRY(launch_cond_inputs(ctx, proj, e->cap_A1, e->cap_A2, cond_inputs, B, 77, e->ctx_dim));
-        memset(&d, 0, sizeof(d));
-        d.M = B; d.N = e->ted; d.K = e->cap_time.in;
-        d.A = prefix16; d.lda = e->cap_time.in; d.W = e->cap_time.w; d.ldw = e->cap_time.in;
-        d.C = cond_emb; d.ldc = e->ted; d.c_dtype = ODISE_F32; d.bias_n = e->cap_time.b; d.alpha = 1.f; d.batch = 1;
-        return ex.gemm(d);
+        return ex.linear_f32(prefix16, B, e->cap_time, cond_emb);
     };
     // ENQUEUE ORDER (two lanes).  The host issues ~1600 launches per step at roughly 20 us each, so the order in which the two lanes are
     // fed decides whether they overlap at all: with the ~450 launches of the CLIP tower enqueued first, the VAE encoder's first kernel

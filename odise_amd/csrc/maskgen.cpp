@@ -404,9 +404,9 @@ static int prefetch_enqueue(odise_hip_ctx* ctx, ModelStore* ms, MaskGenModel* g)
         ODISE_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_pf_go, 0));
         ms->arena.reset();
         Exec ex{ctx, ms};
-        float* padded = (float*)ex.alloc_bytes((size_t)B * 3 * Hp * Wp * 4);
-        float* crops = (float*)ex.alloc_bytes((size_t)n * 3 * S * S * 4);
-        if (!padded || !crops) return ODISE_ERR_NOMEM;
+        float* padded = ex.buf<float>((size_t)B * 3 * Hp * Wp);
+        float* crops = ex.buf<float>((size_t)n * 3 * S * S);
+        ODISE_TRY(ex.ok());
         for (int b = 0; b < B; ++b)
             ODISE_TRY(launch_image_pad(ctx, key.images[b], key.layout, key.hw[2 * b], key.hw[2 * b + 1], padded + (size_t)b * 3 * Hp * Wp, Hp, Wp));
         ODISE_TRY(launch_crop_extract(ctx, padded, crops, B, 3, Hp, Wp, S, K, hit->dev));
@@ -498,8 +498,8 @@ static int backbone_forward(odise_hip_ctx* ctx, const float* image, int B, int H
     // outputs first (they must outlive everything else of this call)
     for (int gi = 0; gi < 4; ++gi) ODISE_TRY(ex.alloc(g->feats[gi], B, H / kGroupStride[gi], W / kGroupStride[gi], g->proj_dim));
     const size_t mk = ms->arena.mark();
-    float* crops = (float*)ex.alloc_bytes((size_t)B * K * 3 * S * S * 4);
-    if (!crops) return ODISE_ERR_NOMEM;
+    float* crops = ex.buf<float>((size_t)B * K * 3 * S * S);
+    ODISE_TRY(ex.ok());
     if (cs == S) ODISE_TRY(launch_crop_extract(ctx, image, crops, B, 3, H, W, S, K, g->boxes_dev));
     else ODISE_TRY(launch_crop_resize_bicubic(ctx, image, crops, B, 3, H, W, cs, S, K, g->boxes_dev));   // windows below 512: bicubic to 512 x 512
     // The extractor leaves its second lane (CLIP -> UNet) un-joined: the projections of the VAE taps - the whole s2 group (enc5, dec5: the
@@ -560,26 +560,6 @@ static int copy_rows_2d(odise_hip_ctx* ctx, void* dst, size_t dpitch, const void
     return ODISE_OK;
 }
 
-static int gemm_f32out(Exec& ex, const f16* x, int64_t M, const LinW& w, float* y) {
-    odise_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.M = (int)M; d.N = w.out; d.K = w.in;
-    d.A = x; d.lda = w.in; d.W = w.w; d.ldw = w.in;
-    d.C = y; d.ldc = w.out; d.c_dtype = ODISE_F32; d.bias_n = w.b; d.alpha = 1.f; d.batch = 1;
-    return ex.gemm(d);
-}
-
-// V^T[b] = Wv x[b]^T + bv  -> [B, C, ldvt]
-static int gemm_vt(Exec& ex, const LinW& v, const float* v_bias, const f16* x, int B, int64_t L, int64_t ldvt, f16* vt) {
-    odise_gemm_desc d;
-    memset(&d, 0, sizeof(d));
-    d.M = v.out; d.N = (int)L; d.K = v.in;
-    d.A = v.w; d.lda = v.in; d.W = x; d.ldw = v.in; d.strideW = L * v.in;
-    d.C = vt; d.ldc = ldvt; d.strideC = (int64_t)v.out * ldvt; d.c_dtype = ODISE_F16;
-    d.bias_m = v_bias; d.alpha = 1.f; d.batch = B;
-    return ex.gemm(d);
-}
-
 static int mlp3(Exec& ex, const LinW* w, const f16* x, int64_t M, f16* t1, f16* t2, f16* y) {
     ODISE_TRY(ex.linear(x, M, w[0], t1, ODISE_ACT_RELU));
     ODISE_TRY(ex.linear(t1, M, w[1], t2, ODISE_ACT_RELU));
@@ -600,7 +580,7 @@ struct PixDec {
     bool kv_done = false, kv_on_lane2 = false;
 };
 
-static int ensure_pe_tables(odise_hip_ctx* ctx, ModelStore* ms, MaskGenModel* g, const int hs[3], const int ws[3]);
+static int ensure_pe_tables(odise_hip_ctx* ctx, MaskGenModel* g, const int hs[3], const int ws[3]);
 
 // The cross-attention keys and values of ALL decoder layers (odise.py:676-690: src + level_embed, pos; mask2former_transformer_decoder.py:95-118)
 // depend on the encoder output only: 2 x layers GEMMs that sat inside the layers' dependent chains (20-52 us of each) run here, once - on the
@@ -613,21 +593,20 @@ static int decoder_memory_projections(odise_hip_ctx* ctx, MaskGenModel* g, PixDe
     ODISE_REQUIRE(nl <= PixDec::kMaxDecLayers, "masked decoder: %d layers", nl);
     int hs[3], ws[3];
     for (int l = 0; l < 3; ++l) { hs[l] = pd.ms_feat[l].h; ws[l] = pd.ms_feat[l].w; }
-    ODISE_TRY(ensure_pe_tables(ctx, ms, g, hs, ws));
+    ODISE_TRY(ensure_pe_tables(ctx, g, hs, ws));
     f16* valin[3]; f16* keyin[3];
     for (int l = 0; l < 3; ++l) {
         const int64_t P = (int64_t)hs[l] * ws[l];
-        valin[l] = (f16*)ex.alloc_bytes((size_t)B * P * C * 2);
-        keyin[l] = (f16*)ex.alloc_bytes((size_t)B * P * C * 2);
-        if (!valin[l] || !keyin[l]) return ODISE_ERR_NOMEM;
+        valin[l] = ex.buf<f16>((size_t)B * P * C);
+        keyin[l] = ex.buf<f16>((size_t)B * P * C);
     }
     for (int i = 0; i < nl; ++i) {
         const int l = i % 3;
         const int64_t P = (int64_t)hs[l] * ws[l];
-        pd.kproj[i] = (f16*)ex.alloc_bytes((size_t)B * P * C * 2);
-        pd.vtproj[i] = (f16*)ex.alloc_bytes((size_t)B * C * round_up(P, 8) * 2);
-        if (!pd.kproj[i] || !pd.vtproj[i]) return ODISE_ERR_NOMEM;
+        pd.kproj[i] = ex.buf<f16>((size_t)B * P * C);
+        pd.vtproj[i] = ex.buf<f16>((size_t)B * C * round_up(P, 8));
     }
+    ODISE_TRY(ex.ok());
     auto run = [&]() -> int {
         for (int l = 0; l < 3; ++l) {
             const int64_t P = (int64_t)hs[l] * ws[l];
@@ -639,7 +618,7 @@ static int decoder_memory_projections(odise_hip_ctx* ctx, MaskGenModel* g, PixDe
             const int l = i % 3;
             const int64_t P = (int64_t)hs[l] * ws[l];
             ODISE_TRY(ex.linear(keyin[l], B * P, L.cross.k, pd.kproj[i]));
-            ODISE_TRY(gemm_vt(ex, L.cross.v, L.cross.v_bias, valin[l], B, P, round_up(P, 8), pd.vtproj[i]));
+            ODISE_TRY(ex.vt(L.cross.v, L.cross.v_bias, valin[l], B, P, round_up(P, 8), pd.vtproj[i]));
         }
         return ODISE_OK;
     };
@@ -659,8 +638,7 @@ static int decoder_memory_projections(odise_hip_ctx* ctx, MaskGenModel* g, PixDe
 }
 
 // sine positional tables of the three transformer levels (shared by the pixel decoder's encoder and the predictor)
-static int ensure_pe_tables(odise_hip_ctx* ctx, ModelStore* ms, MaskGenModel* g, const int hs[3], const int ws[3]) {
-    (void)ms;
+static int ensure_pe_tables(odise_hip_ctx* ctx, MaskGenModel* g, const int hs[3], const int ws[3]) {
     const int C = g->C;
     MaskGenModel::PeEntry* hit = nullptr;
     for (auto& e : g->pe_cache) {
@@ -714,26 +692,26 @@ static int pixel_decoder_forward(odise_hip_ctx* ctx, const Act feats[4], PixDec&
     ModelStore* ms = store_of(ctx);
     MaskGenModel* g = ms->maskgen;
     Exec ex{ctx, ms};
-    const int C = g->C, B = feats[0].n, Q = g->Q;
+    const int C = g->C, B = feats[0].n;
     const int hs[3] = {feats[3].h, feats[2].h, feats[1].h}, ws[3] = {feats[3].w, feats[2].w, feats[1].w};  // s5, s4, s3
     int starts[3], Lq = 0;
     for (int l = 0; l < 3; ++l) { starts[l] = Lq; Lq += hs[l] * ws[l]; }
-    ODISE_TRY(ensure_pe_tables(ctx, ms, g, hs, ws));
+    ODISE_TRY(ensure_pe_tables(ctx, g, hs, ws));
     const int64_t MT = (int64_t)B * Lq;
     // ---- pixel decoder: input_proj (1x1 + GN) into one [B, Lq, C] token matrix ----------------------------------------------
-    f16* src = (f16*)ex.alloc_bytes((size_t)MT * C * 2);
-    f16* qin = (f16*)ex.alloc_bytes((size_t)MT * C * 2);
-    f16* x1 = (f16*)ex.alloc_bytes((size_t)MT * C * 2);
-    f16* val = (f16*)ex.alloc_bytes((size_t)MT * C * 2);
-    f16* samp = (f16*)ex.alloc_bytes((size_t)MT * C * 2);
-    f16* hid = (f16*)ex.alloc_bytes((size_t)MT * g->enc_layers[0].lin1.out * 2);
+    f16* src = ex.buf<f16>((size_t)MT * C);
+    f16* qin = ex.buf<f16>((size_t)MT * C);
+    f16* x1 = ex.buf<f16>((size_t)MT * C);
+    f16* val = ex.buf<f16>((size_t)MT * C);
+    f16* samp = ex.buf<f16>((size_t)MT * C);
+    f16* hid = ex.buf<f16>((size_t)MT * g->enc_layers[0].lin1.out);
     const int M8 = g->enc_heads, LP = 3 * g->enc_points;
-    float* offaw = (float*)ex.alloc_bytes((size_t)MT * M8 * LP * 3 * 4);   // [MT, 2 MLP | MLP] of the stacked projection; the separate forms use its two parts
+    float* offaw = ex.buf<float>((size_t)MT * M8 * LP * 3);   // [MT, 2 MLP | MLP] of the stacked projection; the separate forms use its two parts
+    float* loc = ex.buf<float>((size_t)MT * M8 * LP * 2);
+    float* wts = ex.buf<float>((size_t)MT * M8 * LP);
+    ODISE_TRY(ex.ok());
     float* off = offaw;
-    float* aw = offaw ? offaw + (size_t)MT * M8 * LP * 2 : nullptr;
-    float* loc = (float*)ex.alloc_bytes((size_t)MT * M8 * LP * 2 * 4);
-    float* wts = (float*)ex.alloc_bytes((size_t)MT * M8 * LP * 4);
-    if (!src || !qin || !x1 || !val || !samp || !hid || !off || !aw || !loc || !wts) return ODISE_ERR_NOMEM;
+    float* aw = offaw + (size_t)MT * M8 * LP * 2;
     for (int l = 0; l < 3; ++l) {
         const Act& f = feats[3 - l];
         const size_t mk = ms->arena.mark();
@@ -756,11 +734,11 @@ static int pixel_decoder_forward(odise_hip_ctx* ctx, const Act feats[4], PixDec&
         ODISE_TRY(ex.linear(src, MT, L.value, val));
         if (fused_msda && L.offaw.w) {
             const int nof = L.off.out, ld = L.offaw.out;
-            ODISE_TRY(gemm_f32out(ex, qin, MT, L.offaw, offaw));
+            ODISE_TRY(ex.linear_f32(qin, MT, L.offaw, offaw));
             ODISE_TRY(launch_msda_fused(ctx, val, offaw, offaw + nof, samp, hs, ws, starts, B, Lq, M8, Lq, ld, ld));
         } else {
-            ODISE_TRY(gemm_f32out(ex, qin, MT, L.off, off));
-            ODISE_TRY(gemm_f32out(ex, qin, MT, L.aw, aw));
+            ODISE_TRY(ex.linear_f32(qin, MT, L.off, off));
+            ODISE_TRY(ex.linear_f32(qin, MT, L.aw, aw));
             if (fused_msda) {
                 ODISE_TRY(launch_msda_fused(ctx, val, off, aw, samp, hs, ws, starts, B, Lq, M8, Lq));
             } else {
@@ -795,14 +773,13 @@ static int pixel_decoder_forward(odise_hip_ctx* ctx, const Act feats[4], PixDec&
     ODISE_TRY(ex.conv(fsum, g->layer1, o3, 1, 1));
     ODISE_TRY(ex.group_norm(o3, g->layer1_gn, o3n, 1e-5f, ODISE_ACT_RELU));
     ODISE_TRY(ex.conv(o3n, g->mask_feat, mf, 1, 0));                     // [B, HW4, C]  (pixel-major: W operand of the mask-logit GEMM)
-    f16* mfT = (f16*)ex.alloc_bytes((size_t)B * C * HW4 * 2);            // [B, C, HW4] (channel-major: W operand of the pooling GEMM)
-    if (!mfT) return ODISE_ERR_NOMEM;
+    f16* mfT = ex.buf<f16>((size_t)B * C * HW4);                         // [B, C, HW4] (channel-major: W operand of the pooling GEMM)
+    ODISE_TRY(ex.ok());
     {
         LinW v; v.w = g->mask_feat_wT; v.in = C; v.out = g->mask_feat.cout; v.b = nullptr;
-        ODISE_TRY(gemm_vt(ex, v, g->mask_feat.b, o3n.p, B, HW4, HW4, mfT));
+        ODISE_TRY(ex.vt(v, g->mask_feat.b, o3n.p, B, HW4, HW4, mfT));
     }
     pd.mfT = mfT; pd.h4 = s2.h; pd.w4 = s2.w;
-    (void)Q;
     return ODISE_OK;
 }
 
@@ -813,8 +790,7 @@ static int predictor_forward(odise_hip_ctx* ctx, PixDec& pd) {
     Exec ex{ctx, ms};
     const int C = g->C, B = pd.ms_feat[0].n, Q = g->Q;
     const int hs[3] = {pd.ms_feat[0].h, pd.ms_feat[1].h, pd.ms_feat[2].h}, ws[3] = {pd.ms_feat[0].w, pd.ms_feat[1].w, pd.ms_feat[2].w};
-    ODISE_TRY(ensure_pe_tables(ctx, ms, g, hs, ws));
-    const Act (&ms_feat)[3] = pd.ms_feat;
+    ODISE_TRY(ensure_pe_tables(ctx, g, hs, ws));
     const Act& mf = pd.mf;
     f16* mfT = pd.mfT;
     struct { int h, w; } s2{pd.h4, pd.w4};
@@ -829,54 +805,44 @@ static int predictor_forward(odise_hip_ctx* ctx, PixDec& pd) {
     // kernel per layer on the serial tail); only the final prediction is computed at H/4 x W/4.
     f16* mfl[3];
     for (int l = 0; l < 3; ++l) {
-        mfl[l] = (f16*)ex.alloc_bytes((size_t)B * hs[l] * ws[l] * C * 2);
-        if (!mfl[l]) return ODISE_ERR_NOMEM;
+        mfl[l] = ex.buf<f16>((size_t)B * hs[l] * ws[l] * C);
+        ODISE_TRY(ex.ok());
         ODISE_TRY(launch_bilinear_add(ctx, nullptr, mf.p, mfl[l], B, s2.h, s2.w, hs[l], ws[l], C));
     }
     const int64_t maxP = (int64_t)hs[2] * ws[2];
     const int64_t ldm = round_up(maxP, 8);
-    f16* out = (f16*)ex.alloc_bytes((size_t)MQ * C * 2);
-    f16* tq = (f16*)ex.alloc_bytes((size_t)MQ * C * 2);
-    f16* tqe = (f16*)ex.alloc_bytes((size_t)MQ * C * 2);
-    f16* t1 = (f16*)ex.alloc_bytes((size_t)MQ * 2048 * 2);
-    f16* t2 = (f16*)ex.alloc_bytes((size_t)MQ * 2 * C * 2);
-    f16* dn = (f16*)ex.alloc_bytes((size_t)MQ * C * 2);
-    f16* me = (f16*)ex.alloc_bytes((size_t)MQ * C * 2);
-    f16* att = (f16*)ex.alloc_bytes((size_t)MQ * C * 2);
-    f16* qb = (f16*)ex.alloc_bytes((size_t)MQ * 2 * C * 2);
-    f16* vtb = (f16*)ex.alloc_bytes((size_t)B * C * round_up(Q, 8) * 2);   // V^T of the queries' self-attention
-    float* lgl = (float*)ex.alloc_bytes((size_t)MQ * maxP * 4);              // prediction at the next layer's level: the GEMM's fp32 accumulators (its sign is the decision)
-    f16* masks = (f16*)ex.alloc_bytes((size_t)MQ * HW4 * 2);
-    uint8_t* amask = (uint8_t*)ex.alloc_bytes((size_t)MQ * ldm);
-    f16* m01 = (f16*)ex.alloc_bytes((size_t)MQ * HW4 * 2);
-    float* inv = (float*)ex.alloc_bytes((size_t)MQ * 4);
-    f16* pooled = (f16*)ex.alloc_bytes((size_t)MQ * C * 2);
-    f16* pooled_x = (f16*)ex.alloc_bytes((size_t)MQ * C * 2);
-    f16* mask_embed = (f16*)ex.alloc_bytes((size_t)MQ * C * 2);
-    if (!out || !tq || !tqe || !t1 || !t2 || !dn || !me || !att || !qb || !lgl || !vtb || !masks || !amask || !m01 || !inv || !pooled || !pooled_x ||
-        !mask_embed)
-        return ODISE_ERR_NOMEM;
+    f16* out = ex.buf<f16>((size_t)MQ * C);
+    f16* tq = ex.buf<f16>((size_t)MQ * C);
+    f16* tqe = ex.buf<f16>((size_t)MQ * C);
+    f16* t1 = ex.buf<f16>((size_t)MQ * 2048);
+    f16* t2 = ex.buf<f16>((size_t)MQ * 2 * C);
+    f16* dn = ex.buf<f16>((size_t)MQ * C);
+    f16* me = ex.buf<f16>((size_t)MQ * C);
+    f16* att = ex.buf<f16>((size_t)MQ * C);
+    f16* qb = ex.buf<f16>((size_t)MQ * 2 * C);
+    f16* vtb = ex.buf<f16>((size_t)B * C * round_up(Q, 8));   // V^T of the queries' self-attention
+    float* lgl = ex.buf<float>((size_t)MQ * maxP);            // prediction at the next layer's level: the GEMM's fp32 accumulators (its sign is the decision)
+    f16* masks = ex.buf<f16>((size_t)MQ * HW4);
+    uint8_t* amask = ex.buf<uint8_t>((size_t)MQ * ldm);
+    f16* m01 = ex.buf<f16>((size_t)MQ * HW4);
+    float* inv = ex.buf<float>((size_t)MQ);
+    f16* pooled = ex.buf<f16>((size_t)MQ * C);
+    f16* pooled_x = ex.buf<f16>((size_t)MQ * C);
+    f16* mask_embed = ex.buf<f16>((size_t)MQ * C);
+    ODISE_TRY(ex.ok());
     // output = query_feat broadcast over the batch
     ODISE_TRY(launch_broadcast_rows(ctx, g->query_feat16, out, (int64_t)Q * C, B));
 
     auto prediction_heads = [&](int target_level) -> int {  // forward_prediction_heads (odise.py:729-776), mask branch only
         ODISE_TRY(ex.layer_norm(out, dn, MQ, g->decoder_norm, 1e-5f));
         ODISE_TRY(mlp3(ex, g->mask_mlp, dn, MQ, t1, t2, me));
-        odise_gemm_desc d;
-        memset(&d, 0, sizeof(d));  // outputs_mask[b] = mask_embed[b] (Q x C) . mask_features[b]^T (HW4 x C)
-        d.M = Q; d.K = C;
-        d.A = me; d.lda = C; d.strideA = (int64_t)Q * C;
-        d.ldw = C; d.c_dtype = ODISE_F16; d.alpha = 1.f; d.batch = B;
+        // outputs_mask[b] = mask_embed[b] (Q x C) . mask_features[b]^T (HW4 x C)
         if (target_level >= 0) {   // ... at the level the next layer attends to
             const int64_t P = (int64_t)hs[target_level] * ws[target_level];
-            d.N = (int)P; d.W = mfl[target_level]; d.strideW = P * C;
-            d.C = lgl; d.ldc = P; d.strideC = (int64_t)Q * P; d.c_dtype = ODISE_F32;
-            ODISE_TRY(ex.gemm(d));
+            ODISE_TRY(ex.gemm(gemm_batched_nt(me, C, (int64_t)Q * C, mfl[target_level], C, P * C, lgl, P, (int64_t)Q * P, Q, P, C, B, ODISE_F32)));
             ODISE_TRY(launch_attn_mask_f32(ctx, lgl, amask, MQ, hs[target_level], ws[target_level], hs[target_level], ws[target_level], ldm));
         } else {                   // the final prediction
-            d.N = (int)HW4; d.W = mf.p; d.strideW = HW4 * C;
-            d.C = masks; d.ldc = HW4; d.strideC = (int64_t)Q * HW4;
-            ODISE_TRY(ex.gemm(d));
+            ODISE_TRY(ex.gemm(gemm_batched_nt(me, C, (int64_t)Q * C, mf.p, C, HW4 * C, masks, HW4, (int64_t)Q * HW4, Q, HW4, C, B)));
         }
         return ODISE_OK;
     };
@@ -892,30 +858,15 @@ static int predictor_forward(odise_hip_ctx* ctx, PixDec& pd) {
         if (i == 0) ODISE_TRY(launch_add_vec_table(ctx, out, nullptr, g->query_embed, tqe, B, Q, C));
         ODISE_TRY(ex.linear(tqe, MQ, L.cross.q, qb));
         if (i == 0 && pd.kv_on_lane2) ODISE_CHECK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));   // the keys / values of every layer (decoder_memory_projections)
-        odise_attn_desc a;
-        memset(&a, 0, sizeof(a));
-        a.B = B; a.H = heads; a.Lq = Q; a.Lk = (int)P; a.D = D;
-        a.Q = qb; a.ldq = C; a.strideQ = (int64_t)Q * C;
-        a.K = pd.kproj[i]; a.ldk = C; a.strideK = P * C;
-        a.Vt = pd.vtproj[i]; a.ldvt = ldv; a.strideVt = (int64_t)C * ldv;
-        a.O = att; a.ldo = C; a.strideO = (int64_t)Q * C;
-        a.mask = amask; a.ldmask = ldm; a.strideMask = (int64_t)Q * ldm;
-        a.scale = 1.0f / sqrtf((float)D);
-        ODISE_TRY(ex.attention(a));
+        ODISE_TRY(ex.attention(attn_desc(B, heads, Q, P, D).q(qb, C, (int64_t)Q * C).k(pd.kproj[i], C, P * C).vt(pd.vtproj[i], ldv, (int64_t)C * ldv)
+                                   .o(att, C, (int64_t)Q * C).mask(amask, ldm, (int64_t)Q * ldm)));
         ODISE_TRY(ex.linear(att, MQ, L.cross.out, tq, ODISE_ACT_NONE, out));
         ODISE_TRY(layer_norm_add_table(ctx, tq, out, L.cross.norm.g, L.cross.norm.b, (int)MQ, C, 1e-5f, tqe, g->query_embed, Q));
         // self-attention over the queries
         ODISE_TRY(ex.linear(tqe, MQ, L.self.qk, qb));
         const int64_t ldq = round_up(Q, 8);
-        ODISE_TRY(gemm_vt(ex, L.self.v, L.self.v_bias, out, B, Q, ldq, vtb));
-        memset(&a, 0, sizeof(a));
-        a.B = B; a.H = heads; a.Lq = Q; a.Lk = Q; a.D = D;
-        a.Q = qb; a.ldq = 2 * C; a.strideQ = (int64_t)Q * 2 * C;
-        a.K = qb + C; a.ldk = 2 * C; a.strideK = (int64_t)Q * 2 * C;
-        a.Vt = vtb; a.ldvt = ldq; a.strideVt = (int64_t)C * ldq;
-        a.O = att; a.ldo = C; a.strideO = (int64_t)Q * C;
-        a.scale = 1.0f / sqrtf((float)D);
-        ODISE_TRY(ex.attention(a));
+        ODISE_TRY(ex.vt(L.self.v, L.self.v_bias, out, B, Q, ldq, vtb));
+        ODISE_TRY(ex.attention(attn_desc(B, heads, Q, Q, D).qk_fused(qb, 2 * C, (int64_t)Q * 2 * C).vt(vtb, ldq, (int64_t)C * ldq).o(att, C, (int64_t)Q * C)));
         ODISE_TRY(ex.linear(att, MQ, L.self.out, tq, ODISE_ACT_NONE, out));
         ODISE_TRY(ex.layer_norm(tq, out, MQ, L.self.norm, 1e-5f));
         // FFN
@@ -927,26 +878,17 @@ static int predictor_forward(odise_hip_ctx* ctx, PixDec& pd) {
     // ---- learned (object, no-object) logits of the final prediction head: outputs_class = class_embed(decoder_output), odise.py:734
     g->class_logits = nullptr;
     if (g->has_class_embed) {
-        float* cl = (float*)ex.alloc_bytes((size_t)MQ * 2 * 4);
-        if (!cl) return ODISE_ERR_NOMEM;
-        odise_gemm_desc d;
-        memset(&d, 0, sizeof(d));
-        d.M = (int)MQ; d.N = 2; d.K = C;
-        d.A = dn; d.lda = C; d.W = g->class_embed.w; d.ldw = C;
-        d.C = cl; d.ldc = 2; d.c_dtype = ODISE_F32; d.bias_n = g->class_embed.b; d.alpha = 1.f; d.batch = 1;
-        ODISE_TRY(ex.gemm(d));
+        float* cl = ex.buf<float>((size_t)MQ * 2);
+        ODISE_TRY(ex.ok());
+        ODISE_TRY(ex.linear_f32(dn, MQ, g->class_embed, cl));
         g->class_logits = cl;
     }
     // ---- PooledMaskEmbed on the final prediction (odise.py:984-1015) ------------------------------------------------------------
     ODISE_TRY(launch_mask_binarize_f16(ctx, masks, m01, inv, MQ, (int)HW4));
     for (int b = 0; b < B; ++b) {
-        odise_gemm_desc d;
-        memset(&d, 0, sizeof(d));  // pooled[b] = (m01[b] (Q x HW4) . x[b]^T (C x HW4)) / count
-        d.M = Q; d.N = C; d.K = (int)HW4;
-        d.A = m01 + (size_t)b * Q * HW4; d.lda = HW4;
-        d.W = mfT + (size_t)b * C * HW4; d.ldw = HW4;
-        d.C = pooled + (size_t)b * Q * C; d.ldc = C; d.c_dtype = ODISE_F16;
-        d.scale_m = inv + (size_t)b * Q; d.alpha = 1.f; d.batch = 1;
+        // pooled[b] = (m01[b] (Q x HW4) . x[b]^T (C x HW4)) / count
+        odise_gemm_desc d = gemm_batched_nt(m01 + (size_t)b * Q * HW4, HW4, 0, mfT + (size_t)b * C * HW4, HW4, 0, pooled + (size_t)b * Q * C, C, 0, Q, C, HW4, 1);
+        d.scale_m = inv + (size_t)b * Q;
         ODISE_TRY(ex.gemm(d));
     }
     ODISE_TRY(ex.layer_norm(pooled, tq, MQ, g->pool_ln, 1e-5f));
@@ -1151,8 +1093,8 @@ extern "C" int odise_hip_predictor_forward(odise_hip_ctx* ctx, const float* cons
     }
     ODISE_TRY(ex.alloc(pd.mf, B, H4, W4, C));
     ODISE_TRY(odise_hip_nchw_f32_to_nhwc_f16(ctx, mask_features, pd.mf.p, B, C, H4, W4, C));
-    pd.mfT = (f16*)ex.alloc_bytes((size_t)B * C * H4 * W4 * 2);
-    if (!pd.mfT) return ODISE_ERR_NOMEM;
+    pd.mfT = ex.buf<f16>((size_t)B * C * H4 * W4);
+    ODISE_TRY(ex.ok());
     ODISE_TRY(odise_hip_cast_f32_to_f16(ctx, mask_features, pd.mfT, (size_t)B * C * H4 * W4));
     pd.h4 = H4; pd.w4 = W4;
     ODISE_TRY(predictor_forward(ctx, pd));

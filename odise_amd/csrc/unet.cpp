@@ -283,53 +283,27 @@ static int run_st(UNetRun& r, const STBlockW& w, const Act& x, Act& out) {
     const size_t mk = ex.ms->arena.mark();
     Act t;
     ODISE_TRY(ex.group_norm(x, w.gn, t, 1e-6f, ODISE_ACT_NONE));
-    f16* hs = (f16*)ex.alloc_bytes((size_t)M * C * 2);
-    f16* nrm = (f16*)ex.alloc_bytes((size_t)M * C * 2);
-    f16* qk = (f16*)ex.alloc_bytes((size_t)M * 2 * C * 2);
+    f16* hs = ex.buf<f16>((size_t)M * C);
+    f16* nrm = ex.buf<f16>((size_t)M * C);
+    f16* qk = ex.buf<f16>((size_t)M * 2 * C);
     const int64_t ldvt = round_up(HW, 8);
-    f16* vt = (f16*)ex.alloc_bytes((size_t)x.n * C * ldvt * 2);
-    f16* att = (f16*)ex.alloc_bytes((size_t)M * C * 2);
-    f16* hs2 = (f16*)ex.alloc_bytes((size_t)M * C * 2);
-    f16* ffh = (f16*)ex.alloc_bytes((size_t)M * 4 * C * 2);
-    if (!hs || !nrm || !qk || !vt || !att || !hs2 || !ffh) return ODISE_ERR_NOMEM;
+    f16* vt = ex.buf<f16>((size_t)x.n * C * ldvt);
+    f16* att = ex.buf<f16>((size_t)M * C);
+    f16* hs2 = ex.buf<f16>((size_t)M * C);
+    f16* ffh = ex.buf<f16>((size_t)M * 4 * C);
+    ODISE_TRY(ex.ok());
     ODISE_TRY(ex.linear(t.p, M, w.proj_in, hs));
     // ---- self attention ---------------------------------------------------------------------------------
     ODISE_TRY(ex.layer_norm(hs, nrm, M, w.ln1, 1e-5f));
     ODISE_TRY(ex.linear(nrm, M, w.qk1, qk));
-    {
-        odise_gemm_desc d;  // V^T[b] = Wv @ n[b]^T  -> [B, C, HW]
-        memset(&d, 0, sizeof(d));
-        d.M = C; d.N = (int)HW; d.K = C;
-        d.A = w.v1.w; d.lda = C; d.strideA = 0;
-        d.W = nrm; d.ldw = C; d.strideW = HW * C;
-        d.C = vt; d.ldc = ldvt; d.strideC = (int64_t)C * ldvt; d.c_dtype = ODISE_F16;
-        d.alpha = 1.f; d.batch = x.n;
-        ODISE_TRY(ex.gemm(d));
-        odise_attn_desc a;
-        memset(&a, 0, sizeof(a));
-        a.B = x.n; a.H = heads; a.Lq = (int)HW; a.Lk = (int)HW; a.D = D;
-        a.Q = qk; a.ldq = 2 * C; a.strideQ = HW * 2 * C;
-        a.K = qk + C; a.ldk = 2 * C; a.strideK = HW * 2 * C;
-        a.Vt = vt; a.ldvt = ldvt; a.strideVt = (int64_t)C * ldvt;
-        a.O = att; a.ldo = C; a.strideO = HW * C;
-        a.scale = 1.0f / sqrtf((float)D);
-        ODISE_TRY(ex.attention(a));
-    }
+    ODISE_TRY(ex.vt(w.v1, nullptr, nrm, x.n, HW, ldvt, vt));  // V^T[b] = Wv @ n[b]^T  -> [B, C, HW]
+    ODISE_TRY(ex.attention(attn_desc(x.n, heads, HW, HW, D).qk_fused(qk, 2 * C, HW * 2 * C).vt(vt, ldvt, (int64_t)C * ldvt).o(att, C, HW * C)));
     ODISE_TRY(ex.linear(att, M, w.o1, hs2, ODISE_ACT_NONE, hs));  // hs2 = attn1 + hs
     // ---- cross attention (77 context tokens; K / V^T precomputed per layer) -------------------------------
     ODISE_TRY(ex.layer_norm(hs2, nrm, M, w.ln2, 1e-5f));
     ODISE_TRY(ex.linear(nrm, M, w.q2, qk));  // reuse qk buffer as [M, C]
-    {
-        odise_attn_desc a;
-        memset(&a, 0, sizeof(a));
-        a.B = x.n; a.H = heads; a.Lq = (int)HW; a.Lk = 77; a.D = D;
-        a.Q = qk; a.ldq = C; a.strideQ = HW * C;
-        a.K = r.ctxK[w.ctx_slot]; a.ldk = C; a.strideK = 77 * (int64_t)C;
-        a.Vt = r.ctxVt[w.ctx_slot]; a.ldvt = 80; a.strideVt = (int64_t)C * 80;
-        a.O = att; a.ldo = C; a.strideO = HW * C;
-        a.scale = 1.0f / sqrtf((float)D);
-        ODISE_TRY(ex.attention(a));
-    }
+    ODISE_TRY(ex.attention(attn_desc(x.n, heads, HW, 77, D).q(qk, C, HW * C).k(r.ctxK[w.ctx_slot], C, 77 * (int64_t)C)
+                               .vt(r.ctxVt[w.ctx_slot], 80, (int64_t)C * 80).o(att, C, HW * C)));
     ODISE_TRY(ex.linear(att, M, w.o2, hs, ODISE_ACT_NONE, hs2));  // hs = attn2 + hs2
     // ---- GEGLU feed-forward ----------------------------------------------------------------------------
     ODISE_TRY(ex.layer_norm(hs, nrm, M, w.ln3, 1e-5f));
@@ -360,50 +334,32 @@ int unet_launch(odise_hip_ctx* ctx, ModelStore* ms, UNetModel* u, const float* x
     }
 
     // ---- time embedding: emb = time_embed(t_emb) + cond_emb; every ResBlock consumes Linear(SiLU(emb)) -------------
-    f16* te_h = (f16*)ex.alloc_bytes((size_t)B * u->ted * 2);
-    f16* emb_silu = (f16*)ex.alloc_bytes((size_t)B * u->ted * 2);
-    float* emb_out = (float*)ex.alloc_bytes((size_t)B * u->emb_total * 4);
-    if (!te_h || !emb_silu || !emb_out) return ODISE_ERR_NOMEM;
+    f16* te_h = ex.buf<f16>((size_t)B * u->ted);
+    f16* emb_silu = ex.buf<f16>((size_t)B * u->ted);
+    float* emb_out = ex.buf<float>((size_t)B * u->emb_total);
+    ODISE_TRY(ex.ok());
     ODISE_TRY(ex.linear((const f16*)u->temb_in.ptr, B, u->te0, te_h, ODISE_ACT_SILU));
     {
-        odise_gemm_desc d;
-        memset(&d, 0, sizeof(d));
-        d.M = B; d.N = u->ted; d.K = u->ted;
-        d.A = te_h; d.lda = u->ted; d.W = u->te2.w; d.ldw = u->ted;
-        d.C = emb_silu; d.ldc = u->ted; d.c_dtype = ODISE_F16;
-        d.bias_n = u->te2.b;
+        odise_gemm_desc d = gemm_linear(te_h, B, u->te2, emb_silu, ODISE_F16, ODISE_ACT_SILU);
         d.rowgroup_add = cond_emb; d.rows_per_group = 1; d.ldg = u->ted;  // emb += cond_emb (ldm.py:474-477)
-        d.act = ODISE_ACT_SILU; d.alpha = 1.f; d.batch = 1;
-        ODISE_TRY(ex.gemm(d));
-        memset(&d, 0, sizeof(d));
-        d.M = B; d.N = u->emb_total; d.K = u->ted;
-        d.A = emb_silu; d.lda = u->ted; d.W = u->emb_all.w; d.ldw = u->ted;
-        d.C = emb_out; d.ldc = u->emb_total; d.c_dtype = ODISE_F32;
-        d.bias_n = u->emb_all.b; d.alpha = 1.f; d.batch = 1;
         ODISE_TRY(ex.gemm(d));
     }
+    ODISE_TRY(ex.linear_f32(emb_silu, B, u->emb_all, emb_out));
     r.emb_out = emb_out;
 
     // ---- context: fp16 copy + per-layer K and V^T ---------------------------------------------------------------
-    r.ctx16 = (f16*)ex.alloc_bytes((size_t)B * 77 * u->cdim * 2);
-    if (!r.ctx16) return ODISE_ERR_NOMEM;
+    r.ctx16 = ex.buf<f16>((size_t)B * 77 * u->cdim);
+    ODISE_TRY(ex.ok());
     ODISE_TRY(odise_hip_cast_f32_to_f16(ctx, context, r.ctx16, (size_t)B * 77 * u->cdim));
     r.ctxK.assign(u->n_ctx_slots, nullptr);
     r.ctxVt.assign(u->n_ctx_slots, nullptr);
     auto prep_ctx = [&](const STBlockW& s) -> int {
         const int C = s.c;
-        f16* k = (f16*)ex.alloc_bytes((size_t)B * 77 * C * 2);
-        f16* vt = (f16*)ex.alloc_bytes((size_t)B * C * 80 * 2);
-        if (!k || !vt) return ODISE_ERR_NOMEM;
+        f16* k = ex.buf<f16>((size_t)B * 77 * C);
+        f16* vt = ex.buf<f16>((size_t)B * C * 80);
+        ODISE_TRY(ex.ok());
         ODISE_TRY(ex.linear(r.ctx16, (int64_t)B * 77, s.k2, k));
-        odise_gemm_desc d;
-        memset(&d, 0, sizeof(d));
-        d.M = C; d.N = 77; d.K = u->cdim;
-        d.A = s.v2.w; d.lda = u->cdim; d.strideA = 0;
-        d.W = r.ctx16; d.ldw = u->cdim; d.strideW = 77 * (int64_t)u->cdim;
-        d.C = vt; d.ldc = 80; d.strideC = (int64_t)C * 80; d.c_dtype = ODISE_F16;
-        d.alpha = 1.f; d.batch = B;
-        ODISE_TRY(ex.gemm(d));
+        ODISE_TRY(ex.vt(s.v2, nullptr, r.ctx16, B, 77, 80, vt));
         r.ctxK[s.ctx_slot] = k;
         r.ctxVt[s.ctx_slot] = vt;
         return ODISE_OK;
