@@ -746,6 +746,64 @@ typedef struct {
     int iou_cap;
 } odise_track_desc;
 int odise_hip_track_frame(odise_hip_ctx* ctx, const odise_track_desc* d);
+/* ---- overlapping instance masks keep their colours from frame to frame (run_on_video's instance branch) ----------------------------
+ * For a box-less _DetectedInstance detectron2's _assign_colors matches on mask IoU; that path is what is built here (host restatement:
+ * odise_amd/video.py InstanceColorTracker).  It is NOT what the reference's run_on_video produces on this model: there the instances
+ * carry pred_boxes of all zeros, box IoU is 0 / 0 and every instance takes a fresh colour in every frame.
+ * Instance masks overlap, so a frame is no label map: the tracker retains the bit-packed words of rle_pack.h (exactly the pixels of
+ * odise_hip_instance_rle / odise_hip_instance_draw) and the IoU of two masks is the popcount of an AND.
+ *   instances   of a frame: the table indices i < n with inst_scores[i] >= min_score whose mask has a pixel (the `kept` rule of
+ *               odise_hip_instance_draw), in ascending table index; (label = class, mask, area, ttl = the tracker's ttl).
+ *   live list   ordered, empty at the start; after a frame: that frame's instances in their order, then the surviving old ones in theirs.
+ *   iou         of live row o and new instance j: inter / (area_o + area_j - inter) as the double division of the two integers, 0 where
+ *               the classes differ.
+ *   matching    every live row takes j = the FIRST maximum of its iou row.  If that iou > 0.5 (strict) and o is the smallest list position
+ *               among the rows that chose j this way, j takes o's colour and o leaves the list; every other live row loses one ttl and
+ *               stays iff ttl > 0 (also a row whose j went to an earlier row, whatever its second-best is).
+ *   colours     new instances without a colour take pool[counter % n_pool], counter += 1, in instance order; the counter lives on.
+ * ttl 1..8, topk 1..100, at most 800 live rows.  The detections are those of odise_inst_draw_desc: dense `masks` [topk,h,w] (inst_table
+ * NULL: n = topk and every class is 0; inst_scores NULL: no score test), or masks == NULL = the selection of image b of the last head
+ * forward, sampled from the mask logits (inst_table and inst_scores required).
+ * colors is in/out and indexed by table index: only the rows of this frame's instances are written; edge_colors (optional) gets, in the
+ * same rows, the outline colour odise_hip_instance_draw is given for them (3/10 of a colour whose channels sum to >= 384, else the
+ * colour moved 7/10 of the way to white, per channel in integers).  live rows carry id = table index.
+ * Memory: a row made in frame f with ttl T is still matched against in frame f + T, so the tracker owns a ring of ttl + 1 slots of
+ * topk * h-word-rows * w words of 8 bytes ((ttl + 1) * topk * w * ceil(h / 64) * 8 bytes; at 1024 x 1024 and topk 100 a slot is 13.1 MB,
+ * nine of them 118 MB), an 800 x topk int32 intersection matrix that is zero between calls and the 800 live rows; all of it is allocated
+ * by odise_hip_inst_track_create and released by odise_hip_inst_track_destroy, so the masks may be reused as soon as the call has returned.
+ * Per frame, on the context's stream, without a synchronisation or a count read by the host: the pack launch of rle_pack.h into the ring
+ * slot frame mod (ttl + 1) (the frame number is counted on the host, so a call cannot be replayed from a captured graph); areas and the
+ * kept test; the gathered intersection - tiles of 64 live rows x 32 new masks x 32 words in LDS, a live row's words found through its
+ * (frame, id) in the device-resident list, the grid sized for 800 x topk with the word axis split over blockIdx.z, a tile past either
+ * count or without a (live, new) pair of one class leaving before it loads a word; one block that matches, colours and compacts the
+ * list.  Integer atomics only: the same bytes from run to run.
+ * ODISE_ERR_ARG and nothing written: a null required pointer, h or w < 1, h * w > 2^29 - 1, topk outside 1..100, ttl outside 1..8,
+ * n_pool outside 1..2^20, a descriptor whose h, w or topk are not the tracker's, a dtype other than ODISE_F32 / ODISE_U8, a negative
+ * cap, live without n_live, the geometry errors of odise_hip_instance_rle.  ODISE_ERR_NOMEM: the ring could not be allocated. */
+typedef struct odise_inst_track odise_inst_track;
+int odise_hip_inst_track_create(odise_hip_ctx* ctx, int H, int W, int topk, int ttl, const uint8_t* pool_rgb /* HOST [n_pool][3] */, int n_pool,
+                                odise_inst_track** out);
+int odise_hip_inst_track_reset(odise_hip_ctx* ctx, odise_inst_track* track);     /* empties the live list, the counter and the frame number */
+int odise_hip_inst_track_destroy(odise_hip_ctx* ctx, odise_inst_track* track);   /* waits for the stream */
+typedef struct {
+    odise_inst_track* track;
+    int h, w;                       /* must be the tracker's */
+    const void* masks; int dtype;   /* dense [topk,h,w] (ODISE_F32 / ODISE_U8), or NULL = from the mask logits of image b of the last head forward: */
+    int b, pad_h, pad_w, img_h, img_w;   /* as odise_hip_instance_rle */
+    const int32_t* inst_table;      /* device [1 + 2*topk]: n | query index | class  (n read on the device) */
+    const float* inst_scores;       /* device [topk] */
+    int topk;                       /* must be the tracker's */
+    float min_score;
+    uint8_t* colors;                /* device [topk][3], in/out */
+    uint8_t* edge_colors;           /* optional, device [topk][3], in/out */
+    odise_track_row* live;          /* optional, device [live_cap]: the live list AFTER the frame, in list order; nothing past live_cap rows */
+    int live_cap;
+    int32_t* n_live;                /* device [1], required with live: the length of the list (not clipped to live_cap) */
+    double* iou;                    /* optional, device [iou_cap][100]: iou[o * 100 + j] of live row o of the list BEFORE the frame and this
+                                       frame's instance j (its position among the instances); other cells are left alone */
+    int iou_cap;
+} odise_inst_track_desc;
+int odise_hip_inst_track_frame(odise_hip_ctx* ctx, const odise_inst_track_desc* d);
 
 /* ---- test-time augmentation of the semantic head (Mask2Former SemanticSegmentorWithTTA: several short-edge sizes, each also mirrored,
  * sem_seg averaged at the original size) ------------------------------------------------------------------------------------------

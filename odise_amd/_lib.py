@@ -149,6 +149,14 @@ class TrackDesc(C.Structure):
                 ("live", c_void_p), ("live_cap", c_int), ("n_live", c_void_p), ("iou", c_void_p), ("iou_cap", c_int)]
 
 
+class InstTrackDesc(C.Structure):
+    """odise_inst_track_desc (include/odise_hip.h)."""
+    _fields_ = [("track", c_void_p), ("h", c_int), ("w", c_int), ("masks", c_void_p), ("dtype", c_int), ("b", c_int), ("pad_h", c_int),
+                ("pad_w", c_int), ("img_h", c_int), ("img_w", c_int), ("inst_table", c_void_p), ("inst_scores", c_void_p), ("topk", c_int),
+                ("min_score", c_float), ("colors", c_void_p), ("edge_colors", c_void_p), ("live", c_void_p), ("live_cap", c_int),
+                ("n_live", c_void_p), ("iou", c_void_p), ("iou_cap", c_int)]
+
+
 MAX_SEGMENTS = 100          # ODISE_MAX_SEGMENTS
 COMM_ID_BYTES = 128         # ODISE_COMM_ID_BYTES
 RECORD_TABLE_LEN = 1 + 3 * MAX_SEGMENTS   # the tail of a panoptic record: n | rows (id, isthing, category)

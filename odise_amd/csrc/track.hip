@@ -18,16 +18,14 @@
 #include "lds_hist.h"
 #include "record.h"
 #include "rgb.h"
+#include "track_match.h"
 #include "vis_scan.h"
 
 namespace odise {
 
-constexpr int kTrackRing = 8;                                            // retained frames = the largest ttl
+// kTrackRing (retained frames = the largest ttl), kTrackLiveCap and kTrackMatchThreads: track_match.h
 constexpr int kTrackSlots = ODISE_MAX_SEGMENTS + 1;                      // 0 = no instance, 1 + table row
-constexpr int kTrackLiveCap = kTrackRing * ODISE_MAX_SEGMENTS;
 constexpr int kTrackMatrixCells = kTrackRing * kTrackSlots * kTrackSlots;
-constexpr int kTrackMatchThreads = 1024;                                 // >= kTrackLiveCap: a thread per live row
-static_assert(kTrackMatchThreads >= kTrackLiveCap, "a thread per live row");
 
 struct TrackState {   // device
     int frame, counter, n_live, pad;         // frames since the reset, pool counter (kept modulo n_pool), rows of `live`
@@ -57,8 +55,6 @@ struct TrackLayout {
     int off[kTrackRing];       // first cell of its matrix
     int pass_of[kTrackRing];   // ring slot -> pass, -1 = not retained
 };
-
-__device__ __forceinline__ int track_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // tab[i] = id of table row i when the row can be an instance (a thing, id > 0, the first row of its id), else 0.  Whole block; no barrier.
 __device__ __forceinline__ void track_load_table(const int* __restrict__ seg, int n, int* tab) {
@@ -184,20 +180,15 @@ __global__ void __launch_bounds__(256) track_pixel_kernel(const int* __restrict_
 }
 
 // One block of kTrackMatchThreads.  matrix: the pair counts of the frame (zeroed on return); st: the tracker before the frame -> after it.
+// The match, colour and compact step itself is track_match_block (track_match.h), shared with inst_track.hip.
 __global__ void __launch_bounds__(kTrackMatchThreads) track_match_kernel(int* __restrict__ matrix, const int* __restrict__ pred_segments,
                                                                         TrackState* __restrict__ st, const uint8_t* __restrict__ pool, int n_pool,
                                                                         int ttl, uint8_t* __restrict__ colors, odise_track_row* __restrict__ live_out,
                                                                         int live_cap, int* __restrict__ n_live_out, double* __restrict__ iou_out,
                                                                         int iou_cap) {
     __shared__ int tab[ODISE_MAX_SEGMENTS], cat[ODISE_MAX_SEGMENTS], area[ODISE_MAX_SEGMENTS];
-    __shared__ int rank[ODISE_MAX_SEGMENTS];      // position of a row among the frame's instances, -1 = no instance
-    __shared__ int winner[ODISE_MAX_SEGMENTS];    // smallest list position of the live rows that chose the instance
-    __shared__ int urank[ODISE_MAX_SEGMENTS];     // position among the instances that take a new colour
-    __shared__ int rgb[ODISE_MAX_SEGMENTS];
     __shared__ int active[kTrackRing];
     __shared__ TrackLayout L;
-    __shared__ int wave_sum[kTrackMatchThreads / 64];
-    __shared__ int n_inst, n_new;
     const int tid = threadIdx.x;
     const int n = record_rows(pred_segments);
     const int n_live = track_clamp(st->n_live, kTrackLiveCap), frame = st->frame, counter = st->counter;
@@ -214,92 +205,20 @@ __global__ void __launch_bounds__(kTrackMatchThreads) track_match_kernel(int* __
         }
         area[tid] = a;
         cat[tid] = record_category(pred_segments, tid);
-        winner[tid] = INT32_MAX;
     }
     __syncthreads();
+    const TrackMatchIo io = {pool, n_pool, ttl, colors, nullptr, live_out, live_cap, n_live_out, iou_out, iou_cap};
+    // the cell of live row (frame, table row aux) and new row j; a row whose frame has no matrix shares no pixel
+    const TrackMatched m = track_match_block(n, tab, cat, area, st->live, st->live_row, n_live, frame, counter, io,
+                                             [&](int, const odise_track_row& row, int aux, int j) {
+                                                 const int k = L.pass_of[row.frame & (kTrackRing - 1)];
+                                                 return k < 0 ? 0 : matrix[L.off[k] + (aux + 1) * w + j + 1];
+                                             });
     if (tid == 0) {
-        int c = 0;
-        for (int j = 0; j < n; ++j) rank[j] = area[j] > 0 ? c++ : -1;
-        n_inst = c;
-    }
-    __syncthreads();
-
-    // a thread per live row: its iou row, the first maximum
-    odise_track_row row = {};
-    int my_row = 0, choice = -1;
-    if (tid < n_live) {
-        row = st->live[tid];
-        my_row = st->live_row[tid];
-        const int k = L.pass_of[row.frame & (kTrackRing - 1)];
-        const int* m = matrix + L.off[k < 0 ? 0 : k] + (my_row + 1) * w;
-        double best = 0.0;
-        for (int j = 0; j < n; ++j) {
-            if (rank[j] < 0) continue;
-            double iou = 0.0;
-            if (k >= 0 && cat[j] == row.category) {
-                const int inter = m[j + 1];
-                iou = (double)inter / (double)((int64_t)row.area + area[j] - inter);
-            }
-            if (iou_out && tid < iou_cap) iou_out[(int64_t)tid * ODISE_MAX_SEGMENTS + rank[j]] = iou;
-            if (iou > best) { best = iou; choice = j; }
-        }
-        if (best > 0.5) atomicMin(&winner[choice], tid);
-        else choice = -1;
-    }
-    __syncthreads();
-    if (tid < n && rank[tid] >= 0 && winner[tid] != INT32_MAX) rgb[tid] = st->live[winner[tid]].rgb;   // read before the list is rewritten
-    if (tid == 0) {
-        int u = 0;
-        for (int j = 0; j < n; ++j) urank[j] = (rank[j] >= 0 && winner[j] == INT32_MAX) ? u++ : -1;
-        n_new = u;
-    }
-    __syncthreads();
-    if (tid < n && rank[tid] >= 0) {
-        if (urank[tid] >= 0) rgb[tid] = (int)rgb_load(pool + 3 * ((counter + urank[tid]) % n_pool));
-        rgb_store(colors + 3 * tid, (unsigned)rgb[tid]);
-    }
-
-    // the survivors keep their order behind the new instances: an exclusive block scan of the keep flags
-    const bool matched = choice >= 0 && winner[choice] == tid;
-    const int keep = (tid < n_live && !matched && row.ttl - 1 > 0) ? 1 : 0;
-    const int lane = tid & 63, wave = tid >> 6;
-    int inc = keep;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int up = __shfl_up(inc, d);
-        if (lane >= d) inc += up;
-    }
-    if (lane == 63) wave_sum[wave] = inc;
-    __syncthreads();   // also: every thread holds its row and the winners' colours are read, the list may be rewritten
-    int before = 0, kept = 0;
-    for (int v = 0; v < kTrackMatchThreads / 64; ++v) {
-        const int s = wave_sum[v];
-        if (v < wave) before += s;
-        kept += s;
-    }
-    const int total = min(n_inst + kept, kTrackLiveCap);
-    if (keep) {
-        const int pos = n_inst + before + inc - 1;
-        if (pos < kTrackLiveCap) {
-            row.ttl -= 1;
-            st->live[pos] = row;
-            st->live_row[pos] = my_row;
-            if (live_out && pos < live_cap) live_out[pos] = row;
-        }
-    }
-    if (tid < n && rank[tid] >= 0) {
-        odise_track_row r;
-        r.frame = frame; r.id = tab[tid]; r.category = cat[tid]; r.area = area[tid]; r.ttl = ttl; r.rgb = rgb[tid]; r.pad0 = 0; r.pad1 = 0;
-        const int pos = rank[tid];
-        st->live[pos] = r;
-        st->live_row[pos] = tid;
-        if (live_out && pos < live_cap) live_out[pos] = r;
-    }
-    if (tid == 0) {
-        st->n_live = total;
+        st->n_live = m.total;
         st->frame = frame + 1;
-        st->counter = (counter + n_new) % n_pool;
+        st->counter = (counter + m.n_new) % n_pool;
         st->slot_rows[frame & (kTrackRing - 1)] = n;
-        if (n_live_out) n_live_out[0] = total;
     }
     for (int i = tid; i < L.cells; i += kTrackMatchThreads) matrix[i] = 0;
 }

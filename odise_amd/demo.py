@@ -1,4 +1,4 @@
-"""`python -m odise_amd.demo (--input FILE... | --video-input SRC [--ttl N]) --output DIR [--vocab "a, b; c"] [--synthetic] [--task panoptic|semantic|instance] [--tta 768,1024,1280 [--no-tta-flip]]`:
+"""`python -m odise_amd.demo (--input FILE... | --video-input SRC [--ttl N] [--track-masks]) --output DIR [--vocab "a, b; c"] [--synthetic] [--task panoptic|semantic|instance] [--tta 768,1024,1280 [--no-tta-flip]]`:
 demo/demo.py on the device path.
 
 A picture is read (JPEG through HipDatasetMapper, anything else through Pillow), resized by ResizeShortestEdge(1024, 2560) on the device,
@@ -16,7 +16,10 @@ the semantic map (HipVisualizer.draw_sem_seg), then the instance selection (draw
 file Pillow opens (no container decoding); every frame goes through the same model call and is drawn by
 HipVideoVisualizer.draw_panoptic_seg_predictions, which keeps a thing's colour from frame to frame (`--ttl` frames of memory), and saved as
 DIR/frame_%06d.png - or, when `--output` ends in .gif, all frames as one animated GIF.  `--task semantic` draws every frame on its own;
-`--task instance` is refused (the reference tracks pred_boxes there, which are all zeros on this model).
+`--task instance` is refused (the reference tracks pred_boxes there, which are all zeros on this model) unless `--track-masks` is given:
+then the instances of every frame are matched to the earlier ones on mask IoU (HipVideoVisualizer.draw_instance_predictions: detectron2's
+rule for instances without a box; not what the reference's zero boxes produce, which is a fresh colour per instance and frame) and
+`--confidence-threshold` is honoured as on single pictures.
 
 Weights come from `$ODISE_MODEL_ZOO` through odise_amd/checkpoint.py; `--synthetic` takes random tensors of the real shapes and seeded
 text banks instead (odise_amd/synthetic.py), which draws arbitrary segments but needs no file.
@@ -38,6 +41,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     src.add_argument("--video-input", metavar="SRC", help="a directory of frames (sorted by name) or a multi-frame file Pillow opens")
     ap.add_argument("--output", required=True, metavar="DIR", help="directory for the drawn pictures (--video-input: or a .gif file)")
     ap.add_argument("--ttl", type=int, default=8, help="--video-input: frames an unseen thing keeps its colour for (1..8)")
+    ap.add_argument("--track-masks", action="store_true", help="--video-input --task instance: keep an instance's colour from frame to frame by "
+                    "mask IoU (detectron2's rule for instances without a box; the reference's zero boxes track nothing)")
     ap.add_argument("--vocab", default="", help='extra classes, demo.py style: "black pickup truck, pickup truck; blue sky, sky"')
     ap.add_argument("--synthetic", action="store_true", help="random weights of the real shapes and seeded text banks: needs no checkpoint")
     ap.add_argument("--device", type=int, default=0)
@@ -61,7 +66,11 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
             ap.error("--tta with --video-input: test-time augmentation runs on single pictures")
     elif args.no_tta_flip:
         ap.error("--no-tta-flip without --tta")
-    if args.video_input is not None and args.task == "instance":
+    if args.track_masks and args.video_input is None:
+        ap.error("--track-masks without --video-input: single pictures have nothing to track")
+    if args.track_masks and args.task != "instance":
+        ap.error(f"--track-masks with --task {args.task}: mask tracking exists for the instance head only")
+    if args.video_input is not None and args.task == "instance" and not args.track_masks:
         ap.error("--task instance with --video-input: the reference tracks pred_boxes there, which are all zeros on this model")
     if not 1 <= args.ttl <= 8:
         ap.error(f"--ttl {args.ttl} outside 1..8")
@@ -160,17 +169,18 @@ def frame_path(out_dir: str, index: int) -> str:
     return os.path.join(out_dir, "frame_%06d.png" % index)
 
 
-def run_on_video(ctx, model, visualizer, frames, task: str = "panoptic"):
+def run_on_video(ctx, model, visualizer, frames, task: str = "panoptic", confidence_threshold: float = 0.5):
     """VisualizationDemo.run_on_video (demo.py:201-243): yields the drawn frames.  visualizer: a HipVideoVisualizer (panoptic: its
-    tracker colours the things; semantic: every frame on its own).  A frame of another size than the first is refused by name."""
+    tracker colours the things; semantic: every frame on its own; instance: its mask tracker colours the instances).  A frame of another size than the first is refused by name."""
     size = None
+    options = {"confidence_threshold": confidence_threshold} if task == "instance" else {}   # the only branch that reads it
     for name, load in frames:
         image_dev = load(ctx)
         hw = tuple(image_dev.shape[:2])
         size = size or hw
         if hw != size:
             raise SystemExit(f"{name}: a {hw[0]}x{hw[1]} frame in a video of {size[0]}x{size[1]}")
-        yield run_on_image(ctx, model, visualizer, image_dev, task, video=True)
+        yield run_on_image(ctx, model, visualizer, image_dev, task, video=True, **options)
 
 
 def run_on_image(ctx, model, visualizer, image_dev, task: str = "panoptic", confidence_threshold: float = 0.5,
@@ -224,7 +234,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     model, metadata = build_model(ctx, labels, num_things, args.synthetic, args.task)
     if args.video_input is not None:
         visualizer = HipVideoVisualizer(ctx, metadata, ttl=args.ttl)
-        drawn = run_on_video(ctx, model, visualizer, video_frames(args.video_input), args.task)
+        drawn = run_on_video(ctx, model, visualizer, video_frames(args.video_input), args.task, args.confidence_threshold)
         if args.output.lower().endswith(".gif"):
             os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
             pictures = [Image.fromarray(p) for p in drawn]

@@ -637,6 +637,52 @@ class Context:
         check(self.lib.odise_hip_track_frame(self.h, C.byref(d)), "track_frame")
         return colors
 
+    # ---- colours of overlapping instance masks across frames (odise_hip_inst_track_*; host restatement: video.InstanceColorTracker) -----
+    def inst_track_create(self, hw, topk: int, ttl: int = 8, pool=None) -> "InstTracker":
+        """A tracker for selections of `topk` instance masks of hw = (H, W): pool uint8 [P,3] on the host (video.default_pool() when None).
+        It owns (ttl + 1) * topk * W * ceil(H / 64) * 8 bytes of packed masks."""
+        return InstTracker(self, hw, topk, ttl, pool)
+
+    def inst_track_frame(self, tracker: "InstTracker", table_row=None, scores_row=None, masks: Optional[DeviceArray] = None, b: int = 0,
+                         pad_hw=(0, 0), img_hw=(0, 0), min_score: float = 0.0, colors: Optional[DeviceArray] = None,
+                         edge_colors: Optional[DeviceArray] = None, live: Optional[DeviceArray] = None, n_live: Optional[DeviceArray] = None,
+                         iou: Optional[DeviceArray] = None, live_cap: Optional[int] = None, iou_cap: Optional[int] = None) -> DeviceArray:
+        """One frame, enqueued.  Detections as in `instance_draw`: the selection table_row [1 + 2 topk] / scores_row [topk] of image b of
+        the last head forward, or dense `masks` [topk, h, w] (table_row / scores_row then optional).  colors uint8 [topk,3] in/out by table
+        index (allocated as zeros when None; the rows of the frame's instances are rewritten), edge_colors the same for the outline
+        colours.  Optional dumps as in `track_frame`: live [cap] records of video.TRACK_ROW_DTYPE with n_live int32 [1], iou float64
+        [cap, MAX_SEGMENTS]."""
+        from ._lib import MAX_SEGMENTS, InstTrackDesc
+        from .video import TRACK_ROW_DTYPE
+        (h, w), topk = tracker.hw, tracker.topk
+        d = InstTrackDesc()
+        d.track, d.h, d.w, d.topk, d.min_score = tracker.handle, h, w, topk, float(min_score)
+        if masks is not None:
+            assert tuple(masks.shape) == (topk, h, w), (masks.shape, topk, tracker.hw)
+            d.masks, d.dtype = masks.ptr, (F32 if masks.dtype == np.float32 else U8)
+        d.b, d.pad_h, d.pad_w, d.img_h, d.img_w = int(b), int(pad_hw[0]), int(pad_hw[1]), int(img_hw[0]), int(img_hw[1])
+        ptr = lambda a: a.ptr if isinstance(a, DeviceArray) else a
+        d.inst_table, d.inst_scores = ptr(table_row), ptr(scores_row)
+        if colors is None:
+            colors = self.zeros((topk, 3), np.uint8)
+        assert colors.dtype == np.uint8 and colors.nbytes >= 3 * topk, (colors.dtype, colors.shape)
+        d.colors = colors.ptr
+        if edge_colors is not None:
+            assert edge_colors.dtype == np.uint8 and edge_colors.nbytes >= 3 * topk, (edge_colors.dtype, edge_colors.shape)
+            d.edge_colors = edge_colors.ptr
+        if live is not None:
+            assert live.dtype == TRACK_ROW_DTYPE and (n_live is None or n_live.dtype == np.int32)
+            d.live, d.live_cap = live.ptr, live.shape[0] if live_cap is None else int(live_cap)
+            assert d.live_cap <= live.shape[0]
+        if n_live is not None:
+            d.n_live = n_live.ptr
+        if iou is not None:
+            assert iou.dtype == np.float64 and len(iou.shape) == 2 and iou.shape[1] == MAX_SEGMENTS, (iou.dtype, iou.shape)
+            d.iou, d.iou_cap = iou.ptr, iou.shape[0] if iou_cap is None else int(iou_cap)
+            assert d.iou_cap <= iou.shape[0]
+        check(self.lib.odise_hip_inst_track_frame(self.h, C.byref(d)), "inst_track_frame")
+        return colors
+
     # ---- drawing instance and semantic results (include/odise_hip.h odise_hip_instance_draw / odise_hip_semantic_record) ----------------
     def instance_draw(self, out_hw, topk: int, table_row=None, scores_row=None, masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0),
                       img_hw=(0, 0), min_score: float = 0.0, image: Optional[DeviceArray] = None, colors: Optional[DeviceArray] = None,
@@ -912,6 +958,34 @@ class Tracker:
     def close(self) -> None:
         if self.handle and self.ctx.h:
             self.ctx.lib.odise_hip_track_destroy(self.ctx.h, C.c_void_p(self.handle))
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class InstTracker:
+    """odise_inst_track (include/odise_hip.h): the library's tracker object for selections of `topk` instance masks of one size;
+    `close()` (or collection) releases it."""
+
+    def __init__(self, ctx: Context, hw, topk: int, ttl: int = 8, pool=None):
+        from .video import default_pool
+        pool = default_pool() if pool is None else np.ascontiguousarray(np.asarray(pool, np.uint8).reshape(-1, 3))
+        self.ctx, self.hw, self.topk, self.ttl, self.pool = ctx, (int(hw[0]), int(hw[1])), int(topk), int(ttl), pool
+        h = C.c_void_p()
+        check(ctx.lib.odise_hip_inst_track_create(ctx.h, self.hw[0], self.hw[1], self.topk, self.ttl, pool.ctypes.data_as(C.c_void_p), len(pool),
+                                                  C.byref(h)), "inst_track_create")
+        self.handle = h.value
+
+    def reset(self) -> None:
+        check(self.ctx.lib.odise_hip_inst_track_reset(self.ctx.h, C.c_void_p(self.handle)), "inst_track_reset")
+
+    def close(self) -> None:
+        if self.handle and self.ctx.h:
+            self.ctx.lib.odise_hip_inst_track_destroy(self.ctx.h, C.c_void_p(self.handle))
         self.handle = None
 
     def __del__(self):

@@ -1,15 +1,22 @@
 """A thing keeps its colour from frame to frame: `VisualizationDemo.run_on_video` (demo/demo.py:201-243) -> detectron2
-`VideoVisualizer.draw_panoptic_seg_predictions` -> `_assign_colors`, the mask-IoU path.
+`VideoVisualizer.draw_panoptic_seg_predictions` / `draw_instance_predictions` -> `_assign_colors`, the mask-IoU path.
 
-This module holds the numpy restatement of the rule - the reference the device tracker (csrc/track.hip: odise_hip_track_frame) is held to
-byte for byte (tests/test_gpu_track.py), itself pinned to a literal sequential formulation (tests/test_track_cpu.py) - and the host twin
-of `HipVideoVisualizer.draw_panoptic_seg_predictions`.
+This module holds the numpy restatement of the rule - the reference the device trackers (csrc/track.hip: odise_hip_track_frame;
+csrc/inst_track.hip: odise_hip_inst_track_frame) are held to byte for byte (tests/test_gpu_track.py, tests/test_gpu_inst_track.py), itself
+pinned to a literal sequential formulation (tests/test_track_cpu.py, tests/test_inst_track_cpu.py) - and the host twins of
+`HipVideoVisualizer.draw_panoptic_seg_predictions` and `HipVideoVisualizer.draw_instance_predictions`.
 
 The rule (include/odise_hip.h states it in full): the instances of a frame are the thing rows that are the first row of their id, have an
-id > 0 and own a pixel, in table-row order.  Every live instance takes the first maximum of its IoU row against them (0 where the
-categories differ); if that IoU is above 0.5 and no earlier live instance chose the same new one, the new instance inherits its colour and
-the old one leaves the list, otherwise the old one loses one ttl and stays while ttl > 0.  New instances without a colour take the next
-one of a fixed pool (detectron2 draws a random one).  The live list is the frame's instances, then the surviving old ones, in order.
+id > 0 and own a pixel, in table-row order (`ColorTracker`), or the entries of an instance selection whose score reaches `min_score` and
+whose mask has a pixel, in table order (`InstanceColorTracker`: these masks may overlap).  Every live instance takes the first maximum
+of its IoU row against them (0 where the categories differ); if that IoU is above 0.5 and no earlier live instance chose the same new one,
+the new instance inherits its colour and the old one leaves the list, otherwise the old one loses one ttl and stays while ttl > 0.  New
+instances without a colour take the next one of a fixed pool (detectron2 draws a random one).  The live list is the frame's instances,
+then the surviving old ones, in order.
+
+Mask-IoU matching of instances is detectron2's path for a `_DetectedInstance` without a box.  It is not what the reference's
+run_on_video shows on this model: its instances carry pred_boxes of zeros, box IoU is 0 / 0, and every instance gets a fresh colour in
+every frame.
 """
 from __future__ import annotations
 
@@ -17,14 +24,15 @@ from typing import Optional
 
 import numpy as np
 
-from .visualize import (LARGE_AREA, SMALL_AREA, _fallback_color, _row_of_id, _table, draw_labels, panoptic_overlay, segment_anchors,
-                        segment_colors)
+from .visualize import (LARGE_AREA, SMALL_AREA, _fallback_color, _row_of_id, _table, draw_labels, draw_texts, instance_anchors, instance_colors,
+                        instance_edge_colors, instance_order, instance_overlay, instance_texts, panoptic_overlay, segment_anchors, segment_colors)
 
 TRACK_ROW_DTYPE = np.dtype([("frame", np.int32), ("id", np.int32), ("category", np.int32), ("area", np.int32), ("ttl", np.int32),
                             ("rgb", np.int32), ("pad0", np.int32), ("pad1", np.int32)])   # odise_track_row, 32 bytes
 assert TRACK_ROW_DTYPE.itemsize == 32
 MAX_TTL = 8                 # retained frames of the device tracker
 POOL_COLORS = 74            # detectron2 VideoVisualizer max_num_instances
+MAX_INSTANCES = 100         # topk limit of the device instance tracker
 
 
 def default_pool(n: int = POOL_COLORS) -> np.ndarray:
@@ -46,6 +54,19 @@ def frame_instances(pred_ids, segments) -> list:
     return out
 
 
+def selection_instances(classes, scores, masks, min_score: float = 0.0) -> list:
+    """[(table index, table index, class, bool mask)] of an instance selection: the entries with score >= min_score (scores None: all)
+    whose mask has a pixel - the `kept` rule of odise_hip_instance_draw - in table order."""
+    masks = np.asarray(masks) != 0
+    out = []
+    for i, mask in enumerate(masks):
+        if scores is not None and not np.float32(scores[i]) >= np.float32(min_score):
+            continue
+        if mask.any():
+            out.append((i, i, int(classes[i]), mask))
+    return out
+
+
 def pack_rgb(c) -> int:
     return int(c[0]) | (int(c[1]) << 8) | (int(c[2]) << 16)
 
@@ -64,9 +85,8 @@ def match_winners(iou) -> tuple:
     return choice, winner
 
 
-class ColorTracker:
-    """`assign(pred_ids, segments, colors) -> colors` per frame.  `live` is the list after the last frame (dicts with frame, id, category,
-    area, ttl, rgb, mask), `last_iou` the float64 [live before the frame, instances of the frame] matrix of the last frame."""
+class _LiveList:
+    """What both trackers are: the ttl, the pool and its counter, the live list and one step of the rule on a frame's instances."""
 
     def __init__(self, ttl: int = MAX_TTL, pool=None):
         if not 1 <= int(ttl) <= MAX_TTL:
@@ -87,17 +107,14 @@ class ColorTracker:
             out[k] = (o["frame"], o["id"], o["category"], o["area"], o["ttl"], o["rgb"], 0, 0)
         return out
 
-    def assign(self, pred_ids, segments, colors: Optional[np.ndarray] = None) -> np.ndarray:
-        """pred_ids int [H,W], segments rows (id, isthing, category), colors uint8 [n,3] (what the rows have so far; zeros when not
-        given) -> uint8 [n,3]: the rows of the frame's instances recoloured, every other row as it came."""
-        pred_ids = np.asarray(pred_ids)
-        segments = _table(segments)
+    def _check_size(self, hw) -> None:
         if self.hw is None:
-            self.hw = tuple(pred_ids.shape)
-        if tuple(pred_ids.shape) != self.hw:
-            raise ValueError(f"a {pred_ids.shape} frame for a tracker of {self.hw}")
-        out = np.zeros((len(segments), 3), np.uint8) if colors is None else np.array(colors, np.uint8).reshape(len(segments), 3)
-        new = frame_instances(pred_ids, segments)
+            self.hw = tuple(hw)
+        if tuple(hw) != self.hw:
+            raise ValueError(f"a {tuple(hw)} frame for a tracker of {self.hw}")
+
+    def _step(self, new: list, out: np.ndarray) -> np.ndarray:
+        """new: the frame's instances [(row of `out`, id, category, bool mask)]; their rows of `out` are recoloured."""
         area = [int(m.sum()) for _, _, _, m in new]
         iou = np.zeros((len(self.live), len(new)), np.float64)
         for a, o in enumerate(self.live):
@@ -130,6 +147,37 @@ class ColorTracker:
         return out
 
 
+class ColorTracker(_LiveList):
+    """`assign(pred_ids, segments, colors) -> colors` per frame.  `live` is the list after the last frame (dicts with frame, id, category,
+    area, ttl, rgb, mask), `last_iou` the float64 [live before the frame, instances of the frame] matrix of the last frame."""
+
+    def assign(self, pred_ids, segments, colors: Optional[np.ndarray] = None) -> np.ndarray:
+        """pred_ids int [H,W], segments rows (id, isthing, category), colors uint8 [n,3] (what the rows have so far; zeros when not
+        given) -> uint8 [n,3]: the rows of the frame's instances recoloured, every other row as it came."""
+        pred_ids = np.asarray(pred_ids)
+        segments = _table(segments)
+        self._check_size(pred_ids.shape)
+        out = np.zeros((len(segments), 3), np.uint8) if colors is None else np.array(colors, np.uint8).reshape(len(segments), 3)
+        return self._step(frame_instances(pred_ids, segments), out)
+
+
+class InstanceColorTracker(_LiveList):
+    """`assign(classes, scores, masks, min_score, colors) -> colors` per frame, for instance masks that may overlap (the restatement of
+    odise_hip_inst_track_frame).  `live` / `last_iou` / `live_rows()` as ColorTracker's; a live row's id is its table index."""
+
+    def assign(self, classes, scores, masks, min_score: float = 0.0, colors: Optional[np.ndarray] = None) -> np.ndarray:
+        """classes int [n], scores float [n] (None: no score test), masks bool [n,h,w], colors uint8 [m >= n,3] by table index (zeros [n,3]
+        when not given) -> the same with the rows of the frame's instances recoloured, every other row as it came."""
+        masks = np.asarray(masks) != 0
+        if masks.ndim != 3 or len(classes) != len(masks) or len(masks) > MAX_INSTANCES:
+            raise ValueError(f"masks {masks.shape} for {len(classes)} classes (at most {MAX_INSTANCES} instances [n,h,w])")
+        self._check_size(masks.shape[1:])
+        out = np.zeros((len(masks), 3), np.uint8) if colors is None else np.array(colors, np.uint8).reshape(-1, 3)
+        if len(out) < len(masks):
+            raise ValueError(f"{len(out)} colours for {len(masks)} instances")
+        return self._step(selection_instances(classes, scores, masks, min_score), out)
+
+
 def draw_panoptic_seg_predictions(image, pred_ids, segments, tracker: ColorTracker, metadata=None, alpha256: int = 128, edge_rgb=(0, 0, 0),
                                   small_area: int = SMALL_AREA, large_area: int = LARGE_AREA, labels: bool = True) -> np.ndarray:
     """`draw_panoptic_seg` with the tracker's colours for things: what HipVideoVisualizer.draw_panoptic_seg_predictions returns, computed
@@ -140,3 +188,17 @@ def draw_panoptic_seg_predictions(image, pred_ids, segments, tracker: ColorTrack
     if not labels:
         return pic
     return draw_labels(pic, segment_anchors(pred_ids, segments, small_area, large_area), segments, metadata)
+
+
+def draw_instance_predictions(image, masks, classes, scores, tracker: InstanceColorTracker, metadata=None, alpha256: int = 128,
+                              min_score: float = 0.0, labels: bool = True) -> np.ndarray:
+    """visualize.draw_instance_predictions with the tracker's colours (and the outlines derived from them): what
+    HipVideoVisualizer.draw_instance_predictions returns, computed by the restatement (labels=False: before the texts are drawn)."""
+    colors = tracker.assign(classes, scores, masks, min_score, instance_colors(classes, metadata))
+    pic = instance_overlay(image, masks, colors, instance_edge_colors(colors), alpha256, scores, min_score)
+    if not labels:
+        return pic
+    anchors = instance_anchors(masks, scores, min_score)
+    order = instance_order(masks, scores, min_score)
+    kept = sorted((i for i in range(len(anchors)) if order[i] >= 0), key=lambda i: order[i])
+    return draw_texts(pic, anchors[kept], instance_texts(classes, scores, metadata))

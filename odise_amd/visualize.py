@@ -377,20 +377,53 @@ class HipVisualizer:
 class HipVideoVisualizer(HipVisualizer):
     """detectron2 `VideoVisualizer(metadata)` for results that are still on the device: `draw_panoptic_seg_predictions` per frame, with
     the colours of things carried from frame to frame by the library's tracker (odise_hip_track_frame; the rule: odise_amd/video.py).
+    `draw_instance_predictions` does the same for the overlapping masks of the instance head (odise_hip_inst_track_frame; mask IoU,
+    detectron2's rule for instances without a box - the reference's zero boxes give every instance a fresh colour in every frame).
     `draw_sem_seg` is HipVisualizer's per-picture call: semantic maps are not tracked."""
 
     def __init__(self, ctx, metadata=None, ttl: int = 8, pool=None, **kwargs):
         super().__init__(ctx, metadata, **kwargs)
-        self.ttl, self.pool, self.tracker = int(ttl), pool, None
+        self.ttl, self.pool, self.tracker, self.inst_tracker = int(ttl), pool, None, None
 
     def reset(self) -> None:
-        if self.tracker is not None:
-            self.tracker.reset()
+        for t in (self.tracker, self.inst_tracker):
+            if t is not None:
+                t.reset()
 
     def close(self) -> None:
-        if self.tracker is not None:
-            self.tracker.close()
-            self.tracker = None
+        for t in (self.tracker, self.inst_tracker):
+            if t is not None:
+                t.close()
+        self.tracker, self.inst_tracker = None, None
+
+    def draw_instance_predictions(self, frame_dev, b, table_row, scores_row, topk, pad_hw, img_hw, out_hw, min_score: float = 0.0,
+                                  labels: bool = True) -> np.ndarray:
+        """HipVisualizer.draw_instance_predictions with the colours of the library's instance tracker: the fill and outline colours of the
+        frame's instances are written on the device and drawn from there; the masks never travel (labels=False: the picture before the
+        texts are drawn).  The tracker is made at the first frame, for its size and its topk; another size or topk is an error."""
+        ctx, topk = self.ctx, int(topk)
+        h, w = int(out_hw[0]), int(out_hw[1])
+        if self.inst_tracker is None:
+            self.inst_tracker = ctx.inst_track_create((h, w), topk, self.ttl, self.pool)
+        if self.inst_tracker.hw != (h, w) or self.inst_tracker.topk != topk:
+            raise ValueError(f"a {h}x{w} frame of {topk} instances for a tracker of {self.inst_tracker.hw[0]}x{self.inst_tracker.hw[1]} "
+                             f"and {self.inst_tracker.topk}")
+        table, scores = table_row.numpy().reshape(-1), scores_row.numpy().reshape(-1)
+        n = min(max(int(table[0]), 0), topk)
+        classes = table[1 + topk:1 + topk + n]
+        host_colors = np.zeros((topk, 3), np.uint8)
+        host_colors[:n] = instance_colors(classes, self.metadata)          # what a row has before the tracker; drawn rows are rewritten
+        colors, edges = ctx.to_device(host_colors), ctx.to_device(instance_edge_colors(host_colors))
+        ctx.inst_track_frame(self.inst_tracker, table_row, scores_row, b=b, pad_hw=pad_hw, img_hw=img_hw, min_score=min_score, colors=colors,
+                             edge_colors=edges)
+        want = ("out", "anchors", "order") if labels else ("out",)
+        res = ctx.instance_draw((h, w), topk, table_row, scores_row, b=b, pad_hw=pad_hw, img_hw=img_hw, min_score=min_score, image=frame_dev,
+                                colors=colors, edge_colors=edges, alpha256=self.alpha256, want=want)
+        if not labels:
+            return res["out"].numpy()
+        picture, anchors, order = res["out"].numpy(), res["anchors"].numpy(), res["order"].numpy()
+        kept = sorted((i for i in range(n) if order[i] >= 0), key=lambda i: order[i])
+        return draw_texts(picture, anchors[kept], instance_texts(classes, scores[:n], self.metadata))
 
     def draw_panoptic_seg_predictions(self, frame_dev, record_dev, hw, labels: bool = True) -> np.ndarray:
         """frame_dev uint8 [h,w,3] and the frame's panoptic record on the device -> host uint8 [h,w,3] (labels=False: before the names
