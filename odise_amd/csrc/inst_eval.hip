@@ -3,15 +3,19 @@
 // per-picture part of InstanceSegEvaluator / COCOEvaluator(tasks=("segm",)), odise/evaluation/d2_evaluator.py:29,104).  Host restatement:
 // odise_amd/instance_eval.py.
 //
-//   1. pack     the detections into words [n][w][R] (rle_pack.h: the kernels of rle.hip, the pixels of odise_hip_instance_rle).
+//   1. pack     the detections into words [n][w][R] (inst_geom / inst_pack of inst_words.h: the kernels of rle.hip, the pixels of
+//               odise_hip_instance_rle).
 //   2. decode   the ground truth from uncompressed COCO run lengths into the same layout.  One block per mask walks its runs 1024 at a time:
 //               a block scan gives the end position of every run of the chunk, then a thread per word of the chunk's span searches the first
 //               run that reaches into its word and walks on from there.  Every position is clamped to h * w: counts that sum to anything
 //               else raise flag 1 and never move a read or a write outside the mask.  A ground truth given as polygons
 //               (odise_hip_instance_eval_poly) is left empty here and rasterised into the same words by poly.hip right behind.
 //   3. inter    inter[d][g] = sum of popcount(words_d & words_g), tiled like a small GEMM: a block holds 32 words of 64 detections and 32
-//               ground truths in LDS and a thread forms 4 x 2 pairs from them; the word axis is split over blockIdx.z and the partial
-//               counts meet in integer atomics (exact, and the same from run to run).  Areas are the popcounts of one side.
+//               ground truths in LDS and a thread forms 4 x 2 pairs from them; the word axis is split over blockIdx.z (inst_inter_split
+//               of inst_words.h, which also holds the tile sizes) and the partial counts meet in integer atomics (exact, and the same
+//               from run to run).  inst_track_inter_kernel (inst_track.hip) is this loop over gathered rows; the two stay written out:
+//               on one shared tile function this kernel took 3 to 5 us longer per call (profiles/README.md, inst_words_bench.json).
+//               Areas are the popcounts of one side (block_popcount of inst_words.h).
 //   4. iou      rleIou in double: inter == 0 -> 0, crowd -> inter / area_d, else inter / (area_d + area_g - inter).
 //   5. match    one block.  Detections in descending score (ties keep table order), ground truths of a category in annotation order.  The 40
 //               (area range, threshold) cells of a detection are the lanes 10 a + t of ONE wave, which walks the ground truths of the
@@ -20,18 +24,12 @@
 //               sorted by ignore, with its break.  The IoUs of 64 ground truths are computed by the 64 lanes at once and handed round by
 //               lane index.  Categories are independent, so the 16 waves of the block share the detections by category.  The matched /
 //               ignored words of a row are the ballots of the wave.
-#include <algorithm>
-
-#include "rle_pack.h"
+#include "inst_words.h"
 
 namespace odise {
 
-constexpr int kInstMaxDet = 100;       // the evaluator looks at no more than 100 detections per picture and category
 constexpr int kInstMaxGt = 1024;
 constexpr int kInstCells = 40;         // 4 area ranges x 10 thresholds, bit 10 a + t
-constexpr int kInterTD = 64, kInterTG = 32, kInterKC = 32;   // tile of the intersection kernel: detections, ground truths, words per step
-
-typedef unsigned long long u64;
 
 __device__ __forceinline__ double rle_iou(int inter, long long area_d, long long area_g, bool crowd) {
     if (inter == 0) return 0.0;
@@ -101,18 +99,18 @@ __global__ void __launch_bounds__(kRleThreads) inst_decode_kernel(const uint32_t
 // inter[n][n_gt] += over the words [blockIdx.z * per, + per) of the masks; `per` is a multiple of kInterKC
 __global__ void __launch_bounds__(256) inst_inter_kernel(const u64* __restrict__ wd_d, const u64* __restrict__ wd_g, int n, int n_gt, int64_t nw,
                                                         int64_t per, int* __restrict__ inter) {
-    __shared__ u64 sd[kInterTD][kInterKC + 1];
-    __shared__ u64 sg[kInterTG][kInterKC + 1];
+    __shared__ u64 sd[kInterRows][kInterKC + 1];
+    __shared__ u64 sg[kInterCols][kInterKC + 1];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int d0 = blockIdx.x * kInterTD, g0 = blockIdx.y * kInterTG;
+    const int d0 = blockIdx.x * kInterRows, g0 = blockIdx.y * kInterCols;
     const int64_t k_begin = (int64_t)blockIdx.z * per, k_end = min(nw, k_begin + per);
     int acc[4][2] = {};
     for (int64_t k0 = k_begin; k0 < k_end; k0 += kInterKC) {
-        for (int e = tid; e < (kInterTD + kInterTG) * kInterKC; e += 256) {
+        for (int e = tid; e < (kInterRows + kInterCols) * kInterKC; e += 256) {
             const int row = e / kInterKC, kk = e - row * kInterKC;
             const int64_t k = k0 + kk;
-            if (row < kInterTD) sd[row][kk] = (d0 + row < n && k < k_end) ? wd_d[(int64_t)(d0 + row) * nw + k] : 0ull;
-            else sg[row - kInterTD][kk] = (g0 + row - kInterTD < n_gt && k < k_end) ? wd_g[(int64_t)(g0 + row - kInterTD) * nw + k] : 0ull;
+            if (row < kInterRows) sd[row][kk] = (d0 + row < n && k < k_end) ? wd_d[(int64_t)(d0 + row) * nw + k] : 0ull;
+            else sg[row - kInterRows][kk] = (g0 + row - kInterRows < n_gt && k < k_end) ? wd_g[(int64_t)(g0 + row - kInterRows) * nw + k] : 0ull;
         }
         __syncthreads();
 #pragma unroll 4
@@ -138,15 +136,8 @@ __global__ void __launch_bounds__(256) inst_inter_kernel(const u64* __restrict__
 
 // area[row] = ones of a row of words; one block per row
 __global__ void __launch_bounds__(256) inst_area_kernel(const u64* __restrict__ words, int64_t nw, long long* __restrict__ area) {
-    __shared__ long long part[4];
-    const u64* wd = words + (int64_t)blockIdx.x * nw;
-    long long s = 0;
-    for (int64_t i = threadIdx.x; i < nw; i += 256) s += __popcll(wd[i]);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_down(s, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) area[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+    const long long s = block_popcount(words + (int64_t)blockIdx.x * nw, nw);
+    if (threadIdx.x == 0) area[blockIdx.x] = s;
 }
 
 // ---- 4. iou (odise_hip_mask_iou) ----------------------------------------------------------------------------------------------------------
@@ -185,12 +176,12 @@ __device__ __forceinline__ bool inst_area_outside(int area, int a) {   // [0, 1e
 __global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A) {
     __shared__ int g_cat[kInstMaxGt], g_flag[kInstMaxGt], g_area[kInstMaxGt], g_sorted[kInstMaxGt];   // g_flag: iscrowd | outside bits << 1
     __shared__ u64 g_matched[kInstMaxGt];                                                             // bit = cell
-    __shared__ int d_cls[kInstMaxDet], d_area[kInstMaxDet], d_order[kInstMaxDet], d_lo[kInstMaxDet], d_cnt[kInstMaxDet];
-    __shared__ float d_score[kInstMaxDet];
+    __shared__ int d_cls[kInstMaxTopk], d_area[kInstMaxTopk], d_order[kInstMaxTopk], d_lo[kInstMaxTopk], d_cnt[kInstMaxTopk];
+    __shared__ float d_score[kInstMaxTopk];
     __shared__ int bad;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int topk = A.topk, n_gt = A.n_gt;
-    const int n = min(max(A.inst_table[0], 0), topk);
+    const int n = inst_count(A.inst_table, topk);
     if (tid == 0) bad = A.status[0];
     __syncthreads();
     int f = 0;
@@ -315,12 +306,9 @@ static int inst_overlaps(odise_hip_ctx* ctx, const InstScratch& s, const RleGrid
                            G, flag, p ? (const int*)p->gt_polys : nullptr);
         ODISE_CHECK_HIP(hipGetLastError());
         if (p) ODISE_TRY(poly_fill_words(ctx, p->xy, p->poly_offsets, p->gt_polys, n_gt, p->n_poly, G, s.words_g, s.toggle, false, gt_offsets, flag));
-        // split the word axis until the grid fills the chip about twice
-        const int64_t tiles = ceil_div(n, kInterTD) * ceil_div(n_gt, kInterTG), steps = ceil_div(G.nw, kInterKC);
-        const int64_t kz = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(steps, 1024), 2 * ctx->cu_count / tiles));
-        const int64_t per = ceil_div(steps, kz) * kInterKC;
-        const dim3 grid((unsigned)ceil_div(n, kInterTD), (unsigned)ceil_div(n_gt, kInterTG), (unsigned)ceil_div(G.nw, per));
-        hipLaunchKernelGGL(inst_inter_kernel, grid, dim3(256), 0, ctx->stream, (const u64*)s.words_d, (const u64*)s.words_g, n, n_gt, G.nw, per,
+        // split the word axis until the grid fills the chip about twice (at most 2 * cu_count ways: far below the grid's z limit)
+        const InterSplit sp = inst_inter_split(n, n_gt, G.nw, 2 * ctx->cu_count);
+        hipLaunchKernelGGL(inst_inter_kernel, sp.grid, dim3(256), 0, ctx->stream, (const u64*)s.words_d, (const u64*)s.words_g, n, n_gt, G.nw, sp.per,
                            s.inter);
         ODISE_CHECK_HIP(hipGetLastError());
     }
@@ -359,27 +347,24 @@ extern "C" int odise_hip_instance_eval(odise_hip_ctx* ctx, const odise_inst_eval
 
 extern "C" int odise_hip_instance_eval_poly(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p) {
     ODISE_REQUIRE(ctx && d, "instance_eval: null argument");
-    ODISE_REQUIRE(d->inst_table && d->inst_scores && d->iou_thresholds && d->rows && d->n_rows && d->flags, "instance_eval: null pointer");
-    ODISE_REQUIRE(d->topk >= 1 && d->topk <= kInstMaxDet, "instance_eval: topk %d (1..%d)", d->topk, kInstMaxDet);
+    ODISE_REQUIRE(d->iou_thresholds && d->rows && d->n_rows && d->flags, "instance_eval: null pointer");
+    const InstSource src = inst_source(*d);
+    ODISE_TRY(inst_source_check("instance_eval", src, true, kRleMaxPixels));   // the match step reads the table and the scores of dense masks too
     ODISE_REQUIRE(d->n_gt >= 0 && d->n_gt <= kInstMaxGt, "instance_eval: %d ground-truth masks (0..%d)", d->n_gt, kInstMaxGt);
     ODISE_REQUIRE(d->n_gt == 0 || (d->gt_runs && d->gt_offsets && d->gt_rows), "instance_eval: null ground truth");
     ODISE_REQUIRE(!p || p->n_poly >= 0, "instance_eval: %d polygons", p->n_poly);
     if (p && (d->n_gt == 0 || p->n_poly == 0)) p = nullptr;   // nothing to rasterise
     ODISE_REQUIRE(!p || (p->xy && p->poly_offsets && p->gt_polys), "instance_eval: null polygon ground truth");
     ODISE_REQUIRE(d->num_categories >= 1, "instance_eval: num_categories %d", d->num_categories);
-    ODISE_REQUIRE(d->h >= 1 && d->w >= 1 && (int64_t)d->h * d->w <= kRleMaxPixels, "instance_eval: mask size %dx%d out of range", d->h, d->w);
-    ODISE_REQUIRE(!d->masks || d->dtype == ODISE_F32 || d->dtype == ODISE_U8, "instance_eval: dtype %d (ODISE_F32 or ODISE_U8)", d->dtype);
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    PostGeom g;
-    const f16* logits = nullptr;
-    if (!d->masks) ODISE_TRY(rle_instance_geom(ctx, "instance_eval", d->b, d->pad_h, d->pad_w, d->img_h, d->img_w, d->h, d->w, &g, &logits));
+    InstGeom ig;
+    ODISE_TRY(inst_geom(ctx, "instance_eval", src, &ig));
     const RleGrid G = rle_grid(d->h, d->w);
     InstScratch s;
     ODISE_TRY(inst_scratch(ctx, d->topk, d->n_gt, G, &s, p != nullptr));
     ODISE_CHECK_HIP(hipMemsetAsync(s.inter, 0, s.inter_bytes, ctx->stream));
     int* status = s.inter + (size_t)d->topk * d->n_gt;
-    if (d->masks) ODISE_TRY(rle_pack_dense(ctx, d->masks, d->dtype, d->topk, G, s.words_d));
-    else ODISE_TRY(rle_pack_logits(ctx, logits, (const int*)d->inst_table, d->topk, g, G, s.words_d));
+    ODISE_TRY(inst_pack(ctx, src, ig, G, s.words_d));
     ODISE_TRY(inst_overlaps(ctx, s, G, d->topk, d->gt_runs, d->gt_offsets, d->n_gt, status, p));
     InstMatchArgs A;
     A.inst_table = (const int*)d->inst_table; A.inst_scores = d->inst_scores; A.gt_rows = (const int*)d->gt_rows;

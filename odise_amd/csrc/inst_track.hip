@@ -6,30 +6,24 @@
 // never lands in a slot a live row points to - and a live row finds its words through its (frame, id).  Four launches per frame, no
 // synchronisation, no count read by the host:
 //
-//   pack                     rle_pack_dense / rle_pack_logits (rle.hip) straight into the ring slot frame mod (ttl + 1)
-//   inst_track_area_kernel   a block per table index: area = popcount of its words when the index is below the count and its score passes,
-//                            else 0 (area > 0 is the `kept` rule of odise_hip_instance_draw), and its class
-//   inst_track_inter_kernel  inter[live o][new j] += popcount(words_o & words_j), tiled like inst_inter_kernel (inst_eval.hip): 64 live rows
-//                            x 32 new masks x 32 words in LDS, padded rows, a thread forms 4 x 2 pairs, the word axis split over
-//                            blockIdx.z.  The grid is sized for the caps (800 x topk): a tile past the live count or the table count
+//   pack                     inst_pack (inst_words.h) straight into the ring slot frame mod (ttl + 1)
+//   inst_track_area_kernel   a block per table index: area = popcount of its words when the index is a candidate (inst_candidate, the rule
+//                            of odise_hip_instance_draw: area > 0 is its `kept`), else 0, and its class
+//   inst_track_inter_kernel  inter[live o][new j] += popcount(words_o & words_j), tiled like inst_inter_kernel (inst_eval.hip; the tile
+//                            sizes and the split of the word axis are the ones of inst_words.h): 64 live rows x 32 new masks x 32 words
+//                            in LDS, padded rows, a thread forms 4 x 2 pairs, the word axis split over blockIdx.z.
+//                            The grid is sized for the caps (800 x topk): a tile past the live count or the table count
 //                            leaves at once, and so does - decided once per tile, by the whole block - a tile in which no live row
 //                            shares a class with a kept new mask.  Neither has loaded a word by then.  Integer atomics; pairs of
 //                            different classes are not added (the matching never reads them).
 //   inst_track_match_kernel  one block: track_match_block (track_match.h, shared with track.hip), then the matrix zeroed again
-#include <algorithm>
-
-#include "rle_pack.h"
+#include "inst_words.h"
 #include "track_match.h"
 #include "vis_scan.h"
 
 namespace odise {
 
-constexpr int kInstTrackMax = 100;                                       // topk limit (the instance head keeps at most 100 per picture)
-static_assert(kInstTrackMax <= ODISE_MAX_SEGMENTS, "the shared match step holds ODISE_MAX_SEGMENTS entries");
-constexpr int kGatherTL = 64, kGatherTN = 32, kGatherKC = 32;            // tile: live rows, new masks, words per step
 constexpr int kGatherBlocks = 2048;                                      // the grid's target size; most of it leaves at once
-
-typedef unsigned long long u64;
 
 struct InstTrackState {   // device
     int counter, n_live, pad0, pad1;         // pool counter (kept modulo n_pool), rows of `live`
@@ -51,48 +45,33 @@ struct odise_inst_track {
 
 namespace odise {
 
-__device__ __forceinline__ int inst_track_count(const int* __restrict__ table, int topk) {
-    if (!table) return topk;
-    const int n = table[0];
-    return n < 0 ? 0 : (n > topk ? topk : n);
-}
-
 // words: the new frame's slot.  area[i] = pixels of mask i when i is an instance candidate (below the count, score >= min_score), else 0.
 __global__ void __launch_bounds__(256) inst_track_area_kernel(const u64* __restrict__ words, int64_t nw, const int* __restrict__ table,
                                                              const float* __restrict__ scores, int topk, float min_score, int* __restrict__ area,
                                                              int* __restrict__ cls) {
-    __shared__ int part[4];
     const int i = blockIdx.x;
-    const bool cand = i < inst_track_count(table, topk) && (!scores || scores[i] >= min_score);
-    int s = 0;
-    if (cand) {
-        const u64* wd = words + (int64_t)i * nw;
-        for (int64_t k = threadIdx.x; k < nw; k += 256) s += __popcll(wd[k]);
-    }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_down(s, o);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
-    __syncthreads();
+    const bool cand = inst_candidate(table, scores, topk, min_score, i);
+    const long long s = block_popcount(words + (int64_t)i * nw, cand ? nw : 0);
     if (threadIdx.x == 0) {
-        area[i] = part[0] + part[1] + part[2] + part[3];   // at most h * w < 2^29
+        area[i] = (int)s;   // at most h * w < 2^29
         cls[i] = (table && cand) ? table[1 + topk + i] : 0;
     }
 }
 
-// inter[o][j] += over the words [blockIdx.z * per, + per) of live row o and new mask j; `per` is a multiple of kGatherKC
+// inter[o][j] += over the words [blockIdx.z * per, + per) of live row o and new mask j; `per` is a multiple of kInterKC
 __global__ void __launch_bounds__(256) inst_track_inter_kernel(const u64* __restrict__ ring, const InstTrackState* __restrict__ st,
                                                               const int* __restrict__ table, const int* __restrict__ area,
                                                               const int* __restrict__ cls, int topk, int slots, int new_slot, int64_t nw, int64_t per,
                                                               int* __restrict__ inter) {
-    __shared__ u64 sl[kGatherTL][kGatherKC + 1];
-    __shared__ u64 sn[kGatherTN][kGatherKC + 1];
-    __shared__ long long base[kGatherTL + kGatherTN];   // first word of a row's mask in the ring, -1 = no such row
-    __shared__ int cat[kGatherTL + kGatherTN];
+    __shared__ u64 sl[kInterRows][kInterKC + 1];
+    __shared__ u64 sn[kInterCols][kInterKC + 1];
+    __shared__ long long base[kInterRows + kInterCols];   // first word of a row's mask in the ring, -1 = no such row
+    __shared__ int cat[kInterRows + kInterCols];
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
-    const int o0 = blockIdx.x * kGatherTL, j0 = blockIdx.y * kGatherTN;
-    const int n_live = track_clamp(st->n_live, kTrackLiveCap), n = inst_track_count(table, topk);
+    const int o0 = blockIdx.x * kInterRows, j0 = blockIdx.y * kInterCols;
+    const int n_live = track_clamp(st->n_live, kTrackLiveCap), n = inst_count(table, topk);
     if (o0 >= n_live || j0 >= n) return;   // block-uniform: nothing is loaded for a tile past either count
-    if (tid < kGatherTL) {
+    if (tid < kInterRows) {
         long long b = -1;
         int c = 0;
         const int o = o0 + tid;
@@ -104,10 +83,10 @@ __global__ void __launch_bounds__(256) inst_track_inter_kernel(const u64* __rest
             }
         }
         base[tid] = b; cat[tid] = c;
-    } else if (tid < kGatherTL + kGatherTN) {
+    } else if (tid < kInterRows + kInterCols) {
         long long b = -1;
         int c = 0;
-        const int j = j0 + tid - kGatherTL;
+        const int j = j0 + tid - kInterRows;
         if (j < n && area[j] > 0) {
             b = ((long long)new_slot * topk + j) * nw;
             c = cls[j];
@@ -121,7 +100,7 @@ __global__ void __launch_bounds__(256) inst_track_inter_kernel(const u64* __rest
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int a = ty + 16 * i, b = kGatherTL + tx + 16 * j;
+            const int a = ty + 16 * i, b = kInterRows + tx + 16 * j;
             pair[i][j] = base[a] >= 0 && base[b] >= 0 && cat[a] == cat[b];
             any |= pair[i][j] ? 1 : 0;
         }
@@ -129,18 +108,18 @@ __global__ void __launch_bounds__(256) inst_track_inter_kernel(const u64* __rest
 
     const int64_t k_begin = (int64_t)blockIdx.z * per, k_end = min(nw, k_begin + per);
     int acc[4][2] = {};
-    for (int64_t k0 = k_begin; k0 < k_end; k0 += kGatherKC) {
-        for (int e = tid; e < (kGatherTL + kGatherTN) * kGatherKC; e += 256) {
-            const int row = e / kGatherKC, kk = e - row * kGatherKC;
+    for (int64_t k0 = k_begin; k0 < k_end; k0 += kInterKC) {
+        for (int e = tid; e < (kInterRows + kInterCols) * kInterKC; e += 256) {
+            const int row = e / kInterKC, kk = e - row * kInterKC;
             const int64_t k = k0 + kk;
             const long long b = base[row];
             const u64 v = (b >= 0 && k < k_end) ? ring[b + k] : 0ull;
-            if (row < kGatherTL) sl[row][kk] = v;
-            else sn[row - kGatherTL][kk] = v;
+            if (row < kInterRows) sl[row][kk] = v;
+            else sn[row - kInterRows][kk] = v;
         }
         __syncthreads();
 #pragma unroll 4
-        for (int kk = 0; kk < kGatherKC; ++kk) {
+        for (int kk = 0; kk < kInterKC; ++kk) {
             const u64 b0 = sn[tx][kk], b1 = sn[tx + 16][kk];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -164,7 +143,7 @@ __global__ void __launch_bounds__(kTrackMatchThreads) inst_track_match_kernel(in
                                                                              InstTrackState* __restrict__ st, int topk, int frame, TrackMatchIo io) {
     __shared__ int tab[ODISE_MAX_SEGMENTS], cat[ODISE_MAX_SEGMENTS], area[ODISE_MAX_SEGMENTS];
     const int tid = threadIdx.x;
-    const int n = inst_track_count(table, topk);
+    const int n = inst_count(table, topk);
     const int n_live = track_clamp(st->n_live, kTrackLiveCap), counter = st->counter;
     if (tid < n) {
         tab[tid] = tid;
@@ -203,18 +182,14 @@ static int inst_track_clear(odise_hip_ctx* ctx, odise_inst_track* t) {
 static int inst_track_check_args(const odise_inst_track_desc* d) {
     ODISE_REQUIRE(d, "inst_track_frame: null descriptor");
     ODISE_REQUIRE(d->track && d->colors, "inst_track_frame: null pointer");
-    ODISE_REQUIRE(d->masks || (d->inst_table && d->inst_scores),
-                  "inst_track_frame: the selection of the last head forward needs inst_table and inst_scores");
-    ODISE_TRY(vis_check_size("inst_track_frame", d->h, d->w));
+    ODISE_TRY(inst_source_check("inst_track_frame", inst_source(*d), false, kVisMaxPixels));
     const odise_inst_track* t = d->track;
     ODISE_REQUIRE(d->h == t->H && d->w == t->W && d->topk == t->topk, "inst_track_frame: a %dx%d frame of %d masks for a tracker of %dx%d and %d",
                   d->h, d->w, d->topk, t->H, t->W, t->topk);
-    ODISE_REQUIRE(!d->masks || d->dtype == ODISE_F32 || d->dtype == ODISE_U8, "inst_track_frame: dtype %d (ODISE_F32 or ODISE_U8)", d->dtype);
     ODISE_REQUIRE(d->live_cap >= 0 && d->iou_cap >= 0, "inst_track_frame: negative cap (live_cap %d, iou_cap %d)", d->live_cap, d->iou_cap);
     ODISE_REQUIRE(!d->live || d->n_live, "inst_track_frame: live without n_live");
-    ODISE_REQUIRE((((uintptr_t)d->inst_table | (uintptr_t)d->inst_scores | (uintptr_t)d->live | (uintptr_t)d->n_live) & 3) == 0 &&
-                      ((uintptr_t)d->iou & 7) == 0,
-                  "inst_track_frame: int32 / float buffers must be 4-byte aligned, iou 8-byte aligned");
+    ODISE_REQUIRE((((uintptr_t)d->live | (uintptr_t)d->n_live) & 3) == 0 && ((uintptr_t)d->iou & 7) == 0,
+                  "inst_track_frame: live / n_live must be 4-byte aligned, iou 8-byte aligned");
     return ODISE_OK;
 }
 
@@ -227,7 +202,7 @@ extern "C" int odise_hip_inst_track_create(odise_hip_ctx* ctx, int H, int W, int
     ODISE_REQUIRE(ctx, "inst_track_create: null context");
     ODISE_REQUIRE(out && pool_rgb, "inst_track_create: null pointer");
     ODISE_TRY(vis_check_size("inst_track_create", H, W));
-    ODISE_REQUIRE(topk >= 1 && topk <= kInstTrackMax, "inst_track_create: topk %d outside 1..%d", topk, kInstTrackMax);
+    ODISE_REQUIRE(topk >= 1 && topk <= kInstMaxTopk, "inst_track_create: topk %d outside 1..%d", topk, kInstMaxTopk);
     ODISE_REQUIRE(ttl >= 1 && ttl <= kTrackRing, "inst_track_create: ttl %d outside 1..%d", ttl, kTrackRing);
     ODISE_REQUIRE(n_pool >= 1 && n_pool <= (1 << 20), "inst_track_create: n_pool %d outside 1..2^20", n_pool);
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
@@ -284,25 +259,21 @@ extern "C" int odise_hip_inst_track_frame(odise_hip_ctx* ctx, const odise_inst_t
     odise_inst_track* t = d->track;
     const int topk = t->topk;
     const RleGrid& G = t->G;
-    PostGeom g;
-    const f16* logits = nullptr;
-    if (!d->masks) ODISE_TRY(rle_instance_geom(ctx, "inst_track_frame", d->b, d->pad_h, d->pad_w, d->img_h, d->img_w, d->h, d->w, &g, &logits));
+    const InstSource src = inst_source(*d);
+    InstGeom ig;
+    ODISE_TRY(inst_geom(ctx, "inst_track_frame", src, &ig));
     const int new_slot = t->frame % t->slots;
     u64* words = t->ring + (int64_t)new_slot * topk * G.nw;
     const int* table = (const int*)d->inst_table;
     int* cls = t->area + topk;
-    if (d->masks) ODISE_TRY(rle_pack_dense(ctx, d->masks, d->dtype, topk, G, words));
-    else ODISE_TRY(rle_pack_logits(ctx, logits, table, topk, g, G, words));
+    ODISE_TRY(inst_pack(ctx, src, ig, G, words));
     hipLaunchKernelGGL(inst_track_area_kernel, dim3((unsigned)topk), dim3(256), 0, ctx->stream, (const u64*)words, G.nw, table, d->inst_scores, topk,
                        d->min_score, t->area, cls);
     ODISE_CHECK_HIP(hipGetLastError());
     // the counts are device values: the grid covers the caps, and the word axis is split until it has about kGatherBlocks blocks
-    const int64_t tiles = ceil_div(kTrackLiveCap, kGatherTL) * ceil_div(topk, kGatherTN), steps = ceil_div(G.nw, kGatherKC);
-    const int64_t kz = std::max<int64_t>(1, std::min<int64_t>(steps, kGatherBlocks / tiles));
-    const int64_t per = ceil_div(steps, kz) * kGatherKC;
-    const dim3 grid((unsigned)ceil_div(kTrackLiveCap, kGatherTL), (unsigned)ceil_div(topk, kGatherTN), (unsigned)ceil_div(G.nw, per));
-    hipLaunchKernelGGL(inst_track_inter_kernel, grid, dim3(256), 0, ctx->stream, (const u64*)t->ring, (const InstTrackState*)t->state, table,
-                       (const int*)t->area, (const int*)cls, topk, t->slots, new_slot, G.nw, per, t->inter);
+    const InterSplit sp = inst_inter_split(kTrackLiveCap, topk, G.nw, kGatherBlocks);
+    hipLaunchKernelGGL(inst_track_inter_kernel, sp.grid, dim3(256), 0, ctx->stream, (const u64*)t->ring, (const InstTrackState*)t->state, table,
+                       (const int*)t->area, (const int*)cls, topk, t->slots, new_slot, G.nw, sp.per, t->inter);
     ODISE_CHECK_HIP(hipGetLastError());
     TrackMatchIo io;
     io.pool = t->pool; io.n_pool = t->n_pool; io.ttl = t->ttl;

@@ -1,0 +1,90 @@
+// inst_words.h — "the instance masks of a picture" as the bit-packed words of rle_pack.h, written once for the four entry points that
+// take them: odise_hip_instance_eval(_poly) (inst_eval.hip), odise_hip_instance_draw (vis_inst.hip), odise_hip_inst_track_frame
+// (inst_track.hip) and odise_hip_instance_rle (rle.hip, which also compiles inst_source_check, inst_geom and inst_pack).
+//   host    InstSource (the detection fields the three public descriptors share), its check, the geometry lookup and the pack launch,
+//           the split of the word axis of the intersection kernels
+//   device  the clamped count of a selection and the candidate rule, the block popcount of a row of words, the tile sizes of the
+//           intersection kernels
+#pragma once
+#include <algorithm>
+
+#include "rle_pack.h"
+
+namespace odise {
+
+typedef unsigned long long u64;
+
+constexpr int kInstMaxTopk = 100;   // the instance head keeps, and the evaluator looks at, no more than 100 detections per picture
+static_assert(kInstMaxTopk <= ODISE_MAX_SEGMENTS, "the shared match step holds ODISE_MAX_SEGMENTS entries");
+
+// The detections of a picture: dense masks [topk, h, w] (ODISE_F32 / ODISE_U8), or masks == nullptr = the selection inst_table /
+// inst_scores of image b of the last head forward, sampled from its mask logits.
+struct InstSource {
+    int h, w;
+    const void* masks;
+    int dtype, b, pad_h, pad_w, img_h, img_w;
+    const int* inst_table;
+    const float* inst_scores;
+    int topk;
+};
+template <class Desc>
+static inline InstSource inst_source(const Desc& d) {   // odise_inst_eval_desc, odise_inst_draw_desc, odise_inst_track_desc
+    return InstSource{d.h, d.w, d.masks, d.dtype, d.b, d.pad_h, d.pad_w, d.img_h, d.img_w, (const int*)d.inst_table, d.inst_scores, d.topk};
+}
+// What can be refused without the model (the errors carry `what`).  need_table: the caller reads inst_table and inst_scores with dense
+// masks too; max_pixels: the caller's bound on h * w.
+int inst_source_check(const char* what, const InstSource& s, bool need_table, int64_t max_pixels);
+// The sampling geometry and the mask logits of a source without dense masks (unused with them): image b of the last head forward, its
+// geometry checked (the errors carry `what`).  Enqueues nothing and touches no scratch, so a caller runs it before it reserves any.
+struct InstGeom {
+    PostGeom g;
+    const f16* logits;
+};
+int inst_geom(odise_hip_ctx* ctx, const char* what, const InstSource& s, InstGeom* ig);
+// words [topk][G.nw] of the source: the dense pack, or the logits pack, which leaves the masks past the count of the table unwritten
+int inst_pack(odise_hip_ctx* ctx, const InstSource& s, const InstGeom& ig, const RleGrid& G, u64* words);
+
+// ---- device: count, candidates, area -------------------------------------------------------------------------------------------------
+// the instances of a selection: table[0] clamped to 0..topk; no table = all topk
+__device__ __forceinline__ int inst_count(const int* __restrict__ table, int topk) {
+    if (!table) return topk;
+    const int n = table[0];
+    return n < 0 ? 0 : (n > topk ? topk : n);
+}
+// table index i is a candidate: below the count, and its score passes.  A candidate with a pixel is `kept`.
+__device__ __forceinline__ bool inst_candidate(const int* __restrict__ table, const float* __restrict__ scores, int topk, float min_score, int i) {
+    return i < inst_count(table, topk) && (!scores || scores[i] >= min_score);
+}
+// ones of nw words, summed over a block of 256 threads (shuffles, then the four wave partials through LDS); ends in a barrier
+__device__ __forceinline__ long long block_popcount(const u64* __restrict__ wd, int64_t nw) {
+    __shared__ long long part[4];
+    long long s = 0;
+    for (int64_t i = threadIdx.x; i < nw; i += 256) s += __popcll(wd[i]);
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_down(s, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    return part[0] + part[1] + part[2] + part[3];
+}
+
+// ---- the intersection kernels (inst_inter_kernel, inst_track_inter_kernel) --------------------------------------------------------------
+// A block of 256 threads counts popcount(a & b) for kInterRows x kInterCols pairs of masks, tiled like a small GEMM: kInterKC words of
+// every row in LDS (padded rows), a thread forms 4 x 2 pairs from them.  The loop itself is written out in both kernels.
+constexpr int kInterRows = 64, kInterCols = 32, kInterKC = 32;
+
+// The grid of an intersection kernel over rows x cols masks of nw words: the word axis is split over blockIdx.z until the grid has about
+// target_blocks blocks; a block takes `per` words, a multiple of kInterKC.
+struct InterSplit {
+    int64_t per;
+    dim3 grid;
+};
+static inline InterSplit inst_inter_split(int64_t rows, int64_t cols, int64_t nw, int64_t target_blocks) {
+    const int64_t rt = ceil_div(rows, kInterRows), ct = ceil_div(cols, kInterCols), steps = ceil_div(nw, kInterKC);
+    const int64_t kz = std::max<int64_t>(1, std::min<int64_t>(steps, target_blocks / (rt * ct)));
+    InterSplit s;
+    s.per = ceil_div(steps, kz) * kInterKC;
+    s.grid = dim3((unsigned)rt, (unsigned)ct, (unsigned)ceil_div(nw, s.per));
+    return s;
+}
+
+}  // namespace odise

@@ -19,7 +19,7 @@
 // Integer scans only, no atomics: the output is deterministic.
 #include <string.h>
 
-#include "rle_pack.h"   // RleGrid, kRleThreads, block_scan_sum: shared with inst_eval.hip
+#include "inst_words.h"   // rle_pack.h (RleGrid, kRleThreads, block_scan_sum) and InstSource, whose check and pack launch live here
 
 namespace odise {
 
@@ -260,8 +260,11 @@ int rle_pack_dense(odise_hip_ctx* ctx, const void* masks, int dtype, int n, cons
     return ODISE_OK;
 }
 
-int rle_instance_geom(odise_hip_ctx* ctx, const char* what, int b, int pad_h, int pad_w, int img_h, int img_w, int out_h, int out_w, PostGeom* g,
-                      const f16** logits) {
+int inst_geom(odise_hip_ctx* ctx, const char* what, const InstSource& s, InstGeom* ig) {
+    ig->logits = nullptr;
+    if (s.masks) return ODISE_OK;
+    const int b = s.b, pad_h = s.pad_h, pad_w = s.pad_w, img_h = s.img_h, img_w = s.img_w, out_h = s.h, out_w = s.w;
+    PostGeom* g = &ig->g;
     ModelStore* ms = store_of(ctx);
     HeadOutputs ho;
     ODISE_TRY(head_outputs(ms, &ho));
@@ -272,12 +275,14 @@ int rle_instance_geom(odise_hip_ctx* ctx, const char* what, int b, int pad_h, in
                   "%s: bad geometry (image %dx%d, padded %dx%d, output %dx%d)", what, img_h, img_w, pad_h, pad_w, out_h, out_w);
     g->h4 = ho.h4; g->w4 = ho.w4; g->ph = pad_h; g->pw = pad_w; g->ih = img_h; g->iw = img_w; g->oh = out_h; g->ow = out_w;
     g->Q = ho.Q; g->Qpad = (int)round_up(ho.Q, 8);
-    *logits = ho.pred_masks + (size_t)b * ho.Q * ho.h4 * ho.w4;
+    ig->logits = ho.pred_masks + (size_t)b * ho.Q * ho.h4 * ho.w4;
     return ODISE_OK;
 }
 
-int rle_pack_logits(odise_hip_ctx* ctx, const f16* logits, const int* inst_table, int topk, const PostGeom& g, const RleGrid& G,
-                    unsigned long long* words) {
+// words [topk][G.nw] of the selection inst_table = n | query index [topk] | .., sampled from the mask logits with the taps of
+// instance_masks(_x4)_kernel; masks past the count n (read on the device) are not written
+static int rle_pack_logits(odise_hip_ctx* ctx, const f16* logits, const int* inst_table, int topk, const PostGeom& g, const RleGrid& G,
+                           unsigned long long* words) {
     if (instance_masks_x4(g)) {
         const dim3 grid((unsigned)ceil_div((int64_t)G.R * (g.ow / 4), 256), (unsigned)topk);
         hipLaunchKernelGGL(rle_pack_x4_kernel, grid, dim3(256), 0, ctx->stream, logits, inst_table + 1, words, g, G, inst_table);
@@ -287,6 +292,20 @@ int rle_pack_logits(odise_hip_ctx* ctx, const f16* logits, const int* inst_table
     }
     ODISE_CHECK_HIP(hipGetLastError());
     return ODISE_OK;
+}
+
+int inst_source_check(const char* what, const InstSource& s, bool need_table, int64_t max_pixels) {
+    ODISE_REQUIRE((s.inst_table && s.inst_scores) || (s.masks && !need_table), "%s: null inst_table / inst_scores (optional only with dense masks)", what);
+    ODISE_REQUIRE(s.topk >= 1 && s.topk <= kInstMaxTopk, "%s: topk %d (1..%d)", what, s.topk, kInstMaxTopk);
+    ODISE_REQUIRE(s.h >= 1 && s.w >= 1 && (int64_t)s.h * s.w <= max_pixels, "%s: mask size %dx%d out of range", what, s.h, s.w);
+    ODISE_REQUIRE(!s.masks || s.dtype == ODISE_F32 || s.dtype == ODISE_U8, "%s: dtype %d (ODISE_F32 or ODISE_U8)", what, s.dtype);
+    ODISE_REQUIRE((((uintptr_t)s.inst_table | (uintptr_t)s.inst_scores) & 3) == 0, "%s: inst_table / inst_scores must be 4-byte aligned", what);
+    return ODISE_OK;
+}
+
+int inst_pack(odise_hip_ctx* ctx, const InstSource& s, const InstGeom& ig, const RleGrid& G, u64* words) {
+    if (s.masks) return rle_pack_dense(ctx, s.masks, s.dtype, s.topk, G, words);
+    return rle_pack_logits(ctx, ig.logits, s.inst_table, s.topk, ig.g, G, words);
 }
 
 int rle_scratch(odise_hip_ctx* ctx, int n, const RleGrid& G, RleScratch* s, size_t extra) {
@@ -345,12 +364,12 @@ extern "C" int odise_hip_instance_rle(odise_hip_ctx* ctx, int b, const int* inst
     ODISE_REQUIRE(topk >= 1 && topk <= 4096, "instance_rle: topk %d out of range", topk);
     ODISE_REQUIRE(capacity >= 0 && (rle || capacity == 0), "instance_rle: capacity %lld without an output buffer", (long long)capacity);
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    PostGeom g;
-    const f16* logits = nullptr;
-    ODISE_TRY(rle_instance_geom(ctx, "instance_rle", b, pad_h, pad_w, img_h, img_w, out_h, out_w, &g, &logits));
+    const InstSource src = {out_h, out_w, nullptr, 0, b, pad_h, pad_w, img_h, img_w, inst_table, nullptr, topk};
+    InstGeom ig;
+    ODISE_TRY(inst_geom(ctx, "instance_rle", src, &ig));
     const RleGrid G = rle_grid(out_h, out_w);
     RleScratch s;
     ODISE_TRY(rle_scratch(ctx, topk, G, &s));
-    ODISE_TRY(rle_pack_logits(ctx, logits, inst_table, topk, g, G, s.words));
+    ODISE_TRY(inst_pack(ctx, src, ig, G, s.words));
     return rle_finish(ctx, s, G, topk, rle, capacity, offsets, area, inst_table);
 }

@@ -1,7 +1,7 @@
-// rle_pack.h — what rle.hip (COCO RLE strings), inst_eval.hip (mask IoU and segm matching), poly.hip (polygon rasterisation) and sem_rle.hip
-// (per-class strings of a label map) share: the
-// bit-packed mask layout, the block scan, the launchers of the pack kernels and the string passes (defined in rle.hip, compiled once) and
-// the launcher of the polygon kernel (poly.hip).
+// rle_pack.h — what rle.hip (COCO RLE strings), inst_eval.hip (mask IoU and segm matching), poly.hip (polygon rasterisation), sem_rle.hip
+// (per-class strings of a label map), vis_inst.hip (drawing) and inst_track.hip (colours across frames) share: the
+// bit-packed mask layout, the block scan, the launchers of the dense pack kernel and the string passes (defined in rle.hip, compiled once)
+// and the launcher of the polygon kernel (poly.hip).  What the users of INSTANCE masks share on top of it is in inst_words.h.
 //   word (x, r) of a mask holds pixels (64 r .. 64 r + 63, x), bit k = row 64 r + k, stored [n][w][R], R = ceil(h / 64): the words of a
 //   mask are consecutive pieces of the column-major order j = x * h + y.
 #pragma once
@@ -47,15 +47,6 @@ __device__ inline long long block_scan_sum(long long v, long long* lds, long lon
 
 // words [n][G.nw] of n dense masks [n, h, w] (ODISE_F32 / ODISE_U8; any nonzero value is 1), on the context's stream
 int rle_pack_dense(odise_hip_ctx* ctx, const void* masks, int dtype, int n, const RleGrid& G, unsigned long long* words);
-
-// The instance selection of image b of the last head forward: checks the geometry (the errors carry `what`), fills the sampling geometry
-// and the image's mask logits.
-int rle_instance_geom(odise_hip_ctx* ctx, const char* what, int b, int pad_h, int pad_w, int img_h, int img_w, int out_h, int out_w, PostGeom* g,
-                      const f16** logits);
-// words [topk][G.nw] of the selection inst_table = n | query index [topk] | .., sampled from the mask logits with the taps of
-// instance_masks(_x4)_kernel; masks past the count n (read on the device) are not written
-int rle_pack_logits(odise_hip_ctx* ctx, const f16* logits, const int* inst_table, int topk, const PostGeom& g, const RleGrid& G,
-                    unsigned long long* words);
 
 // The context's scratch of the string passes for n masks (grown on demand; earlier calls on the stream may still read the old buffer) and
 // `extra` bytes behind it for the caller.

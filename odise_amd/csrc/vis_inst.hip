@@ -23,15 +23,14 @@
 // tensor), the rank of every present class by counting, and one pass that turns labels into ids.
 #include <algorithm>
 
+#include "inst_words.h"
 #include "lds_hist.h"
 #include "record.h"
 #include "rgb.h"
-#include "rle_pack.h"
 #include "vis_scan.h"
 
 namespace odise {
 
-constexpr int kInstDrawMax = 100;          // topk limit (the instance head keeps at most 100 per picture)
 constexpr int kDrawThreads = 256;
 constexpr int kDrawChunk = 50;             // masks staged at a time
 constexpr int kDrawStride = 256 + 16;      // dwords per staged mask: 16 row groups x 16 column groups, + 16 so that the 32 lanes of a
@@ -39,17 +38,11 @@ constexpr int kDrawStride = 256 + 16;      // dwords per staged mask: 16 row gro
 constexpr int kSemMaxClasses = kLdsHistCells;
 
 struct InstDrawState {
-    int area[kInstDrawMax];                // pixels of a kept instance, 0 when it is not kept
-    int list[kInstDrawMax];                // list[k] = the instance drawn k-th
+    int area[kInstMaxTopk];                // pixels of a kept instance, 0 when it is not kept
+    int list[kInstMaxTopk];                // list[k] = the instance drawn k-th
     int n_kept;
     int pad[3];
 };
-
-__device__ __forceinline__ int inst_count(const int* __restrict__ table, int topk) {
-    if (!table) return topk;
-    const int n = table[0];
-    return n < 0 ? 0 : (n > topk ? topk : n);
-}
 
 __global__ void __launch_bounds__(kDrawThreads) inst_col_kernel(const unsigned long long* __restrict__ words, RleGrid G, const int* __restrict__ table,
                                                                int topk, int* __restrict__ colhist) {
@@ -92,11 +85,11 @@ __global__ void __launch_bounds__(64) inst_anchor_kernel(const int* __restrict__
     const int nb = axis ? H : W;
     const int* h = axis ? rowhist + (int64_t)i * H : colhist + (int64_t)i * W;
     int N = 0;
-    if (i < inst_count(table, topk)) {
+    if (inst_candidate(table, scores, topk, min_score, i)) {
         for (int b0 = 0; b0 < nb; b0 += 64) N += b0 + lane < nb ? h[b0 + lane] : 0;
         for (int d = 32; d; d >>= 1) N += __shfl_xor(N, d);
     }
-    const bool kept = N > 0 && (!scores || scores[i] >= min_score);
+    const bool kept = N > 0;
     if (!kept) {
         if (lane == 0 && axis == 0) {
             st->area[i] = 0;
@@ -115,7 +108,7 @@ __global__ void __launch_bounds__(64) inst_anchor_kernel(const int* __restrict__
 }
 
 __global__ void __launch_bounds__(128) inst_order_kernel(InstDrawState* __restrict__ st, int topk, int* __restrict__ order) {
-    __shared__ int a[kInstDrawMax];
+    __shared__ int a[kInstMaxTopk];
     const int t = threadIdx.x;
     if (t < topk) a[t] = st->area[t];
     __syncthreads();
@@ -167,7 +160,7 @@ __global__ void __launch_bounds__(kDrawThreads) inst_overlay_kernel(const unsign
         }
     }
 
-    const int n_kept = min(max(st->n_kept, 0), kInstDrawMax);
+    const int n_kept = min(max(st->n_kept, 0), kInstMaxTopk);
     const int rows = min(64, H - 64 * r);
     const unsigned long long padbits = rows == 64 ? 0ull : ~0ull << rows;   // rows past the picture count as inside the mask: no edge there
     for (int k0 = 0; k0 < n_kept; k0 += kDrawChunk) {
@@ -302,24 +295,20 @@ using namespace odise;
 
 extern "C" int odise_hip_instance_draw(odise_hip_ctx* ctx, const odise_inst_draw_desc* d) {
     ODISE_REQUIRE(ctx && d, "instance_draw: null argument");
-    ODISE_REQUIRE(d->masks || (d->inst_table && d->inst_scores), "instance_draw: the selection of the last head forward needs inst_table and inst_scores");
+    const InstSource src = inst_source(*d);
+    ODISE_TRY(inst_source_check("instance_draw", src, false, kVisMaxPixels));
     ODISE_REQUIRE(!d->out || (d->image && d->colors && d->edge_colors), "instance_draw: an output picture needs image, colors and edge_colors");
     ODISE_REQUIRE(d->out || d->anchors || d->order, "instance_draw: no output");
-    ODISE_TRY(vis_check_size("instance_draw", d->h, d->w));
-    ODISE_REQUIRE(d->topk >= 1 && d->topk <= kInstDrawMax, "instance_draw: topk %d (1..%d)", d->topk, kInstDrawMax);
     ODISE_REQUIRE(d->alpha256 >= 0 && d->alpha256 <= 256, "instance_draw: alpha256 %d outside 0..256", d->alpha256);
-    ODISE_REQUIRE(!d->masks || d->dtype == ODISE_F32 || d->dtype == ODISE_U8, "instance_draw: dtype %d (ODISE_F32 or ODISE_U8)", d->dtype);
-    ODISE_REQUIRE((((uintptr_t)d->inst_table | (uintptr_t)d->inst_scores | (uintptr_t)d->anchors | (uintptr_t)d->order) & 3) == 0,
-                  "instance_draw: int32 / float buffers must be 4-byte aligned");
+    ODISE_REQUIRE((((uintptr_t)d->anchors | (uintptr_t)d->order) & 3) == 0, "instance_draw: anchors / order must be 4-byte aligned");
     const int H = d->h, W = d->w, topk = d->topk;
     if (d->out && d->out != d->image) {
         const uintptr_t a = (uintptr_t)d->image, b = (uintptr_t)d->out, nb = (uintptr_t)3 * H * W;
         ODISE_REQUIRE(a + nb <= b || b + nb <= a, "instance_draw: out overlaps image without being equal to it");
     }
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    PostGeom g;
-    const f16* logits = nullptr;
-    if (!d->masks) ODISE_TRY(rle_instance_geom(ctx, "instance_draw", d->b, d->pad_h, d->pad_w, d->img_h, d->img_w, H, W, &g, &logits));
+    InstGeom ig;
+    ODISE_TRY(inst_geom(ctx, "instance_draw", src, &ig));
     const RleGrid G = rle_grid(H, W);
     const size_t col_b = (size_t)round_up((int64_t)topk * W * 4, 16), row_b = d->anchors ? (size_t)round_up((int64_t)topk * H * 4, 16) : 0;
     RleScratch s;
@@ -327,9 +316,8 @@ extern "C" int odise_hip_instance_draw(odise_hip_ctx* ctx, const odise_inst_draw
     InstDrawState* st = (InstDrawState*)s.extra;
     int* colhist = (int*)((char*)s.extra + sizeof(InstDrawState));
     int* rowhist = (int*)((char*)colhist + col_b);
-    const int* table = (const int*)d->inst_table;
-    if (d->masks) ODISE_TRY(rle_pack_dense(ctx, d->masks, d->dtype, topk, G, s.words));
-    else ODISE_TRY(rle_pack_logits(ctx, logits, table, topk, g, G, s.words));
+    const int* table = src.inst_table;
+    ODISE_TRY(inst_pack(ctx, src, ig, G, s.words));
     hipLaunchKernelGGL(inst_col_kernel, dim3((unsigned)ceil_div(W, kDrawThreads), (unsigned)topk), dim3(kDrawThreads), 0, ctx->stream,
                        (const unsigned long long*)s.words, G, table, topk, colhist);
     ODISE_CHECK_HIP(hipGetLastError());

@@ -43,8 +43,9 @@ __device__ __forceinline__ odise_anchor_row vis_anchor_row(int segment_row, int 
     return r;
 }
 
+constexpr int64_t kVisMaxPixels = INT32_MAX / 4;   // of a picture that is drawn
 static inline int vis_check_size(const char* who, int H, int W) {
-    ODISE_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= INT32_MAX / 4, "%s: bad size %dx%d", who, H, W);
+    ODISE_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= kVisMaxPixels, "%s: bad size %dx%d", who, H, W);
     return ODISE_OK;
 }
 

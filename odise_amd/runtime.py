@@ -82,6 +82,29 @@ def _p(a: Optional[DeviceArray]):
     return C.c_void_p(a.ptr) if a is not None else C.c_void_p(None)
 
 
+def _ptr(a):
+    return a.ptr if isinstance(a, DeviceArray) else a
+
+
+def _mask_dtype(masks: DeviceArray, what: str) -> int:
+    """ODISE_F32 / ODISE_U8 of dense masks (float32, or uint8 / bool; nonzero = 1)."""
+    dt = {np.dtype(np.float32): F32, np.dtype(np.uint8): U8, np.dtype(np.bool_): U8}.get(np.dtype(masks.dtype))
+    if dt is None:
+        raise ValueError(f"{what}: masks of dtype {masks.dtype} (float32, uint8 or bool)")
+    return dt
+
+
+def _fill_inst_source(d, what: str, hw, topk: int, table_row, scores_row, masks: Optional[DeviceArray], b: int, pad_hw, img_hw) -> None:
+    """The detection fields that InstEvalDesc, InstDrawDesc and InstTrackDesc share: dense `masks` [topk, h, w], or the selection
+    table_row / scores_row (DeviceArray or pointer) of image b of the last head forward."""
+    d.h, d.w, d.topk = int(hw[0]), int(hw[1]), int(topk)
+    if masks is not None:
+        assert tuple(masks.shape) == (d.topk, d.h, d.w), (masks.shape, topk, hw)
+        d.masks, d.dtype = masks.ptr, _mask_dtype(masks, what)
+    d.b, d.pad_h, d.pad_w, d.img_h, d.img_w = int(b), int(pad_hw[0]), int(pad_hw[1]), int(img_hw[0]), int(img_hw[1])
+    d.inst_table, d.inst_scores = _ptr(table_row), _ptr(scores_row)
+
+
 class Context:
     def __init__(self, device: int = 0):
         self.lib = _lib.load()
@@ -654,15 +677,10 @@ class Context:
         [cap, MAX_SEGMENTS]."""
         from ._lib import MAX_SEGMENTS, InstTrackDesc
         from .video import TRACK_ROW_DTYPE
-        (h, w), topk = tracker.hw, tracker.topk
+        topk = tracker.topk
         d = InstTrackDesc()
-        d.track, d.h, d.w, d.topk, d.min_score = tracker.handle, h, w, topk, float(min_score)
-        if masks is not None:
-            assert tuple(masks.shape) == (topk, h, w), (masks.shape, topk, tracker.hw)
-            d.masks, d.dtype = masks.ptr, (F32 if masks.dtype == np.float32 else U8)
-        d.b, d.pad_h, d.pad_w, d.img_h, d.img_w = int(b), int(pad_hw[0]), int(pad_hw[1]), int(img_hw[0]), int(img_hw[1])
-        ptr = lambda a: a.ptr if isinstance(a, DeviceArray) else a
-        d.inst_table, d.inst_scores = ptr(table_row), ptr(scores_row)
+        d.track, d.min_score = tracker.handle, float(min_score)
+        _fill_inst_source(d, "inst_track_frame", tracker.hw, topk, table_row, scores_row, masks, b, pad_hw, img_hw)
         if colors is None:
             colors = self.zeros((topk, 3), np.uint8)
         assert colors.dtype == np.uint8 and colors.nbytes >= 3 * topk, (colors.dtype, colors.shape)
@@ -696,18 +714,13 @@ class Context:
         from .visualize import ANCHOR_DTYPE
         h, w, topk = int(out_hw[0]), int(out_hw[1]), int(topk)
         d = InstDrawDesc()
-        d.h, d.w, d.topk, d.min_score, d.alpha256 = h, w, topk, float(min_score), int(alpha256)
-        if masks is not None:
-            assert tuple(masks.shape) == (topk, h, w), (masks.shape, topk, out_hw)
-            d.masks, d.dtype = masks.ptr, (F32 if masks.dtype == np.float32 else U8)
-        d.b, d.pad_h, d.pad_w, d.img_h, d.img_w = int(b), int(pad_hw[0]), int(pad_hw[1]), int(img_hw[0]), int(img_hw[1])
-        ptr = lambda a: a.ptr if isinstance(a, DeviceArray) else a
-        d.inst_table, d.inst_scores = ptr(table_row), ptr(scores_row)
+        d.min_score, d.alpha256 = float(min_score), int(alpha256)
+        _fill_inst_source(d, "instance_draw", (h, w), topk, table_row, scores_row, masks, b, pad_hw, img_hw)
         res = {}
         if "out" in want:
             assert image is not None and image.dtype == np.uint8 and tuple(image.shape) == (h, w, 3), "instance_draw: image uint8 [h,w,3]"
             res["out"] = out if out is not None else self.empty((h, w, 3), np.uint8)
-            d.image, d.colors, d.edge_colors, d.out = image.ptr, ptr(colors), ptr(edge_colors), res["out"].ptr
+            d.image, d.colors, d.edge_colors, d.out = image.ptr, _ptr(colors), _ptr(edge_colors), res["out"].ptr
         if "anchors" in want:
             res["anchors"] = anchors if anchors is not None else self.empty((topk,), ANCHOR_DTYPE)
             d.anchors = res["anchors"].ptr
@@ -744,9 +757,7 @@ class Context:
     def rle_encode_async(self, masks: DeviceArray, capacity: Optional[int] = None, bufs=None, grow=None) -> "RlePending":
         """Enqueue the COCO RLE of masks [n, h, w] (float32, or uint8 / bool; nonzero = 1) on the context's stream."""
         n, h, w = masks.shape
-        dt = {np.dtype(np.float32): F32, np.dtype(np.uint8): U8, np.dtype(np.bool_): U8}.get(np.dtype(masks.dtype))
-        if dt is None:
-            raise ValueError(f"rle_encode: masks of dtype {masks.dtype} (float32, uint8 or bool)")
+        dt = _mask_dtype(masks, "rle_encode")
 
         def launch(buf, cap, off, area):
             check(self.lib.odise_hip_rle_encode(self.h, _p(masks), dt, n, h, w, _p(buf), int(cap), _p(off), _p(area)), "rle_encode")
@@ -829,9 +840,7 @@ class Context:
         flags int32 [1]); with_counts adds (inter int32 [n, n_gt], area_d int64 [n], area_g int64 [n_gt]).  Temporaries uploaded here are
         freed on return by the library's synchronising free."""
         n, h, w = masks.shape
-        dt = {np.dtype(np.float32): F32, np.dtype(np.uint8): U8, np.dtype(np.bool_): U8}.get(np.dtype(masks.dtype))
-        if dt is None:
-            raise ValueError(f"mask_iou: masks of dtype {masks.dtype} (float32, uint8 or bool)")
+        dt = _mask_dtype(masks, "mask_iou")
         if not isinstance(gt_counts, dict):
             offs = np.concatenate(([0], np.cumsum([len(c) for c in gt_counts]))).astype(np.int64)
             runs = np.concatenate([np.asarray(c, np.uint32) for c in gt_counts]) if len(gt_counts) else np.zeros(0, np.uint32)
@@ -857,16 +866,10 @@ class Context:
         thr = np.ascontiguousarray(IOU_THRS if iou_thresholds is None else iou_thresholds, np.float64)
         assert thr.shape == (10,), thr.shape
         d = InstEvalDesc()
-        d.h, d.w = int(out_hw[0]), int(out_hw[1])
-        if masks is not None:
-            assert tuple(masks.shape) == (int(topk), d.h, d.w), (masks.shape, topk, out_hw)
-            d.masks, d.dtype = masks.ptr, (F32 if masks.dtype == np.float32 else U8)
-        d.b, d.pad_h, d.pad_w, d.img_h, d.img_w = int(b), int(pad_hw[0]), int(pad_hw[1]), int(img_hw[0]), int(img_hw[1])
-        ptr = lambda a: a.ptr if isinstance(a, DeviceArray) else a
-        d.inst_table, d.inst_scores, d.topk = ptr(table_row), ptr(scores_row), int(topk)
+        _fill_inst_source(d, "instance_eval", out_hw, topk, table_row, scores_row, masks, b, pad_hw, img_hw)
         d.gt_runs, d.gt_offsets, d.gt_rows, d.n_gt = gt["runs"].ptr, gt["offsets"].ptr, gt["rows"].ptr, int(gt["n_gt"])
         d.num_categories, d.image, d.iou_thresholds = int(num_categories), int(image), thr.ctypes.data
-        d.rows, d.n_rows, d.flags = ptr(rows), ptr(n_rows), ptr(flags)
+        d.rows, d.n_rows, d.flags = _ptr(rows), _ptr(n_rows), _ptr(flags)
         if "gt_polys" in gt:
             p = InstPolyGt()
             p.xy, p.poly_offsets, p.gt_polys, p.n_poly = gt["xy"].ptr, gt["poly_offsets"].ptr, gt["gt_polys"].ptr, int(gt["n_poly"])

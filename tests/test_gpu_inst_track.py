@@ -170,6 +170,26 @@ def test_bad_arguments_are_refused_and_nothing_is_written(ctx):
         ctx.inst_track_create((8, 8), 7, ttl=9)
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.int32])
+def test_masks_of_an_unsupported_dtype_raise_and_write_nothing(ctx, dtype):
+    """The smallest legal call but for the dtype of its masks: refused by the binding, before the library is called; the tracker stays at
+    frame 0 (the sequence of the 1 x 1 case runs as on a fresh one)."""
+    case = CASES["one_pixel"]
+    assert case.hw == (1, 1) and case.topk == 1
+    trk = ctx.inst_track_create(case.hw, case.topk, case.ttl, case.pool)
+    try:
+        colors, edges = ctx.to_device(IC.prefill(1)), ctx.to_device(edge_prefill(1))
+        live, n_live = ctx.to_device(live_guard(1)), ctx.to_device(np.full(1, -9, np.int32))
+        with pytest.raises(ValueError, match="dtype"):
+            ctx.inst_track_frame(trk, masks=ctx.to_device(np.ones((1, 1, 1), dtype)), colors=colors, edge_colors=edges, live=live, n_live=n_live)
+        ctx.sync()
+        assert colors.numpy().tobytes() == IC.prefill(1).tobytes() and edges.numpy().tobytes() == edge_prefill(1).tobytes()
+        assert live.numpy().tobytes() == live_guard(1).tobytes() and int(n_live.numpy()[0]) == -9
+        run_sequence(ctx, case, trk)
+    finally:
+        trk.close()
+
+
 # ---- the selection of the last head forward (masks sampled from the mask logits) ------------------------------------------------------------
 @pytest.fixture(scope="module")
 def clip(ctx):

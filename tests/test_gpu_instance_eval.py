@@ -230,6 +230,19 @@ def test_bad_arguments_write_nothing(ctx):
     assert int(n_rows.read()[0]) == 2
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.int32])
+def test_masks_of_an_unsupported_dtype_raise_and_write_nothing(ctx, dtype):
+    """The smallest legal call but for the dtype of its masks: refused by the binding, before the library is called."""
+    gt = ctx.instance_gt_to_device(np.zeros((0, 3), np.int32), np.zeros(0, np.uint32), np.zeros(1, np.int64))
+    rows, n_rows, flags = Guarded(ctx, (1,), IE.ROW_DTYPE), Guarded(ctx, (1,), np.int32), Guarded(ctx, (1,), np.int32)
+    with pytest.raises(ValueError, match="dtype"):
+        ctx.instance_eval((1, 1), ctx.zeros((3,), np.int32), ctx.zeros((1,), np.float32), 1, gt, 1, 0, rows.arr, n_rows.arr, flags.arr,
+                          masks=ctx.to_device(np.ones((1, 1, 1), dtype)))
+    ctx.sync()
+    for o in (rows, n_rows, flags):
+        o.read(intact=True)
+
+
 # ---- the small model: from the mask logits ------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def small(ctx):

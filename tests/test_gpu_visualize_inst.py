@@ -134,6 +134,19 @@ def test_bad_arguments_are_refused_and_nothing_is_written(ctx):
     assert order.numpy().tobytes() == case.order().tobytes() and out.numpy().tobytes() == case.overlay().tobytes()
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.int32])
+def test_masks_of_an_unsupported_dtype_raise_and_write_nothing(ctx, dtype):
+    """The smallest legal call but for the dtype of its masks: refused by the binding, before the library is called."""
+    image, colors = ctx.to_device(np.full((1, 1, 3), 9, np.uint8)), ctx.to_device(np.full((1, 3), 200, np.uint8))
+    out = ctx.to_device(np.full((1, 1, 3), 55, np.uint8))
+    rows, order = ctx.to_device(np.full(8, -1, np.int32)), ctx.to_device(np.full(1, -4, np.int32))
+    with pytest.raises(ValueError, match="dtype"):
+        ctx.instance_draw((1, 1), 1, masks=ctx.to_device(np.ones((1, 1, 1), dtype)), image=image, colors=colors, edge_colors=colors, out=out,
+                          anchors=rows, order=order)
+    ctx.sync()
+    assert (out.numpy() == 55).all() and (rows.numpy() == -1).all() and (order.numpy() == -4).all() and (image.numpy() == 9).all()
+
+
 @pytest.mark.parametrize("name", sorted(SEM))
 def test_semantic_record_from_labels_and_from_scores(ctx, name):
     case = SEM[name]
