@@ -564,6 +564,48 @@ typedef struct {
     int n_poly;
 } odise_inst_poly_gt;
 int odise_hip_instance_eval_poly(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p);
+/* The boxes of a picture's instance selection: detectron2 BitMasks.get_bounding_boxes of every mask, XYXY = [first column with a pixel,
+ * first row with a pixel, last column + 1, last row + 1], a mask without a pixel [0, 0, 0, 0] - the line maskformer_model.py:372 leaves
+ * commented out ("this is slow"), which is why the reference's pred_boxes are zeros.  The detections are those of odise_inst_eval_desc:
+ * dense `masks` [topk,h,w] (inst_table optional: NULL = all topk), or masks == NULL = the selection inst_table of image b of the last
+ * head forward, sampled from the mask logits.  Rows past the count of the table are zeros.  ODISE_ERR_ARG and nothing written: a null
+ * required pointer, topk outside 1..100, h or w < 1, h * w > 2^30, a dtype other than ODISE_F32 / ODISE_U8, the geometry errors of
+ * odise_hip_instance_rle.  Scratch comes from the context.  Asynchronous on the context's stream; no host synchronisation. */
+typedef struct {
+    int h, w;
+    const void* masks; int dtype;
+    int b, pad_h, pad_w, img_h, img_w;
+    const int32_t* inst_table;
+    const float* inst_scores;       /* unused, may be NULL */
+    int topk;
+    float* boxes;                   /* device [topk][4] XYXY; rows past the count are zeros */
+} odise_inst_boxes_desc;
+int odise_hip_instance_boxes(odise_hip_ctx* ctx, const odise_inst_boxes_desc* d);
+/* pycocotools' mask.iou of boxes: maskApi.c bbIou of n XYWH boxes against n_gt XYWH boxes, all device doubles.  With D a box of dt and G
+ * one of gt: da = D.w * D.h, ga = G.w * G.h, w = fmin(D.x + D.w, G.x + G.w) - fmax(D.x, G.x), h the same in y; w <= 0 or h <= 0 -> 0;
+ * i = w * h; iou = i / (crowd ? da : da + ga - i), every operation rounded on its own (no fused multiply-add).  iscrowd: device uint8
+ * [n_gt] or NULL.  iou: device double [n][n_gt].  n == 0 or n_gt == 0 writes nothing and succeeds.  n, n_gt <= 65535, n * n_gt <= 2^26.
+ * Asynchronous on the context's stream. */
+int odise_hip_box_iou(odise_hip_ctx* ctx, const double* dt, int n, const double* gt, int n_gt, const uint8_t* iscrowd, double* iou);
+/* COCOeval.evaluateImg for iouType "bbox", optionally together with "segm", from ONE pack of the detections (sampling the mask logits is
+ * the expensive part of either).  The detection boxes are those of odise_hip_instance_boxes as XYWH, the IoU is odise_hip_box_iou against
+ * bb->gt_boxes, and the walk is the one of odise_hip_instance_eval.  A bbox row's `area` is its box's w * h (COCO.loadRes' bb[2] * bb[3]),
+ * which is also what the ignore rule of an unmatched detection looks at; the ignore bits of the ground truth are d->gt_rows for both tasks
+ * (COCO compares the annotation's `area` in both).
+ * segm part: with d->rows and d->n_rows set it is exactly odise_hip_instance_eval_poly(d, p).  With both NULL it is skipped, and
+ * d->gt_runs / d->gt_offsets / p are not read.
+ * d->flags collects the flags of both tasks.  For bbox, 4 is also raised by a ground-truth box with a non-finite member, and 1 cannot
+ * occur.  Flags 1 and 8 zero the segm rows only (n_rows = 0); flags 2 and 4 zero the rows of both tasks.
+ * ODISE_ERR_ARG and nothing written: what odise_hip_instance_eval refuses, a null bb, bb->rows or bb->n_rows, a null bb->gt_boxes with
+ * n_gt > 0, only one of d->rows / d->n_rows.  Scratch comes from the context.  Asynchronous on the context's stream; no host
+ * synchronisation. */
+typedef struct {
+    const double* gt_boxes;         /* device [n_gt][4] XYWH */
+    odise_inst_eval_row* rows;      /* device [topk] */
+    int32_t* n_rows;                /* device [1] */
+    float* boxes;                   /* device [topk][4] XYXY, optional */
+} odise_inst_bbox_task;
+int odise_hip_instance_eval_bbox(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p, const odise_inst_bbox_task* bb);
 /* COCOeval.accumulate for iouType "segm" on the rows of odise_hip_instance_eval as they lie on the device: maxDets (1, 10, 100), the four
  * area ranges, the ten IoU thresholds and the caller's table of recall thresholds; byte for byte what odise_amd/instance_eval.py
  * accumulate returns for the same rows.

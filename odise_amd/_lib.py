@@ -117,6 +117,17 @@ class InstPolyGt(C.Structure):
     _fields_ = [("xy", c_void_p), ("poly_offsets", c_void_p), ("gt_polys", c_void_p), ("n_poly", c_int)]
 
 
+class InstBoxesDesc(C.Structure):
+    """odise_inst_boxes_desc (include/odise_hip.h)."""
+    _fields_ = [("h", c_int), ("w", c_int), ("masks", c_void_p), ("dtype", c_int), ("b", c_int), ("pad_h", c_int), ("pad_w", c_int),
+                ("img_h", c_int), ("img_w", c_int), ("inst_table", c_void_p), ("inst_scores", c_void_p), ("topk", c_int), ("boxes", c_void_p)]
+
+
+class InstBboxTask(C.Structure):
+    """odise_inst_bbox_task (include/odise_hip.h)."""
+    _fields_ = [("gt_boxes", c_void_p), ("rows", c_void_p), ("n_rows", c_void_p), ("boxes", c_void_p)]
+
+
 class InstAccumDesc(C.Structure):
     """odise_inst_accum_desc (include/odise_hip.h)."""
     _fields_ = [("n_blocks", c_int), ("rows", c_void_p), ("counts", c_void_p), ("slots", c_void_p), ("topk", c_int), ("num_categories", c_int),

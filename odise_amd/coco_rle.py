@@ -80,12 +80,13 @@ def area(rle: dict) -> int:
     return int(string_to_counts(s.decode("utf-8") if isinstance(s, (bytes, bytearray)) else s)[1::2].sum())
 
 
-def instances_to_coco_json(instances: dict, img_id) -> list:
+def instances_to_coco_json(instances: dict, img_id, boxes=None) -> list:
     """detectron2.evaluation.coco_evaluation.instances_to_coco_json for one image's "instances" of HipCategoryODISE: records
     {"image_id", "category_id" (contiguous class; the evaluator maps it to the dataset id), "bbox", "score", "segmentation"}.  The
     reference's instance head returns zero boxes (maskformer_model.py:372), which XYXY -> XYWH keeps zero.  Takes the default result
     (`pred_masks` [n, h, w]: host array, torch tensor, or device array, which is encoded on its device) or the `instance_rle` result
-    (`pred_masks_rle`: the strings are already there)."""
+    (`pred_masks_rle`: the strings are already there).  boxes: XYXY [n, 4] (HipCategoryODISE.instance_boxes -> "pred_boxes",
+    `Context.instance_boxes`), written as XYWH floats the way BoxMode.convert(XYXY_ABS, XYWH_ABS) does; without them the zeros stay."""
     scores = np.asarray(instances["scores"], np.float32)
     classes = np.asarray(instances["pred_classes"])
     n = len(scores)
@@ -102,5 +103,11 @@ def instances_to_coco_json(instances: dict, img_id) -> list:
                 masks = masks.detach().cpu().numpy()
             rles = [encode(m) for m in np.asarray(masks)]
     assert len(rles) == n, (len(rles), n)
-    return [{"image_id": img_id, "category_id": int(classes[k]), "bbox": [0.0, 0.0, 0.0, 0.0], "score": float(scores[k]),
+    if boxes is None:
+        xywh = [[0.0, 0.0, 0.0, 0.0]] * n
+    else:
+        b = np.asarray(boxes, np.float64).reshape(-1, 4)
+        assert len(b) == n, (len(b), n)
+        xywh = [[float(x0), float(y0), float(x1 - x0), float(y1 - y0)] for x0, y0, x1, y1 in b]
+    return [{"image_id": img_id, "category_id": int(classes[k]), "bbox": list(xywh[k]), "score": float(scores[k]),
              "segmentation": rles[k]} for k in range(n)]

@@ -24,6 +24,9 @@
 //               sorted by ignore, with its break.  The IoUs of 64 ground truths are computed by the 64 lanes at once and handed round by
 //               lane index.  Categories are independent, so the 16 waves of the block share the detections by category.  The matched /
 //               ignored words of a row are the ballots of the wave.
+// The walk is written once and takes its IoU as a template argument: SegmIou is steps 3 and 4, BoxIou (odise_hip_instance_eval_bbox, iouType
+// "bbox") is maskApi.c bbIou of the detections' boxes (inst_box.hip, from the words of step 1) against the annotations' boxes.  Both tasks of a
+// picture run behind ONE pack.
 #include "inst_words.h"
 
 namespace odise {
@@ -159,9 +162,7 @@ struct InstMatchArgs {
     const int* inst_table;       // n | query index [topk] | class [topk]
     const float* inst_scores;    // [topk]
     const int* gt_rows;          // [n_gt][3]
-    const int* inter;            // [topk][n_gt]
-    const long long* area;       // [topk + n_gt]
-    const int* status;           // flag 1 of this picture's decode
+    int* status;                 // the flags of this picture so far: 1 / 4 / 8 of the decode and the polygons, 2 / 4 of a match that ran before
     odise_inst_eval_row* rows;
     int* n_rows;
     int* flags;
@@ -173,7 +174,39 @@ __device__ __forceinline__ bool inst_area_outside(int area, int a) {   // [0, 1e
     return a == 1 ? area > 1024 : a == 2 ? (area < 1024 || area > 9216) : a == 3 ? area < 9216 : false;
 }
 
-__global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A) {
+// What the walk asks of an IoU: the area of a detection and of a ground truth, the check of a ground truth (flag bits), the IoU of a pair.
+// kStatusMask: the flags of the picture that empty this task's rows; kPublish: the flags found here join `status` for the match behind.
+struct SegmIou {   // rleIou on the pixel counts of inst_inter_kernel / inst_area_kernel
+    static constexpr int kStatusMask = ~0;
+    static constexpr bool kPublish = false;
+    const int* inter;            // [topk][n_gt]
+    const long long* area;       // [topk + n_gt]
+    int topk, n_gt;
+    __device__ int det_area(int i) const { return (int)area[i]; }
+    __device__ int gt_area(int j) const { return (int)area[topk + j]; }
+    __device__ int gt_check(int) const { return 0; }
+    __device__ double operator()(int d, int j, int ad, int ag, bool crowd) const { return rle_iou(inter[(int64_t)d * n_gt + j], ad, ag, crowd); }
+};
+struct BoxIou {    // bbIou of the detection's box (XYXY integers, here as XYWH) and the annotation's box
+    static constexpr int kStatusMask = 2 | 4;   // bad runs (1) and bad polygons (8) are the segm task's alone
+    static constexpr bool kPublish = true;
+    const float* boxes;          // [topk][4] XYXY
+    const double* gt_boxes;      // [n_gt][4] XYWH
+    __device__ int det_area(int i) const { return (int)(boxes[4 * i + 2] - boxes[4 * i]) * (int)(boxes[4 * i + 3] - boxes[4 * i + 1]); }
+    __device__ int gt_area(int) const { return 0; }
+    __device__ int gt_check(int j) const {
+        const double* g = gt_boxes + 4 * j;
+        return isfinite(g[0]) && isfinite(g[1]) && isfinite(g[2]) && isfinite(g[3]) ? 0 : 4;
+    }
+    __device__ double operator()(int d, int j, int, int, bool crowd) const {
+        const float* b = boxes + 4 * d;
+        const double* g = gt_boxes + 4 * j;
+        return bb_iou((double)b[0], (double)b[1], (double)(b[2] - b[0]), (double)(b[3] - b[1]), g[0], g[1], g[2], g[3], crowd);
+    }
+};
+
+template <class Iou>
+__global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A, Iou iou_of) {
     __shared__ int g_cat[kInstMaxGt], g_flag[kInstMaxGt], g_area[kInstMaxGt], g_sorted[kInstMaxGt];   // g_flag: iscrowd | outside bits << 1
     __shared__ u64 g_matched[kInstMaxGt];                                                             // bit = cell
     __shared__ int d_cls[kInstMaxTopk], d_area[kInstMaxTopk], d_order[kInstMaxTopk], d_lo[kInstMaxTopk], d_cnt[kInstMaxTopk];
@@ -182,7 +215,7 @@ __global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int topk = A.topk, n_gt = A.n_gt;
     const int n = inst_count(A.inst_table, topk);
-    if (tid == 0) bad = A.status[0];
+    if (tid == 0) bad = A.status[0] & Iou::kStatusMask;
     __syncthreads();
     int f = 0;
     for (int j = tid; j < n_gt; j += kRleThreads) {
@@ -190,7 +223,8 @@ __global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A
         if ((unsigned)cat >= (unsigned)A.num_categories || (unsigned)crowd > 1u) f |= 4;
         g_cat[j] = cat;
         g_flag[j] = (crowd & 1) | ((A.gt_rows[3 * j + 2] & 15) << 1);
-        g_area[j] = (int)A.area[topk + j];
+        f |= iou_of.gt_check(j);
+        g_area[j] = iou_of.gt_area(j);
         g_matched[j] = 0ull;
     }
     for (int i = tid; i < n; i += kRleThreads) {
@@ -198,9 +232,12 @@ __global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A
         if ((unsigned)d_cls[i] >= (unsigned)A.num_categories) f |= 2;
         const float s = A.inst_scores[i];
         d_score[i] = s == s ? s : -INFINITY;
-        d_area[i] = (int)A.area[i];
+        d_area[i] = iou_of.det_area(i);
     }
-    if (f) atomicOr(&bad, f);
+    if (f) {
+        atomicOr(&bad, f);
+        if (Iou::kPublish) atomicOr(A.status, f);
+    }
     __syncthreads();
     const odise_inst_eval_row zero = {};
     if (bad) {   // the picture counts nothing
@@ -245,7 +282,7 @@ __global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A
             double mine = 0.0;
             if (base + lane < cnt) {
                 const int j = g_sorted[lo + base + lane];
-                mine = rle_iou(A.inter[(int64_t)d * n_gt + j], ad, g_area[j], g_flag[j] & 1);
+                mine = iou_of(d, j, ad, g_area[j], g_flag[j] & 1);
             }
             const int step = min(64, cnt - base);
             for (int q = 0; q < step; ++q) {
@@ -283,18 +320,21 @@ struct InstScratch {
     int* inter;        // [n][n_gt], then one int: the status of the call
     size_t inter_bytes;
     u64* toggle;       // with polygon ground truth: the toggle planes of poly.hip, [n_gt] masks
+    float* boxes;      // the bbox task without an output for them: [n][4]
 };
-static int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, InstScratch* s, bool polygons = false) {
+static int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, InstScratch* s, bool polygons = false, bool boxes = false) {
     const size_t wb = (size_t)round_up((int64_t)(n + n_gt) * G.nw * 8, 256), ab = (size_t)round_up((int64_t)(n + n_gt) * 8, 256);
     s->inter_bytes = ((size_t)n * n_gt + 1) * sizeof(int);
     const size_t ib = (size_t)round_up((int64_t)s->inter_bytes, 256);
-    ODISE_TRY(scratch_reserve(ctx->rle, wb + ab + ib + (polygons ? (size_t)n_gt * G.nw * 8 : 0), 8, drain_streams(ctx->stream), "rle"));
+    const size_t bb = boxes ? (size_t)round_up((int64_t)n * 16, 256) : 0;
+    ODISE_TRY(scratch_reserve(ctx->rle, wb + ab + ib + bb + (polygons ? (size_t)n_gt * G.nw * 8 : 0), 8, drain_streams(ctx->stream), "rle"));
     char* p = (char*)ctx->rle.ptr;
     s->words_d = (u64*)p;
     s->words_g = s->words_d + (int64_t)n * G.nw;
     s->area = (long long*)(p + wb);
     s->inter = (int*)(p + wb + ab);
-    s->toggle = (u64*)(p + wb + ab + ib);
+    s->boxes = (float*)(p + wb + ab + ib);
+    s->toggle = (u64*)(p + wb + ab + ib + bb);
     return ODISE_OK;
 }
 
@@ -343,36 +383,60 @@ extern "C" int odise_hip_mask_iou(odise_hip_ctx* ctx, const void* masks, int dty
     return ODISE_OK;
 }
 
-extern "C" int odise_hip_instance_eval(odise_hip_ctx* ctx, const odise_inst_eval_desc* d) { return odise_hip_instance_eval_poly(ctx, d, nullptr); }
-
-extern "C" int odise_hip_instance_eval_poly(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p) {
+// evaluateImg of one picture for "segm" (d->rows), "bbox" (bb), or both from one pack of the detections
+static int inst_eval_run(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p, const odise_inst_bbox_task* bb, bool want_bbox) {
     ODISE_REQUIRE(ctx && d, "instance_eval: null argument");
-    ODISE_REQUIRE(d->iou_thresholds && d->rows && d->n_rows && d->flags, "instance_eval: null pointer");
+    ODISE_REQUIRE(!want_bbox || (bb && bb->rows && bb->n_rows), "instance_eval: null bbox task");
+    const bool segm = !want_bbox || d->rows || d->n_rows;   // the bbox call skips the segm part when it has nowhere to go
+    ODISE_REQUIRE(d->iou_thresholds && d->flags && (!segm || (d->rows && d->n_rows)), "instance_eval: null pointer");
     const InstSource src = inst_source(*d);
     ODISE_TRY(inst_source_check("instance_eval", src, true, kRleMaxPixels));   // the match step reads the table and the scores of dense masks too
     ODISE_REQUIRE(d->n_gt >= 0 && d->n_gt <= kInstMaxGt, "instance_eval: %d ground-truth masks (0..%d)", d->n_gt, kInstMaxGt);
-    ODISE_REQUIRE(d->n_gt == 0 || (d->gt_runs && d->gt_offsets && d->gt_rows), "instance_eval: null ground truth");
+    ODISE_REQUIRE(d->n_gt == 0 || (d->gt_rows && (!segm || (d->gt_runs && d->gt_offsets)) && (!want_bbox || bb->gt_boxes)),
+                  "instance_eval: null ground truth");
+    if (!segm) p = nullptr;
     ODISE_REQUIRE(!p || p->n_poly >= 0, "instance_eval: %d polygons", p->n_poly);
     if (p && (d->n_gt == 0 || p->n_poly == 0)) p = nullptr;   // nothing to rasterise
     ODISE_REQUIRE(!p || (p->xy && p->poly_offsets && p->gt_polys), "instance_eval: null polygon ground truth");
     ODISE_REQUIRE(d->num_categories >= 1, "instance_eval: num_categories %d", d->num_categories);
+    ODISE_REQUIRE(!want_bbox || (((uintptr_t)bb->gt_boxes & 7) == 0 && ((uintptr_t)bb->boxes & 3) == 0), "instance_eval: gt_boxes / boxes misaligned");
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
     InstGeom ig;
     ODISE_TRY(inst_geom(ctx, "instance_eval", src, &ig));
     const RleGrid G = rle_grid(d->h, d->w);
     InstScratch s;
-    ODISE_TRY(inst_scratch(ctx, d->topk, d->n_gt, G, &s, p != nullptr));
+    ODISE_TRY(inst_scratch(ctx, d->topk, d->n_gt, G, &s, p != nullptr, want_bbox && !bb->boxes));
     ODISE_CHECK_HIP(hipMemsetAsync(s.inter, 0, s.inter_bytes, ctx->stream));
     int* status = s.inter + (size_t)d->topk * d->n_gt;
     ODISE_TRY(inst_pack(ctx, src, ig, G, s.words_d));
-    ODISE_TRY(inst_overlaps(ctx, s, G, d->topk, d->gt_runs, d->gt_offsets, d->n_gt, status, p));
+    if (segm) ODISE_TRY(inst_overlaps(ctx, s, G, d->topk, d->gt_runs, d->gt_offsets, d->n_gt, status, p));
     InstMatchArgs A;
     A.inst_table = (const int*)d->inst_table; A.inst_scores = d->inst_scores; A.gt_rows = (const int*)d->gt_rows;
-    A.inter = s.inter; A.area = s.area; A.status = status;
-    A.rows = d->rows; A.n_rows = (int*)d->n_rows; A.flags = (int*)d->flags;
+    A.status = status; A.flags = (int*)d->flags;
     A.topk = d->topk; A.n_gt = d->n_gt; A.num_categories = d->num_categories; A.image = d->image;
     for (int t = 0; t < 10; ++t) A.thr[t] = d->iou_thresholds[t];
-    hipLaunchKernelGGL(inst_match_kernel, dim3(1), dim3(kRleThreads), 0, ctx->stream, A);
-    ODISE_CHECK_HIP(hipGetLastError());
+    if (want_bbox) {   // first: a flag it raises (2, 4) is in `status` when the segm match reads it
+        float* boxes = bb->boxes ? bb->boxes : s.boxes;
+        ODISE_TRY(inst_boxes_launch(ctx, s.words_d, G, src.inst_table, d->topk, boxes));
+        A.rows = bb->rows; A.n_rows = (int*)bb->n_rows;
+        hipLaunchKernelGGL(inst_match_kernel<BoxIou>, dim3(1), dim3(kRleThreads), 0, ctx->stream, A, BoxIou{boxes, bb->gt_boxes});
+        ODISE_CHECK_HIP(hipGetLastError());
+    }
+    if (segm) {
+        A.rows = d->rows; A.n_rows = (int*)d->n_rows;
+        hipLaunchKernelGGL(inst_match_kernel<SegmIou>, dim3(1), dim3(kRleThreads), 0, ctx->stream, A, SegmIou{s.inter, s.area, d->topk, d->n_gt});
+        ODISE_CHECK_HIP(hipGetLastError());
+    }
     return ODISE_OK;
+}
+
+extern "C" int odise_hip_instance_eval(odise_hip_ctx* ctx, const odise_inst_eval_desc* d) { return inst_eval_run(ctx, d, nullptr, nullptr, false); }
+
+extern "C" int odise_hip_instance_eval_poly(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p) {
+    return inst_eval_run(ctx, d, p, nullptr, false);
+}
+
+extern "C" int odise_hip_instance_eval_bbox(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p,
+                                            const odise_inst_bbox_task* bb) {
+    return inst_eval_run(ctx, d, p, bb, true);
 }

@@ -1,6 +1,7 @@
-// inst_words.h — "the instance masks of a picture" as the bit-packed words of rle_pack.h, written once for the four entry points that
-// take them: odise_hip_instance_eval(_poly) (inst_eval.hip), odise_hip_instance_draw (vis_inst.hip), odise_hip_inst_track_frame
-// (inst_track.hip) and odise_hip_instance_rle (rle.hip, which also compiles inst_source_check, inst_geom and inst_pack).
+// inst_words.h — "the instance masks of a picture" as the bit-packed words of rle_pack.h, written once for the entry points that
+// take them: odise_hip_instance_eval(_poly, _bbox) (inst_eval.hip), odise_hip_instance_draw (vis_inst.hip), odise_hip_inst_track_frame
+// (inst_track.hip), odise_hip_instance_boxes (inst_box.hip) and odise_hip_instance_rle (rle.hip, which also compiles inst_source_check,
+// inst_geom and inst_pack).
 //   host    InstSource (the detection fields the three public descriptors share), its check, the geometry lookup and the pack launch,
 //           the split of the word axis of the intersection kernels
 //   device  the clamped count of a selection and the candidate rule, the block popcount of a row of words, the tile sizes of the
@@ -65,6 +66,25 @@ __device__ __forceinline__ long long block_popcount(const u64* __restrict__ wd, 
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = s;
     __syncthreads();
     return part[0] + part[1] + part[2] + part[3];
+}
+
+// ---- boxes (inst_box.hip) ---------------------------------------------------------------------------------------------------------------
+// boxes float [topk][4] XYXY of words [topk][G.nw] (BitMasks.get_bounding_boxes); rows past the count of inst_table (nullptr: none) are
+// zeros and their words are not read
+int inst_boxes_launch(odise_hip_ctx* ctx, const u64* words, const RleGrid& G, const int* inst_table, int topk, float* boxes);
+// maskApi.c bbIou of two XYWH boxes, every product and sum rounded on its own: contraction is off inside (as poly.hip has it for its
+// whole file), since the compiler would fuse da + ga - i and the like into multiply-adds, which the host restatement
+// (instance_eval.box_iou) does not have.  The rounding intrinsics (__dmul_rn ..) are plain operators in this toolchain and fuse as well.
+__device__ __forceinline__ double bb_iou(double dx, double dy, double dw, double dh, double gx, double gy, double gw, double gh, bool crowd) {
+#pragma clang fp contract(off)
+    const double da = dw * dh, ga = gw * gh;
+    const double w = fmin(dx + dw, gx + gw) - fmax(dx, gx);
+    if (w <= 0.0) return 0.0;
+    const double h = fmin(dy + dh, gy + gh) - fmax(dy, gy);
+    if (h <= 0.0) return 0.0;
+    const double i = w * h;
+    const double u = crowd ? da : da + ga - i;
+    return i / u;
 }
 
 // ---- the intersection kernels (inst_inter_kernel, inst_track_inter_kernel) --------------------------------------------------------------

@@ -331,7 +331,7 @@ class ODISE(nn.Module):
 
     def __init__(self, *, backbone, sem_seg_head, criterion=None, num_queries: int, object_mask_threshold: float, overlap_threshold: float, metadata,
                  size_divisibility: int, sem_seg_postprocess_before_inference: bool, pixel_mean, pixel_std, semantic_on: bool, panoptic_on: bool,
-                 instance_on: bool, test_topk_per_image: int):
+                 instance_on: bool, test_topk_per_image: int, instance_boxes: bool = False):
         super().__init__()
         self.backbone, self.sem_seg_head, self.criterion = backbone, sem_seg_head, None   # losses are training-only
         self.num_queries, self.object_mask_threshold, self.overlap_threshold = num_queries, object_mask_threshold, overlap_threshold
@@ -343,6 +343,7 @@ class ODISE(nn.Module):
         if [float(v) for v in pixel_mean] != [0.0] * 3 or [float(v) for v in pixel_std] != [255.0] * 3 or not sem_seg_postprocess_before_inference:
             raise NotImplementedError("libodise_hip implements the released normalisation (mean 0, std 255) and sem_seg_postprocess_before_inference=True")
         self.semantic_on, self.instance_on, self.panoptic_on, self.test_topk_per_image = semantic_on, instance_on, panoptic_on, test_topk_per_image
+        self.instance_boxes = instance_boxes   # True: pred_boxes = BitMasks(mask_pred > 0).get_bounding_boxes() (maskformer_model.py:372, commented out there)
         self._hip, self._built_version = None, None
 
     @property
@@ -407,6 +408,7 @@ class ODISE(nn.Module):
             self.sem_seg_head._built_version = tuple(p._version for p in self.sem_seg_head.parameters())   # the head's weights are in the library now
         hip = self._hip
         hip.semantic_on, hip.panoptic_on, hip.instance_on = self.semantic_on, self.panoptic_on, self.instance_on
+        hip.instance_boxes = bool(self.instance_boxes)
         hip.object_mask_threshold, hip.overlap_threshold, hip.test_topk_per_image = self.object_mask_threshold, self.overlap_threshold, self.test_topk_per_image
         return hip
 
@@ -477,8 +479,8 @@ class ODISE(nn.Module):
             if "instances" in r:
                 inst = r["instances"]
                 n = len(inst["scores"])
-                o["instances"] = _instances({"pred_masks": outs.tensors[f"masks{i}"][:n], "scores": inst["scores"], "pred_classes": inst["pred_classes"]},
-                                            self.device)
+                o["instances"] = _instances({"pred_masks": outs.tensors[f"masks{i}"][:n], "pred_boxes": inst["pred_boxes"], "scores": inst["scores"],
+                                             "pred_classes": inst["pred_classes"]}, self.device)
             out.append(o)
         return out
 
@@ -493,10 +495,11 @@ def _ready_alloc(outs):
 
 
 def _instances(inst, device):
-    """detectron2 `Instances` (maskformer_model.py:369-379: pred_masks, pred_boxes = zeros, scores, pred_classes) when detectron2 is there,
-    a namespace with the same fields otherwise."""
+    """detectron2 `Instances` (maskformer_model.py:369-379: pred_masks, pred_boxes = zeros unless the model's instance_boxes is set, scores,
+    pred_classes) when detectron2 is there, a namespace with the same fields otherwise."""
     masks = inst["pred_masks"] if torch.is_tensor(inst["pred_masks"]) else torch.from_numpy(inst["pred_masks"]).to(device)
-    fields = {"pred_masks": masks, "pred_boxes": torch.zeros(masks.shape[0], 4, device=device), "scores": torch.from_numpy(inst["scores"]).to(device),
+    boxes = torch.from_numpy(inst["pred_boxes"]).to(device) if "pred_boxes" in inst else torch.zeros(masks.shape[0], 4, device=device)
+    fields = {"pred_masks": masks, "pred_boxes": boxes, "scores": torch.from_numpy(inst["scores"]).to(device),
               "pred_classes": torch.from_numpy(inst["pred_classes"]).to(device)}
     try:
         from detectron2.structures import Boxes, Instances

@@ -17,6 +17,10 @@ What it keeps of a detection is one `ROW_DTYPE` record (odise_inst_eval_row): sc
 bits of the 40 (range a, threshold t) cells, bit 10 a + t.  `accumulate` is `COCOeval.accumulate` over such rows and the count of
 non-ignored ground truths per (category, range), `summarize` the twelve COCO numbers, `results` detectron2's dict.
 
+iouType "bbox" is the same walk over another IoU: `image_rows(..., iou_type="bbox", gt_boxes=...)` takes the detections' boxes from their
+masks (`mask_boxes`: detectron2 BitMasks.get_bounding_boxes; csrc/inst_box.hip), `box_iou` is maskApi.c bbIou, a row's area is its box's
+w * h (COCO.loadRes), and the ignore bits of the ground truth stay those of `gt_rows` (the annotation's `area` in both tasks).
+
 Ground truth is RLE (compressed or uncompressed) or polygons: `gt_rows(..., polygons=True)` packs the polygons for the device, which
 rasterises them (csrc/poly.hip; host reference: odise_amd/coco_poly.py).
 """
@@ -38,8 +42,8 @@ MAX_DETECTIONS, MAX_GT = 100, 1024
 FLAG_BAD_RUNS, FLAG_BAD_CLASS, FLAG_BAD_GT, FLAG_BAD_POLYGON = 1, 2, 4, 8
 FLAG_NAMES = {FLAG_BAD_RUNS: "the run lengths of a ground-truth mask do not sum to h * w",
               FLAG_BAD_CLASS: "a predicted class is outside [0, num_categories)",
-              FLAG_BAD_GT: "a ground-truth category is outside [0, num_categories), iscrowd is not 0 / 1, or a ground truth has both runs "
-                           "and polygons",
+              FLAG_BAD_GT: "a ground-truth category is outside [0, num_categories), iscrowd is not 0 / 1, a ground truth has both runs "
+                           "and polygons, or a ground-truth box has a member that is not finite",
               FLAG_BAD_POLYGON: "a polygon has fewer than three vertices, or a coordinate is NaN or larger than 2^26 in magnitude"}
 
 
@@ -75,6 +79,67 @@ def mask_iou(dense_masks, gt_counts, iscrowd=None) -> np.ndarray:
     for i in range(n):
         for j in range(len(g)):
             out[i, j] = rle_iou(int(np.count_nonzero(d[i] & g[j])), int(area_d[i]), int(area_g[j]), bool(crowd[j]))
+    return out
+
+
+# ---- boxes --------------------------------------------------------------------------------------------------------------------------------
+def mask_boxes(masks) -> np.ndarray:
+    """float32 [n, 4] XYXY: detectron2 BitMasks.get_bounding_boxes of masks [n, h, w] (nonzero = 1) - first column with a pixel, first row
+    with a pixel, last column + 1, last row + 1; a mask without a pixel gives zeros."""
+    m = np.asarray(masks) != 0
+    boxes = np.zeros((m.shape[0], 4), np.float32)
+    for i in range(m.shape[0]):
+        x, y = np.flatnonzero(m[i].any(axis=0)), np.flatnonzero(m[i].any(axis=1))
+        if len(x) > 0 and len(y) > 0:
+            boxes[i] = (x[0], y[0], x[-1] + 1, y[-1] + 1)
+    return boxes
+
+
+def xyxy_to_xywh(boxes) -> np.ndarray:
+    """float64 [n, 4] XYWH of XYXY boxes (BoxMode.convert(XYXY_ABS, XYWH_ABS): exact on the integers of `mask_boxes`)."""
+    b = np.array(boxes, np.float64).reshape(-1, 4)
+    b[:, 2] -= b[:, 0]
+    b[:, 3] -= b[:, 1]
+    return b
+
+
+def box_iou(dt_xywh, gt_xywh, iscrowd=None) -> np.ndarray:
+    """float64 [n, n_gt]: maskApi.c bbIou (pycocotools mask.iou of boxes) in Python floats, one rounded operation per statement."""
+    dt = np.asarray(dt_xywh, np.float64).reshape(-1, 4).tolist()
+    gt = np.asarray(gt_xywh, np.float64).reshape(-1, 4).tolist()
+    crowd = [False] * len(gt) if iscrowd is None else [bool(c) for c in np.asarray(iscrowd).reshape(-1)]
+    out = np.zeros((len(dt), len(gt)), np.float64)
+    for g, G in enumerate(gt):
+        ga = G[2] * G[3]
+        for d, D in enumerate(dt):
+            da = D[2] * D[3]
+            dr = D[2] + D[0]
+            gr = G[2] + G[0]
+            w = min(dr, gr) - max(D[0], G[0])
+            if w <= 0:
+                continue
+            db = D[3] + D[1]
+            gb = G[3] + G[1]
+            h = min(db, gb) - max(D[1], G[1])
+            if h <= 0:
+                continue
+            i = w * h
+            if crowd[g]:
+                u = da
+            else:
+                u = da + ga
+                u = u - i
+            out[d, g] = i / u
+    return out
+
+
+def gt_boxes(annotations) -> np.ndarray:
+    """float64 [n_gt, 4]: the XYWH `bbox` of every annotation; one without a `bbox` raises ValueError."""
+    out = np.zeros((len(annotations), 4), np.float64)
+    for i, ann in enumerate(annotations):
+        if "bbox" not in ann:
+            raise ValueError(f"bbox evaluation: annotation {i} has no bbox")
+        out[i] = np.asarray(ann["bbox"], np.float64).reshape(4)
     return out
 
 
@@ -141,17 +206,27 @@ def area_outside(area, a: int) -> bool:
     return bool(area < AREA_RNG[a][0] or area > AREA_RNG[a][1])
 
 
-def image_rows(masks, scores, classes, gt_counts, gt_table, image: int = 0, iou_thrs=IOU_THRS, num_categories=None):
+def image_rows(masks, scores, classes, gt_counts, gt_table, image: int = 0, iou_thrs=IOU_THRS, num_categories=None, iou_type: str = "segm",
+               gt_boxes=None):
     """COCOeval.evaluateImg of one picture -> (rows ROW_DTYPE [n] in descending score, flags).  masks [n, h, w] (nonzero = 1), n <= 100;
-    gt_counts: the run lengths of every ground truth; gt_table: `gt_rows`' table.  A picture that raises a flag has no rows."""
+    gt_counts: the run lengths of every ground truth; gt_table: `gt_rows`' table.  A picture that raises a flag has no rows.
+    iou_type "bbox": the IoU is `box_iou` of `mask_boxes(masks)` against gt_boxes float64 [n_gt, 4] XYWH, a row's area is its box's
+    w * h, and gt_counts is not looked at (None will do)."""
+    assert iou_type in ("segm", "bbox"), iou_type
+    bbox = iou_type == "bbox"
     d = np.asarray(masks) != 0
     n, h, w = d.shape
     scores, classes = np.asarray(scores, np.float32).reshape(-1), np.asarray(classes, np.int64).reshape(-1)
     table = np.asarray(gt_table, np.int64).reshape(-1, 3)
     n_gt = len(table)
-    assert n <= MAX_DETECTIONS and len(scores) >= n and len(classes) >= n and len(gt_counts) == n_gt
+    assert n <= MAX_DETECTIONS and len(scores) >= n and len(classes) >= n and (bbox or len(gt_counts) == n_gt)
     flags = 0
-    if any(int(np.asarray(c, np.int64).sum()) != h * w for c in gt_counts):
+    if bbox:
+        gtb = np.asarray(gt_boxes, np.float64).reshape(-1, 4)
+        assert len(gtb) == n_gt, (len(gtb), n_gt)
+        if not np.isfinite(gtb).all():
+            flags |= FLAG_BAD_GT
+    elif any(int(np.asarray(c, np.int64).sum()) != h * w for c in gt_counts):
         flags |= FLAG_BAD_RUNS
     if num_categories is not None:
         if n and (classes[:n].min() < 0 or classes[:n].max() >= num_categories):
@@ -162,11 +237,15 @@ def image_rows(masks, scores, classes, gt_counts, gt_table, image: int = 0, iou_
         flags |= FLAG_BAD_GT
     if flags:
         return np.zeros(0, ROW_DTYPE), flags
-    ious = mask_iou(d, gt_counts, table[:, 1])
+    if bbox:
+        dtb = xyxy_to_xywh(mask_boxes(d))
+        ious, areas = box_iou(dtb, gtb, table[:, 1]), (dtb[:, 2] * dtb[:, 3]).astype(np.int64)
+    else:
+        ious, areas = mask_iou(d, gt_counts, table[:, 1]), d.reshape(n, h * w).sum(1)
     order = np.argsort(-scores[:n], kind="mergesort")
     rows = np.zeros(n, ROW_DTYPE)
     rows["score"], rows["category"], rows["image"] = scores[order], classes[order], image
-    rows["area"] = d.reshape(n, h * w).sum(1)[order]
+    rows["area"] = areas[order]
     pos = {int(dd): k for k, dd in enumerate(order)}
     for c in np.unique(classes[:n]):
         dt = [int(i) for i in order if classes[i] == c]

@@ -5,7 +5,12 @@ COCOeval.accumulate on the device too (`odise_hip_instance_accumulate`: on one r
 gathered on the host first and go up again as one block), which leaves the host summarize / results (odise_amd/instance_eval.py).
 
 Ground truth is what COCO's instance annotations hold: polygons (rasterised on the device, pycocotools' annToRLE bit for bit) for the
-objects, RLE (compressed or uncompressed) for the crowds, mixed freely in one picture."""
+objects, RLE (compressed or uncompressed) for the crowds, mixed freely in one picture.
+
+tasks=("bbox",) or ("bbox", "segm") is COCOEvaluator's bbox task beside (or without) segm: `process` enqueues one
+`odise_hip_instance_eval_bbox`, which takes the detections' boxes from the same packed masks (BitMasks.get_bounding_boxes, the line the
+reference leaves out as slow) and matches them against the annotations' `bbox`; every task keeps row blocks of its own, the row format
+and everything behind it are shared."""
 from __future__ import annotations
 
 from typing import Dict, Sequence
@@ -20,10 +25,16 @@ from .runtime import Context, DeviceArray, InstanceAccumulateError
 class HipInstanceSegEvaluator:
     CHUNK = 64          # pictures per block of the row buffer: it grows by whole blocks, rows already written stay where they are
 
-    def __init__(self, ctx: Context, thing_dataset_id_to_contiguous_id: Dict[int, int], class_names: Sequence[str], topk: int = 100):
+    TASKS = ("bbox", "segm")                                                   # detectron2's order of the result groups
+
+    def __init__(self, ctx: Context, thing_dataset_id_to_contiguous_id: Dict[int, int], class_names: Sequence[str], topk: int = 100,
+                 tasks: Sequence[str] = ("segm",)):
         """thing_dataset_id_to_contiguous_id: the annotation's category ids -> 0..K-1, the space the model's pred_classes live in;
-        class_names [K] per contiguous id; topk: the model's test_topk_per_image (at most 100, COCOeval's last maxDets)."""
+        class_names [K] per contiguous id; topk: the model's test_topk_per_image (at most 100, COCOeval's last maxDets);
+        tasks: ("segm",), ("bbox",) or ("bbox", "segm") - with "bbox" every annotation needs its `bbox`."""
         self.ctx = ctx
+        assert len(tasks) > 0 and set(tasks) <= set(self.TASKS) and len(set(tasks)) == len(tasks), tasks
+        self.tasks = tuple(t for t in self.TASKS if t in tasks)
         self.to_contiguous = {int(k): int(v) for k, v in thing_dataset_id_to_contiguous_id.items()}
         self.class_names = list(class_names)
         self.K, self.topk = len(self.class_names), int(topk)
@@ -35,17 +46,21 @@ class HipInstanceSegEvaluator:
     def reset(self) -> None:
         from ._lib import check
         check(self.ctx.lib.odise_hip_memset(self.ctx.h, self.flags.ptr, 0, 4), "memset")
-        self._chunks, self._pictures, self._images = [], 0, []
+        self._task_chunks, self._pictures, self._images = {t: [] for t in self.tasks}, 0, []
+        self._chunks = self._task_chunks[self.tasks[-1]]                       # the segm task's blocks when it is there
         self._npig = np.zeros((self.K, 4), np.int64)
 
     def _slot(self):
-        """(rows [topk], n_rows [1]) of the next picture."""
+        """{task: (rows [topk], n_rows [1])} of the next picture."""
         i = self._pictures % self.CHUNK
-        if i == 0:
-            self._chunks.append((self.ctx.empty((self.CHUNK * self.topk,), IE.ROW_DTYPE), self.ctx.zeros((self.CHUNK,), np.int32)))
-        rows, counts = self._chunks[-1]
+        out = {}
+        for t in self.tasks:
+            if i == 0:
+                self._task_chunks[t].append((self.ctx.empty((self.CHUNK * self.topk,), IE.ROW_DTYPE), self.ctx.zeros((self.CHUNK,), np.int32)))
+            rows, counts = self._task_chunks[t][-1]
+            out[t] = rows.view((self.topk,), IE.ROW_DTYPE, i * self.topk * IE.ROW_DTYPE.itemsize), counts.view((1,), np.int32, 4 * i)
         self._pictures += 1
-        return rows.view((self.topk,), IE.ROW_DTYPE, i * self.topk * IE.ROW_DTYPE.itemsize), counts.view((1,), np.int32, 4 * i)
+        return out
 
     def process(self, b: int, inst_table_row, inst_scores_row, pad_hw, img_hw, out_hw, annotations, image_index: int, pred_masks=None) -> None:
         """One picture: inst_table_row [1 + 2 topk] / inst_scores_row [topk] = image b's rows of the device instance table of the last
@@ -59,11 +74,16 @@ class HipInstanceSegEvaluator:
         table, runs, offsets, xy, poly_offsets, gt_polys = IE.gt_rows(annotations, self.to_contiguous, polygons=True, hw=out_hw)
         assert len(table) <= IE.MAX_GT, f"{len(table)} ground-truth masks in one picture (at most {IE.MAX_GT})"
         self._npig += IE.npig(table, self.K)
-        gt = self.ctx.instance_gt_to_device(table, runs, offsets, *((xy, poly_offsets, gt_polys) if len(poly_offsets) > 1 else ()))
-        rows, n_rows = self._slot()
+        boxes = IE.gt_boxes(annotations) if "bbox" in self.tasks else None
+        gt = self.ctx.instance_gt_to_device(table, runs, offsets, *((xy, poly_offsets, gt_polys) if len(poly_offsets) > 1 else ()), boxes=boxes)
+        slot = self._slot()
         self._images.append(int(image_index))
-        self.ctx.instance_eval(out_hw, inst_table_row, inst_scores_row, self.topk, gt, self.K, int(image_index), rows, n_rows, self.flags,
-                               masks=pred_masks, b=b, pad_hw=pad_hw, img_hw=img_hw)
+        if "bbox" in self.tasks:
+            self.ctx.instance_eval_bbox(out_hw, inst_table_row, inst_scores_row, self.topk, gt, self.K, int(image_index), *slot["bbox"], self.flags,
+                                        *slot.get("segm", (None, None)), masks=pred_masks, b=b, pad_hw=pad_hw, img_hw=img_hw)
+        else:
+            self.ctx.instance_eval(out_hw, inst_table_row, inst_scores_row, self.topk, gt, self.K, int(image_index), *slot["segm"], self.flags,
+                                   masks=pred_masks, b=b, pad_hw=pad_hw, img_hw=img_hw)
 
     def process_selection(self, selection: dict, annotations_per_image, image_indices) -> None:
         """`process` for every picture of a batch from `HipCategoryODISE.last_selection`."""
@@ -74,10 +94,10 @@ class HipInstanceSegEvaluator:
                          selection["inst_scores"].view((topk,), np.float32, b * topk * 4), selection["pad_hw"], selection["img_hw"][b],
                          selection["out_hw"][b], anns, idx)
 
-    def rows(self) -> np.ndarray:
-        """This rank's rows so far (one read per block of pictures)."""
+    def rows(self, task: str = None) -> np.ndarray:
+        """This rank's rows of a task so far (one read per block of pictures); task: "segm" where it runs, else "bbox"."""
         out = []
-        for c, (rows, counts) in enumerate(self._chunks):
+        for c, (rows, counts) in enumerate(self._task_chunks[task or self.tasks[-1]]):
             host, n = rows.numpy().reshape(self.CHUNK, self.topk), counts.numpy()
             used = min(self.CHUNK, self._pictures - c * self.CHUNK)
             out += [host[i, :n[i]] for i in range(used)]
@@ -100,35 +120,42 @@ class HipInstanceSegEvaluator:
     def evaluate(self, accumulate_on: str = "device") -> dict:
         """accumulate_on: "device" = odise_hip_instance_accumulate, "host" = instance_eval.accumulate; the results are bit-identical.  When an
         image number was given twice the host path is taken whatever was asked: the host function merges such pictures and the device
-        order is not defined for them."""
+        order is not defined for them.
+        -> detectron2's results of the task; with tasks other than ("segm",) one such group per task, {"bbox": .., "segm": ..}.
+        `precision` / `recall` are those of the last task, `task_precision` / `task_recall` hold every task's."""
         import torch
         import torch.distributed as dist
         assert accumulate_on in ("device", "host"), accumulate_on
         many = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         flags, npig = int(self.flags.numpy()[0]), self._npig
-        blocks = None
+        gathered = None
         if many:
-            rows = self.rows()
             parts = [None] * dist.get_world_size()
-            dist.all_gather_object(parts, (rows, flags))
-            rows = np.concatenate([p[0] for p in parts])
+            dist.all_gather_object(parts, ({t: self.rows(t) for t in self.tasks}, flags))
+            gathered = {t: np.concatenate([p[0][t] for p in parts]) for t in self.tasks}
             for p in parts:
                 flags |= int(p[1])                                           # every rank raises when any rank saw a flag
             npig = D.sum_confusion(torch.from_numpy(npig.copy())).numpy()
-            if accumulate_on == "device" and not flags:
-                block = self.slots_of(rows, self.topk)                       # the same decision on every rank: it is made on the gathered rows
-                blocks = [block] if block is not None else None
-        elif accumulate_on == "device" and len(set(self._images)) == len(self._images):
-            blocks = self._chunks                                            # as they lie
         if flags:
             raise RuntimeError("instance evaluation: malformed input(s): " + "; ".join(IE.flag_names(flags)))
-        if blocks is not None:
-            try:
-                self.precision, self.recall = self.ctx.instance_accumulate(blocks, npig, self.K, self.topk)
-            except InstanceAccumulateError as e:
-                if e.flags != IE.ACCUM_FLAG_NAN_SCORE:
-                    raise
-                blocks = None                                                # a NaN score: the device sort has no place for it, numpy's has
-        if blocks is None:
-            self.precision, self.recall = IE.accumulate(rows if many else self.rows(), npig, self.K)
-        return IE.results(self.precision, self.recall, self.class_names)
+        self.task_precision, self.task_recall, out = {}, {}, {}
+        for t in self.tasks:
+            blocks = None
+            if many:
+                if accumulate_on == "device":
+                    block = self.slots_of(gathered[t], self.topk)            # the same decision on every rank: it is made on the gathered rows
+                    blocks = [block] if block is not None else None
+            elif accumulate_on == "device" and len(set(self._images)) == len(self._images):
+                blocks = self._task_chunks[t]                                # as they lie
+            if blocks is not None:
+                try:
+                    self.precision, self.recall = self.ctx.instance_accumulate(blocks, npig, self.K, self.topk)
+                except InstanceAccumulateError as e:
+                    if e.flags != IE.ACCUM_FLAG_NAN_SCORE:
+                        raise
+                    blocks = None                                            # a NaN score: the device sort has no place for it, numpy's has
+            if blocks is None:
+                self.precision, self.recall = IE.accumulate(gathered[t] if many else self.rows(t), npig, self.K)
+            self.task_precision[t], self.task_recall[t] = self.precision, self.recall
+            out[t] = IE.results(self.precision, self.recall, self.class_names)
+        return out["segm"] if self.tasks == ("segm",) else out

@@ -128,13 +128,13 @@ class HipCategoryODISE(HipODISE):
     """The whole CategoryODISE eval forward on the device.  `forward(batched_inputs)` takes the reference's input format
     (list of {"image": uint8/float CHW, "height", "width"}; images of one call may differ in size, odise.py:238-244) and returns the
     reference's output format (list of dicts with "sem_seg" [K,h,w] fp32, "panoptic_seg" (int32 [h,w], segments_info), "instances"
-    {pred_masks, scores, pred_classes}).  One library call per batch (`odise_hip_infer`); every decision of the three heads is taken on
+    {pred_masks, pred_boxes, scores, pred_classes}).  One library call per batch (`odise_hip_infer`); every decision of the three heads is taken on
     the device, the host reads back the segment / instance tables (a few hundred bytes per image) once at the end."""
 
     HEAD_KEYS = ("category_head.text_proj.weight", "category_head.text_proj.bias", "category_head.null_embed")
 
     def __init__(self, ctx: Context, state, semantic_on=True, panoptic_on=True, instance_on=True, object_mask_threshold=0.0,
-                 overlap_threshold=0.8, test_topk_per_image=100, size_divisibility=64):
+                 overlap_threshold=0.8, test_topk_per_image=100, size_divisibility=64, instance_boxes: bool = False):
         super().__init__(ctx, {k: v for k, v in state.items()})
         self.load_category_head(state)
         self.semantic_on, self.panoptic_on, self.instance_on = semantic_on, panoptic_on, instance_on
@@ -142,6 +142,9 @@ class HipCategoryODISE(HipODISE):
         self.instance_rle = False             # True: "pred_masks_rle" (COCO RLE strings, encoded from the mask logits) instead of "pred_masks" [n,h,w]
         self.keep_instance_selection = False  # True: `last_selection` = the device inst_table / inst_scores of the last call (HipInstanceSegEvaluator.process)
         self.last_selection = None
+        # True: the instances' "pred_boxes" are BitMasks(mask_pred > 0).get_bounding_boxes(), the line the reference leaves commented out
+        # (maskformer_model.py:372), from odise_hip_instance_boxes on the selection of the call; False: the reference's zeros
+        self.instance_boxes = bool(instance_boxes)
         self.object_mask_threshold, self.overlap_threshold = object_mask_threshold, overlap_threshold
         self.test_topk_per_image, self.size_divisibility = test_topk_per_image, size_divisibility
         assert size_divisibility == 64, "the feature extractor fixes size_divisibility at 64 (feature_extractor.py:126-128)"
@@ -327,6 +330,16 @@ class HipCategoryODISE(HipODISE):
                                                     grow=grow))
         bufs["rle"] = pend
 
+    def _enqueue_boxes(self, bufs, pad_hw, img_hw, out_sizes) -> None:
+        """instance_boxes: one odise_hip_instance_boxes per image behind the call that produced the selection (same stream)."""
+        if not (self.instance_on and self.instance_boxes):
+            return
+        topk = int(self.test_topk_per_image)
+        bufs["boxes"] = self._buf("inst_boxes", (len(out_sizes), topk, 4), np.float32)
+        for i, (ihw, ohw) in enumerate(zip(img_hw, out_sizes)):
+            self.ctx.instance_boxes(ohw, topk, bufs["itable"].view((1 + 2 * topk,), np.int32, i * (1 + 2 * topk) * 4), b=i, pad_hw=pad_hw, img_hw=ihw,
+                                    boxes=bufs["boxes"].view((topk, 4), np.float32, i * topk * 16))
+
     def _keep_selection(self, bufs, pad_hw, img_hw, out_sizes) -> None:
         """keep_instance_selection: what an evaluator needs to go on from the selection on the same stream, nothing read back.  The buffers
         are the pooled ones: they hold this batch until the next call."""
@@ -342,6 +355,7 @@ class HipCategoryODISE(HipODISE):
         results = [dict() for _ in range(n)]
         itable = bufs["itable"].numpy() if self.instance_on else None
         iscores = bufs["iscores"].numpy() if self.instance_on else None
+        iboxes = bufs["boxes"].numpy() if "boxes" in bufs else None
         for i, (oh, ow) in enumerate(out_sizes):
             r = results[i]
             if self.semantic_on and not self.semantic_argmax:
@@ -368,6 +382,8 @@ class HipCategoryODISE(HipODISE):
                 masks = bufs["masks"][i].view((cnt, oh, ow))
                 r["instances"] = {"pred_masks": masks.numpy() if to_host else masks, "scores": iscores[i, :cnt].copy(),
                                   "pred_classes": itable[i, 1 + topk:1 + topk + cnt].astype(np.int64), "query_index": itable[i, 1:1 + cnt].copy()}
+            if self.instance_on:
+                r["instances"]["pred_boxes"] = iboxes[i, :cnt].copy() if iboxes is not None else np.zeros((cnt, 4), np.float32)
         return results
 
     def postprocess_batch(self, mask_cls, pad_hw, img_hw, out_sizes, to_host: bool = True, pan_out=None) -> list:
@@ -382,6 +398,7 @@ class HipCategoryODISE(HipODISE):
         d.B, d.pad_h, d.pad_w, d.img_hw, d.mask_cls = n, int(pad_hw[0]), int(pad_hw[1]), C.cast(iarr, C.c_void_p), dcls.ptr
         check(self.ctx.lib.odise_hip_postprocess_batch(self.ctx.h, C.byref(d)), "postprocess_batch")
         self._enqueue_rle(bufs, pad_hw, ihw, sizes)
+        self._enqueue_boxes(bufs, pad_hw, ihw, sizes)
         self._keep_selection(bufs, pad_hw, ihw, sizes)
         return self._collect(bufs, sizes, to_host)
 
@@ -415,6 +432,7 @@ class HipCategoryODISE(HipODISE):
         check(self.ctx.lib.odise_hip_infer(self.ctx.h, C.byref(d)), "infer")
         hp = -(-max(int(h) for h, _ in img_hw) // 64) * 64, -(-max(int(w) for _, w in img_hw) // 64) * 64   # the library's padding (size_divisibility 64)
         self._enqueue_rle(bufs, hp, img_hw, out_sizes)
+        self._enqueue_boxes(bufs, hp, img_hw, out_sizes)
         self._keep_selection(bufs, hp, img_hw, out_sizes)
         return self._collect(bufs, out_sizes, to_host)
 

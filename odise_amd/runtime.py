@@ -807,11 +807,12 @@ class Context:
 
     # ---- segm evaluation of instance masks (include/odise_hip.h odise_hip_mask_iou / odise_hip_instance_eval; host restatement:
     # odise_amd/instance_eval.py) ------------------------------------------------------------------------------------------------------
-    def instance_gt_to_device(self, gt_table, runs, offsets, xy=None, poly_offsets=None, gt_polys=None) -> dict:
+    def instance_gt_to_device(self, gt_table, runs, offsets, xy=None, poly_offsets=None, gt_polys=None, boxes=None) -> dict:
         """The ground truth of one picture (instance_eval.gt_rows) as ONE packed upload: offsets int64 [n_gt + 1] | table int32 [n_gt, 3] |
         runs uint32 -> {"n_gt", "offsets", "rows", "runs"} (views of one device buffer).  With the polygon part of
         `gt_rows(..., polygons=True)` the same upload carries poly_offsets int64 | xy float64 in front of the table and gt_polys int32
-        behind it, and the dict gains {"n_poly", "xy", "poly_offsets", "gt_polys"}.  The upload waits for the stream."""
+        behind it, and the dict gains {"n_poly", "xy", "poly_offsets", "gt_polys"}.  With `boxes` (instance_eval.gt_boxes: float64
+        [n_gt, 4] XYWH) the same upload carries them in front of the table and the dict gains {"boxes"}.  The upload waits for the stream."""
         table = np.ascontiguousarray(np.asarray(gt_table, np.int32).reshape(-1, 3))
         runs, offsets = np.ascontiguousarray(runs, np.uint32), np.ascontiguousarray(offsets, np.int64)
         n_gt = table.shape[0]
@@ -824,6 +825,11 @@ class Context:
             assert gt_polys.shape == (n_gt + 1,) and int(gt_polys[-1]) == n_poly and 2 * int(poly_offsets[-1]) == xy.size, \
                 (gt_polys.shape, n_gt, n_poly, xy.size)
             parts += [poly_offsets, xy]                                  # the 8-byte items first: every view stays aligned
+        if boxes is not None:
+            boxes = np.ascontiguousarray(boxes, np.float64).reshape(-1)
+            assert boxes.size == 4 * n_gt, (boxes.size, n_gt)
+            at_boxes = len(parts)
+            parts.append(boxes)
         parts += [table.reshape(-1)] + ([gt_polys] if gt_polys is not None else []) + [runs]
         buf = self.to_device(np.concatenate([p.view(np.uint8) for p in parts]))
         at = np.concatenate(([0], np.cumsum([p.nbytes for p in parts]))).tolist()
@@ -832,6 +838,8 @@ class Context:
         if gt_polys is not None:
             gt.update(n_poly=n_poly, poly_offsets=buf.view((n_poly + 1,), np.int64, at[1]), xy=buf.view((xy.size,), np.float64, at[2]),
                       gt_polys=buf.view((n_gt + 1,), np.int32, at[-3]))
+        if boxes is not None:
+            gt["boxes"] = buf.view((n_gt, 4), np.float64, at[at_boxes])
         return gt
 
     def mask_iou(self, masks: DeviceArray, gt_counts, iscrowd=None, flags: Optional[DeviceArray] = None, with_counts: bool = False):
@@ -876,6 +884,61 @@ class Context:
             check(self.lib.odise_hip_instance_eval_poly(self.h, C.byref(d), C.byref(p)), "instance_eval_poly")
         else:
             check(self.lib.odise_hip_instance_eval(self.h, C.byref(d)), "instance_eval")
+
+    def instance_boxes(self, out_hw, topk: int, table_row=None, masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0), img_hw=(0, 0),
+                       boxes: Optional[DeviceArray] = None) -> DeviceArray:
+        """Enqueue the boxes of a picture's instance selection (odise_hip_instance_boxes: detectron2 BitMasks.get_bounding_boxes) ->
+        float32 [topk, 4] XYXY on the device, rows past the count of the table zeros.  The detections are the selection table_row
+        [1 + 2 topk] of image b of the last head forward, sampled from its mask logits (pad_hw / img_hw as in `instance_rle`), or the
+        dense `masks` [topk, h, w] when given (table_row optional: without one every mask counts).  Host restatement:
+        instance_eval.mask_boxes."""
+        from ._lib import InstBoxesDesc
+        d = InstBoxesDesc()
+        _fill_inst_source(d, "instance_boxes", out_hw, topk, table_row, None, masks, b, pad_hw, img_hw)
+        if boxes is None:
+            boxes = self.empty((int(topk), 4), np.float32)
+        assert boxes.dtype == np.float32 and boxes.nbytes >= 16 * int(topk), (boxes.dtype, boxes.shape)
+        d.boxes = boxes.ptr
+        check(self.lib.odise_hip_instance_boxes(self.h, C.byref(d)), "instance_boxes")
+        return boxes
+
+    def box_iou(self, dt_xywh, gt_xywh, iscrowd=None) -> DeviceArray:
+        """pycocotools' mask.iou of boxes (odise_hip_box_iou: maskApi.c bbIou) -> float64 [n, n_gt] on the device, bit for bit
+        instance_eval.box_iou.  dt_xywh [n, 4] / gt_xywh [n_gt, 4] float64 and iscrowd [n_gt]: device arrays, or host arrays, which
+        are uploaded (that waits)."""
+        dev = lambda a, dt: a if isinstance(a, DeviceArray) else self.to_device(np.ascontiguousarray(a, dt))
+        dt, gt = dev(dt_xywh, np.float64), dev(gt_xywh, np.float64)
+        assert dt.dtype == np.float64 and gt.dtype == np.float64, (dt.dtype, gt.dtype)
+        n, n_gt = dt.nbytes // 32, gt.nbytes // 32
+        crowd = None if iscrowd is None else dev(iscrowd, np.uint8)
+        iou = self.empty((n, n_gt), np.float64)
+        check(self.lib.odise_hip_box_iou(self.h, _p(dt), n, _p(gt), n_gt, _p(crowd), _p(iou)), "box_iou")
+        return iou
+
+    def instance_eval_bbox(self, out_hw, table_row, scores_row, topk: int, gt: dict, num_categories: int, image: int, bbox_rows, bbox_n_rows,
+                           flags, rows=None, n_rows=None, boxes=None, masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0),
+                           img_hw=(0, 0), iou_thresholds=None) -> None:
+        """Enqueue COCOeval.evaluateImg of one picture for "bbox" (odise_hip_instance_eval_bbox) and, when `rows` / `n_rows` are given,
+        for "segm" from the same pack of the detections (exactly `instance_eval`).  Arguments as in `instance_eval`; gt must carry
+        "boxes" (`instance_gt_to_device(..., boxes=instance_eval.gt_boxes(annotations))`); bbox_rows / bbox_n_rows take the bbox
+        task's rows; boxes (optional, float32 [topk, 4]) the detections' XYXY boxes."""
+        from ._lib import InstBboxTask, InstEvalDesc, InstPolyGt
+        from .instance_eval import IOU_THRS
+        thr = np.ascontiguousarray(IOU_THRS if iou_thresholds is None else iou_thresholds, np.float64)
+        assert thr.shape == (10,), thr.shape
+        assert "boxes" in gt, "instance_eval_bbox: the ground truth carries no boxes"
+        d = InstEvalDesc()
+        _fill_inst_source(d, "instance_eval_bbox", out_hw, topk, table_row, scores_row, masks, b, pad_hw, img_hw)
+        d.gt_runs, d.gt_offsets, d.gt_rows, d.n_gt = gt["runs"].ptr, gt["offsets"].ptr, gt["rows"].ptr, int(gt["n_gt"])
+        d.num_categories, d.image, d.iou_thresholds = int(num_categories), int(image), thr.ctypes.data
+        d.rows, d.n_rows, d.flags = _ptr(rows), _ptr(n_rows), _ptr(flags)
+        t = InstBboxTask()
+        t.gt_boxes, t.rows, t.n_rows, t.boxes = gt["boxes"].ptr, _ptr(bbox_rows), _ptr(bbox_n_rows), _ptr(boxes)
+        p = None
+        if "gt_polys" in gt:
+            p = InstPolyGt()
+            p.xy, p.poly_offsets, p.gt_polys, p.n_poly = gt["xy"].ptr, gt["poly_offsets"].ptr, gt["gt_polys"].ptr, int(gt["n_poly"])
+        check(self.lib.odise_hip_instance_eval_bbox(self.h, C.byref(d), C.byref(p) if p is not None else None, C.byref(t)), "instance_eval_bbox")
 
     def instance_accumulate(self, blocks, npig, num_categories: int, topk: int, rec_thrs=None):
         """COCOeval.accumulate on the device (odise_hip_instance_accumulate; host restatement: instance_eval.accumulate, which this
