@@ -738,6 +738,30 @@ typedef struct {
     int32_t* order;                 /* device [topk], optional */
 } odise_inst_draw_desc;
 int odise_hip_instance_draw(odise_hip_ctx* ctx, const odise_inst_draw_desc* d);
+/* odise_hip_instance_draw for instances that carry boxes: detectron2 Visualizer.overlay_instances(boxes=..., masks=...), which draws a
+ * rectangle frame per box, orders the instances by BOX area and puts the label on the box corner.  d is read as above; bx adds the boxes
+ * (as odise_hip_instance_boxes writes them, or any other).  What differs:
+ *   kept       additionally the box is finite and has a positive width and height (x1 > x0 and y1 > y0).
+ *   order      descending box area, the float product (x1 - x0) * (y1 - y0); ties by ascending table index.
+ *   anchors    x0..y1 = the box, the floats truncated toward zero (clamped to +-2^29); the label position (x2 / 2, y2 / 2) is (x0, y0);
+ *              when the box area (that float product) < small_area or y1 - y0 < 40 (floats) it is (x1, y0) if y1 >= h - 5, else
+ *              (x0, y1).  `area` stays the mask's pixel count.  detectron2's small_area is _SMALL_OBJECT_AREA_THRESH = 1000.
+ *   out        walking the kept instances in the new order, instance i first lays its frame: with bx0 = max(x0, 0), by0 = max(y0, 0),
+ *              bx1 = min(x1, w), by1 = min(y1, h) of the truncated members (the box clipped to the picture), a pixel with
+ *              bx0 <= x < bx1, by0 <= y < by1 and x < bx0 + box_width or x >= bx1 - box_width or y < by0 + box_width or
+ *              y >= by1 - box_width takes c = (c * (256 - box_alpha256) + colors[i] * box_alpha256 + 128) >> 8 per channel; then the
+ *              mask step of odise_hip_instance_draw, unchanged.  A box narrower than 2 * box_width is all frame.
+ * The same tiles as odise_hip_instance_draw; the bounds of the boxes lie in LDS and a tile that no kept mask touches still gets its frames.
+ * With box_alpha256 = 0 and a box order equal to the mask order the picture is odise_hip_instance_draw's.
+ * ODISE_ERR_ARG and nothing written: what odise_hip_instance_draw refuses, a null bx or bx->boxes, boxes not 4-byte aligned,
+ * box_width < 1, box_alpha256 outside 0..256.  Scratch comes from the context.  Asynchronous on the context's stream. */
+typedef struct {
+    const float* boxes;             /* device [topk][4] XYXY */
+    int box_width;                  /* >= 1, pixels */
+    int box_alpha256;               /* 0 (no frame) .. 256 (the colour) */
+    int small_area;                 /* the label of a box below this area moves off the corner */
+} odise_inst_box_draw;
+int odise_hip_instance_draw_boxes(odise_hip_ctx* ctx, const odise_inst_draw_desc* d, const odise_inst_box_draw* bx);
 /* A semantic result as a panoptic record that odise_hip_segment_anchors and odise_hip_panoptic_overlay draw unchanged (draw_sem_seg).
  * Input: labels int32 [H,W] (the fused arg-max map) or sem_seg fp32 [K,H,W] (arg-max over the planes, ties to the lower class, as
  * odise_hip_semantic_confusion takes it); exactly one of the two.  record int32 [H*W | 1 | 3*ODISE_MAX_SEGMENTS] (device, must not
@@ -846,6 +870,54 @@ typedef struct {
     int iou_cap;
 } odise_inst_track_desc;
 int odise_hip_inst_track_frame(odise_hip_ctx* ctx, const odise_inst_track_desc* d);
+/* ---- instances that carry boxes keep their colours from frame to frame (the FIRST path of _assign_colors) ----------------------------
+ * For a _DetectedInstance with a box detectron2's _assign_colors matches on box IoU at 0.6; mask IoU at 0.5 (above) is only its path for
+ * box-less instances.  Host restatement: odise_amd/video.py BoxColorTracker.  A box tracker needs neither pixels nor a ring: its state is
+ * the 800 live rows and one float [4] per row.
+ *   instances   of a frame: the table indices i < n with inst_scores[i] >= min_score whose box is finite and has x1 > x0 && y1 > y0 (for
+ *               the tight boxes of odise_hip_instance_boxes the `kept` rule of odise_hip_instance_draw), in ascending table index;
+ *               (label = class, box, ttl = the tracker's ttl).  A row with a non-finite box member is no instance.
+ *   live list   ordered, empty at the start; after a frame: that frame's instances in their order, then the surviving old ones in theirs.
+ *   iou         of live row o and new instance j: the arithmetic of odise_hip_box_iou (maskApi.c bbIou in doubles, every operation rounded
+ *               on its own, crowd = 0) on the two boxes as XYWH = (x0, y0, x1 - x0, y1 - y0) computed in double from the floats; 0 where
+ *               the classes differ.
+ *   matching    every live row takes j = the FIRST maximum of its iou row.  If that iou > 0.6 (strict) and o is the smallest list position
+ *               among the rows that chose j this way, j takes o's colour and o leaves the list; every other live row loses one ttl and
+ *               stays iff ttl > 0 (also a row whose j went to an earlier row, whatever its second-best is).
+ *   colours     new instances without a colour take pool[counter % n_pool], counter += 1, in instance order; the counter lives on.
+ * Deviation, asked for by its own flag (demo --track-boxes) as the mask tracker is: as far as detectron2's source can be read without
+ * the package at hand, _assign_colors hands its XYXY rows to pycocotools' iou, which reads them as XYWH; here the IoU is the geometric
+ * one of the boxes.
+ * ttl 1..8, topk 1..100, at most 800 live rows.  boxes: device float [topk][4] XYXY as odise_hip_instance_boxes writes them.  inst_table
+ * NULL: n = topk and every class is 0; inst_scores NULL: no score test.  colors / edge_colors / live / n_live / iou as in
+ * odise_inst_track_desc; a live row carries id = table index, area = (int32) of its box's w * h (the double product, at most 2^31 - 1)
+ * and frame = frames since the reset.
+ * One launch of one block per frame, no pixel memory, no synchronisation.  The frame number lives on the device with the list, so -
+ * unlike odise_hip_inst_track_frame - the call can be replayed from a captured graph.  The same bytes from run to run.
+ * ODISE_ERR_ARG and nothing written: a null required pointer (track, boxes, colors), topk outside 1..100, ttl outside 1..8, n_pool
+ * outside 1..2^20, a descriptor whose topk is not the tracker's, a negative cap, live without n_live, a misaligned buffer.
+ * ODISE_ERR_NOMEM: the state could not be allocated. */
+typedef struct odise_box_track odise_box_track;
+int odise_hip_box_track_create(odise_hip_ctx* ctx, int topk, int ttl, const uint8_t* pool_rgb /* HOST [n_pool][3] */, int n_pool, odise_box_track** out);
+int odise_hip_box_track_reset(odise_hip_ctx* ctx, odise_box_track* track);     /* empties the live list, the counter and the frame number */
+int odise_hip_box_track_destroy(odise_hip_ctx* ctx, odise_box_track* track);   /* waits for the stream */
+typedef struct {
+    odise_box_track* track;
+    const float* boxes;             /* device [topk][4] XYXY */
+    const int32_t* inst_table;      /* device [1 + 2*topk]: n | query index | class  (n read on the device), optional */
+    const float* inst_scores;       /* device [topk], optional */
+    int topk;                       /* must be the tracker's */
+    float min_score;
+    uint8_t* colors;                /* device [topk][3], in/out */
+    uint8_t* edge_colors;           /* optional, device [topk][3], in/out */
+    odise_track_row* live;          /* optional, device [live_cap]: the live list AFTER the frame, in list order; nothing past live_cap rows */
+    int live_cap;
+    int32_t* n_live;                /* device [1], required with live: the length of the list (not clipped to live_cap) */
+    double* iou;                    /* optional, device [iou_cap][100]: iou[o * 100 + j] of live row o of the list BEFORE the frame and this
+                                       frame's instance j (its position among the instances); other cells are left alone */
+    int iou_cap;
+} odise_box_track_desc;
+int odise_hip_box_track_frame(odise_hip_ctx* ctx, const odise_box_track_desc* d);
 
 /* ---- test-time augmentation of the semantic head (Mask2Former SemanticSegmentorWithTTA: several short-edge sizes, each also mirrored,
  * sem_seg averaged at the original size) ------------------------------------------------------------------------------------------

@@ -26,6 +26,8 @@ int odise_hip_sizeof_inst_poly_gt(void);
 int odise_hip_sizeof_inst_accum_desc(void);
 int odise_hip_sizeof_inst_boxes_desc(void);
 int odise_hip_sizeof_inst_bbox_task(void);
+int odise_hip_sizeof_box_track_desc(void);
+int odise_hip_sizeof_inst_box_draw(void);
 
 /* odise_hip_gemm / odise_hip_conv2d with the tile shape and the split-K factor forced instead of chosen by the cost model
  * (tile ids: gemm.hip kTileBM / kTileBN; -1 / 0 = automatic) */

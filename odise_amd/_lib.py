@@ -168,6 +168,18 @@ class InstTrackDesc(C.Structure):
                 ("n_live", c_void_p), ("iou", c_void_p), ("iou_cap", c_int)]
 
 
+class BoxTrackDesc(C.Structure):
+    """odise_box_track_desc (include/odise_hip.h)."""
+    _fields_ = [("track", c_void_p), ("boxes", c_void_p), ("inst_table", c_void_p), ("inst_scores", c_void_p), ("topk", c_int),
+                ("min_score", c_float), ("colors", c_void_p), ("edge_colors", c_void_p), ("live", c_void_p), ("live_cap", c_int),
+                ("n_live", c_void_p), ("iou", c_void_p), ("iou_cap", c_int)]
+
+
+class InstBoxDraw(C.Structure):
+    """odise_inst_box_draw (include/odise_hip.h)."""
+    _fields_ = [("boxes", c_void_p), ("box_width", c_int), ("box_alpha256", c_int), ("small_area", c_int)]
+
+
 MAX_SEGMENTS = 100          # ODISE_MAX_SEGMENTS
 COMM_ID_BYTES = 128         # ODISE_COMM_ID_BYTES
 RECORD_TABLE_LEN = 1 + 3 * MAX_SEGMENTS   # the tail of a panoptic record: n | rows (id, isthing, category)

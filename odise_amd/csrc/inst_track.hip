@@ -151,8 +151,8 @@ __global__ void __launch_bounds__(kTrackMatchThreads) inst_track_match_kernel(in
         area[tid] = area_g[tid];
     }
     __syncthreads();   // also: n_live and the counter are read before anything is written
-    const TrackMatched m = track_match_block(n, tab, cat, area, st->live, nullptr, n_live, frame, counter, io,
-                                             [&](int o, const odise_track_row&, int, int j) { return inter[o * topk + j]; });
+    const TrackMatched m = track_match_block(n, tab, cat, area, area, st->live, nullptr, n_live, frame, counter, io, 0.5,
+                                             [&](int o, const odise_track_row& row, int, int j) { return track_count_iou(row.area, area[j], inter[o * topk + j]); });
     if (tid == 0) {
         st->n_live = m.total;
         st->counter = (counter + m.n_new) % io.n_pool;

@@ -209,10 +209,10 @@ __global__ void __launch_bounds__(kTrackMatchThreads) track_match_kernel(int* __
     __syncthreads();
     const TrackMatchIo io = {pool, n_pool, ttl, colors, nullptr, live_out, live_cap, n_live_out, iou_out, iou_cap};
     // the cell of live row (frame, table row aux) and new row j; a row whose frame has no matrix shares no pixel
-    const TrackMatched m = track_match_block(n, tab, cat, area, st->live, st->live_row, n_live, frame, counter, io,
+    const TrackMatched m = track_match_block(n, tab, cat, area, area, st->live, st->live_row, n_live, frame, counter, io, 0.5,
                                              [&](int, const odise_track_row& row, int aux, int j) {
                                                  const int k = L.pass_of[row.frame & (kTrackRing - 1)];
-                                                 return k < 0 ? 0 : matrix[L.off[k] + (aux + 1) * w + j + 1];
+                                                 return track_count_iou(row.area, area[j], k < 0 ? 0 : matrix[L.off[k] + (aux + 1) * w + j + 1]);
                                              });
     if (tid == 0) {
         st->n_live = m.total;

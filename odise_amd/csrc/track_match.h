@@ -1,7 +1,7 @@
-// track_match.h — what the two colour trackers share (track.hip: panoptic things, a byte map per retained frame; inst_track.hip: instance
-// masks, packed words per retained frame): the limits of the live list and the one-block match / colour / compact step of detectron2's
+// track_match.h — what the colour trackers share (track.hip: panoptic things, a byte map per retained frame; inst_track.hip: instance
+// masks, packed words per retained frame; box_track.hip: instance boxes, four floats per live row): the limits of the live list and the one-block match / colour / compact step of detectron2's
 // VideoVisualizer._assign_colors (the rule: include/odise_hip.h above odise_hip_track_frame; host restatement: odise_amd/video.py).
-// Where the intersections come from is the caller's business: it hands in a functor.
+// Where the IoU comes from is the caller's business: it hands in a functor.
 #pragma once
 #include "common.h"
 #include "rgb.h"
@@ -32,14 +32,19 @@ struct TrackMatchIo {
 };
 struct TrackMatched { int total, n_new; };   // rows of the list after the frame, instances that took a pool colour
 
-// One block of kTrackMatchThreads, all of it.  tab / cat / area [n] (LDS, complete and published by a barrier of the caller's): the id a
-// fresh row gets, the category, the pixels of table entry j - area 0 = no instance of this frame.  live / live_aux [kTrackLiveCap]: the
-// list before the frame -> after it (live_aux, optional: one int of the caller's per row, aux_new[j] for a fresh one).  n_live, frame and
-// counter were read by the caller before any barrier.  inter(o, row, aux, j) = common pixels of live row o and entry j; it is asked for
-// instances of the row's category only.  Returns the same to every thread; the caller stores the counts.
-template <class Inter>
-__device__ __forceinline__ TrackMatched track_match_block(int n, const int* tab, const int* cat, const int* area, odise_track_row* live, int* live_aux,
-                                                          int n_live, int frame, int counter, const TrackMatchIo& io, Inter inter) {
+// The IoU of two pixel counts and their common pixels, as the double division of the integers (the mask trackers)
+__device__ __forceinline__ double track_count_iou(int area_o, int area_j, int in) { return (double)in / (double)((int64_t)area_o + area_j - in); }
+
+// One block of kTrackMatchThreads, all of it.  tab / cat / inst / area [n] (LDS, complete and published by a barrier of the caller's): the
+// id a fresh row gets, the category, inst > 0 = entry j is an instance of this frame, and the area its row carries (the mask trackers
+// pass the pixels for both: area 0 = no instance).  live / live_aux [kTrackLiveCap]: the list before the frame -> after it (live_aux,
+// optional: one int of the caller's per row, j for a fresh one).  n_live, frame and counter were read by the caller before any barrier.
+// iou_of(o, row, aux, j) = the IoU (a double) of live row o and entry j; it is asked for instances of the row's category only.  A match
+// needs an IoU above `threshold` (strict).  Returns the same to every thread; the caller stores the counts.
+template <class Iou>
+__device__ __forceinline__ TrackMatched track_match_block(int n, const int* tab, const int* cat, const int* inst, const int* area, odise_track_row* live,
+                                                          int* live_aux, int n_live, int frame, int counter, const TrackMatchIo& io, double threshold,
+                                                          Iou iou_of) {
     __shared__ int rank[ODISE_MAX_SEGMENTS];      // position of an entry among the frame's instances, -1 = no instance
     __shared__ int winner[ODISE_MAX_SEGMENTS];    // smallest list position of the live rows that chose the instance
     __shared__ int urank[ODISE_MAX_SEGMENTS];     // position among the instances that take a new colour
@@ -50,7 +55,7 @@ __device__ __forceinline__ TrackMatched track_match_block(int n, const int* tab,
     if (tid < n) winner[tid] = INT32_MAX;
     if (tid == 0) {
         int c = 0;
-        for (int j = 0; j < n; ++j) rank[j] = area[j] > 0 ? c++ : -1;
+        for (int j = 0; j < n; ++j) rank[j] = inst[j] > 0 ? c++ : -1;
         n_inst = c;
     }
     __syncthreads();
@@ -65,14 +70,11 @@ __device__ __forceinline__ TrackMatched track_match_block(int n, const int* tab,
         for (int j = 0; j < n; ++j) {
             if (rank[j] < 0) continue;
             double iou = 0.0;
-            if (cat[j] == row.category) {
-                const int in = inter(tid, row, my_aux, j);
-                iou = (double)in / (double)((int64_t)row.area + area[j] - in);
-            }
+            if (cat[j] == row.category) iou = iou_of(tid, row, my_aux, j);
             if (io.iou_out && tid < io.iou_cap) io.iou_out[(int64_t)tid * ODISE_MAX_SEGMENTS + rank[j]] = iou;
             if (iou > best) { best = iou; choice = j; }
         }
-        if (best > 0.5) atomicMin(&winner[choice], tid);
+        if (best > threshold) atomicMin(&winner[choice], tid);
         else choice = -1;
     }
     __syncthreads();

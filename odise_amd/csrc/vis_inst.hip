@@ -19,6 +19,10 @@
 //                        and reads one conflict-free dword per mask, which it skips when its mask bits are zero.  A row of four pixels
 //                        travels as three dwords where its 12 bytes are 4-byte aligned in both pictures, byte by byte otherwise.
 //
+// With boxes (odise_hip_instance_draw_boxes: overlay_instances(boxes=, masks=)) inst_box_anchor_kernel stands in for inst_anchor_kernel
+// (kept also asks for a box with an area; the anchors are the box and its corner), inst_order_kernel<true> ranks by box area and
+// inst_overlay_kernel<true> lays the frame of a box before its mask.  The <false> forms are the kernels described above.
+//
 // The semantic record: a per-block LDS histogram of the labels (lds_hist.h; the arg-max of semantic_confusion_kernel for a score
 // tensor), the rank of every present class by counting, and one pass that turns labels into ids.
 #include <algorithm>
@@ -42,6 +46,10 @@ struct InstDrawState {
     int list[kInstMaxTopk];                // list[k] = the instance drawn k-th
     int n_kept;
     int pad[3];
+};
+struct InstBoxState {                      // odise_hip_instance_draw_boxes, by table index
+    float barea[kInstMaxTopk];             // (x1 - x0) * (y1 - y0) of a kept instance's box as the float product: the order key
+    int box[kInstMaxTopk][4];              // bx0, by0, bx1, by1: the box clipped to the picture, members truncated
 };
 
 __global__ void __launch_bounds__(kDrawThreads) inst_col_kernel(const unsigned long long* __restrict__ words, RleGrid G, const int* __restrict__ table,
@@ -107,16 +115,67 @@ __global__ void __launch_bounds__(64) inst_anchor_kernel(const int* __restrict__
     }
 }
 
-__global__ void __launch_bounds__(128) inst_order_kernel(InstDrawState* __restrict__ st, int topk, int* __restrict__ order) {
+// The box variant (odise_hip_instance_draw_boxes): a wave per table index.  kept = a candidate with a pixel AND a finite box of positive
+// width and height; its order key, its box clipped to the picture and - the box, not the mask median, decides where the label goes - its
+// anchor row (Visualizer.overlay_instances with boxes: the text at the box corner, moved for a small box).
+__device__ __forceinline__ int box_trunc(float v) { return (int)fminf(fmaxf(v, -536870912.f), 536870912.f); }   // toward zero, within +-2^29
+
+__global__ void __launch_bounds__(64) inst_box_anchor_kernel(const int* __restrict__ colhist, int H, int W, const int* __restrict__ table,
+                                                            const float* __restrict__ scores, int topk, float min_score,
+                                                            const float* __restrict__ boxes, int small_area, InstDrawState* __restrict__ st,
+                                                            InstBoxState* __restrict__ bs, odise_anchor_row* __restrict__ anchors) {
+    const int i = blockIdx.x, lane = threadIdx.x;
+    int N = 0;
+    if (inst_candidate(table, scores, topk, min_score, i)) {
+        const int* h = colhist + (int64_t)i * W;
+        for (int b0 = 0; b0 < W; b0 += 64) N += b0 + lane < W ? h[b0 + lane] : 0;
+        for (int d = 32; d; d >>= 1) N += __shfl_xor(N, d);
+    }
+    if (lane != 0) return;
+    const float x0 = boxes[4 * i], y0 = boxes[4 * i + 1], x1 = boxes[4 * i + 2], y1 = boxes[4 * i + 3];
+    const bool kept = N > 0 && isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1) && x1 > x0 && y1 > y0;
+    st->area[i] = kept ? N : 0;
+    if (!kept) {
+        bs->barea[i] = 0.f;
+        bs->box[i][0] = 0; bs->box[i][1] = 0; bs->box[i][2] = 0; bs->box[i][3] = 0;
+        if (anchors) anchors[i] = vis_anchor_row(-1, 0);
+        return;
+    }
+    const float ba = (x1 - x0) * (y1 - y0);
+    const int ix0 = box_trunc(x0), iy0 = box_trunc(y0), ix1 = box_trunc(x1), iy1 = box_trunc(y1);
+    bs->barea[i] = ba;
+    bs->box[i][0] = max(ix0, 0); bs->box[i][1] = max(iy0, 0); bs->box[i][2] = min(ix1, W); bs->box[i][3] = min(iy1, H);
+    if (!anchors) return;
+    int tx = ix0, ty = iy0;
+    if (ba < (float)small_area || y1 - y0 < 40.f) {
+        if (y1 >= (float)(H - 5)) tx = ix1;
+        else ty = iy1;
+    }
+    odise_anchor_row a;
+    a.segment_row = i; a.area = N; a.x2 = 2 * tx; a.y2 = 2 * ty; a.x0 = ix0; a.y0 = iy0; a.x1 = ix1; a.y1 = iy1;
+    anchors[i] = a;
+}
+
+// kBox: the order key is the box area (kept: area > 0), else the pixels
+template <bool kBox>
+__global__ void __launch_bounds__(128) inst_order_kernel(InstDrawState* __restrict__ st, const InstBoxState* __restrict__ bs, int topk,
+                                                        int* __restrict__ order) {
     __shared__ int a[kInstMaxTopk];
+    __shared__ float ba[kBox ? kInstMaxTopk : 1];
     const int t = threadIdx.x;
-    if (t < topk) a[t] = st->area[t];
+    if (t < topk) {
+        a[t] = st->area[t];
+        if (kBox) ba[t] = bs->barea[t];
+    }
     __syncthreads();
     if (t < topk) {
         int rank = -1;
         if (a[t] > 0) {
             rank = 0;
-            for (int j = 0; j < topk; ++j) rank += (a[j] > a[t] || (a[j] == a[t] && j < t)) ? 1 : 0;
+            for (int j = 0; j < topk; ++j) {
+                if (kBox) rank += (a[j] > 0 && (ba[j] > ba[t] || (ba[j] == ba[t] && j < t))) ? 1 : 0;
+                else rank += (a[j] > a[t] || (a[j] == a[t] && j < t)) ? 1 : 0;
+            }
             st->list[rank] = t;
         }
         if (order) order[t] = rank;
@@ -129,12 +188,19 @@ __global__ void __launch_bounds__(128) inst_order_kernel(InstDrawState* __restri
 }
 
 // image == out is safe: a thread reads its own 16 pixels before it writes them and no other thread reads them.
+// kBox (odise_hip_instance_draw_boxes): before the mask step of instance i its rectangle frame - the pixels of the clipped box bs->box[i]
+// within box_width of one of its four sides - is blended with colors[i] at box_alpha.  The bounds of a chunk's boxes lie in LDS (every
+// thread reads the same dword: a broadcast); a thread whose 4 x 4 pixels miss the box, or lie in its interior, makes four compares.
+template <bool kBox>
 __global__ void __launch_bounds__(kDrawThreads) inst_overlay_kernel(const unsigned long long* __restrict__ words, RleGrid G, int ntx,
                                                                    const InstDrawState* __restrict__ st, const uint8_t* image,
                                                                    const uint8_t* __restrict__ colors, const uint8_t* __restrict__ edge_colors,
-                                                                   int alpha, uint8_t* out) {
+                                                                   int alpha, uint8_t* out, const InstBoxState* __restrict__ bs, int box_width,
+                                                                   int box_alpha) {
     __shared__ unsigned sl[kDrawChunk * kDrawStride];
     __shared__ unsigned s_crb[kDrawChunk], s_cg[kDrawChunk], s_edge[kDrawChunk];
+    __shared__ int s_box[kBox ? kDrawChunk : 1][4];
+    __shared__ unsigned s_brb[kBox ? kDrawChunk : 1], s_bg[kBox ? kDrawChunk : 1];
     const int t = threadIdx.x, H = G.h, W = G.w;
     const int r = blockIdx.x / ntx, x0 = (blockIdx.x - r * ntx) * 64;
     const int xq = t & 15, rg = t >> 4;
@@ -170,6 +236,11 @@ __global__ void __launch_bounds__(kDrawThreads) inst_overlay_kernel(const unsign
             const int i = st->list[k0 + t];
             blend_color(rgb_load(colors + 3 * i), (unsigned)alpha, s_crb[t], s_cg[t]);
             s_edge[t] = rgb_load(edge_colors + 3 * i);
+            if (kBox) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) s_box[t][c] = bs->box[i][c];
+                blend_color(rgb_load(colors + 3 * i), (unsigned)box_alpha, s_brb[t], s_bg[t]);
+            }
         }
         for (int it = t; it < nk * 16; it += kDrawThreads) {                // item = (mask k, four columns q)
             const int k = it >> 4, q = it & 15, xa = x0 + 4 * q;
@@ -207,6 +278,23 @@ __global__ void __launch_bounds__(kDrawThreads) inst_overlay_kernel(const unsign
         }
         __syncthreads();
         for (int k = 0; k < nk; ++k) {
+            if (kBox) {                                                     // the frame first; a tile no mask touches may still hold one
+                const int bx0 = s_box[k][0], by0 = s_box[k][1], bx1 = s_box[k][2], by1 = s_box[k][3];
+                const bool touches = px_x < bx1 && px_x + 4 > bx0 && px_y < by1 && px_y + 4 > by0;
+                const bool interior = px_x >= bx0 + box_width && px_x + 4 <= bx1 - box_width && px_y >= by0 + box_width && px_y + 4 <= by1 - box_width;
+                if (touches && !interior) {
+                    const unsigned brb = s_brb[k], bg = s_bg[k], iab = (unsigned)(256 - box_alpha);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) {
+                            const int x = px_x + c, y = px_y + j;
+                            const bool in = x >= bx0 && x < bx1 && y >= by0 && y < by1;
+                            const bool side = x < bx0 + box_width || x >= bx1 - box_width || y < by0 + box_width || y >= by1 - box_width;
+                            if (in && side) px[j][c] = blend_rgb(px[j][c], iab, brb, bg);
+                        }
+                }
+            }
             const unsigned s = sl[k * kDrawStride + t];                     // t = rg * 16 + xq
             if ((s & 0xffffu) == 0u) continue;
             const unsigned crb = s_crb[k], cg = s_cg[k], edge = s_edge[k];
@@ -293,54 +381,87 @@ __global__ void __launch_bounds__(256) sem_ids_kernel(const int* __restrict__ la
 
 using namespace odise;
 
-extern "C" int odise_hip_instance_draw(odise_hip_ctx* ctx, const odise_inst_draw_desc* d) {
-    ODISE_REQUIRE(ctx && d, "instance_draw: null argument");
+// odise_hip_instance_draw (bx == nullptr) and odise_hip_instance_draw_boxes: one pack, the column (and row) histograms, kept / anchors /
+// order by the masks alone or with the boxes, the picture
+static int inst_draw(odise_hip_ctx* ctx, const char* what, const odise_inst_draw_desc* d, const odise_inst_box_draw* bx) {
     const InstSource src = inst_source(*d);
-    ODISE_TRY(inst_source_check("instance_draw", src, false, kVisMaxPixels));
-    ODISE_REQUIRE(!d->out || (d->image && d->colors && d->edge_colors), "instance_draw: an output picture needs image, colors and edge_colors");
-    ODISE_REQUIRE(d->out || d->anchors || d->order, "instance_draw: no output");
-    ODISE_REQUIRE(d->alpha256 >= 0 && d->alpha256 <= 256, "instance_draw: alpha256 %d outside 0..256", d->alpha256);
-    ODISE_REQUIRE((((uintptr_t)d->anchors | (uintptr_t)d->order) & 3) == 0, "instance_draw: anchors / order must be 4-byte aligned");
+    ODISE_TRY(inst_source_check(what, src, false, kVisMaxPixels));
+    ODISE_REQUIRE(!d->out || (d->image && d->colors && d->edge_colors), "%s: an output picture needs image, colors and edge_colors", what);
+    ODISE_REQUIRE(d->out || d->anchors || d->order, "%s: no output", what);
+    ODISE_REQUIRE(d->alpha256 >= 0 && d->alpha256 <= 256, "%s: alpha256 %d outside 0..256", what, d->alpha256);
+    ODISE_REQUIRE((((uintptr_t)d->anchors | (uintptr_t)d->order) & 3) == 0, "%s: anchors / order must be 4-byte aligned", what);
+    if (bx) {
+        ODISE_REQUIRE(bx->boxes && ((uintptr_t)bx->boxes & 3) == 0, "%s: boxes must be a 4-byte aligned device pointer", what);
+        ODISE_REQUIRE(bx->box_width >= 1, "%s: box_width %d below 1", what, bx->box_width);
+        ODISE_REQUIRE(bx->box_alpha256 >= 0 && bx->box_alpha256 <= 256, "%s: box_alpha256 %d outside 0..256", what, bx->box_alpha256);
+    }
     const int H = d->h, W = d->w, topk = d->topk;
     if (d->out && d->out != d->image) {
         const uintptr_t a = (uintptr_t)d->image, b = (uintptr_t)d->out, nb = (uintptr_t)3 * H * W;
-        ODISE_REQUIRE(a + nb <= b || b + nb <= a, "instance_draw: out overlaps image without being equal to it");
+        ODISE_REQUIRE(a + nb <= b || b + nb <= a, "%s: out overlaps image without being equal to it", what);
     }
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
     InstGeom ig;
-    ODISE_TRY(inst_geom(ctx, "instance_draw", src, &ig));
+    ODISE_TRY(inst_geom(ctx, what, src, &ig));
     const RleGrid G = rle_grid(H, W);
-    const size_t col_b = (size_t)round_up((int64_t)topk * W * 4, 16), row_b = d->anchors ? (size_t)round_up((int64_t)topk * H * 4, 16) : 0;
+    const bool rows_wanted = d->anchors && !bx;   // with boxes the anchors come from the boxes
+    const size_t col_b = (size_t)round_up((int64_t)topk * W * 4, 16), row_b = rows_wanted ? (size_t)round_up((int64_t)topk * H * 4, 16) : 0;
+    const size_t box_b = bx ? sizeof(InstBoxState) : 0;
     RleScratch s;
-    ODISE_TRY(rle_scratch(ctx, topk, G, &s, sizeof(InstDrawState) + col_b + row_b));
+    ODISE_TRY(rle_scratch(ctx, topk, G, &s, sizeof(InstDrawState) + box_b + col_b + row_b));
     InstDrawState* st = (InstDrawState*)s.extra;
-    int* colhist = (int*)((char*)s.extra + sizeof(InstDrawState));
+    InstBoxState* bs = (InstBoxState*)((char*)s.extra + sizeof(InstDrawState));
+    int* colhist = (int*)((char*)bs + box_b);
     int* rowhist = (int*)((char*)colhist + col_b);
     const int* table = src.inst_table;
     ODISE_TRY(inst_pack(ctx, src, ig, G, s.words));
     hipLaunchKernelGGL(inst_col_kernel, dim3((unsigned)ceil_div(W, kDrawThreads), (unsigned)topk), dim3(kDrawThreads), 0, ctx->stream,
                        (const unsigned long long*)s.words, G, table, topk, colhist);
     ODISE_CHECK_HIP(hipGetLastError());
-    if (d->anchors) {
+    if (rows_wanted) {
         hipLaunchKernelGGL(inst_row_kernel, dim3((unsigned)G.R, (unsigned)topk), dim3(64), 0, ctx->stream, (const unsigned long long*)s.words, G, table,
                            topk, rowhist);
         ODISE_CHECK_HIP(hipGetLastError());
     }
-    const int axes = d->anchors ? 2 : 1;
-    hipLaunchKernelGGL(inst_anchor_kernel, dim3((unsigned)(axes * topk)), dim3(64), 0, ctx->stream, (const int*)colhist, (const int*)rowhist, H, W, table,
-                       d->inst_scores, topk, d->min_score, axes, st, d->anchors);
+    if (bx) {
+        hipLaunchKernelGGL(inst_box_anchor_kernel, dim3((unsigned)topk), dim3(64), 0, ctx->stream, (const int*)colhist, H, W, table, d->inst_scores, topk,
+                           d->min_score, bx->boxes, bx->small_area, st, bs, d->anchors);
+    } else {
+        const int axes = d->anchors ? 2 : 1;
+        hipLaunchKernelGGL(inst_anchor_kernel, dim3((unsigned)(axes * topk)), dim3(64), 0, ctx->stream, (const int*)colhist, (const int*)rowhist, H, W, table,
+                           d->inst_scores, topk, d->min_score, axes, st, d->anchors);
+    }
     ODISE_CHECK_HIP(hipGetLastError());
     if (d->order || d->out) {
-        hipLaunchKernelGGL(inst_order_kernel, dim3(1), dim3(128), 0, ctx->stream, st, topk, (int*)d->order);
+        if (bx) hipLaunchKernelGGL(inst_order_kernel<true>, dim3(1), dim3(128), 0, ctx->stream, st, (const InstBoxState*)bs, topk, (int*)d->order);
+        else hipLaunchKernelGGL(inst_order_kernel<false>, dim3(1), dim3(128), 0, ctx->stream, st, (const InstBoxState*)nullptr, topk, (int*)d->order);
         ODISE_CHECK_HIP(hipGetLastError());
     }
     if (d->out) {
         const int ntx = (int)ceil_div(W, 64);
-        hipLaunchKernelGGL(inst_overlay_kernel, dim3((unsigned)((int64_t)ntx * G.R)), dim3(kDrawThreads), 0, ctx->stream,
-                           (const unsigned long long*)s.words, G, ntx, (const InstDrawState*)st, d->image, d->colors, d->edge_colors, d->alpha256, d->out);
+        const dim3 grid((unsigned)((int64_t)ntx * G.R));
+        if (bx)   // a width beyond the picture draws what the picture's longer side draws
+            hipLaunchKernelGGL(inst_overlay_kernel<true>, grid, dim3(kDrawThreads), 0, ctx->stream, (const unsigned long long*)s.words, G, ntx,
+                               (const InstDrawState*)st, d->image, d->colors, d->edge_colors, d->alpha256, d->out, (const InstBoxState*)bs,
+                               std::min(bx->box_width, std::max(H, W)), bx->box_alpha256);
+        else
+            hipLaunchKernelGGL(inst_overlay_kernel<false>, grid, dim3(kDrawThreads), 0, ctx->stream, (const unsigned long long*)s.words, G, ntx,
+                               (const InstDrawState*)st, d->image, d->colors, d->edge_colors, d->alpha256, d->out, (const InstBoxState*)nullptr, 0, 0);
         ODISE_CHECK_HIP(hipGetLastError());
     }
     return ODISE_OK;
+}
+
+extern "C" int odise_hip_instance_draw(odise_hip_ctx* ctx, const odise_inst_draw_desc* d) {
+    ODISE_REQUIRE(ctx && d, "instance_draw: null argument");
+    return inst_draw(ctx, "instance_draw", d, nullptr);
+}
+
+extern "C" int odise_hip_sizeof_inst_box_draw(void) { return (int)sizeof(odise_inst_box_draw); }
+
+extern "C" int odise_hip_instance_draw_boxes(odise_hip_ctx* ctx, const odise_inst_draw_desc* d, const odise_inst_box_draw* bx) {
+    ODISE_REQUIRE(ctx && d && bx, "instance_draw_boxes: null argument");
+    return inst_draw(ctx, "instance_draw_boxes", d, bx);
 }
 
 extern "C" int odise_hip_semantic_record(odise_hip_ctx* ctx, const int32_t* labels, const float* sem_seg, int K, int H, int W, int32_t* record) {

@@ -43,6 +43,10 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     ap.add_argument("--ttl", type=int, default=8, help="--video-input: frames an unseen thing keeps its colour for (1..8)")
     ap.add_argument("--track-masks", action="store_true", help="--video-input --task instance: keep an instance's colour from frame to frame by "
                     "mask IoU (detectron2's rule for instances without a box; the reference's zero boxes track nothing)")
+    ap.add_argument("--track-boxes", action="store_true", help="--video-input --task instance: give the instances the boxes of their masks and keep "
+                    "an instance's colour from frame to frame by box IoU above 0.6 (detectron2's rule for instances with a box); implies --draw-boxes")
+    ap.add_argument("--draw-boxes", action="store_true", help="--task instance: give the instances the boxes of their masks and draw them as "
+                    "detectron2 draws instances with boxes (a frame per box, the order by box area, the label on the box corner)")
     ap.add_argument("--vocab", default="", help='extra classes, demo.py style: "black pickup truck, pickup truck; blue sky, sky"')
     ap.add_argument("--synthetic", action="store_true", help="random weights of the real shapes and seeded text banks: needs no checkpoint")
     ap.add_argument("--device", type=int, default=0)
@@ -70,7 +74,16 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
         ap.error("--track-masks without --video-input: single pictures have nothing to track")
     if args.track_masks and args.task != "instance":
         ap.error(f"--track-masks with --task {args.task}: mask tracking exists for the instance head only")
-    if args.video_input is not None and args.task == "instance" and not args.track_masks:
+    if args.track_boxes and args.video_input is None:
+        ap.error("--track-boxes without --video-input: single pictures have nothing to track")
+    if args.track_boxes and args.task != "instance":
+        ap.error(f"--track-boxes with --task {args.task}: box tracking exists for the instance head only")
+    if args.track_boxes and args.track_masks:
+        ap.error("--track-boxes with --track-masks: an instance is tracked by its box or by its mask, not both")
+    if args.draw_boxes and args.task != "instance":
+        ap.error(f"--draw-boxes with --task {args.task}: only the instances of the instance head carry boxes")
+    args.draw_boxes = args.draw_boxes or args.track_boxes
+    if args.video_input is not None and args.task == "instance" and not (args.track_masks or args.track_boxes):
         ap.error("--task instance with --video-input: the reference tracks pred_boxes there, which are all zeros on this model")
     if not 1 <= args.ttl <= 8:
         ap.error(f"--ttl {args.ttl} outside 1..8")
@@ -169,11 +182,14 @@ def frame_path(out_dir: str, index: int) -> str:
     return os.path.join(out_dir, "frame_%06d.png" % index)
 
 
-def run_on_video(ctx, model, visualizer, frames, task: str = "panoptic", confidence_threshold: float = 0.5):
+def run_on_video(ctx, model, visualizer, frames, task: str = "panoptic", confidence_threshold: float = 0.5, draw_boxes: bool = False,
+                 track_boxes: bool = False):
     """VisualizationDemo.run_on_video (demo.py:201-243): yields the drawn frames.  visualizer: a HipVideoVisualizer (panoptic: its
-    tracker colours the things; semantic: every frame on its own; instance: its mask tracker colours the instances).  A frame of another size than the first is refused by name."""
+    tracker colours the things; semantic: every frame on its own; instance: its mask tracker colours the instances, or with track_boxes its box tracker; draw_boxes: the instances carry and show the boxes of their masks).  A frame of another size than the first is refused by name."""
     size = None
     options = {"confidence_threshold": confidence_threshold} if task == "instance" else {}   # the only branch that reads it
+    if draw_boxes or track_boxes:
+        options.update(draw_boxes=True, track_boxes=track_boxes)
     for name, load in frames:
         image_dev = load(ctx)
         hw = tuple(image_dev.shape[:2])
@@ -184,7 +200,7 @@ def run_on_video(ctx, model, visualizer, frames, task: str = "panoptic", confide
 
 
 def run_on_image(ctx, model, visualizer, image_dev, task: str = "panoptic", confidence_threshold: float = 0.5,
-                 video: bool = False, tta=None) -> np.ndarray:
+                 video: bool = False, tta=None, draw_boxes: bool = False, track_boxes: bool = False) -> np.ndarray:
     """VisualizationDemo.run_on_image (demo.py:173-199) for a picture that is on the device; the result never leaves it before it is drawn."""
     from ._lib import record_len
     from .ingest import HipDatasetMapper
@@ -218,9 +234,10 @@ def run_on_image(ctx, model, visualizer, image_dev, task: str = "panoptic", conf
     if task == "instance":
         sel = inner.last_selection
         topk = sel["topk"]
+        boxes = dict(boxes=True, **({"track_boxes": track_boxes} if video else {})) if draw_boxes else {}
         picture = visualizer.draw_instance_predictions(picture, 0, sel["inst_table"].view((1 + 2 * topk,), np.int32),
                                                        sel["inst_scores"].view((topk,), np.float32), topk, sel["pad_hw"], sel["img_hw"][0],
-                                                       sel["out_hw"][0], min_score=confidence_threshold)
+                                                       sel["out_hw"][0], min_score=confidence_threshold, **boxes)
     return picture if isinstance(picture, np.ndarray) else picture.numpy()
 
 
@@ -234,7 +251,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     model, metadata = build_model(ctx, labels, num_things, args.synthetic, args.task)
     if args.video_input is not None:
         visualizer = HipVideoVisualizer(ctx, metadata, ttl=args.ttl)
-        drawn = run_on_video(ctx, model, visualizer, video_frames(args.video_input), args.task, args.confidence_threshold)
+        drawn = run_on_video(ctx, model, visualizer, video_frames(args.video_input), args.task, args.confidence_threshold, args.draw_boxes,
+                             args.track_boxes)
         if args.output.lower().endswith(".gif"):
             os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
             pictures = [Image.fromarray(p) for p in drawn]
@@ -257,7 +275,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         from .tta import HipSemanticTTA
         tta = HipSemanticTTA(model, args.tta, 2560, flip=not args.no_tta_flip)
     for file_name in args.input:
-        picture = run_on_image(ctx, model, visualizer, read_picture(ctx, file_name), args.task, args.confidence_threshold, tta=tta)
+        picture = run_on_image(ctx, model, visualizer, read_picture(ctx, file_name), args.task, args.confidence_threshold, tta=tta,
+                               draw_boxes=args.draw_boxes)
         Image.fromarray(picture).save(output_path(args.output, file_name))
         print(f"{file_name} -> {output_path(args.output, file_name)}")
     if tta is not None:

@@ -701,11 +701,61 @@ class Context:
         check(self.lib.odise_hip_inst_track_frame(self.h, C.byref(d)), "inst_track_frame")
         return colors
 
+    # ---- colours of instances that carry boxes across frames (odise_hip_box_track_*; host restatement: video.BoxColorTracker) -----------
+    def box_track_create(self, topk: int, ttl: int = 8, pool=None) -> "BoxTracker":
+        """A tracker for selections of `topk` instance boxes: pool uint8 [P,3] on the host (video.default_pool() when None).  It owns no
+        pixels: 800 live rows and their boxes."""
+        return BoxTracker(self, topk, ttl, pool)
+
+    def box_track_frame(self, tracker: "BoxTracker", boxes: DeviceArray, table_row=None, scores_row=None, min_score: float = 0.0,
+                        colors: Optional[DeviceArray] = None, edge_colors: Optional[DeviceArray] = None, live: Optional[DeviceArray] = None,
+                        n_live: Optional[DeviceArray] = None, iou: Optional[DeviceArray] = None, live_cap: Optional[int] = None,
+                        iou_cap: Optional[int] = None) -> DeviceArray:
+        """One frame, enqueued (one launch): boxes float32 [topk,4] XYXY on the device (as `instance_boxes` returns them), the selection
+        table_row [1 + 2 topk] / scores_row [topk] (both optional: every box counts, every class is 0, no score test).  colors /
+        edge_colors and the dumps as in `inst_track_frame`."""
+        from ._lib import MAX_SEGMENTS, BoxTrackDesc
+        from .video import TRACK_ROW_DTYPE
+        topk = tracker.topk
+        assert boxes.dtype == np.float32 and boxes.nbytes >= 16 * topk, (boxes.dtype, boxes.shape)
+        d = BoxTrackDesc()
+        d.track, d.boxes, d.inst_table, d.inst_scores, d.topk, d.min_score = tracker.handle, boxes.ptr, _ptr(table_row), _ptr(scores_row), topk, float(min_score)
+        if colors is None:
+            colors = self.zeros((topk, 3), np.uint8)
+        assert colors.dtype == np.uint8 and colors.nbytes >= 3 * topk, (colors.dtype, colors.shape)
+        d.colors = colors.ptr
+        if edge_colors is not None:
+            assert edge_colors.dtype == np.uint8 and edge_colors.nbytes >= 3 * topk, (edge_colors.dtype, edge_colors.shape)
+            d.edge_colors = edge_colors.ptr
+        if live is not None:
+            assert live.dtype == TRACK_ROW_DTYPE and (n_live is None or n_live.dtype == np.int32)
+            d.live, d.live_cap = live.ptr, live.shape[0] if live_cap is None else int(live_cap)
+            assert d.live_cap <= live.shape[0]
+        if n_live is not None:
+            d.n_live = n_live.ptr
+        if iou is not None:
+            assert iou.dtype == np.float64 and len(iou.shape) == 2 and iou.shape[1] == MAX_SEGMENTS, (iou.dtype, iou.shape)
+            d.iou, d.iou_cap = iou.ptr, iou.shape[0] if iou_cap is None else int(iou_cap)
+            assert d.iou_cap <= iou.shape[0]
+        check(self.lib.odise_hip_box_track_frame(self.h, C.byref(d)), "box_track_frame")
+        return colors
+
     # ---- drawing instance and semantic results (include/odise_hip.h odise_hip_instance_draw / odise_hip_semantic_record) ----------------
+    def instance_draw_boxes(self, out_hw, topk: int, boxes: DeviceArray, box_width: int = 1, box_alpha256: int = 128, small_area: int = 1000,
+                            **kw) -> dict:
+        """`instance_draw` for instances that carry boxes (odise_hip_instance_draw_boxes: overlay_instances(boxes=, masks=)): boxes
+        float32 [topk,4] XYXY on the device; a frame of box_width pixels per box, the draw order by box area, the anchors on the box
+        corners.  Every other argument and the result are `instance_draw`'s."""
+        from ._lib import InstBoxDraw
+        assert boxes.dtype == np.float32 and boxes.nbytes >= 16 * int(topk), (boxes.dtype, boxes.shape)
+        bx = InstBoxDraw()
+        bx.boxes, bx.box_width, bx.box_alpha256, bx.small_area = boxes.ptr, int(box_width), int(box_alpha256), int(small_area)
+        return self.instance_draw(out_hw, topk, _boxes=bx, **kw)
+
     def instance_draw(self, out_hw, topk: int, table_row=None, scores_row=None, masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0),
                       img_hw=(0, 0), min_score: float = 0.0, image: Optional[DeviceArray] = None, colors: Optional[DeviceArray] = None,
                       edge_colors: Optional[DeviceArray] = None, alpha256: int = 128, want=("out", "anchors", "order"), out=None, anchors=None,
-                      order=None) -> dict:
+                      order=None, _boxes=None) -> dict:
         """Enqueue odise_hip_instance_draw.  Detections as in `instance_eval`: the selection table_row [1 + 2 topk] / scores_row [topk]
         of image b of the last head forward, or dense `masks` [topk, h, w] (table_row / scores_row then optional).  `want` names the
         outputs; buffers given for them are used, others are allocated -> {"out": uint8 [h,w,3], "anchors": visualize.ANCHOR_DTYPE
@@ -727,7 +777,10 @@ class Context:
         if "order" in want:
             res["order"] = order if order is not None else self.empty((topk,), np.int32)
             d.order = res["order"].ptr
-        check(self.lib.odise_hip_instance_draw(self.h, C.byref(d)), "instance_draw")
+        if _boxes is not None:
+            check(self.lib.odise_hip_instance_draw_boxes(self.h, C.byref(d), C.byref(_boxes)), "instance_draw_boxes")
+        else:
+            check(self.lib.odise_hip_instance_draw(self.h, C.byref(d)), "instance_draw")
         return res
 
     def semantic_record(self, labels_or_sem_seg: DeviceArray, K: Optional[int] = None, out: Optional[DeviceArray] = None) -> DeviceArray:
@@ -1052,6 +1105,33 @@ class InstTracker:
     def close(self) -> None:
         if self.handle and self.ctx.h:
             self.ctx.lib.odise_hip_inst_track_destroy(self.ctx.h, C.c_void_p(self.handle))
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BoxTracker:
+    """odise_box_track (include/odise_hip.h): the library's tracker object for selections of `topk` instance boxes; `close()` (or
+    collection) releases it."""
+
+    def __init__(self, ctx: Context, topk: int, ttl: int = 8, pool=None):
+        from .video import default_pool
+        pool = default_pool() if pool is None else np.ascontiguousarray(np.asarray(pool, np.uint8).reshape(-1, 3))
+        self.ctx, self.topk, self.ttl, self.pool = ctx, int(topk), int(ttl), pool
+        h = C.c_void_p()
+        check(ctx.lib.odise_hip_box_track_create(ctx.h, self.topk, self.ttl, pool.ctypes.data_as(C.c_void_p), len(pool), C.byref(h)), "box_track_create")
+        self.handle = h.value
+
+    def reset(self) -> None:
+        check(self.ctx.lib.odise_hip_box_track_reset(self.ctx.h, C.c_void_p(self.handle)), "box_track_reset")
+
+    def close(self) -> None:
+        if self.handle and self.ctx.h:
+            self.ctx.lib.odise_hip_box_track_destroy(self.ctx.h, C.c_void_p(self.handle))
         self.handle = None
 
     def __del__(self):

@@ -179,6 +179,103 @@ def instance_overlay(image, masks, colors, edge_colors, alpha256: int = 128, sco
     return out.astype(np.uint8)
 
 
+# ---- the restatement: instances that carry boxes (odise_hip_instance_draw_boxes: overlay_instances(boxes=, masks=)) ----------------------
+BOX_ALPHA256 = 128
+
+
+def default_box_width(h: int, w: int) -> int:
+    """A quarter of detectron2's default font size max(sqrt(h * w) // 90, 10) - its box line width is font_size / 3, drawn by
+    matplotlib in points - rounded, at least one pixel."""
+    return max(1, round(max(float(np.sqrt(h * w)) // 90, 10) / 4))
+
+
+def _boxes32(boxes, n: int) -> np.ndarray:
+    return np.asarray(boxes, np.float32).reshape(-1, 4)[:n]
+
+
+def _box_trunc(v) -> int:
+    """A float member toward zero, within +-2^29 (what the device keeps of it)"""
+    return int(np.trunc(np.clip(np.float32(v), -536870912.0, 536870912.0)))
+
+
+def _box_area32(b) -> np.float32:
+    return np.float32(np.float32(b[2] - b[0]) * np.float32(b[3] - b[1]))      # the float product of the float differences
+
+
+def _kept_boxes(masks, boxes, scores, min_score) -> np.ndarray:
+    """`_kept`, and the box is finite with a positive width and height"""
+    kept = _kept(masks, scores, min_score)
+    for i, b in enumerate(_boxes32(boxes, len(kept))):
+        kept[i] &= bool(np.isfinite(b).all() and b[2] > b[0] and b[3] > b[1])
+    return kept
+
+
+def instance_order_boxes(masks, boxes, scores=None, min_score: float = 0.0, topk: Optional[int] = None) -> np.ndarray:
+    """int32 [topk]: the position of instance i in the draw order with boxes (descending BOX area as the float product, ties by
+    ascending index), -1 when it is not kept."""
+    masks = np.asarray(masks) != 0
+    topk = len(masks) if topk is None else int(topk)
+    kept, b = _kept_boxes(masks, boxes, scores, min_score), _boxes32(boxes, len(masks))
+    out = np.full(topk, -1, np.int32)
+    for rank, i in enumerate(sorted((i for i in range(len(masks)) if kept[i]), key=lambda i: (-float(_box_area32(b[i])), i))):
+        out[i] = rank
+    return out
+
+
+def instance_anchors_boxes(masks, boxes, scores=None, min_score: float = 0.0, topk: Optional[int] = None, small_area: int = SMALL_AREA) -> np.ndarray:
+    """ANCHOR_DTYPE [topk], one row per table index: (i, mask pixels, twice the label position, the box truncated to integers) of a kept
+    instance, (-1, 0, ..) otherwise and past n.  The label goes to the box corner (x0, y0); for a box below small_area or lower than 40
+    rows to (x1, y0) when the box reaches the last five rows of the picture, else to (x0, y1)."""
+    masks = np.asarray(masks) != 0
+    topk = len(masks) if topk is None else int(topk)
+    h = masks.shape[1] if masks.ndim == 3 else 0
+    kept, bb = _kept_boxes(masks, boxes, scores, min_score), _boxes32(boxes, len(masks))
+    out = np.zeros(topk, ANCHOR_DTYPE)
+    out["segment_row"] = -1
+    for i in range(len(masks)):
+        if not kept[i]:
+            continue
+        b = bb[i]
+        x0, y0, x1, y1 = (_box_trunc(v) for v in b)
+        tx, ty = x0, y0
+        if _box_area32(b) < np.float32(small_area) or np.float32(b[3] - b[1]) < np.float32(40):
+            if b[3] >= np.float32(h - 5):
+                tx = x1
+            else:
+                ty = y1
+        out[i] = (i, int(masks[i].sum()), 2 * tx, 2 * ty, x0, y0, x1, y1)
+    return out
+
+
+def instance_overlay_boxes(image, masks, boxes, colors, edge_colors, alpha256: int = 128, scores=None, min_score: float = 0.0, box_width: int = 1,
+                           box_alpha256: int = BOX_ALPHA256) -> np.ndarray:
+    """`instance_overlay` with boxes: the kept instances in box order; each first blends its frame - the pixels of its box (truncated,
+    clipped to the picture) within box_width of one of the four sides - with its colour at box_alpha256, then lays its mask."""
+    out = np.asarray(image, np.uint8).astype(np.int64)
+    H, W = out.shape[:2]
+    masks = np.asarray(masks) != 0
+    colors, edge_colors = np.asarray(colors, np.int64).reshape(-1, 3), np.asarray(edge_colors, np.int64).reshape(-1, 3)
+    assert 0 <= alpha256 <= 256 and 0 <= box_alpha256 <= 256 and box_width >= 1
+    order, bb = instance_order_boxes(masks, boxes, scores, min_score), _boxes32(boxes, len(masks))
+    ys, xs = np.mgrid[0:H, 0:W]
+    for i in sorted((i for i in range(len(masks)) if order[i] >= 0), key=lambda i: order[i]):
+        x0, y0, x1, y1 = (_box_trunc(v) for v in bb[i])
+        x0, y0, x1, y1 = max(x0, 0), max(y0, 0), min(x1, W), min(y1, H)
+        inside = (xs >= x0) & (xs < x1) & (ys >= y0) & (ys < y1)
+        side = (xs < x0 + box_width) | (xs >= x1 - box_width) | (ys < y0 + box_width) | (ys >= y1 - box_width)
+        out = np.where((inside & side)[..., None], (out * (256 - box_alpha256) + colors[i] * box_alpha256 + 128) >> 8, out)
+        m = masks[i]
+        edge = np.zeros(m.shape, bool)
+        edge[:, 1:] |= ~m[:, :-1]
+        edge[:, :-1] |= ~m[:, 1:]
+        edge[1:, :] |= ~m[:-1, :]
+        edge[:-1, :] |= ~m[1:, :]
+        blend = (out * (256 - alpha256) + colors[i] * alpha256 + 128) >> 8
+        out = np.where((m & ~edge)[..., None], blend, out)
+        out = np.where((m & edge)[..., None], edge_colors[i], out)
+    return out.astype(np.uint8)
+
+
 def semantic_record(labels, K: int, max_segments: Optional[int] = None) -> np.ndarray:
     """labels int [H,W] -> int32 [H*W + 1 + 3*MAX_SEGMENTS]: ids | n | rows (id, 0, category), id = category + 1, rows by descending
     pixel count (ties: the smaller category), at most MAX_SEGMENTS of them; a label outside [0, K) or without a row has id 0."""
@@ -310,12 +407,21 @@ def draw_sem_seg(image, labels_or_sem_seg, K: int, metadata=None, alpha256: int 
                              small_area, large_area)
 
 
-def draw_instance_predictions(image, masks, classes, scores, metadata=None, alpha256: int = 128, min_score: float = 0.0) -> np.ndarray:
-    """The host twin of HipVisualizer.draw_instance_predictions: masks [n,H,W], classes / scores [n]."""
+def draw_instance_predictions(image, masks, classes, scores, metadata=None, alpha256: int = 128, min_score: float = 0.0, boxes=None,
+                              box_width: Optional[int] = None, box_alpha256: int = BOX_ALPHA256) -> np.ndarray:
+    """The host twin of HipVisualizer.draw_instance_predictions: masks [n,H,W], classes / scores [n]; boxes float32 [n,4] XYXY (None:
+    the instances carry none) are drawn as frames, order the instances and anchor the texts."""
     colors = instance_colors(classes, metadata)
-    pic = instance_overlay(image, masks, colors, instance_edge_colors(colors), alpha256, scores, min_score)
-    anchors = instance_anchors(masks, scores, min_score)
-    order = instance_order(masks, scores, min_score)
+    if boxes is not None:
+        h, w = np.asarray(image).shape[:2]
+        bw = default_box_width(h, w) if box_width is None else int(box_width)
+        pic = instance_overlay_boxes(image, masks, boxes, colors, instance_edge_colors(colors), alpha256, scores, min_score, bw, box_alpha256)
+        anchors = instance_anchors_boxes(masks, boxes, scores, min_score)
+        order = instance_order_boxes(masks, boxes, scores, min_score)
+    else:
+        pic = instance_overlay(image, masks, colors, instance_edge_colors(colors), alpha256, scores, min_score)
+        anchors = instance_anchors(masks, scores, min_score)
+        order = instance_order(masks, scores, min_score)
     kept = sorted((i for i in range(len(anchors)) if order[i] >= 0), key=lambda i: order[i])
     return draw_texts(pic, anchors[kept], instance_texts(classes, scores, metadata))
 
@@ -356,19 +462,31 @@ class HipVisualizer:
         h, w = labels_or_sem_seg.shape[-2:]
         return self.draw_panoptic_seg(image_dev, self.ctx.semantic_record(labels_or_sem_seg, K), (h, w))
 
-    def draw_instance_predictions(self, image_dev, b, table_row, scores_row, topk, pad_hw, img_hw, out_hw, min_score: float = 0.0) -> np.ndarray:
+    def _instance_draw(self, out_hw, topk, boxes: bool, box_width, box_alpha256, **kw) -> dict:
+        """ctx.instance_draw, or with boxes: odise_hip_instance_boxes of the same selection, then ctx.instance_draw_boxes (nothing is
+        read back between them)."""
+        if not boxes:
+            return self.ctx.instance_draw(out_hw, topk, **kw)
+        bx = self.ctx.instance_boxes(out_hw, topk, kw.get("table_row"), b=kw.get("b", 0), pad_hw=kw.get("pad_hw", (0, 0)), img_hw=kw.get("img_hw", (0, 0)))
+        bw = default_box_width(int(out_hw[0]), int(out_hw[1])) if box_width is None else int(box_width)
+        return self.ctx.instance_draw_boxes(out_hw, topk, bx, bw, box_alpha256, self.small_area, **kw)
+
+    def draw_instance_predictions(self, image_dev, b, table_row, scores_row, topk, pad_hw, img_hw, out_hw, min_score: float = 0.0,
+                                  boxes: bool = False, box_width: Optional[int] = None, box_alpha256: int = BOX_ALPHA256) -> np.ndarray:
         """`draw_instance_predictions(predictions["instances"])` for the selection of image b of the last head forward, as it lies on the
         device (table_row int32 [1 + 2 topk], scores_row float32 [topk]) -> host uint8 [h,w,3].  The table and the scores travel first
         (their classes choose colours and texts), the masks never do: overlay, anchors and order on the device, one read-back, then
-        "<class> <score>%" at the anchors, in draw order."""
+        "<class> <score>%" at the anchors, in draw order.  boxes=True: the instances carry the boxes of their masks
+        (odise_hip_instance_boxes) and are drawn as detectron2 draws instances with boxes (odise_hip_instance_draw_boxes)."""
         ctx, topk = self.ctx, int(topk)
         table, scores = table_row.numpy().reshape(-1), scores_row.numpy().reshape(-1)
         n = min(max(int(table[0]), 0), topk)
         classes = table[1 + topk:1 + topk + n]
         colors = np.zeros((topk, 3), np.uint8)
         colors[:n] = instance_colors(classes, self.metadata)
-        res = ctx.instance_draw(out_hw, topk, table_row, scores_row, b=b, pad_hw=pad_hw, img_hw=img_hw, min_score=min_score, image=image_dev,
-                                colors=ctx.to_device(colors), edge_colors=ctx.to_device(instance_edge_colors(colors)), alpha256=self.alpha256)
+        res = self._instance_draw(out_hw, topk, boxes, box_width, box_alpha256, table_row=table_row, scores_row=scores_row, b=b, pad_hw=pad_hw,
+                                  img_hw=img_hw, min_score=min_score, image=image_dev, colors=ctx.to_device(colors),
+                                  edge_colors=ctx.to_device(instance_edge_colors(colors)), alpha256=self.alpha256)
         picture, anchors, order = res["out"].numpy(), res["anchors"].numpy(), res["order"].numpy()
         kept = sorted((i for i in range(n) if order[i] >= 0), key=lambda i: order[i])
         return draw_texts(picture, anchors[kept], instance_texts(classes, scores[:n], self.metadata))
@@ -383,26 +501,58 @@ class HipVideoVisualizer(HipVisualizer):
 
     def __init__(self, ctx, metadata=None, ttl: int = 8, pool=None, **kwargs):
         super().__init__(ctx, metadata, **kwargs)
-        self.ttl, self.pool, self.tracker, self.inst_tracker = int(ttl), pool, None, None
+        self.ttl, self.pool, self.tracker, self.inst_tracker, self.box_tracker = int(ttl), pool, None, None, None
 
     def reset(self) -> None:
-        for t in (self.tracker, self.inst_tracker):
+        for t in (self.tracker, self.inst_tracker, self.box_tracker):
             if t is not None:
                 t.reset()
 
     def close(self) -> None:
-        for t in (self.tracker, self.inst_tracker):
+        for t in (self.tracker, self.inst_tracker, self.box_tracker):
             if t is not None:
                 t.close()
-        self.tracker, self.inst_tracker = None, None
+        self.tracker, self.inst_tracker, self.box_tracker = None, None, None
+
+    def _draw_tracked_boxes(self, frame_dev, b, table_row, scores_row, topk, pad_hw, img_hw, hw, min_score, labels, box_width, box_alpha256):
+        """Per frame on the device, nothing read back in between: odise_hip_instance_boxes, the box tracker, odise_hip_instance_draw_boxes"""
+        ctx = self.ctx
+        if self.box_tracker is None:
+            self.box_tracker = ctx.box_track_create(topk, self.ttl, self.pool)
+        if self.box_tracker.topk != topk:
+            raise ValueError(f"a frame of {topk} instances for a tracker of {self.box_tracker.topk}")
+        table, scores = table_row.numpy().reshape(-1), scores_row.numpy().reshape(-1)
+        n = min(max(int(table[0]), 0), topk)
+        classes = table[1 + topk:1 + topk + n]
+        host_colors = np.zeros((topk, 3), np.uint8)
+        host_colors[:n] = instance_colors(classes, self.metadata)
+        colors, edges = ctx.to_device(host_colors), ctx.to_device(instance_edge_colors(host_colors))
+        bx = ctx.instance_boxes(hw, topk, table_row, b=b, pad_hw=pad_hw, img_hw=img_hw)
+        ctx.box_track_frame(self.box_tracker, bx, table_row, scores_row, min_score, colors, edges)
+        bw = default_box_width(*hw) if box_width is None else int(box_width)
+        want = ("out", "anchors", "order") if labels else ("out",)
+        res = ctx.instance_draw_boxes(hw, topk, bx, bw, box_alpha256, self.small_area, table_row=table_row, scores_row=scores_row, b=b, pad_hw=pad_hw,
+                                      img_hw=img_hw, min_score=min_score, image=frame_dev, colors=colors, edge_colors=edges, alpha256=self.alpha256,
+                                      want=want)
+        if not labels:
+            return res["out"].numpy()
+        picture, anchors, order = res["out"].numpy(), res["anchors"].numpy(), res["order"].numpy()
+        kept = sorted((i for i in range(n) if order[i] >= 0), key=lambda i: order[i])
+        return draw_texts(picture, anchors[kept], instance_texts(classes, scores[:n], self.metadata))
 
     def draw_instance_predictions(self, frame_dev, b, table_row, scores_row, topk, pad_hw, img_hw, out_hw, min_score: float = 0.0,
-                                  labels: bool = True) -> np.ndarray:
+                                  labels: bool = True, boxes: bool = False, box_width: Optional[int] = None,
+                                  box_alpha256: int = BOX_ALPHA256, track_boxes: Optional[bool] = None) -> np.ndarray:
         """HipVisualizer.draw_instance_predictions with the colours of the library's instance tracker: the fill and outline colours of the
         frame's instances are written on the device and drawn from there; the masks never travel (labels=False: the picture before the
-        texts are drawn).  The tracker is made at the first frame, for its size and its topk; another size or topk is an error."""
+        texts are drawn).  The tracker is made at the first frame, for its size and its topk; another size or topk is an error.
+        boxes=True: the instances carry the boxes of their masks, the colours come from the BOX tracker (odise_hip_box_track_frame: box
+        IoU above 0.6, detectron2's first path; no pixels are retained) and the boxes are drawn.  track_boxes=False with boxes=True
+        draws the boxes and keeps the colours of the mask tracker."""
         ctx, topk = self.ctx, int(topk)
         h, w = int(out_hw[0]), int(out_hw[1])
+        if boxes and (track_boxes is None or track_boxes):
+            return self._draw_tracked_boxes(frame_dev, b, table_row, scores_row, topk, pad_hw, img_hw, (h, w), min_score, labels, box_width, box_alpha256)
         if self.inst_tracker is None:
             self.inst_tracker = ctx.inst_track_create((h, w), topk, self.ttl, self.pool)
         if self.inst_tracker.hw != (h, w) or self.inst_tracker.topk != topk:
@@ -417,8 +567,8 @@ class HipVideoVisualizer(HipVisualizer):
         ctx.inst_track_frame(self.inst_tracker, table_row, scores_row, b=b, pad_hw=pad_hw, img_hw=img_hw, min_score=min_score, colors=colors,
                              edge_colors=edges)
         want = ("out", "anchors", "order") if labels else ("out",)
-        res = ctx.instance_draw((h, w), topk, table_row, scores_row, b=b, pad_hw=pad_hw, img_hw=img_hw, min_score=min_score, image=frame_dev,
-                                colors=colors, edge_colors=edges, alpha256=self.alpha256, want=want)
+        res = self._instance_draw((h, w), topk, boxes, box_width, box_alpha256, table_row=table_row, scores_row=scores_row, b=b, pad_hw=pad_hw,
+                                  img_hw=img_hw, min_score=min_score, image=frame_dev, colors=colors, edge_colors=edges, alpha256=self.alpha256, want=want)
         if not labels:
             return res["out"].numpy()
         picture, anchors, order = res["out"].numpy(), res["anchors"].numpy(), res["order"].numpy()
