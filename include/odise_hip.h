@@ -606,6 +606,42 @@ typedef struct {
     float* boxes;                   /* device [topk][4] XYXY, optional */
 } odise_inst_bbox_task;
 int odise_hip_instance_eval_bbox(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p, const odise_inst_bbox_task* bb);
+/* The boundaries of n dense masks (layout / dtype as odise_hip_rle_encode): boundary = mask & ~erode(mask), the rule of Boundary IoU (Cheng
+ * et al., CVPR 2021) and of detectron2's _mask_to_boundary on a binary mask - erode is the (2 r + 1)^2 minimum that sees zeros outside the
+ * picture (r 3x3 erosions behind a ring of zeros); with 2 r + 1 > min(h, w) everything erodes and the boundary is the mask.  radius <= 0:
+ * r = odise_hip_boundary_radius(h, w).  boundary: device uint8 [n][h][w] of 0 / 1.  area: device int64 [n] (optional), the pixels of each
+ * boundary.  The masks are packed into 64-bit words, eroded there in O(log r) passes whatever the radius, and unpacked.  n == 0 writes
+ * nothing and succeeds.  h * w <= 2^30, n <= 65535.  Scratch comes from the context.  Asynchronous on the context's stream.
+ * The rule is restated from the paper and from _mask_to_boundary and pinned to the literal repeated erosion and to hand-worked pictures;
+ * parity with the published boundary-iou package is unpinned (no test compares against it). */
+int odise_hip_mask_boundary(odise_hip_ctx* ctx, const void* masks, int dtype, int n, int h, int w, int radius, uint8_t* boundary,
+                            int64_t* area);
+/* odise_hip_mask_iou with the Boundary IoU beside it: boundary_iou = rleIou on the exact pixel counts of the two boundaries
+ * (odise_hip_mask_boundary of the dense masks and of the decoded ground truth, same radius; inter == 0 -> 0, crowd -> inter / the area of
+ * the detection's boundary), mask_iou = what odise_hip_mask_iou writes, iou = fmin(mask_iou, boundary_iou), the IoU Boundary AP matches
+ * on.  iou: device double [n][n_gt]; mask_iou, boundary_iou: the same shape, optional.  inter, area_d, area_g: optional, the counts of the
+ * MASKS as in odise_hip_mask_iou.  Everything else - arguments, flag 1, the empty cases, limits - as odise_hip_mask_iou. */
+int odise_hip_mask_boundary_iou(odise_hip_ctx* ctx, const void* masks, int dtype, int n, int h, int w, const uint32_t* gt_runs,
+                                const int64_t* gt_offsets, int n_gt, const uint8_t* iscrowd, int radius, double* iou, double* mask_iou,
+                                double* boundary_iou, int32_t* inter, int64_t* area_d, int64_t* area_g, int32_t* flags);
+/* COCOeval.evaluateImg with the IoU of Boundary AP (LVIS' "boundary" iouType), beside "segm" and, with bb != NULL, "bbox", all from ONE
+ * pack of the detections and ONE decode of the ground truth.  The walk is the one of odise_hip_instance_eval over
+ * iou = fmin(mask IoU, boundary IoU) as odise_hip_mask_boundary_iou defines them; a boundary row's `area`, and with it the ignore rule of
+ * an unmatched detection, is the segm task's (the pixels of the mask, not of its boundary), and the ignore bits of the ground truth are
+ * d->gt_rows, as for the other tasks.  Detections past the count of the table are not read.
+ * bd == NULL is odise_hip_instance_eval_bbox (bb set) or odise_hip_instance_eval_poly (bb NULL).  With bd set, d->rows and d->n_rows may
+ * both be NULL: the segm rows are skipped then, but d->gt_runs / d->gt_offsets / p are still read, since the minimum needs the masks'
+ * counts.  Flags 1, 2, 4 and 8 zero the boundary rows (n_rows = 0) exactly as they zero the segm rows.
+ * ODISE_ERR_ARG and nothing written: a null bd->rows or bd->n_rows, and what odise_hip_instance_eval_bbox refuses (a null bb is no error
+ * here).  Scratch comes from the context: the words of the topk + n_gt masks three times over (masks, boundaries, one temporary).
+ * Asynchronous on the context's stream; no host synchronisation. */
+typedef struct {
+    int radius;                     /* <= 0: odise_hip_boundary_radius(d->h, d->w) */
+    odise_inst_eval_row* rows;      /* device [topk] */
+    int32_t* n_rows;                /* device [1] */
+} odise_inst_boundary_task;
+int odise_hip_instance_eval_boundary(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p, const odise_inst_bbox_task* bb,
+                                     const odise_inst_boundary_task* bd);
 /* COCOeval.accumulate for iouType "segm" on the rows of odise_hip_instance_eval as they lie on the device: maxDets (1, 10, 100), the four
  * area ranges, the ten IoU thresholds and the caller's table of recall thresholds; byte for byte what odise_amd/instance_eval.py
  * accumulate returns for the same rows.

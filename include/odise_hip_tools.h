@@ -26,6 +26,7 @@ int odise_hip_sizeof_inst_poly_gt(void);
 int odise_hip_sizeof_inst_accum_desc(void);
 int odise_hip_sizeof_inst_boxes_desc(void);
 int odise_hip_sizeof_inst_bbox_task(void);
+int odise_hip_sizeof_inst_boundary_task(void);
 int odise_hip_sizeof_box_track_desc(void);
 int odise_hip_sizeof_inst_box_draw(void);
 

@@ -128,6 +128,11 @@ class InstBboxTask(C.Structure):
     _fields_ = [("gt_boxes", c_void_p), ("rows", c_void_p), ("n_rows", c_void_p), ("boxes", c_void_p)]
 
 
+class InstBoundaryTask(C.Structure):
+    """odise_inst_boundary_task (include/odise_hip.h)."""
+    _fields_ = [("radius", c_int), ("rows", c_void_p), ("n_rows", c_void_p)]
+
+
 class InstAccumDesc(C.Structure):
     """odise_inst_accum_desc (include/odise_hip.h)."""
     _fields_ = [("n_blocks", c_int), ("rows", c_void_p), ("counts", c_void_p), ("slots", c_void_p), ("topk", c_int), ("num_categories", c_int),

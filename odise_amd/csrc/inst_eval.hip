@@ -25,8 +25,10 @@
 //               lane index.  Categories are independent, so the 16 waves of the block share the detections by category.  The matched /
 //               ignored words of a row are the ballots of the wave.
 // The walk is written once and takes its IoU as a template argument: SegmIou is steps 3 and 4, BoxIou (odise_hip_instance_eval_bbox, iouType
-// "bbox") is maskApi.c bbIou of the detections' boxes (inst_box.hip, from the words of step 1) against the annotations' boxes.  Both tasks of a
-// picture run behind ONE pack.
+// "bbox") is maskApi.c bbIou of the detections' boxes (inst_box.hip, from the words of step 1) against the annotations' boxes, BoundaryIou
+// (odise_hip_instance_eval_boundary, Boundary AP) is the minimum of SegmIou and of the same rleIou on the boundaries of both sides
+// (inst_boundary.hip, from the words of steps 1 and 2; step 3 runs once more on them).  All tasks of a picture run behind ONE pack and ONE
+// decode.
 #include "inst_words.h"
 
 namespace odise {
@@ -142,6 +144,12 @@ __global__ void __launch_bounds__(256) inst_area_kernel(const u64* __restrict__ 
     const long long s = block_popcount(words + (int64_t)blockIdx.x * nw, nw);
     if (threadIdx.x == 0) area[blockIdx.x] = s;
 }
+int inst_area_launch(odise_hip_ctx* ctx, const u64* words, int n, int64_t nw, long long* area) {
+    if (n <= 0) return ODISE_OK;
+    hipLaunchKernelGGL(inst_area_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, words, nw, area);
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}
 
 // ---- 4. iou (odise_hip_mask_iou) ----------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) inst_iou_kernel(const int* __restrict__ inter, const long long* __restrict__ area, int n, int n_gt,
@@ -153,6 +161,23 @@ __global__ void __launch_bounds__(256) inst_iou_kernel(const int* __restrict__ i
     const int in = inter[i];
     iou[i] = rle_iou(in, area[d], area[n + g], iscrowd && iscrowd[g] != 0);
     if (inter_out) inter_out[i] = in;
+    if (area_d && g == 0) area_d[d] = area[d];
+    if (area_g && d == 0) area_g[g] = area[n + g];
+}
+// odise_hip_mask_boundary_iou: the same on the boundaries' counts beside it, and the minimum of the two
+__global__ void __launch_bounds__(256) inst_biou_kernel(const int* __restrict__ inter, const long long* __restrict__ area, const int* __restrict__ inter_b,
+                                                       const long long* __restrict__ area_b, int n, int n_gt, const uint8_t* __restrict__ iscrowd,
+                                                       double* __restrict__ iou, double* __restrict__ mask_iou, double* __restrict__ boundary_iou,
+                                                       int* __restrict__ inter_out, long long* __restrict__ area_d, long long* __restrict__ area_g) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)n * n_gt) return;
+    const int d = (int)(i / n_gt), g = (int)(i - (int64_t)d * n_gt);
+    const bool crowd = iscrowd && iscrowd[g] != 0;
+    const double m = rle_iou(inter[i], area[d], area[n + g], crowd), b = rle_iou(inter_b[i], area_b[d], area_b[n + g], crowd);
+    iou[i] = fmin(m, b);
+    if (mask_iou) mask_iou[i] = m;
+    if (boundary_iou) boundary_iou[i] = b;
+    if (inter_out) inter_out[i] = inter[i];
     if (area_d && g == 0) area_d[d] = area[d];
     if (area_g && d == 0) area_g[g] = area[n + g];
 }
@@ -202,6 +227,17 @@ struct BoxIou {    // bbIou of the detection's box (XYXY integers, here as XYWH)
         const float* b = boxes + 4 * d;
         const double* g = gt_boxes + 4 * j;
         return bb_iou((double)b[0], (double)b[1], (double)(b[2] - b[0]), (double)(b[3] - b[1]), g[0], g[1], g[2], g[3], crowd);
+    }
+};
+struct BoundaryIou {   // Boundary AP's IoU: min(rleIou of the masks, rleIou of their boundaries); areas and flags are the segm task's
+    static constexpr int kStatusMask = ~0;
+    static constexpr bool kPublish = false;
+    SegmIou mask, bnd;           // the counts of the masks and of inst_boundary_words of them
+    __device__ int det_area(int i) const { return mask.det_area(i); }
+    __device__ int gt_area(int j) const { return mask.gt_area(j); }
+    __device__ int gt_check(int) const { return 0; }
+    __device__ double operator()(int d, int j, int ad, int ag, bool crowd) const {
+        return fmin(mask(d, j, ad, ag, crowd), bnd(d, j, bnd.det_area(d), bnd.gt_area(j), crowd));
     }
 };
 
@@ -321,13 +357,20 @@ struct InstScratch {
     size_t inter_bytes;
     u64* toggle;       // with polygon ground truth: the toggle planes of poly.hip, [n_gt] masks
     float* boxes;      // the bbox task without an output for them: [n][4]
+    // the boundary task: the boundaries of all n + n_gt masks (detections first, like the words they come from), the temporary of
+    // inst_boundary_words, their areas [n + n_gt] and intersections [n][n_gt]
+    u64 *bwords, *btmp;
+    long long* barea;
+    int* binter;
 };
-static int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, InstScratch* s, bool polygons = false, bool boxes = false) {
+static int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, InstScratch* s, bool polygons = false, bool boxes = false,
+                        bool boundary = false) {
     const size_t wb = (size_t)round_up((int64_t)(n + n_gt) * G.nw * 8, 256), ab = (size_t)round_up((int64_t)(n + n_gt) * 8, 256);
     s->inter_bytes = ((size_t)n * n_gt + 1) * sizeof(int);
     const size_t ib = (size_t)round_up((int64_t)s->inter_bytes, 256);
     const size_t bb = boxes ? (size_t)round_up((int64_t)n * 16, 256) : 0;
-    ODISE_TRY(scratch_reserve(ctx->rle, wb + ab + ib + bb + (polygons ? (size_t)n_gt * G.nw * 8 : 0), 8, drain_streams(ctx->stream), "rle"));
+    const size_t tb = polygons ? (size_t)round_up((int64_t)n_gt * G.nw * 8, 256) : 0;
+    ODISE_TRY(scratch_reserve(ctx->rle, wb + ab + ib + bb + tb + (boundary ? 2 * wb + ab + ib : 0), 8, drain_streams(ctx->stream), "rle"));
     char* p = (char*)ctx->rle.ptr;
     s->words_d = (u64*)p;
     s->words_g = s->words_d + (int64_t)n * G.nw;
@@ -335,7 +378,23 @@ static int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, I
     s->inter = (int*)(p + wb + ab);
     s->boxes = (float*)(p + wb + ab + ib);
     s->toggle = (u64*)(p + wb + ab + ib + bb);
+    char* q = p + wb + ab + ib + bb + tb;
+    s->bwords = (u64*)q;
+    s->btmp = (u64*)(q + wb);
+    s->barea = (long long*)(q + 2 * wb);
+    s->binter = (int*)(q + 2 * wb + ab);
     return ODISE_OK;
+}
+
+// stage 3 on words [n + n_gt][G.nw], detections first: inter [n][n_gt] (zeroed by the caller) and area [n + n_gt]
+static int inst_counts(odise_hip_ctx* ctx, const u64* words, const RleGrid& G, int n, int n_gt, int* inter, long long* area) {
+    if (n_gt) {
+        // split the word axis until the grid fills the chip about twice (at most 2 * cu_count ways: far below the grid's z limit)
+        const InterSplit sp = inst_inter_split(n, n_gt, G.nw, 2 * ctx->cu_count);
+        hipLaunchKernelGGL(inst_inter_kernel, sp.grid, dim3(256), 0, ctx->stream, words, words + (int64_t)n * G.nw, n, n_gt, G.nw, sp.per, inter);
+        ODISE_CHECK_HIP(hipGetLastError());
+    }
+    return inst_area_launch(ctx, words, n + n_gt, G.nw, area);
 }
 
 // stages 2 and 3 behind the packed detections: ground-truth words, inter, area; flag 1 (and 4, 8 of polygon ground truth) goes to `flag`
@@ -346,15 +405,16 @@ static int inst_overlaps(odise_hip_ctx* ctx, const InstScratch& s, const RleGrid
                            G, flag, p ? (const int*)p->gt_polys : nullptr);
         ODISE_CHECK_HIP(hipGetLastError());
         if (p) ODISE_TRY(poly_fill_words(ctx, p->xy, p->poly_offsets, p->gt_polys, n_gt, p->n_poly, G, s.words_g, s.toggle, false, gt_offsets, flag));
-        // split the word axis until the grid fills the chip about twice (at most 2 * cu_count ways: far below the grid's z limit)
-        const InterSplit sp = inst_inter_split(n, n_gt, G.nw, 2 * ctx->cu_count);
-        hipLaunchKernelGGL(inst_inter_kernel, sp.grid, dim3(256), 0, ctx->stream, (const u64*)s.words_d, (const u64*)s.words_g, n, n_gt, G.nw, sp.per,
-                           s.inter);
-        ODISE_CHECK_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(inst_area_kernel, dim3((unsigned)(n + n_gt)), dim3(256), 0, ctx->stream, (const u64*)s.words_d, G.nw, s.area);
-    ODISE_CHECK_HIP(hipGetLastError());
-    return ODISE_OK;
+    return inst_counts(ctx, s.words_d, G, n, n_gt, s.inter, s.area);
+}
+
+// the same counts of the boundaries of the words inst_overlaps left (binter is zeroed here).  The first n masks are the selection
+// inst_table (nullptr: all n): the logits pack leaves the words past its count unwritten, and their boundaries are zeros.
+static int inst_boundary_overlaps(odise_hip_ctx* ctx, const InstScratch& s, const RleGrid& G, int n, int n_gt, int radius, const int* inst_table) {
+    ODISE_CHECK_HIP(hipMemsetAsync(s.binter, 0, std::max<size_t>(1, (size_t)n * n_gt) * sizeof(int), ctx->stream));
+    ODISE_TRY(inst_boundary_words(ctx, s.words_d, n + n_gt, G, radius > 0 ? radius : odise_hip_boundary_radius(G.h, G.w), inst_table, n, s.bwords, s.btmp));
+    return inst_counts(ctx, s.bwords, G, n, n_gt, s.binter, s.barea);
 }
 
 }  // namespace odise
@@ -383,12 +443,40 @@ extern "C" int odise_hip_mask_iou(odise_hip_ctx* ctx, const void* masks, int dty
     return ODISE_OK;
 }
 
-// evaluateImg of one picture for "segm" (d->rows), "bbox" (bb), or both from one pack of the detections
-static int inst_eval_run(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p, const odise_inst_bbox_task* bb, bool want_bbox) {
+extern "C" int odise_hip_mask_boundary_iou(odise_hip_ctx* ctx, const void* masks, int dtype, int n, int h, int w, const uint32_t* gt_runs,
+                                           const int64_t* gt_offsets, int n_gt, const uint8_t* iscrowd, int radius, double* iou, double* mask_iou,
+                                           double* boundary_iou, int32_t* inter, int64_t* area_d, int64_t* area_g, int32_t* flags) {
+    ODISE_REQUIRE(ctx && flags, "mask_boundary_iou: null argument");
+    ODISE_REQUIRE(n >= 0 && n <= 65535 && n_gt >= 0 && n_gt <= 65535 && (int64_t)n * n_gt <= (1 << 26), "mask_boundary_iou: %d x %d masks out of range", n,
+                  n_gt);
+    ODISE_REQUIRE(h >= 1 && w >= 1 && (int64_t)h * w <= kRleMaxPixels, "mask_boundary_iou: mask size %dx%d out of range", h, w);
+    ODISE_REQUIRE(dtype == ODISE_F32 || dtype == ODISE_U8, "mask_boundary_iou: dtype %d (ODISE_F32 or ODISE_U8)", dtype);
+    if (n == 0 || n_gt == 0) return ODISE_OK;
+    ODISE_REQUIRE(masks && gt_runs && gt_offsets && iou, "mask_boundary_iou: null argument");
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    const RleGrid G = rle_grid(h, w);
+    InstScratch s;
+    ODISE_TRY(inst_scratch(ctx, n, n_gt, G, &s, false, false, true));
+    ODISE_CHECK_HIP(hipMemsetAsync(s.inter, 0, s.inter_bytes, ctx->stream));
+    ODISE_TRY(rle_pack_dense(ctx, masks, dtype, n, G, s.words_d));
+    ODISE_TRY(inst_overlaps(ctx, s, G, n, gt_runs, gt_offsets, n_gt, (int*)flags));
+    ODISE_TRY(inst_boundary_overlaps(ctx, s, G, n, n_gt, radius, nullptr));
+    hipLaunchKernelGGL(inst_biou_kernel, dim3((unsigned)ceil_div((int64_t)n * n_gt, 256)), dim3(256), 0, ctx->stream, (const int*)s.inter,
+                       (const long long*)s.area, (const int*)s.binter, (const long long*)s.barea, n, n_gt, iscrowd, iou, mask_iou, boundary_iou,
+                       (int*)inter, (long long*)area_d, (long long*)area_g);
+    ODISE_CHECK_HIP(hipGetLastError());
+    return ODISE_OK;
+}
+
+// evaluateImg of one picture for "segm" (d->rows), "bbox" (bb), "boundary" (bd), or any of them from one pack of the detections
+static int inst_eval_run(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p, const odise_inst_bbox_task* bb, bool want_bbox,
+                         const odise_inst_boundary_task* bd = nullptr) {
     ODISE_REQUIRE(ctx && d, "instance_eval: null argument");
     ODISE_REQUIRE(!want_bbox || (bb && bb->rows && bb->n_rows), "instance_eval: null bbox task");
-    const bool segm = !want_bbox || d->rows || d->n_rows;   // the bbox call skips the segm part when it has nowhere to go
-    ODISE_REQUIRE(d->iou_thresholds && d->flags && (!segm || (d->rows && d->n_rows)), "instance_eval: null pointer");
+    ODISE_REQUIRE(!bd || (bd->rows && bd->n_rows), "instance_eval: null boundary task");
+    const bool segm_rows = !(want_bbox || bd) || d->rows || d->n_rows;   // beside another task the segm rows are skipped when they have nowhere to go
+    const bool segm = segm_rows || bd;                                   // the boundary task needs the masks' counts too
+    ODISE_REQUIRE(d->iou_thresholds && d->flags && (!segm_rows || (d->rows && d->n_rows)), "instance_eval: null pointer");
     const InstSource src = inst_source(*d);
     ODISE_TRY(inst_source_check("instance_eval", src, true, kRleMaxPixels));   // the match step reads the table and the scores of dense masks too
     ODISE_REQUIRE(d->n_gt >= 0 && d->n_gt <= kInstMaxGt, "instance_eval: %d ground-truth masks (0..%d)", d->n_gt, kInstMaxGt);
@@ -405,11 +493,12 @@ static int inst_eval_run(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, cons
     ODISE_TRY(inst_geom(ctx, "instance_eval", src, &ig));
     const RleGrid G = rle_grid(d->h, d->w);
     InstScratch s;
-    ODISE_TRY(inst_scratch(ctx, d->topk, d->n_gt, G, &s, p != nullptr, want_bbox && !bb->boxes));
+    ODISE_TRY(inst_scratch(ctx, d->topk, d->n_gt, G, &s, p != nullptr, want_bbox && !bb->boxes, bd != nullptr));
     ODISE_CHECK_HIP(hipMemsetAsync(s.inter, 0, s.inter_bytes, ctx->stream));
     int* status = s.inter + (size_t)d->topk * d->n_gt;
     ODISE_TRY(inst_pack(ctx, src, ig, G, s.words_d));
     if (segm) ODISE_TRY(inst_overlaps(ctx, s, G, d->topk, d->gt_runs, d->gt_offsets, d->n_gt, status, p));
+    if (bd) ODISE_TRY(inst_boundary_overlaps(ctx, s, G, d->topk, d->n_gt, bd->radius, src.inst_table));
     InstMatchArgs A;
     A.inst_table = (const int*)d->inst_table; A.inst_scores = d->inst_scores; A.gt_rows = (const int*)d->gt_rows;
     A.status = status; A.flags = (int*)d->flags;
@@ -422,9 +511,16 @@ static int inst_eval_run(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, cons
         hipLaunchKernelGGL(inst_match_kernel<BoxIou>, dim3(1), dim3(kRleThreads), 0, ctx->stream, A, BoxIou{boxes, bb->gt_boxes});
         ODISE_CHECK_HIP(hipGetLastError());
     }
-    if (segm) {
+    const SegmIou mask_iou{s.inter, s.area, d->topk, d->n_gt};
+    if (segm_rows) {
         A.rows = d->rows; A.n_rows = (int*)d->n_rows;
-        hipLaunchKernelGGL(inst_match_kernel<SegmIou>, dim3(1), dim3(kRleThreads), 0, ctx->stream, A, SegmIou{s.inter, s.area, d->topk, d->n_gt});
+        hipLaunchKernelGGL(inst_match_kernel<SegmIou>, dim3(1), dim3(kRleThreads), 0, ctx->stream, A, mask_iou);
+        ODISE_CHECK_HIP(hipGetLastError());
+    }
+    if (bd) {
+        A.rows = bd->rows; A.n_rows = (int*)bd->n_rows;
+        hipLaunchKernelGGL(inst_match_kernel<BoundaryIou>, dim3(1), dim3(kRleThreads), 0, ctx->stream, A,
+                           BoundaryIou{mask_iou, SegmIou{s.binter, s.barea, d->topk, d->n_gt}});
         ODISE_CHECK_HIP(hipGetLastError());
     }
     return ODISE_OK;
@@ -439,4 +535,9 @@ extern "C" int odise_hip_instance_eval_poly(odise_hip_ctx* ctx, const odise_inst
 extern "C" int odise_hip_instance_eval_bbox(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p,
                                             const odise_inst_bbox_task* bb) {
     return inst_eval_run(ctx, d, p, bb, true);
+}
+
+extern "C" int odise_hip_instance_eval_boundary(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p,
+                                                const odise_inst_bbox_task* bb, const odise_inst_boundary_task* bd) {
+    return inst_eval_run(ctx, d, p, bb, bb != nullptr, bd);
 }

@@ -1,7 +1,7 @@
 // inst_words.h — "the instance masks of a picture" as the bit-packed words of rle_pack.h, written once for the entry points that
 // take them: odise_hip_instance_eval(_poly, _bbox) (inst_eval.hip), odise_hip_instance_draw (vis_inst.hip), odise_hip_inst_track_frame
-// (inst_track.hip), odise_hip_instance_boxes (inst_box.hip) and odise_hip_instance_rle (rle.hip, which also compiles inst_source_check,
-// inst_geom and inst_pack).
+// (inst_track.hip), odise_hip_instance_boxes (inst_box.hip), odise_hip_mask_boundary (inst_boundary.hip) and odise_hip_instance_rle
+// (rle.hip, which also compiles inst_source_check, inst_geom and inst_pack).
 //   host    InstSource (the detection fields the three public descriptors share), its check, the geometry lookup and the pack launch,
 //           the split of the word axis of the intersection kernels
 //   device  the clamped count of a selection and the candidate rule, the block popcount of a row of words, the tile sizes of the
@@ -86,6 +86,15 @@ __device__ __forceinline__ double bb_iou(double dx, double dy, double dw, double
     const double u = crowd ? da : da + ga - i;
     return i / u;
 }
+
+// ---- areas and boundaries (inst_eval.hip, inst_boundary.hip) ------------------------------------------------------------------------------
+// area[i] = the ones of words [n][nw] (inst_area_kernel: block_popcount, one block per mask)
+int inst_area_launch(odise_hip_ctx* ctx, const u64* words, int n, int64_t nw, long long* area);
+// words_out [n][G.nw] = words_in & ~erode(words_in), the (2 r + 1)^2 erosion that sees zeros outside the picture (r >= 1).  The first
+// topk masks are a selection: those past the count of inst_table (nullptr: none) are not read and their output is zeros.  words_tmp:
+// [n][G.nw] words of scratch.  The padding bits past row h of words_in must be zero (every producer of these words leaves them so).
+int inst_boundary_words(odise_hip_ctx* ctx, const u64* words_in, int n, const RleGrid& G, int r, const int* inst_table, int topk, u64* words_out,
+                        u64* words_tmp);
 
 // ---- the intersection kernels (inst_inter_kernel, inst_track_inter_kernel) --------------------------------------------------------------
 // A block of 256 threads counts popcount(a & b) for kInterRows x kInterCols pairs of masks, tiled like a small GEMM: kInterKC words of

@@ -21,6 +21,13 @@ iouType "bbox" is the same walk over another IoU: `image_rows(..., iou_type="bbo
 masks (`mask_boxes`: detectron2 BitMasks.get_bounding_boxes; csrc/inst_box.hip), `box_iou` is maskApi.c bbIou, a row's area is its box's
 w * h (COCO.loadRes), and the ignore bits of the ground truth stay those of `gt_rows` (the annotation's `area` in both tasks).
 
+iouType "boundary" (Boundary AP: Cheng et al., "Boundary IoU", CVPR 2021; the iouType LVIS scores with) is the same walk again:
+`image_rows(..., iou_type="boundary")` matches on `boundary_iou` = min(mask IoU, rleIou of the two boundaries), a boundary being
+`mask_boundary` = mask & ~erode(mask) (csrc/inst_boundary.hip); a row's area and the ignore rule of an unmatched detection are the segm
+task's.  The rule is restated from the paper and from detectron2's `_mask_to_boundary` (sem_boundary.py) and pinned to the literal
+repeated 3x3 erosion and to hand-worked pictures (tests/test_instance_boundary_cpu.py); parity with the published boundary-iou package is
+UNPINNED: that package is no dependency of this project and no test compares against it.
+
 Ground truth is RLE (compressed or uncompressed) or polygons: `gt_rows(..., polygons=True)` packs the polygons for the device, which
 rasterises them (csrc/poly.hip; host reference: odise_amd/coco_poly.py).
 """
@@ -30,7 +37,7 @@ from typing import Dict, Sequence
 
 import numpy as np
 
-from . import coco_poly, coco_rle
+from . import coco_poly, coco_rle, sem_boundary
 
 # odise_inst_eval_row (include/odise_hip.h)
 ROW_DTYPE = np.dtype([("score", "<f4"), ("category", "<i4"), ("area", "<i4"), ("image", "<i4"), ("matched", "<u8"), ("ignored", "<u8")])
@@ -80,6 +87,45 @@ def mask_iou(dense_masks, gt_counts, iscrowd=None) -> np.ndarray:
         for j in range(len(g)):
             out[i, j] = rle_iou(int(np.count_nonzero(d[i] & g[j])), int(area_d[i]), int(area_g[j]), bool(crowd[j]))
     return out
+
+
+# ---- boundaries ---------------------------------------------------------------------------------------------------------------------------
+def mask_boundary(masks, radius=None) -> np.ndarray:
+    """uint8 [n, h, w]: m & ~erode(m, r) of masks [n, h, w] (nonzero = 1), erode the (2 r + 1)^2 minimum that sees zeros outside the
+    picture; radius None (or <= 0): sem_boundary.boundary_radius(h, w).  With 2 r + 1 > min(h, w) everything erodes and the boundary is
+    the mask itself.  This is sem_boundary.mask_to_boundary on a 0 / 1 map, written another way (window sums of a zero-padded summed-area
+    table: a pixel survives the erosion when its window holds (2 r + 1)^2 ones), so that a test can hold the two against each other."""
+    m = (np.asarray(masks) != 0).astype(np.uint8)
+    n, h, w = m.shape
+    r = sem_boundary.boundary_radius(h, w) if radius is None or radius <= 0 else int(radius)
+    L = 2 * r + 1
+    if L > min(h, w) or n == 0:
+        return m
+    out = np.empty_like(m)
+    for i in range(n):
+        sat = np.zeros((h + L, w + L), np.int64)                              # sat[y, x] = ones of the padded mask above and left of (y, x)
+        sat[r + 1:r + 1 + h, r + 1:r + 1 + w] = m[i]
+        sat = sat.cumsum(0).cumsum(1)
+        win = sat[L:, L:] - sat[:-L, L:] - sat[L:, :-L] + sat[:-L, :-L]       # [h, w]: the ones of the window centred on every pixel
+        out[i] = m[i] & (win != L * L)
+    return out
+
+
+def boundary_iou(dense_masks, gt_counts, iscrowd=None, radius=None):
+    """-> (iou, mask_iou, b_iou), float64 [n, n_gt] each: `mask_iou`, the same rleIou on the exact pixel counts of the two boundaries
+    (`mask_boundary` of both sides, one radius; inter == 0 -> 0, a crowd -> inter / the area of the detection's boundary), and their
+    minimum, the IoU that Boundary AP matches on (Cheng et al., "Boundary IoU", CVPR 2021)."""
+    d = np.asarray(dense_masks) != 0
+    n, h, w = d.shape
+    g = np.stack([decode_runs(c, h, w) for c in gt_counts]).astype(bool) if len(gt_counts) else np.zeros((0, h, w), bool)
+    crowd = np.zeros(len(g), bool) if iscrowd is None else np.asarray(iscrowd).astype(bool)
+    bd, bg = mask_boundary(d, radius).astype(bool), mask_boundary(g, radius).astype(bool)
+    area_d, area_g = bd.reshape(n, h * w).sum(1), bg.reshape(len(g), h * w).sum(1)
+    m_iou, b_iou = mask_iou(d, gt_counts, iscrowd), np.zeros((n, len(g)), np.float64)
+    for i in range(n):
+        for j in range(len(g)):
+            b_iou[i, j] = rle_iou(int(np.count_nonzero(bd[i] & bg[j])), int(area_d[i]), int(area_g[j]), bool(crowd[j]))
+    return np.minimum(m_iou, b_iou), m_iou, b_iou
 
 
 # ---- boxes --------------------------------------------------------------------------------------------------------------------------------
@@ -207,12 +253,13 @@ def area_outside(area, a: int) -> bool:
 
 
 def image_rows(masks, scores, classes, gt_counts, gt_table, image: int = 0, iou_thrs=IOU_THRS, num_categories=None, iou_type: str = "segm",
-               gt_boxes=None):
+               gt_boxes=None, radius=None):
     """COCOeval.evaluateImg of one picture -> (rows ROW_DTYPE [n] in descending score, flags).  masks [n, h, w] (nonzero = 1), n <= 100;
     gt_counts: the run lengths of every ground truth; gt_table: `gt_rows`' table.  A picture that raises a flag has no rows.
     iou_type "bbox": the IoU is `box_iou` of `mask_boxes(masks)` against gt_boxes float64 [n_gt, 4] XYWH, a row's area is its box's
-    w * h, and gt_counts is not looked at (None will do)."""
-    assert iou_type in ("segm", "bbox"), iou_type
+    w * h, and gt_counts is not looked at (None will do).
+    iou_type "boundary": the IoU is `boundary_iou(masks, gt_counts, iscrowd, radius)[0]`; areas, flags and ignore bits are those of "segm"."""
+    assert iou_type in ("segm", "bbox", "boundary"), iou_type
     bbox = iou_type == "bbox"
     d = np.asarray(masks) != 0
     n, h, w = d.shape
@@ -240,6 +287,8 @@ def image_rows(masks, scores, classes, gt_counts, gt_table, image: int = 0, iou_
     if bbox:
         dtb = xyxy_to_xywh(mask_boxes(d))
         ious, areas = box_iou(dtb, gtb, table[:, 1]), (dtb[:, 2] * dtb[:, 3]).astype(np.int64)
+    elif iou_type == "boundary":
+        ious, areas = boundary_iou(d, gt_counts, table[:, 1], radius)[0], d.reshape(n, h * w).sum(1)
     else:
         ious, areas = mask_iou(d, gt_counts, table[:, 1]), d.reshape(n, h * w).sum(1)
     order = np.argsort(-scores[:n], kind="mergesort")

@@ -10,7 +10,12 @@ objects, RLE (compressed or uncompressed) for the crowds, mixed freely in one pi
 tasks=("bbox",) or ("bbox", "segm") is COCOEvaluator's bbox task beside (or without) segm: `process` enqueues one
 `odise_hip_instance_eval_bbox`, which takes the detections' boxes from the same packed masks (BitMasks.get_bounding_boxes, the line the
 reference leaves out as slow) and matches them against the annotations' `bbox`; every task keeps row blocks of its own, the row format
-and everything behind it are shared."""
+and everything behind it are shared.
+
+"boundary" in `tasks` (any combination with the other two) is Boundary AP (Cheng et al., "Boundary IoU", CVPR 2021; LVIS' third
+iouType): the same matching on min(mask IoU, boundary IoU), the boundaries eroded out of the packed words on the device
+(`odise_hip_instance_eval_boundary`, csrc/inst_boundary.hip) behind the same pack and the same decode.  Its rule is restated from the paper
+and detectron2's `_mask_to_boundary`; parity with the published boundary-iou package is unpinned (odise_amd/instance_eval.py)."""
 from __future__ import annotations
 
 from typing import Dict, Sequence
@@ -25,19 +30,20 @@ from .runtime import Context, DeviceArray, InstanceAccumulateError
 class HipInstanceSegEvaluator:
     CHUNK = 64          # pictures per block of the row buffer: it grows by whole blocks, rows already written stay where they are
 
-    TASKS = ("bbox", "segm")                                                   # detectron2's order of the result groups
+    TASKS = ("bbox", "segm", "boundary")                                       # detectron2's order of the result groups, then Boundary AP
 
     def __init__(self, ctx: Context, thing_dataset_id_to_contiguous_id: Dict[int, int], class_names: Sequence[str], topk: int = 100,
-                 tasks: Sequence[str] = ("segm",)):
+                 tasks: Sequence[str] = ("segm",), boundary_radius: int = 0):
         """thing_dataset_id_to_contiguous_id: the annotation's category ids -> 0..K-1, the space the model's pred_classes live in;
         class_names [K] per contiguous id; topk: the model's test_topk_per_image (at most 100, COCOeval's last maxDets);
-        tasks: ("segm",), ("bbox",) or ("bbox", "segm") - with "bbox" every annotation needs its `bbox`."""
+        tasks: any of "bbox", "segm", "boundary" - with "bbox" every annotation needs its `bbox`; boundary_radius: the erosion radius of
+        the boundary task, 0 = the formula of the picture's size (sem_boundary.boundary_radius)."""
         self.ctx = ctx
         assert len(tasks) > 0 and set(tasks) <= set(self.TASKS) and len(set(tasks)) == len(tasks), tasks
         self.tasks = tuple(t for t in self.TASKS if t in tasks)
         self.to_contiguous = {int(k): int(v) for k, v in thing_dataset_id_to_contiguous_id.items()}
         self.class_names = list(class_names)
-        self.K, self.topk = len(self.class_names), int(topk)
+        self.K, self.topk, self.boundary_radius = len(self.class_names), int(topk), int(boundary_radius)
         assert all(0 <= v < self.K for v in self.to_contiguous.values()), "contiguous ids must lie in [0, len(class_names))"
         assert 1 <= self.topk <= IE.MAX_DETECTIONS, self.topk
         self.flags = ctx.zeros((1,), np.int32)
@@ -47,8 +53,11 @@ class HipInstanceSegEvaluator:
         from ._lib import check
         check(self.ctx.lib.odise_hip_memset(self.ctx.h, self.flags.ptr, 0, 4), "memset")
         self._task_chunks, self._pictures, self._images = {t: [] for t in self.tasks}, 0, []
-        self._chunks = self._task_chunks[self.tasks[-1]]                       # the segm task's blocks when it is there
+        self._chunks = self._task_chunks[self._main_task()]                    # the segm task's blocks when it is there
         self._npig = np.zeros((self.K, 4), np.int64)
+
+    def _main_task(self) -> str:
+        return "segm" if "segm" in self.tasks else self.tasks[-1]
 
     def _slot(self):
         """{task: (rows [topk], n_rows [1])} of the next picture."""
@@ -78,12 +87,13 @@ class HipInstanceSegEvaluator:
         gt = self.ctx.instance_gt_to_device(table, runs, offsets, *((xy, poly_offsets, gt_polys) if len(poly_offsets) > 1 else ()), boxes=boxes)
         slot = self._slot()
         self._images.append(int(image_index))
+        boundary = slot["boundary"] + (self.boundary_radius,) if "boundary" in self.tasks else None
         if "bbox" in self.tasks:
             self.ctx.instance_eval_bbox(out_hw, inst_table_row, inst_scores_row, self.topk, gt, self.K, int(image_index), *slot["bbox"], self.flags,
-                                        *slot.get("segm", (None, None)), masks=pred_masks, b=b, pad_hw=pad_hw, img_hw=img_hw)
+                                        *slot.get("segm", (None, None)), masks=pred_masks, b=b, pad_hw=pad_hw, img_hw=img_hw, boundary=boundary)
         else:
-            self.ctx.instance_eval(out_hw, inst_table_row, inst_scores_row, self.topk, gt, self.K, int(image_index), *slot["segm"], self.flags,
-                                   masks=pred_masks, b=b, pad_hw=pad_hw, img_hw=img_hw)
+            self.ctx.instance_eval(out_hw, inst_table_row, inst_scores_row, self.topk, gt, self.K, int(image_index), *slot.get("segm", (None, None)),
+                                   self.flags, masks=pred_masks, b=b, pad_hw=pad_hw, img_hw=img_hw, boundary=boundary)
 
     def process_selection(self, selection: dict, annotations_per_image, image_indices) -> None:
         """`process` for every picture of a batch from `HipCategoryODISE.last_selection`."""
@@ -95,9 +105,9 @@ class HipInstanceSegEvaluator:
                          selection["out_hw"][b], anns, idx)
 
     def rows(self, task: str = None) -> np.ndarray:
-        """This rank's rows of a task so far (one read per block of pictures); task: "segm" where it runs, else "bbox"."""
+        """This rank's rows of a task so far (one read per block of pictures); task: "segm" where it runs, else the last of the tasks."""
         out = []
-        for c, (rows, counts) in enumerate(self._task_chunks[task or self.tasks[-1]]):
+        for c, (rows, counts) in enumerate(self._task_chunks[task or self._main_task()]):
             host, n = rows.numpy().reshape(self.CHUNK, self.topk), counts.numpy()
             used = min(self.CHUNK, self._pictures - c * self.CHUNK)
             out += [host[i, :n[i]] for i in range(used)]
@@ -121,7 +131,7 @@ class HipInstanceSegEvaluator:
         """accumulate_on: "device" = odise_hip_instance_accumulate, "host" = instance_eval.accumulate; the results are bit-identical.  When an
         image number was given twice the host path is taken whatever was asked: the host function merges such pictures and the device
         order is not defined for them.
-        -> detectron2's results of the task; with tasks other than ("segm",) one such group per task, {"bbox": .., "segm": ..}.
+        -> detectron2's results of the task; with tasks other than ("segm",) one such group per task, {"bbox": .., "segm": .., "boundary": ..}.
         `precision` / `recall` are those of the last task, `task_precision` / `task_recall` hold every task's."""
         import torch
         import torch.distributed as dist

@@ -105,6 +105,14 @@ def _fill_inst_source(d, what: str, hw, topk: int, table_row, scores_row, masks:
     d.inst_table, d.inst_scores = _ptr(table_row), _ptr(scores_row)
 
 
+def _boundary_task(boundary):
+    """InstBoundaryTask of (rows, n_rows) or (rows, n_rows, radius); device arrays or pointers."""
+    from ._lib import InstBoundaryTask
+    t = InstBoundaryTask()
+    t.rows, t.n_rows, t.radius = _ptr(boundary[0]), _ptr(boundary[1]), int(boundary[2]) if len(boundary) > 2 else 0
+    return t
+
+
 class Context:
     def __init__(self, device: int = 0):
         self.lib = _lib.load()
@@ -917,11 +925,13 @@ class Context:
         return (iou, flags) + (extra if with_counts else ())
 
     def instance_eval(self, out_hw, table_row, scores_row, topk: int, gt: dict, num_categories: int, image: int, rows, n_rows, flags,
-                      masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0), img_hw=(0, 0), iou_thresholds=None) -> None:
+                      masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0), img_hw=(0, 0), iou_thresholds=None, boundary=None) -> None:
         """Enqueue COCOeval.evaluateImg of one picture (odise_hip_instance_eval): detections = the selection table_row [1 + 2 topk] /
         scores_row [topk] of image b of the last head forward, sampled from its mask logits (pad_hw / img_hw as in `instance_rle`), or the
         dense `masks` [topk, h, w] when given; gt = `instance_gt_to_device`; rows (instance_eval.ROW_DTYPE [topk]), n_rows and flags
-        (int32 [1]) are device arrays or pointers.  A gt that carries polygons goes through odise_hip_instance_eval_poly."""
+        (int32 [1]) are device arrays or pointers.  A gt that carries polygons goes through odise_hip_instance_eval_poly.
+        boundary = (rows, n_rows) or (rows, n_rows, radius): the Boundary AP task from the same pack and decode
+        (odise_hip_instance_eval_boundary; radius 0 / absent = the formula); `rows` / `n_rows` may both be None then."""
         from ._lib import InstEvalDesc, InstPolyGt
         from .instance_eval import IOU_THRS
         thr = np.ascontiguousarray(IOU_THRS if iou_thresholds is None else iou_thresholds, np.float64)
@@ -931,9 +941,14 @@ class Context:
         d.gt_runs, d.gt_offsets, d.gt_rows, d.n_gt = gt["runs"].ptr, gt["offsets"].ptr, gt["rows"].ptr, int(gt["n_gt"])
         d.num_categories, d.image, d.iou_thresholds = int(num_categories), int(image), thr.ctypes.data
         d.rows, d.n_rows, d.flags = _ptr(rows), _ptr(n_rows), _ptr(flags)
+        p = None
         if "gt_polys" in gt:
             p = InstPolyGt()
             p.xy, p.poly_offsets, p.gt_polys, p.n_poly = gt["xy"].ptr, gt["poly_offsets"].ptr, gt["gt_polys"].ptr, int(gt["n_poly"])
+        if boundary is not None:
+            check(self.lib.odise_hip_instance_eval_boundary(self.h, C.byref(d), C.byref(p) if p is not None else None, None,
+                                                            C.byref(_boundary_task(boundary))), "instance_eval_boundary")
+        elif p is not None:
             check(self.lib.odise_hip_instance_eval_poly(self.h, C.byref(d), C.byref(p)), "instance_eval_poly")
         else:
             check(self.lib.odise_hip_instance_eval(self.h, C.byref(d)), "instance_eval")
@@ -970,11 +985,12 @@ class Context:
 
     def instance_eval_bbox(self, out_hw, table_row, scores_row, topk: int, gt: dict, num_categories: int, image: int, bbox_rows, bbox_n_rows,
                            flags, rows=None, n_rows=None, boxes=None, masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0),
-                           img_hw=(0, 0), iou_thresholds=None) -> None:
+                           img_hw=(0, 0), iou_thresholds=None, boundary=None) -> None:
         """Enqueue COCOeval.evaluateImg of one picture for "bbox" (odise_hip_instance_eval_bbox) and, when `rows` / `n_rows` are given,
         for "segm" from the same pack of the detections (exactly `instance_eval`).  Arguments as in `instance_eval`; gt must carry
         "boxes" (`instance_gt_to_device(..., boxes=instance_eval.gt_boxes(annotations))`); bbox_rows / bbox_n_rows take the bbox
-        task's rows; boxes (optional, float32 [topk, 4]) the detections' XYXY boxes."""
+        task's rows; boxes (optional, float32 [topk, 4]) the detections' XYXY boxes; boundary as in `instance_eval`: the third task
+        of the same call (odise_hip_instance_eval_boundary)."""
         from ._lib import InstBboxTask, InstEvalDesc, InstPolyGt
         from .instance_eval import IOU_THRS
         thr = np.ascontiguousarray(IOU_THRS if iou_thresholds is None else iou_thresholds, np.float64)
@@ -991,7 +1007,43 @@ class Context:
         if "gt_polys" in gt:
             p = InstPolyGt()
             p.xy, p.poly_offsets, p.gt_polys, p.n_poly = gt["xy"].ptr, gt["poly_offsets"].ptr, gt["gt_polys"].ptr, int(gt["n_poly"])
+        if boundary is not None:
+            check(self.lib.odise_hip_instance_eval_boundary(self.h, C.byref(d), C.byref(p) if p is not None else None, C.byref(t),
+                                                            C.byref(_boundary_task(boundary))), "instance_eval_boundary")
+            return
         check(self.lib.odise_hip_instance_eval_bbox(self.h, C.byref(d), C.byref(p) if p is not None else None, C.byref(t)), "instance_eval_bbox")
+
+    def mask_boundary(self, masks: DeviceArray, radius: int = 0, out: Optional[DeviceArray] = None, with_area: bool = False):
+        """The boundaries of dense device masks [n, h, w] (float32 / uint8 / bool; odise_hip_mask_boundary: mask & ~erode(mask), the
+        rule of Boundary IoU) -> uint8 [n, h, w] on the device, byte for byte instance_eval.mask_boundary; radius <= 0: the formula of
+        `boundary_radius`.  with_area adds the pixels of each boundary, int64 [n]."""
+        n, h, w = masks.shape
+        dt = _mask_dtype(masks, "mask_boundary")
+        if out is None:
+            out = self.empty((n, h, w), np.uint8)
+        assert out.dtype == np.uint8 and out.nbytes >= n * h * w, (out.dtype, out.shape)
+        area = self.empty((n,), np.int64) if with_area else None
+        check(self.lib.odise_hip_mask_boundary(self.h, _p(masks), dt, n, h, w, int(radius), _p(out), _p(area)), "mask_boundary")
+        return (out, area) if with_area else out
+
+    def mask_boundary_iou(self, masks: DeviceArray, gt_counts, iscrowd=None, radius: int = 0, flags: Optional[DeviceArray] = None):
+        """`mask_iou` with the Boundary IoU beside it (odise_hip_mask_boundary_iou; host restatement instance_eval.boundary_iou) ->
+        (iou, mask_iou, boundary_iou, flags): float64 [n, n_gt] each on the device, iou = min(mask_iou, boundary_iou); arguments as in
+        `mask_iou`."""
+        n, h, w = masks.shape
+        dt = _mask_dtype(masks, "mask_boundary_iou")
+        if not isinstance(gt_counts, dict):
+            offs = np.concatenate(([0], np.cumsum([len(c) for c in gt_counts]))).astype(np.int64)
+            runs = np.concatenate([np.asarray(c, np.uint32) for c in gt_counts]) if len(gt_counts) else np.zeros(0, np.uint32)
+            gt_counts = self.instance_gt_to_device(np.zeros((len(offs) - 1, 3), np.int32), runs, offs)
+        n_gt = gt_counts["n_gt"]
+        crowd = None if iscrowd is None else (iscrowd if isinstance(iscrowd, DeviceArray) else self.to_device(np.asarray(iscrowd, np.uint8)))
+        if flags is None:
+            flags = self.zeros((1,), np.int32)
+        iou, m_iou, b_iou = (self.empty((n, n_gt), np.float64) for _ in range(3))
+        check(self.lib.odise_hip_mask_boundary_iou(self.h, _p(masks), dt, n, h, w, _p(gt_counts["runs"]), _p(gt_counts["offsets"]), n_gt, _p(crowd),
+                                                   int(radius), _p(iou), _p(m_iou), _p(b_iou), None, None, None, _p(flags)), "mask_boundary_iou")
+        return iou, m_iou, b_iou, flags
 
     def instance_accumulate(self, blocks, npig, num_categories: int, topk: int, rec_thrs=None):
         """COCOeval.accumulate on the device (odise_hip_instance_accumulate; host restatement: instance_eval.accumulate, which this
