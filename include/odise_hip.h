@@ -456,8 +456,8 @@ int odise_hip_pair_histogram(odise_hip_ctx* ctx, const int* a, const int* b, int
  *   [0, num_categories).
  * ODISE_ERR_ARG and nothing written: a null pointer, H * W > 2^29 - 1, n_gt > 254, a ground-truth category outside [0, num_categories), iscrowd not 0 / 1.
  * Asynchronous on the context's stream.  Scratch belongs to the context: it is allocated once, at the first call, at the caps (a matrix of
- * 256 x (ODISE_MAX_SEGMENTS + 2) int32, the device table, 8 pinned table slots; about 140 KB), never resized, and released with the
- * context.  The pixel pass sizes its LDS histogram to the real n_gt but, since n is read on the device, to ODISE_MAX_SEGMENTS on the
+ * 256 x (ODISE_MAX_SEGMENTS + 2) int32, the second matrix of odise_hip_panoptic_quality_boundary, the device table, 8 pinned table slots;
+ * about 250 KB), never resized, and released with the context.  The pixel pass sizes its LDS histogram to the real n_gt but, since n is read on the device, to ODISE_MAX_SEGMENTS on the
  * predicted side (at most 48 KiB); tables beyond that count in the matrix directly. */
 typedef struct { double iou; int64_t tp, fp, fn; } odise_pq_stat;      /* one per category, 32 bytes */
 typedef struct {
@@ -475,6 +475,34 @@ typedef struct {
     int32_t* flags;               /* device [1] */
 } odise_pq_desc;
 int odise_hip_panoptic_quality(odise_hip_ctx* ctx, const odise_pq_desc* d);
+/* The same picture with Boundary PQ beside PQ (Cheng et al., "Boundary IoU", CVPR 2021: PQ with min(mask IoU, boundary IoU) in place of
+ * the mask IoU).  d->stats += exactly what odise_hip_panoptic_quality adds, bit for bit; b->stats += the Boundary PQ statistics; both
+ * come from one translation of the two id maps.  This is the project's restatement of the paper's rule on pq_compute_single_core; parity
+ * with the published boundary-iou package is UNPINNED (the package was never run beside it).  Host restatement:
+ * odise_amd/panoptic_quality.py image_boundary_stats.
+ *   radius     b->radius > 0, else odise_hip_boundary_radius(H, W), as the other two boundary measures.
+ *   B(s)       the boundary of segment s = its pixels minus their erosion (`radius` 3x3 erosions behind a ring of zeros: the binary
+ *              odise_hip_mask_boundary of its mask).  Equivalently a pixel of s lies in B(s) when its (2 radius + 1)^2 window leaves the
+ *              picture or holds a pixel that is not of s; VOID and ids missing from a table are neighbours like any other.  With
+ *              2 radius + 1 > min(H, W) every pixel is a boundary pixel.
+ *   b_iou      of a candidate pair (g, p) - the candidates are those of PQ -: inter_b = |B(g) & B(p)|,
+ *              union_b = |B(p)| + |B(g)| - inter_b - |B(p) over ground-truth VOID|  (|B(g)| counted from the map: the JSON holds none),
+ *              b_iou = inter_b / union_b as the double division of the two integers, 0 when union_b <= 0.
+ *   matching   iou_b = fmin(iou, b_iou) with iou exactly that of odise_hip_panoptic_quality (JSON area included); iou_b > 0.5:
+ *              tp[cat] += 1, iou[cat] += iou_b, in ascending (g, p) order onto the value already in b->stats.
+ *   fn, fp     follow from this matching by the unchanged rules; the fp skip test uses mask areas, VOID and the crowd row.
+ *   flags      the same three; a flagged picture adds nothing to either accumulator.
+ * ODISE_ERR_ARG and nothing enqueued: what odise_hip_panoptic_quality refuses, a null b or b->stats, b->stats overlapping d->stats.
+ * Asynchronous on the context's stream.  Scratch: the context's second matrix ((254 + 3) x (ODISE_MAX_SEGMENTS + 3) int32, allocated with
+ * the first) and its growable boundary scratch (four byte maps - both slot maps and their complements - their erosions and a spare). */
+typedef struct { odise_pq_stat* stats; int radius; } odise_pq_boundary_task;   /* device [num_categories]; radius <= 0: the formula */
+int odise_hip_panoptic_quality_boundary(odise_hip_ctx* ctx, const odise_pq_desc* d, const odise_pq_boundary_task* b);
+/* The erosion stage of the call above on one id map: boundary uint8 [H,W] = 1 where the pixel lies on the boundary B(s) of its own
+ * segment; ids int32 [H,W] (device); table device int32 [n] ids, n <= 254 (the first row of an id counts).  Pixels of id 0 and of ids
+ * absent from the table: 0.  area int64 [n] (optional) = the pixels of each row's boundary.  radius <= 0: the formula.  Same slot and
+ * erosion code as the evaluator call.  Asynchronous on the context's stream. */
+int odise_hip_segment_boundaries(odise_hip_ctx* ctx, const int32_t* ids, int H, int W, const int32_t* table, int n, int radius,
+                                 uint8_t* boundary, int64_t* area);
 /* COCO compressed RLE (pycocotools mask.encode of the Fortran-ordered mask, counts as text) of n masks: the per-mask part of the segm
  * evaluators (COCOEvaluator / InstanceSegEvaluator(tasks=("segm",)) -> detectron2 instances_to_coco_json), byte-identical to
  * `mask.encode(np.asfortranarray(m.astype(np.uint8)))["counts"].decode("utf-8")` (maskApi.c rleEncode + rleToString).

@@ -97,6 +97,11 @@ class PqDesc(C.Structure):
                 ("gt_segments", c_void_p), ("n_gt", c_int), ("num_categories", c_int), ("stats", c_void_p), ("flags", c_void_p)]
 
 
+class PqBoundaryTask(C.Structure):
+    """odise_pq_boundary_task (include/odise_hip.h)."""
+    _fields_ = [("stats", c_void_p), ("radius", c_int)]
+
+
 class SemSegEvalDesc(C.Structure):
     """odise_semseg_eval_desc (include/odise_hip.h)."""
     _fields_ = [("K", c_int), ("H", c_int), ("W", c_int), ("labels", c_void_p), ("sem_seg", c_void_p), ("gt", c_void_p), ("radius", c_int),
@@ -269,21 +274,24 @@ def header_prototypes(path: str = HEADER_PATH) -> dict:
 _lib = None
 
 
-def load() -> C.CDLL:
-    """Load the shared library (building is `python -m odise_amd.build`); fail loudly if absent."""
+def load(path: str | None = None, allow_missing: bool = False) -> C.CDLL:
+    """Load the shared library (building is `python -m odise_amd.build`); fail loudly if absent.  The first call decides which library the
+    process uses: `path` (default LIB_PATH), and with `allow_missing` one that predates this header - the symbols it lacks stay unbound
+    (measurement tools that time an older build of the library; nothing else passes either argument)."""
     global _lib
     if _lib is not None:
         return _lib
-    if not os.path.exists(LIB_PATH):
+    path = path or LIB_PATH
+    if not os.path.exists(path):
         raise RuntimeError(
-            f"{LIB_PATH} is missing: run `python -m odise_amd.build` (hipcc --offload-arch=gfx950). "
+            f"{path} is missing: run `python -m odise_amd.build` (hipcc --offload-arch=gfx950). "
             "There is no CPU fallback for the ODISE hot path.")
-    lib = C.CDLL(LIB_PATH)
+    lib = C.CDLL(path)
     missing = [s for s in header_symbols() + header_symbols(TOOLS_HEADER_PATH) if not hasattr(lib, s)]
-    if missing:
+    if missing and not allow_missing:
         raise RuntimeError(f"libodise_hip.so does not export: {missing}")
     lib.odise_hip_last_error.restype = C.c_char_p
-    protos = {**header_prototypes(), **header_prototypes(TOOLS_HEADER_PATH)}
+    protos = {n: a for n, a in {**header_prototypes(), **header_prototypes(TOOLS_HEADER_PATH)}.items() if n not in missing}
     lab = header_prototypes(LAB_HEADER_PATH)
     if all(hasattr(lib, n) for n in lab):   # the measurement build (ODISE_HIP_LIB=.../libodise_hip_tools.so) also carries the lab hooks
         protos.update(lab)

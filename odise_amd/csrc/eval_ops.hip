@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "common.h"
+#include "label_maps.h"
 #include "lds_hist.h"
 #include "rle_pack.h"   // sem_rle.hip: the per-class strings of odise_hip_semantic_eval
 
@@ -144,12 +145,7 @@ __global__ void __launch_bounds__(256) u8_hwc_to_f32_chw_pad_kernel(const uint8_
 }
 
 // ---- Boundary IoU counters ------------------------------------------------------------------------------------------------------------------
-// A byte label map is [H][Pd] dwords, Pd = ceil(W / 4), byte x & 3 of dword x >> 2; the bytes past W in a row's last dword are never
-// initialised: every dword read masks them (`tail`).  Two maps (prediction, ground truth) lie back to back and share a launch (blockIdx.y).
-struct LabelGrid {
-    int H, W, Pd;
-    unsigned tail;   // the valid bytes of a row's last dword
-};
+// The byte label maps (LabelGrid, store_label, BoundaryMaps): label_maps.h.
 constexpr int kMinTaps = 4;
 struct MinTaps {
     int n, off[kMinTaps];
@@ -175,11 +171,6 @@ __device__ __forceinline__ unsigned label_window(const unsigned* __restrict__ ma
     const int q = xd + (dx >> 2), t = dx & 3;
     const unsigned lo = label_dword(row, q, G), hi = t ? label_dword(row, q + 1, G) : 0u;
     return __builtin_amdgcn_alignbyte(hi, lo, (unsigned)t);
-}
-
-__device__ __forceinline__ void store_label(unsigned* __restrict__ map, int64_t p, const LabelGrid& G, int v) {
-    const int y = (int)(p / G.W), x = (int)(p - (int64_t)y * G.W);
-    ((uint8_t*)map)[(int64_t)y * G.Pd * 4 + x] = (uint8_t)v;
 }
 
 // int32 labels -> one byte map, values outside [0, K] -> K
@@ -330,19 +321,13 @@ static int upload_coeffs(odise_hip_ctx* ctx, const ResampleCoeffs& c, int** d_bo
     return ODISE_OK;
 }
 
-static int boundary_radius(int H, int W) {   // _mask_to_boundary: max(1, int(round(0.02 * sqrt(h^2 + w^2)))), Python's round (half to even)
+int boundary_radius(int H, int W) {   // _mask_to_boundary: max(1, int(round(0.02 * sqrt(h^2 + w^2)))), Python's round (half to even)
     const double r = nearbyint(0.02 * sqrt((double)H * H + (double)W * W));
     return r < 1.0 ? 1 : (int)r;
 }
 
-struct BoundaryMaps {
-    LabelGrid G;
-    int64_t per_map;   // dwords
-    unsigned *m, *e;   // [nmaps] label maps and, after erode_maps, their erosions
-    unsigned* tmp;
-};
 // the context's scratch for the byte maps of one picture (grown on demand; earlier calls on the stream may still read the old buffer)
-static int boundary_maps(odise_hip_ctx* ctx, int H, int W, int nmaps, BoundaryMaps* b) {
+int boundary_maps(odise_hip_ctx* ctx, int H, int W, int nmaps, BoundaryMaps* b) {
     b->G.H = H; b->G.W = W; b->G.Pd = (int)ceil_div(W, 4);
     b->G.tail = (W & 3) ? (1u << (8 * (W & 3))) - 1u : ~0u;
     b->per_map = (int64_t)H * b->G.Pd;
@@ -356,7 +341,7 @@ static int boundary_maps(odise_hip_ctx* ctx, int H, int W, int nmaps, BoundaryMa
 }
 
 // b->e = the (2r+1)^2 minimum of b->m with zeros outside the picture
-static int erode_maps(odise_hip_ctx* ctx, BoundaryMaps* b, int nmaps, int r) {
+int erode_maps(odise_hip_ctx* ctx, BoundaryMaps* b, int nmaps, int r) {
     const LabelGrid& G = b->G;
     if (2 * (int64_t)r + 1 > std::min(G.H, G.W)) {   // every window leaves the picture
         ODISE_CHECK_HIP(hipMemsetAsync(b->e, 0, (size_t)nmaps * b->per_map * 4, ctx->stream));

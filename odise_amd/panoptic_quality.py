@@ -15,6 +15,24 @@ arithmetic of COCOPanopticEvaluator.evaluate, which stays on the host.
 
 Ids are 24-bit values, as in the PNG files; in a table the first row of an id is the one its pixels belong to (a later row of the same
 id, or a row of id 0, has no pixels).
+
+Boundary PQ (`image_boundary_stats`, the reference of `Context.panoptic_quality_boundary`) is the third metric of Cheng et al., "Boundary
+IoU" (CVPR 2021): PQ with min(mask IoU, boundary IoU) in place of the mask IoU, both for the match (> 0.5) and for the SQ sum.  This is the
+project's restatement of the paper's rule on `pq_compute_single_core`; PARITY WITH THE PUBLISHED boundary-iou PACKAGE IS UNPINNED (the
+package was never run beside it).
+
+    radius                   sem_boundary.boundary_radius(H, W) unless the caller gives radius > 0: as the other two boundary measures
+    boundary B(s)            the segment's pixels minus their erosion (r 3x3 erosions behind a ring of zeros: the binary
+                             instance_eval.mask_boundary of its mask); a pixel of s lies in B(s) when its (2r+1)^2 window leaves the
+                             picture or holds a pixel that is not of s.  VOID and ids missing from a table are neighbours like any other
+                             and have no boundary of their own that anyone reads; with 2r+1 > min(H, W) every pixel is a boundary pixel
+    boundary IoU of (g, p)   the candidates are those of PQ; inter_b = |B(g) & B(p)|,
+                             union_b = |B(p)| + |B(g)| - inter_b - |B(p) over ground-truth VOID|  (|B(g)| is counted from the map: the
+                             JSON holds no boundary area), b_iou = inter_b / union_b, 0 when union_b <= 0
+    matching                 iou_b = min(iou, b_iou) with iou exactly as above (JSON area included); iou_b > 0.5: tp, iou_b - added in
+                             ascending (g, p) order onto the running sum
+    fn, fp                   follow from this matching by the unchanged rules; the fp skip test still uses mask areas, VOID and the crowd row
+    flags                    the same three; a flagged picture adds nothing to either accumulator
 """
 from __future__ import annotations
 
@@ -180,6 +198,125 @@ def image_stats(pan_gt, gt_segments, pan_pred, pred_segments, C: int, trace: dic
     return stats, flags
 
 
+def segment_boundaries(pan, table, radius=None) -> np.ndarray:
+    """uint8 [H, W]: 1 where a pixel lies on the boundary B(s) of its own segment, for the segments whose ids `table` lists; pixels of id 0
+    and of ids absent from the table are 0.  Literal: one binary mask per id through instance_eval.mask_boundary (the segments are
+    disjoint, so their boundaries are too).  radius None (or <= 0): sem_boundary.boundary_radius(H, W)."""
+    from .instance_eval import mask_boundary
+    pan = np.asarray(pan).astype(np.int64)
+    assert pan.ndim == 2, pan.shape
+    out = np.zeros(pan.shape, np.uint8)
+    for i in dict.fromkeys(int(v) for v in np.asarray(table, np.int64).reshape(-1)):
+        if i != VOID:
+            out |= mask_boundary((pan == i)[None], radius)[0]
+    return out
+
+
+def image_boundary_stats(pan_gt, gt_segments, pan_pred, pred_segments, C: int, radius=None, into: PQStats | None = None,
+                         trace: dict | None = None):
+    """`image_stats` with min(iou, boundary iou) in place of iou (the rule: the module docstring).  pan_gt / pan_pred must be [H, W] maps.
+    -> (PQStats, flags); `into` as there.  `trace` receives, beside the three counts of `image_stats` (rejected: candidates with
+    iou_b <= 0.5), `demoted`, the pairs with iou > 0.5 >= iou_b, and `lowered`, the pairs matched with b_iou < iou."""
+    stats = into if into is not None else PQStats(C)
+    assert len(stats) == C
+    gt_rows = [tuple(int(v) for v in r) for r in np.asarray(gt_segments, np.int64).reshape(-1, 4)]
+    pred_rows = [tuple(int(v) for v in r) for r in np.asarray(pred_segments, np.int64).reshape(-1, 3)]
+    map_gt, map_pred = np.asarray(pan_gt).astype(np.int64), np.asarray(pan_pred).astype(np.int64)
+    assert map_gt.ndim == 2 and map_gt.shape == map_pred.shape, (map_gt.shape, map_pred.shape)
+    pan_gt, pan_pred = map_gt.reshape(-1), map_pred.reshape(-1)
+    gt_row_of, pred_row_of = {}, {}
+    for i, r in enumerate(gt_rows):
+        if r[0] != VOID:
+            gt_row_of.setdefault(r[0], i)
+    for i, r in enumerate(pred_rows):
+        if r[0] != VOID:
+            pred_row_of.setdefault(r[0], i)
+
+    labels, cnt = np.unique(pan_pred, return_counts=True)
+    area_pred = {int(l): int(c) for l, c in zip(labels, cnt)}
+    flags = 0
+    if any(l != VOID and l not in pred_row_of for l in area_pred):
+        flags |= FLAG_MISSING_ID
+    if any(pred_row_of.get(r[0]) != i or r[0] not in area_pred for i, r in enumerate(pred_rows)):
+        flags |= FLAG_EMPTY_ROW
+    if any(not 0 <= r[2] < C for r in pred_rows):
+        flags |= FLAG_BAD_CATEGORY
+    if flags:
+        return stats, flags
+
+    keys, cnt = np.unique(pan_gt * OFFSET + pan_pred, return_counts=True)
+    inter = {(int(k) // OFFSET, int(k) % OFFSET): int(c) for k, c in zip(keys, cnt)}
+    # the boundaries: pixels of B(g), of B(p), of both
+    on_gt = segment_boundaries(map_gt, list(gt_row_of), radius).reshape(-1) != 0
+    on_pred = segment_boundaries(map_pred, list(pred_row_of), radius).reshape(-1) != 0
+    labels, cnt = np.unique(pan_gt[on_gt], return_counts=True)
+    b_area_gt = {int(l): int(c) for l, c in zip(labels, cnt)}
+    labels, cnt = np.unique(pan_pred[on_pred], return_counts=True)
+    b_area_pred = {int(l): int(c) for l, c in zip(labels, cnt)}
+    labels, cnt = np.unique(pan_pred[on_pred & (pan_gt == VOID)], return_counts=True)
+    b_void = {int(l): int(c) for l, c in zip(labels, cnt)}
+    both = on_gt & on_pred
+    keys, cnt = np.unique(pan_gt[both] * OFFSET + pan_pred[both], return_counts=True)
+    b_inter = {(int(k) // OFFSET, int(k) % OFFSET): int(c) for k, c in zip(keys, cnt)}
+
+    gt_matched, pred_matched = set(), set()
+    rejected = demoted = lowered = 0
+    for (g, p), n in inter.items():                      # np.unique sorts: ascending (g, p)
+        if g not in gt_row_of or p not in pred_row_of:
+            continue
+        gi, pi = gt_row_of[g], pred_row_of[p]
+        _, g_cat, g_crowd, g_area = gt_rows[gi]
+        if g_crowd == 1 or g_cat != pred_rows[pi][2]:
+            continue
+        union = area_pred[p] + g_area - n - inter.get((VOID, p), 0)
+        if union <= 0:
+            continue
+        iou = n / union
+        n_b = b_inter.get((g, p), 0)
+        union_b = b_area_pred.get(p, 0) + b_area_gt.get(g, 0) - n_b - b_void.get(p, 0)
+        b_iou = n_b / union_b if union_b > 0 else 0.0
+        iou_b = min(iou, b_iou)
+        if iou_b > 0.5:
+            stats.tp[g_cat] += 1
+            stats.iou[g_cat] += iou_b
+            gt_matched.add(gi)
+            pred_matched.add(pi)
+            lowered += b_iou < iou
+        else:
+            rejected += 1
+            demoted += iou > 0.5
+
+    crowd_of = {}
+    for gi, (g, g_cat, g_crowd, _) in enumerate(gt_rows):
+        if gi in gt_matched:
+            continue
+        if g_crowd == 1:
+            crowd_of[g_cat] = gi
+            continue
+        stats.fn[g_cat] += 1
+
+    skipped_void = skipped_crowd = 0
+    for pi, (p, _, p_cat) in enumerate(pred_rows):
+        if pi in pred_matched:
+            continue
+        void = inter.get((VOID, p), 0)
+        ign = void
+        if p_cat in crowd_of:
+            gi = crowd_of[p_cat]
+            if gt_row_of.get(gt_rows[gi][0]) == gi:
+                ign += inter.get((gt_rows[gi][0], p), 0)
+        if ign / area_pred[p] > 0.5:
+            if void / area_pred[p] > 0.5:
+                skipped_void += 1
+            else:
+                skipped_crowd += 1
+            continue
+        stats.fp[p_cat] += 1
+    if trace is not None:
+        trace.update(rejected=rejected, skipped_void=skipped_void, skipped_crowd=skipped_crowd, demoted=int(demoted), lowered=int(lowered))
+    return stats, flags
+
+
 def pq_average(stats: PQStats, isthing: Sequence[bool], which: str = "all") -> dict:
     """panopticapi's PQStat.pq_average over the categories of one kind ("all", "things", "stuff") that have a sample (tp + fp + fn > 0):
     pq = iou / (tp + fp / 2 + fn / 2), sq = iou / tp (0 without a tp), rq = tp / (tp + fp / 2 + fn / 2), averaged; `n` = how many.
@@ -209,6 +346,11 @@ def results(stats: PQStats, isthing: Sequence[bool]) -> dict:
         for k in ("pq", "sq", "rq"):
             out[k.upper() + suffix] = 100 * avg[k]
     return out
+
+
+def boundary_results(stats: PQStats, isthing: Sequence[bool]) -> dict:
+    """`results` of the Boundary PQ statistics (`image_boundary_stats`) under their own names: BPQ / BSQ / BRQ and the _th / _st variants."""
+    return {"B" + k: v for k, v in results(stats, isthing).items()}
 
 
 def flag_names(flags: int) -> list:

@@ -542,6 +542,12 @@ class Context:
         pred_segments int32 [n | n x (id, isthing, category)] (the two parts of a panoptic record), gt uint8 [H,W,3] (the annotation PNG
         as decoded) or int32 [H,W] ids, gt_segments HOST rows (id, category, iscrowd, area) -> (stats, flags): `stats` [num_categories]
         records (panoptic_quality.STAT_DTYPE) added to, `flags` int32 [1] OR-ed into; fresh zeroed ones when none are given."""
+        d, _table, stats, flags = self._pq_desc(pred_ids, pred_segments, gt, gt_segments, num_categories, stats, flags)
+        check(self.lib.odise_hip_panoptic_quality(self.h, C.byref(d)), "panoptic_quality")
+        return stats, flags
+
+    def _pq_desc(self, pred_ids, pred_segments, gt, gt_segments, num_categories, stats, flags):
+        """-> (PqDesc, the host table it points to, stats, flags) of the arguments of `panoptic_quality`."""
         from ._lib import PqDesc
         from .panoptic_quality import STAT_DTYPE
         if gt.dtype == np.uint8:
@@ -563,8 +569,7 @@ class Context:
         d.H, d.W, d.pred_ids, d.pred_segments, d.gt, d.gt_layout = H, W, pred_ids.ptr, pred_segments.ptr, gt.ptr, layout
         d.gt_segments, d.n_gt, d.num_categories = table.ctypes.data, table.shape[0], int(num_categories)
         d.stats, d.flags = stats.ptr, flags.ptr
-        check(self.lib.odise_hip_panoptic_quality(self.h, C.byref(d)), "panoptic_quality")
-        return stats, flags
+        return d, table, stats, flags
 
     def panoptic_quality_record(self, record: DeviceArray, hw, gt: DeviceArray, gt_segments, num_categories: int,
                                 stats: Optional[DeviceArray] = None, flags: Optional[DeviceArray] = None):
@@ -573,6 +578,51 @@ class Context:
         from ._lib import split_record
         ids, table = split_record(record, hw)
         return self.panoptic_quality(ids, table, gt, gt_segments, num_categories, stats, flags)
+
+    # Boundary PQ beside PQ (include/odise_hip.h odise_hip_panoptic_quality_boundary; host restatement: panoptic_quality.image_boundary_stats)
+    def panoptic_quality_boundary(self, pred_ids: DeviceArray, pred_segments: DeviceArray, gt: DeviceArray, gt_segments, num_categories: int,
+                                  stats: Optional[DeviceArray] = None, b_stats: Optional[DeviceArray] = None,
+                                  flags: Optional[DeviceArray] = None, radius: int = 0):
+        """`panoptic_quality` with the Boundary PQ statistics beside it, one call: -> (stats, b_stats, flags).  `stats` receives exactly
+        what `panoptic_quality` adds, `b_stats` [num_categories] records the matching on min(mask IoU, boundary IoU); radius <= 0: the
+        formula of `boundary_radius`.  Fresh zeroed accumulators when none are given."""
+        from ._lib import PqBoundaryTask
+        from .panoptic_quality import STAT_DTYPE
+        d, _table, stats, flags = self._pq_desc(pred_ids, pred_segments, gt, gt_segments, num_categories, stats, flags)
+        if b_stats is None:
+            b_stats = self.zeros((int(num_categories),), STAT_DTYPE)
+        assert b_stats.dtype == STAT_DTYPE and b_stats.shape == (int(num_categories),)
+        b = PqBoundaryTask()
+        b.stats, b.radius = b_stats.ptr, int(radius)
+        check(self.lib.odise_hip_panoptic_quality_boundary(self.h, C.byref(d), C.byref(b)), "panoptic_quality_boundary")
+        return stats, b_stats, flags
+
+    def panoptic_quality_boundary_record(self, record: DeviceArray, hw, gt: DeviceArray, gt_segments, num_categories: int,
+                                         stats: Optional[DeviceArray] = None, b_stats: Optional[DeviceArray] = None,
+                                         flags: Optional[DeviceArray] = None, radius: int = 0):
+        """`panoptic_quality_boundary` of a panoptic record, as `panoptic_quality_record`."""
+        from ._lib import split_record
+        ids, table = split_record(record, hw)
+        return self.panoptic_quality_boundary(ids, table, gt, gt_segments, num_categories, stats, b_stats, flags, radius)
+
+    def segment_boundaries(self, ids: DeviceArray, table, radius: int = 0, out: Optional[DeviceArray] = None, with_area: bool = False):
+        """ids int32 [H,W] (device), table: the ids of at most 254 segments (host or device int32) -> uint8 [H,W], 1 where a pixel lies on
+        the boundary of its own segment (odise_hip_segment_boundaries; byte for byte panoptic_quality.segment_boundaries); pixels of id 0
+        and of ids absent from the table are 0.  with_area adds the boundary pixels of each table row, int64 [n] (None for an empty
+        table)."""
+        H, W = ids.shape
+        assert ids.dtype == np.int32
+        if not isinstance(table, DeviceArray):
+            table = np.ascontiguousarray(np.asarray(table, np.int64).reshape(-1), np.int32)
+            table = self.to_device(table) if table.size else None
+        n = int(np.prod(table.shape)) if table is not None else 0
+        assert table is None or table.dtype == np.int32
+        if out is None:
+            out = self.empty((H, W), np.uint8)
+        assert out.dtype == np.uint8 and out.shape == (H, W)
+        area = self.empty((n,), np.int64) if with_area and n else None
+        check(self.lib.odise_hip_segment_boundaries(self.h, _p(ids), H, W, _p(table), n, int(radius), _p(out), _p(area)), "segment_boundaries")
+        return (out, area) if with_area else out
 
     # ---- drawing a panoptic result (include/odise_hip.h odise_hip_connected_components ..; host restatement: odise_amd/visualize.py) ----
     def connected_components(self, labels: DeviceArray, out: Optional[DeviceArray] = None) -> DeviceArray:
