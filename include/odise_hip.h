@@ -497,6 +497,36 @@ int odise_hip_panoptic_quality(odise_hip_ctx* ctx, const odise_pq_desc* d);
  * the first) and its growable boundary scratch (four byte maps - both slot maps and their complements - their erosions and a spare). */
 typedef struct { odise_pq_stat* stats; int radius; } odise_pq_boundary_task;   /* device [num_categories]; radius <= 0: the formula */
 int odise_hip_panoptic_quality_boundary(odise_hip_ctx* ctx, const odise_pq_desc* d, const odise_pq_boundary_task* b);
+/* Panoptic quality of a SEMANTIC segmentation (Mask2Former tools/evaluate_pq_for_semantic_segmentation.py: the PQ number of the
+ * semantic-only evaluation sets), one picture.  Every class of the picture is one stuff segment on either side, pictures accumulate in
+ * one odise_pq_stat per class.  Host restatement: odise_amd/semseg_pq.py.
+ * Prediction, exactly one of: labels int32 [H,W], or sem_seg fp32 [K,H,W] whose first-maximum arg-max (ties to the lower class, as
+ * odise_hip_semantic_confusion takes it) is taken per pixel.  gt int32 [H,W] follows the contract of odise_hip_semantic_eval: the
+ * ignore label already mapped to K, any value outside [0,K] counts as K = VOID.  (A ground-truth value that is neither a class nor the
+ * ignore label would be a segment of an unknown category in the tool; here it is VOID.)
+ *   counts     area_pred[c] = pixels with pred == c, area_gt[c] = pixels with gt == c, inter[c] = pixels with both,
+ *              void_pred[c] = pixels with pred == c on VOID.  A class is present on a side when its area there is > 0.
+ *   matching   only a class with itself, when inter[c] > 0: union = area_pred[c] + area_gt[c] - inter[c] - void_pred[c],
+ *              iou = inter / union as the double division of the two integers; iou > 0.5 (strict): tp[c] += 1, iou[c] += iou.
+ *   fn, fp     a ground-truth class present and unmatched: fn[c] += 1.  A predicted class present and unmatched: skipped when
+ *              void_pred[c] / area_pred[c] > 0.5 (strict), otherwise fp[c] += 1.
+ * `stats` [K] is ADDED to and never cleared.  One adder per class and the pictures of a stream in order: the iou sums grow by one addend
+ * per picture, bit-identical to the tool's in picture order and from run to run.  PQ / SQ / RQ follow on the host with every class a
+ * stuff class (odise_amd/panoptic_quality.py pq_average).
+ * flags int32 [1], OR-ed: 1 = a label outside [0,K) in `labels` (the flag of odise_hip_semantic_eval); a picture that raises it adds
+ * nothing to `stats`, and the next picture counts as if it had not been there.
+ * ODISE_ERR_ARG and nothing written: a null pointer, both or neither prediction, H or W < 1, H * W > 2^29 - 1, K outside 1..12288.
+ * Scratch (4 K int32 counters, in LDS while the pixels are swept for K <= 3072) comes from the context and grows with K.
+ * Asynchronous on the context's stream. */
+int odise_hip_semantic_pq(odise_hip_ctx* ctx, const int32_t* labels, const float* sem_seg, const int32_t* gt, int K, int H, int W,
+                          odise_pq_stat* stats, int32_t* flags);
+/* odise_hip_semantic_eval(ctx, d) with these statistics beside it: conf, b_conf, classes, the RLE strings and flags exactly as that call
+ * leaves them, bit for bit, and t->stats [d->K] += what odise_hip_semantic_pq adds, from the same label map (the arg-max of a score
+ * tensor is taken once for all of it).  Needs d->gt; the statistics alone (no conf, no b_conf, no offsets) are allowed.  A caller that
+ * enqueues a picture again for its strings (capacity, max_classes) uses odise_hip_semantic_eval for that, as for the matrices.
+ * ODISE_ERR_ARG and nothing enqueued: what odise_hip_semantic_eval refuses, a null t, t->stats or d->gt, statistics not 8-byte aligned. */
+typedef struct { odise_pq_stat* stats; } odise_semseg_pq_task;   /* device [K] */
+int odise_hip_semantic_eval_pq(odise_hip_ctx* ctx, const odise_semseg_eval_desc* d, const odise_semseg_pq_task* t);
 /* The erosion stage of the call above on one id map: boundary uint8 [H,W] = 1 where the pixel lies on the boundary B(s) of its own
  * segment; ids int32 [H,W] (device); table device int32 [n] ids, n <= 254 (the first row of an id counts).  Pixels of id 0 and of ids
  * absent from the table: 0.  area int64 [n] (optional) = the pixels of each row's boundary.  radius <= 0: the formula.  Same slot and

@@ -21,6 +21,7 @@ int odise_hip_sizeof_infer_desc(void);
 int odise_hip_sizeof_pq_desc(void);
 int odise_hip_sizeof_pq_stat(void);
 int odise_hip_sizeof_pq_boundary_task(void);
+int odise_hip_sizeof_semseg_pq_task(void);
 int odise_hip_sizeof_inst_eval_desc(void);
 int odise_hip_sizeof_inst_eval_row(void);
 int odise_hip_sizeof_inst_poly_gt(void);

@@ -109,6 +109,11 @@ class SemSegEvalDesc(C.Structure):
                 ("rle", c_void_p), ("capacity", c_int64), ("offsets", c_void_p), ("area", c_void_p), ("flags", c_void_p)]
 
 
+class SemSegPqTask(C.Structure):
+    """odise_semseg_pq_task (include/odise_hip.h)."""
+    _fields_ = [("stats", c_void_p)]
+
+
 class InstEvalDesc(C.Structure):
     """odise_inst_eval_desc (include/odise_hip.h)."""
     _fields_ = [("h", c_int), ("w", c_int), ("masks", c_void_p), ("dtype", c_int), ("b", c_int), ("pad_h", c_int), ("pad_w", c_int),

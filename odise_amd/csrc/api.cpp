@@ -90,6 +90,7 @@ extern "C" int odise_hip_destroy(odise_hip_ctx* ctx) {
     odise::scratch_release(ctx->rle);
     odise::scratch_release(ctx->boundary);
     odise::scratch_release(ctx->vis);
+    odise::scratch_release(ctx->sem_pq);
     odise::pq_release(ctx);
     odise::comm_release(ctx);
     odise::probe_release(ctx);
@@ -378,6 +379,7 @@ extern "C" int odise_hip_sizeof_post_desc(void) { return (int)sizeof(odise_post_
 extern "C" int odise_hip_sizeof_infer_desc(void) { return (int)sizeof(odise_infer_desc); }
 extern "C" int odise_hip_sizeof_pq_desc(void) { return (int)sizeof(odise_pq_desc); }
 extern "C" int odise_hip_sizeof_pq_stat(void) { return (int)sizeof(odise_pq_stat); }
+extern "C" int odise_hip_sizeof_semseg_pq_task(void) { return (int)sizeof(odise_semseg_pq_task); }
 extern "C" int odise_hip_sizeof_inst_eval_desc(void) { return (int)sizeof(odise_inst_eval_desc); }
 extern "C" int odise_hip_sizeof_inst_eval_row(void) { return (int)sizeof(odise_inst_eval_row); }
 extern "C" int odise_hip_sizeof_inst_poly_gt(void) { return (int)sizeof(odise_inst_poly_gt); }

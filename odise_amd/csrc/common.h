@@ -137,6 +137,7 @@ struct odise_hip_ctx {
     odise::DeviceScratch boundary;   // eval_ops.hip: odise_hip_label_boundary / odise_hip_semantic_boundary_confusion (byte label maps, their erosions)
     odise::DeviceScratch vis;        // vis.hip: odise_hip_segment_anchors (roots and areas of the components, the anchor list, the column / row histograms)
     void* pq = nullptr;              // odise::PqScratch* (pq.hip): the pair-count matrix and the ground-truth table staging of odise_hip_panoptic_quality
+    odise::DeviceScratch sem_pq;     // sem_pq.hip: the four count vectors of odise_hip_semantic_pq, zero between pictures
 };
 
 namespace odise {
@@ -200,5 +201,8 @@ int gemm_forced(odise_hip_ctx* ctx, const odise_gemm_desc* d, int force_tile, in
 int gemm_ln(odise_hip_ctx* ctx, const odise_gemm_desc* d, const LnEpi& ln);   // 256x256 ping-pong tile, math-first epilogue
 void jpeg_release(odise_hip_ctx* ctx);
 void pq_release(odise_hip_ctx* ctx);
+// sem_pq.hip: the two launches of odise_hip_semantic_pq behind what is on the stream (exactly one of labels / sem), for eval_ops.hip
+int sem_pq_args(const char* what, int K, int H, int W);
+int sem_pq_enqueue(odise_hip_ctx* ctx, const int* labels, const float* sem, const int* gt, int K, int H, int W, odise_pq_stat* stats, int* flags);
 void comm_release(odise_hip_ctx* ctx);
 }

@@ -15,6 +15,7 @@
 //   odise_hip_semantic_eval        the whole SemSegEvaluator.process step from the prediction as it lies in HBM - the int32 label map of the
 //                                  fused arg-max, or the score tensor with the arg-max taken once into scratch: both matrices below and the
 //                                  per-class COCO RLE strings of sem_seg_predictions.json (sem_rle.hip).
+//   odise_hip_semantic_eval_pq     the same launches, then the PQ-for-semantic-segmentation statistics of the same label map (sem_pq.hip).
 //   odise_hip_label_boundary / odise_hip_semantic_boundary_confusion
 //                                  the second per-pixel job of SemSegEvaluator.process (K < 255, OpenCV importable): prediction and ground
 //                                  truth both go through _mask_to_boundary - a 3x3 grey-scale erosion behind a zero ring, repeated
@@ -485,14 +486,15 @@ extern "C" int odise_hip_semantic_boundary_confusion(odise_hip_ctx* ctx, const f
     return ODISE_OK;
 }
 
-extern "C" int odise_hip_semantic_eval(odise_hip_ctx* ctx, const odise_semseg_eval_desc* d) {
+// odise_hip_semantic_eval, and with `t` odise_hip_semantic_eval_pq: the same launches in the same order, then the PQ statistics of the same label map
+static int semantic_eval_run(odise_hip_ctx* ctx, const odise_semseg_eval_desc* d, const odise_semseg_pq_task* t) {
     ODISE_REQUIRE(ctx && d, "semantic_eval: null argument");
     ODISE_REQUIRE((d->labels != nullptr) != (d->sem_seg != nullptr), "semantic_eval: exactly one of labels / sem_seg");
     ODISE_REQUIRE(d->flags, "semantic_eval: null flags");
     const int K = d->K, H = d->H, W = d->W;
     const bool counting = d->conf || d->b_conf, strings = d->offsets != nullptr;
-    ODISE_REQUIRE(counting || strings, "semantic_eval: nothing to do (no conf, no b_conf, no offsets)");
-    ODISE_REQUIRE(!counting || d->gt, "semantic_eval: counting needs a ground truth");
+    ODISE_REQUIRE(counting || strings || t, "semantic_eval: nothing to do (no conf, no b_conf, no offsets)");
+    ODISE_REQUIRE(!(counting || t) || d->gt, "semantic_eval: counting needs a ground truth");
     ODISE_REQUIRE(H >= 1 && W >= 1 && (int64_t)H * W <= kSemEvalMaxPixels, "semantic_eval: picture size %dx%d out of range", H, W);
     ODISE_REQUIRE(K >= 1 && K <= kLdsHistCells, "semantic_eval: %d classes (1..%d)", K, kLdsHistCells);
     if (d->b_conf) ODISE_TRY(boundary_args("semantic_eval", K, H, W));
@@ -508,7 +510,7 @@ extern "C" int odise_hip_semantic_eval(odise_hip_ctx* ctx, const odise_semseg_ev
     const RleGrid RG = rle_grid(H, W);
     const int nmask = strings ? std::min(d->max_classes, K) : 0;
     SemRleScratch s{};
-    if (strings) ODISE_TRY(sem_rle_scratch(ctx, nmask, RG, K, d->sem_seg != nullptr, &s));   // count only: no label map is kept
+    if (strings || (t && d->sem_seg)) ODISE_TRY(sem_rle_scratch(ctx, nmask, RG, K, d->sem_seg != nullptr, &s));   // count only: no label map is kept
     BoundaryMaps b{};
     if (d->b_conf) ODISE_TRY(boundary_maps(ctx, H, W, 2, &b));
     else { b.G.H = H; b.G.W = W; }
@@ -537,7 +539,17 @@ extern "C" int odise_hip_semantic_eval(odise_hip_ctx* ctx, const odise_semseg_ev
     }
     if (strings)
         ODISE_TRY(sem_rle_encode(ctx, s, RG, labels, K, nmask, d->max_classes, d->classes, d->n_classes, d->rle, d->capacity, d->offsets, d->area, d->flags));
+    if (t) ODISE_TRY(sem_pq_enqueue(ctx, labels, nullptr, d->gt, K, H, W, t->stats, d->flags));   // the labels: the caller's, or the arg-max kept above
     return ODISE_OK;
+}
+
+extern "C" int odise_hip_semantic_eval(odise_hip_ctx* ctx, const odise_semseg_eval_desc* d) { return semantic_eval_run(ctx, d, nullptr); }
+
+extern "C" int odise_hip_semantic_eval_pq(odise_hip_ctx* ctx, const odise_semseg_eval_desc* d, const odise_semseg_pq_task* t) {
+    ODISE_REQUIRE(ctx && d && t && t->stats, "semantic_eval_pq: null argument, task or statistics");
+    ODISE_REQUIRE(d->gt, "semantic_eval_pq: the statistics need a ground truth");
+    ODISE_REQUIRE(((uintptr_t)t->stats & 7) == 0, "semantic_eval_pq: the statistics must be 8-byte aligned");
+    return semantic_eval_run(ctx, d, t);
 }
 
 extern "C" int odise_hip_pair_histogram(odise_hip_ctx* ctx, const int* a, const int* b, int npix, int na, int nb, int* hist) {

@@ -1,6 +1,6 @@
-// lds_hist.h — the per-block counting histogram (eval_ops.hip, pq.hip, track.hip, vis_inst.hip), the run of equal cells that a lane counts
-// in a register before it touches the histogram (pq.hip, track.hip), and the arg-max over class planes that feeds it (eval_ops.hip,
-// vis_inst.hip).
+// lds_hist.h — the per-block counting histogram (eval_ops.hip, pq.hip, sem_pq.hip, track.hip, vis_inst.hip), the run of equal cells that a
+// lane counts in a register before it touches the histogram (pq.hip, sem_pq.hip, track.hip), and the arg-max over class planes that feeds
+// it (eval_ops.hip, sem_pq.hip, vis_inst.hip).
 //
 // A block counts `n` cells in the dynamic LDS of its launch and adds the non-zero ones to the global matrix with integer atomics when it is
 // done (deterministic: integer addition commutes); a matrix of more than kLdsHistCells cells is counted in global memory directly.  Which of
@@ -49,7 +49,8 @@ struct LdsHist {
 
 // A run of equal cells counted in a register and added to the histogram when the cell changes.  LDS = H.lds, decided once per kernel: the
 // pixel loop is a template over it.  The bounds guard is for track.hip, whose cells come from bytes of retained maps (a byte is at most that
-// frame's row count: always inside); in pq.hip a cell is below H.n by construction and the guard costs one compare per change of pair.
+// frame's row count: always inside); in pq.hip a cell is below H.n by construction and the guard costs one compare per change of pair;
+// sem_pq.hip counts "no cell" as cell -1, which the guard drops.
 struct HistRun {
     int cell = 0, run = 0;
     template <bool LDS, class Cell>

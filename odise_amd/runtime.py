@@ -492,14 +492,17 @@ class Context:
     # ---- the whole SemSegEvaluator.process step (include/odise_hip.h odise_hip_semantic_eval; host restatement: odise_amd/semseg_eval.py) ----
     def semantic_eval_async(self, pred: DeviceArray, K: Optional[int] = None, gt: Optional[DeviceArray] = None, conf: Optional[DeviceArray] = None,
                             b_conf: Optional[DeviceArray] = None, flags: Optional[DeviceArray] = None, radius: int = 0, rle: bool = True,
-                            max_classes: Optional[int] = None, capacity: Optional[int] = None, bufs=None) -> "SemSegPending":
+                            max_classes: Optional[int] = None, capacity: Optional[int] = None, bufs=None,
+                            pq_stats: Optional[DeviceArray] = None) -> "SemSegPending":
         """Enqueue one SemSegEvaluator.process step: pred = labels int32 [H,W] (needs K) or sem_seg float32 [K,H,W]; gt int32 [H,W] with the
         ignore label already mapped to K.  conf / b_conf int64 [(K+1),(K+1)] are added to (with a gt and neither given, a fresh zeroed conf
         is counted; b_conf only when given), flags int32 [1] is OR-ed into (a fresh zeroed one when none is given).  rle: also the per-class
         COCO RLE strings, at most max_classes (default MAX_SEGMENTS) of them at first; `SemSegPending.result()` enqueues the call again when
         the strings did not fit the capacity or more classes are present - it reads `pred` again, so `pred` must hold the picture until
         `settle()` or `result()` has run (call `settle()` before a pooled buffer is handed on).  bufs =(bytes uint8 [capacity], meta int32 [1 + max_classes],
-        offsets-and-area int64 [2 max_classes + 1]) device arrays to use instead of fresh ones (a retry still allocates its own)."""
+        offsets-and-area int64 [2 max_classes + 1]) device arrays to use instead of fresh ones (a retry still allocates its own).
+        pq_stats [K] records (panoptic_quality.STAT_DTYPE; needs a gt): the first launch is `odise_hip_semantic_eval_pq` and also adds the
+        picture's semantic PQ statistics (`semantic_pq`) from the same label map; a retry never counts."""
         if pred.dtype == np.float32:
             assert len(pred.shape) == 3 and (K is None or int(K) == pred.shape[0]), (pred.shape, K)
             K, H, W = pred.shape
@@ -508,14 +511,17 @@ class Context:
             H, W = pred.shape
         K = int(K)
         assert gt is None or (gt.dtype == np.int32 and tuple(gt.shape) == (H, W)), "gt must be int32 [H,W]"
-        if gt is not None and conf is None and b_conf is None:
+        if gt is not None and conf is None and b_conf is None and pq_stats is None:
             conf = self.zeros((K + 1, K + 1), np.int64)
         for m in (conf, b_conf):
             assert m is None or (m.dtype == np.int64 and int(np.prod(m.shape)) == (K + 1) * (K + 1)), "conf / b_conf must be int64 [(K+1),(K+1)]"
         if flags is None:
             flags = self.zeros((1,), np.int32)
         assert flags.dtype == np.int32
-        return SemSegPending(self, pred, K, (H, W), gt, conf, b_conf, flags, int(radius), bool(rle), max_classes, capacity, bufs)
+        if pq_stats is not None:
+            from .panoptic_quality import STAT_DTYPE
+            assert gt is not None and pq_stats.dtype == STAT_DTYPE and pq_stats.shape == (K,), "pq_stats needs a gt and [K] records"
+        return SemSegPending(self, pred, K, (H, W), gt, conf, b_conf, flags, int(radius), bool(rle), max_classes, capacity, bufs, pq_stats)
 
     @staticmethod
     def sem_rle_bytes(hw) -> int:
@@ -527,6 +533,32 @@ class Context:
     def semantic_eval(self, pred: DeviceArray, K: Optional[int] = None, gt: Optional[DeviceArray] = None, **kw):
         """`semantic_eval_async(...).result()`: (classes int32 [n], RLE dicts [n], area int64 [n]) of the classes present, ascending."""
         return self.semantic_eval_async(pred, K, gt, **kw).result()
+
+    # PQ of a semantic segmentation (include/odise_hip.h odise_hip_semantic_pq; host restatement: odise_amd/semseg_pq.py)
+    def semantic_pq(self, pred: DeviceArray, gt: DeviceArray, K: Optional[int] = None, stats: Optional[DeviceArray] = None,
+                    flags: Optional[DeviceArray] = None):
+        """One picture of the PQ-for-semantic-segmentation metric, enqueued: pred = labels int32 [H,W] (needs K) or sem_seg float32
+        [K,H,W] (first-maximum arg-max); gt int32 [H,W] with the ignore label already mapped to K (anything outside [0,K] counts as K)
+        -> (stats, flags): `stats` [K] records (panoptic_quality.STAT_DTYPE) added to, `flags` int32 [1] OR-ed into (1 = a label
+        outside [0,K): that picture adds nothing); fresh zeroed ones when none are given."""
+        from .panoptic_quality import STAT_DTYPE
+        if pred.dtype == np.float32:
+            assert len(pred.shape) == 3 and (K is None or int(K) == pred.shape[0]), (pred.shape, K)
+            K, H, W = pred.shape
+            labels, sem = None, pred
+        else:
+            assert pred.dtype == np.int32 and len(pred.shape) == 2 and K is not None, (pred.dtype, pred.shape, K)
+            H, W = pred.shape
+            labels, sem = pred, None
+        K = int(K)
+        assert gt.dtype == np.int32 and tuple(gt.shape) == (H, W), "gt must be int32 [H,W]"
+        if stats is None:
+            stats = self.zeros((K,), STAT_DTYPE)
+        if flags is None:
+            flags = self.zeros((1,), np.int32)
+        assert stats.dtype == STAT_DTYPE and stats.shape == (K,) and flags.dtype == np.int32
+        check(self.lib.odise_hip_semantic_pq(self.h, _p(labels), _p(sem), _p(gt), K, H, W, _p(stats), _p(flags)), "semantic_pq")
+        return stats, flags
 
     def pair_histogram(self, a: DeviceArray, b: DeviceArray, na: int, nb: int, hist: Optional[DeviceArray] = None) -> DeviceArray:
         npix = int(np.prod(a.shape))
@@ -1315,17 +1347,18 @@ class RlePending:
 
 
 class SemSegPending:
-    """An enqueued `odise_hip_semantic_eval` call.  The matrices are counted by the first launch only, and the ground truth is let
-    go of right after it.  `settle()` reads n_classes and the offsets back (one synchronisation) and enqueues the RLE part again -
+    """An enqueued `odise_hip_semantic_eval` call (with `pq_stats`: `odise_hip_semantic_eval_pq`, the first launch and only the first).
+    The matrices and the PQ statistics are counted by the first launch only, and the ground truth is let go of right after it.  `settle()` reads n_classes and the offsets back (one synchronisation) and enqueues the RLE part again -
     without the counters - at most twice: with max_classes = n_classes when more classes are present than were asked for, and with
     exactly offsets[-1] bytes when the strings did not fit.  A retry READS `pred` AGAIN (from a score tensor it takes the whole K-plane
     arg-max again, about the cost of the first call: the labels of the first launch lay in the context's shared scratch and are gone), so
     `settle()` must run while `pred` still holds the picture; after it `pred` is let go of and `result()` reads only buffers of this
     object.  `result()` settles first when nobody has: then the caller keeps `pred` untouched until `result()`."""
 
-    def __init__(self, ctx: Context, pred, K, hw, gt, conf, b_conf, flags, radius, rle, max_classes, capacity, bufs=None):
+    def __init__(self, ctx: Context, pred, K, hw, gt, conf, b_conf, flags, radius, rle, max_classes, capacity, bufs=None, pq_stats=None):
         from ._lib import MAX_SEGMENTS
         self.ctx, self.pred, self.K, self.hw, self.conf, self.b_conf, self.flags, self.radius = ctx, pred, K, hw, conf, b_conf, flags, radius
+        self.pq_stats = pq_stats
         self.rle = rle
         self.max_classes = int(max_classes) if max_classes is not None else MAX_SEGMENTS
         self.capacity = int(capacity) if capacity is not None else Context.sem_rle_bytes(hw)
@@ -1336,7 +1369,7 @@ class SemSegPending:
             assert self.buf.nbytes >= self.capacity and self.meta.nbytes >= 4 * (1 + self.max_classes) and self.off.nbytes >= 8 * (2 * self.max_classes + 1)
         elif rle:
             self._alloc()
-        counting = gt is not None and (conf is not None or b_conf is not None)
+        counting = gt is not None and (conf is not None or b_conf is not None or pq_stats is not None)
         self._launch(gt if counting else None)
         if not rle:
             self.pred = None
@@ -1365,7 +1398,13 @@ class SemSegPending:
             n = self.max_classes
             d.max_classes, d.n_classes, d.classes = n, self.meta.ptr, self.meta.ptr + 4
             d.rle, d.capacity, d.offsets, d.area = self.buf.ptr, self.capacity, self.off.ptr, self.off.ptr + 8 * (n + 1)
-        check(self.ctx.lib.odise_hip_semantic_eval(self.ctx.h, C.byref(d)), "semantic_eval")
+        if gt is not None and self.pq_stats is not None:
+            from ._lib import SemSegPqTask
+            t = SemSegPqTask()
+            t.stats = self.pq_stats.ptr
+            check(self.ctx.lib.odise_hip_semantic_eval_pq(self.ctx.h, C.byref(d), C.byref(t)), "semantic_eval_pq")
+        else:
+            check(self.ctx.lib.odise_hip_semantic_eval(self.ctx.h, C.byref(d)), "semantic_eval")
         self.launches += 1
 
     def settle(self) -> "SemSegPending":

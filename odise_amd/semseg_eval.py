@@ -3,7 +3,9 @@
 `HipSemSegEvaluator.process` enqueues one `odise_hip_semantic_eval` per picture on the prediction as it lies in HBM - the int32 label map
 of the fused arg-max, or the score tensor - which adds to the two confusion matrices and writes the per-class RLE strings, and settles
 the picture (a retry reads the prediction again) before the model may overwrite that buffer; `evaluate` reads the strings, sums the matrices across ranks and does the arithmetic below on the host.  detectron2 is not a dependency of this
-package, so the rules are restated here and this module is their specification:
+package, so the rules are restated here and this module is their specification.  With `pq=True` the per-picture call is
+`odise_hip_semantic_eval_pq`, which also counts the PQ-for-semantic-segmentation statistics (odise_amd/semseg_pq.py: their specification)
+from the same label map, and `evaluate` appends PQ / SQ / RQ and PQ-<name> per class behind the keys below:
 
 process(inputs, outputs), per picture
     pred = output["sem_seg"].argmax(dim=0) as int; gt = the annotation as int, gt[gt == ignore_label] = num_classes
@@ -159,10 +161,11 @@ def _rank() -> int:
 
 class HipSemSegEvaluator:
     def __init__(self, ctx, class_names: Sequence[str], ignore_label: int, dataset_name: str, prefix: str = "",
-                 contiguous_id_to_dataset_id: Optional[Dict[int, int]] = None, compute_boundary_iou: Optional[bool] = None):
+                 contiguous_id_to_dataset_id: Optional[Dict[int, int]] = None, compute_boundary_iou: Optional[bool] = None, pq: bool = False):
         """class_names [K] (metadata.stuff_classes), ignore_label (metadata.ignore_label), contiguous_id_to_dataset_id
         (metadata.stuff_dataset_id_to_contiguous_id reversed, when the dataset has it); compute_boundary_iou None = K < 255, as the
-        reference decides when OpenCV is importable."""
+        reference decides when OpenCV is importable.  pq: also count the PQ-for-semantic-segmentation statistics (semseg_pq.py) in the
+        same call per picture; `evaluate` then appends PQ, SQ, RQ and PQ-<name> per class and keeps `self.pq_stats`."""
         self.ctx = ctx
         self.class_names = list(class_names)
         self.K = len(self.class_names)
@@ -176,11 +179,17 @@ class HipSemSegEvaluator:
         self.conf = self._buf.view((self.K + 1, self.K + 1), np.int64)
         self.b_conf = self._buf.view((self.K + 1, self.K + 1), np.int64, 8 * n) if self.boundary else None
         self.flags = self._buf.view((1,), np.int32, 16 * n)
+        self.pq = bool(pq)
+        if self.pq:
+            from .panoptic_quality import STAT_DTYPE
+            self.stats = ctx.empty((self.K,), STAT_DTYPE)                   # a buffer of its own: the one above stays as it is
         self.reset()
 
     def reset(self) -> None:
         from ._lib import check
         check(self.ctx.lib.odise_hip_memset(self.ctx.h, self._buf.ptr, 0, self._buf.nbytes), "memset")
+        if self.pq:
+            check(self.ctx.lib.odise_hip_memset(self.ctx.h, self.stats.ptr, 0, self.stats.nbytes), "memset")
         self._pending = []
 
     def process(self, pred, gt, file_name, pred_kept: bool = False) -> None:
@@ -200,7 +209,10 @@ class HipSemSegEvaluator:
             g = np.asarray(gt).astype(np.int32)
             g[g == self.ignore_label] = self.K
             gt = self.ctx.to_device(np.ascontiguousarray(g))
-        pending = self.ctx.semantic_eval_async(pred, self.K, gt, conf=self.conf, b_conf=self.b_conf, flags=self.flags)
+        if self.pq:
+            pending = self.ctx.semantic_eval_async(pred, self.K, gt, conf=self.conf, b_conf=self.b_conf, flags=self.flags, pq_stats=self.stats)
+        else:
+            pending = self.ctx.semantic_eval_async(pred, self.K, gt, conf=self.conf, b_conf=self.b_conf, flags=self.flags)
         if not pred_kept:
             pending.settle()
         self._pending.append((file_name, pending))
@@ -230,4 +242,11 @@ class HipSemSegEvaluator:
             os.makedirs(output_dir, exist_ok=True)
             with open(os.path.join(output_dir, "sem_seg_predictions.json"), "w") as f:
                 f.write(json.dumps(rows))
-        return {result_key(self.dataset_name, self.prefix): results(conf, b_conf, self.class_names)}
+        res = results(conf, b_conf, self.class_names)
+        if self.pq:
+            from . import distributed as D
+            from . import semseg_pq as SP
+            from .panoptic_quality import PQStats
+            self.pq_stats = D.sum_pq_stats(PQStats.from_records(self.stats.numpy()))   # K * 32 bytes; the flags travelled with gather()
+            res.update(SP.evaluator_results(self.pq_stats, self.class_names))
+        return {result_key(self.dataset_name, self.prefix): res}
