@@ -25,9 +25,9 @@ struct BoxTrackState {   // device
 }  // namespace odise
 
 struct odise_box_track {
-    int topk = 0, ttl = 0, n_pool = 0;
+    int topk = 0;
     odise::BoxTrackState* state = nullptr;
-    uint8_t* pool = nullptr;                 // [n_pool][3]
+    odise::TrackPool pool;
 };
 
 namespace odise {
@@ -92,8 +92,13 @@ __global__ void __launch_bounds__(kTrackMatchThreads) box_track_kernel(const flo
 
 static void box_track_free(odise_box_track* t) {
     if (t->state) (void)hipFree(t->state);
-    if (t->pool) (void)hipFree(t->pool);
+    track_pool_free(&t->pool);
     delete t;
+}
+
+static int box_track_clear(odise_hip_ctx* ctx, odise_box_track* t) {
+    ODISE_CHECK_HIP(hipMemsetAsync(t->state, 0, sizeof(BoxTrackState), ctx->stream));
+    return ODISE_OK;
 }
 
 }  // namespace odise
@@ -106,47 +111,20 @@ extern "C" int odise_hip_box_track_create(odise_hip_ctx* ctx, int topk, int ttl,
     ODISE_REQUIRE(ctx, "box_track_create: null context");
     ODISE_REQUIRE(out && pool_rgb, "box_track_create: null pointer");
     ODISE_REQUIRE(topk >= 1 && topk <= kInstMaxTopk, "box_track_create: topk %d outside 1..%d", topk, kInstMaxTopk);
-    ODISE_REQUIRE(ttl >= 1 && ttl <= kTrackRing, "box_track_create: ttl %d outside 1..%d", ttl, kTrackRing);
-    ODISE_REQUIRE(n_pool >= 1 && n_pool <= (1 << 20), "box_track_create: n_pool %d outside 1..2^20", n_pool);
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
     odise_box_track* t = new odise_box_track();
-    t->topk = topk; t->ttl = ttl; t->n_pool = n_pool;
-    if (hipMalloc((void**)&t->state, sizeof(BoxTrackState)) != hipSuccess || hipMalloc((void**)&t->pool, (size_t)n_pool * 3) != hipSuccess) {
-        (void)hipGetLastError();
-        box_track_free(t);
-        set_error("box_track_create: could not allocate %zu bytes", sizeof(BoxTrackState) + (size_t)n_pool * 3);
-        return ODISE_ERR_NOMEM;
-    }
-    int rc = ODISE_OK;
-    if (hipMemcpy(t->pool, pool_rgb, (size_t)n_pool * 3, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemsetAsync(t->state, 0, sizeof(BoxTrackState), ctx->stream) != hipSuccess) {
-        set_error("box_track_create: copying the colour pool or clearing the state failed");
-        rc = ODISE_ERR_HIP;
-    }
-    if (rc != ODISE_OK) {
-        (void)hipGetLastError();
-        box_track_free(t);
-        return rc;
-    }
-    *out = t;
-    return ODISE_OK;
+    t->topk = topk;
+    int rc = track_pool_create("box_track_create", ttl, pool_rgb, n_pool, &t->pool);
+    if (rc == ODISE_OK && hipMalloc((void**)&t->state, sizeof(BoxTrackState)) != hipSuccess) rc = track_no_memory("box_track_create", sizeof(BoxTrackState));
+    return track_created(rc, ctx, t, out, box_track_clear, box_track_free);
 }
 
 extern "C" int odise_hip_box_track_reset(odise_hip_ctx* ctx, odise_box_track* track) {
-    ODISE_REQUIRE(ctx, "box_track_reset: null context");
-    ODISE_REQUIRE(track, "box_track_reset: null tracker");
-    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    ODISE_CHECK_HIP(hipMemsetAsync(track->state, 0, sizeof(BoxTrackState), ctx->stream));
-    return ODISE_OK;
+    return track_reset("box_track_reset", ctx, track, box_track_clear);
 }
 
 extern "C" int odise_hip_box_track_destroy(odise_hip_ctx* ctx, odise_box_track* track) {
-    ODISE_REQUIRE(ctx, "box_track_destroy: null context");
-    ODISE_REQUIRE(track, "box_track_destroy: null tracker");
-    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // frames in flight read its memory
-    box_track_free(track);
-    return ODISE_OK;
+    return track_destroy("box_track_destroy", ctx, track, box_track_free);
 }
 
 extern "C" int odise_hip_box_track_frame(odise_hip_ctx* ctx, const odise_box_track_desc* d) {
@@ -155,19 +133,11 @@ extern "C" int odise_hip_box_track_frame(odise_hip_ctx* ctx, const odise_box_tra
     ODISE_REQUIRE(d->track && d->boxes && d->colors, "box_track_frame: null pointer");
     const odise_box_track* t = d->track;
     ODISE_REQUIRE(d->topk == t->topk, "box_track_frame: a frame of %d boxes for a tracker of %d", d->topk, t->topk);
-    ODISE_REQUIRE(d->live_cap >= 0 && d->iou_cap >= 0, "box_track_frame: negative cap (live_cap %d, iou_cap %d)", d->live_cap, d->iou_cap);
-    ODISE_REQUIRE(!d->live || d->n_live, "box_track_frame: live without n_live");
-    ODISE_REQUIRE((((uintptr_t)d->boxes | (uintptr_t)d->inst_table | (uintptr_t)d->inst_scores | (uintptr_t)d->live | (uintptr_t)d->n_live) & 3) == 0 &&
-                      ((uintptr_t)d->iou & 7) == 0,
-                  "box_track_frame: boxes / inst_table / inst_scores / live / n_live must be 4-byte aligned, iou 8-byte aligned");
+    ODISE_TRY(track_check_dumps("box_track_frame", d));
+    ODISE_REQUIRE((((uintptr_t)d->boxes | (uintptr_t)d->inst_table | (uintptr_t)d->inst_scores) & 3) == 0,
+                  "box_track_frame: boxes / inst_table / inst_scores must be 4-byte aligned");
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    TrackMatchIo io;
-    io.pool = t->pool; io.n_pool = t->n_pool; io.ttl = t->ttl;
-    io.colors = d->colors; io.edge_colors = d->edge_colors;
-    io.live_out = d->live; io.live_cap = d->live_cap; io.n_live_out = (int*)d->n_live;
-    io.iou_out = d->iou; io.iou_cap = d->iou_cap;
     hipLaunchKernelGGL(box_track_kernel, dim3(1), dim3(kTrackMatchThreads), 0, ctx->stream, d->boxes, (const int*)d->inst_table, d->inst_scores, t->topk,
-                       d->min_score, t->state, io);
-    ODISE_CHECK_HIP(hipGetLastError());
-    return ODISE_OK;
+                       d->min_score, t->state, track_match_io(t->pool, d));
+    return track_match_launched(ctx, nullptr, 0);   // one launch: nothing was counted before it
 }

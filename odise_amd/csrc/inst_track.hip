@@ -33,14 +33,14 @@ struct InstTrackState {   // device
 }  // namespace odise
 
 struct odise_inst_track {
-    int H = 0, W = 0, topk = 0, ttl = 0, n_pool = 0, slots = 0;
+    int H = 0, W = 0, topk = 0, slots = 0;
     int frame = 0;                           // frames since the reset, counted on the host: it chooses the slot the pack launch writes
     odise::RleGrid G = {};
     odise::InstTrackState* state = nullptr;
     odise::u64* ring = nullptr;              // [slots][topk][G.nw]
     int* inter = nullptr;                    // [kTrackLiveCap][topk], zero between calls
     int* area = nullptr;                     // [topk] areas (0 = not an instance of the frame) | [topk] classes
-    uint8_t* pool = nullptr;                 // [n_pool][3]
+    odise::TrackPool pool;
 };
 
 namespace odise {
@@ -165,7 +165,7 @@ static void inst_track_free(odise_inst_track* t) {
     if (t->ring) (void)hipFree(t->ring);
     if (t->inter) (void)hipFree(t->inter);
     if (t->area) (void)hipFree(t->area);
-    if (t->pool) (void)hipFree(t->pool);
+    track_pool_free(&t->pool);
     delete t;
 }
 
@@ -186,11 +186,7 @@ static int inst_track_check_args(const odise_inst_track_desc* d) {
     const odise_inst_track* t = d->track;
     ODISE_REQUIRE(d->h == t->H && d->w == t->W && d->topk == t->topk, "inst_track_frame: a %dx%d frame of %d masks for a tracker of %dx%d and %d",
                   d->h, d->w, d->topk, t->H, t->W, t->topk);
-    ODISE_REQUIRE(d->live_cap >= 0 && d->iou_cap >= 0, "inst_track_frame: negative cap (live_cap %d, iou_cap %d)", d->live_cap, d->iou_cap);
-    ODISE_REQUIRE(!d->live || d->n_live, "inst_track_frame: live without n_live");
-    ODISE_REQUIRE((((uintptr_t)d->live | (uintptr_t)d->n_live) & 3) == 0 && ((uintptr_t)d->iou & 7) == 0,
-                  "inst_track_frame: live / n_live must be 4-byte aligned, iou 8-byte aligned");
-    return ODISE_OK;
+    return track_check_dumps("inst_track_frame", d);
 }
 
 }  // namespace odise
@@ -203,53 +199,28 @@ extern "C" int odise_hip_inst_track_create(odise_hip_ctx* ctx, int H, int W, int
     ODISE_REQUIRE(out && pool_rgb, "inst_track_create: null pointer");
     ODISE_TRY(vis_check_size("inst_track_create", H, W));
     ODISE_REQUIRE(topk >= 1 && topk <= kInstMaxTopk, "inst_track_create: topk %d outside 1..%d", topk, kInstMaxTopk);
-    ODISE_REQUIRE(ttl >= 1 && ttl <= kTrackRing, "inst_track_create: ttl %d outside 1..%d", ttl, kTrackRing);
-    ODISE_REQUIRE(n_pool >= 1 && n_pool <= (1 << 20), "inst_track_create: n_pool %d outside 1..2^20", n_pool);
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
     odise_inst_track* t = new odise_inst_track();
-    t->H = H; t->W = W; t->topk = topk; t->ttl = ttl; t->n_pool = n_pool; t->slots = ttl + 1;
+    t->H = H; t->W = W; t->topk = topk;
     t->G = rle_grid(H, W);
-    const size_t ring_bytes = (size_t)t->slots * topk * (size_t)t->G.nw * sizeof(u64);
-    const size_t bytes = sizeof(InstTrackState) + ring_bytes + inst_track_inter_bytes(t) + (size_t)2 * topk * sizeof(int) + (size_t)n_pool * 3;
-    const bool ok = hipMalloc((void**)&t->state, sizeof(InstTrackState)) == hipSuccess && hipMalloc((void**)&t->ring, ring_bytes) == hipSuccess &&
-                    hipMalloc((void**)&t->inter, inst_track_inter_bytes(t)) == hipSuccess &&
-                    hipMalloc((void**)&t->area, (size_t)2 * topk * sizeof(int)) == hipSuccess &&
-                    hipMalloc((void**)&t->pool, (size_t)n_pool * 3) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        inst_track_free(t);
-        set_error("inst_track_create: could not allocate %zu bytes", bytes);
-        return ODISE_ERR_NOMEM;
+    int rc = track_pool_create("inst_track_create", ttl, pool_rgb, n_pool, &t->pool);
+    if (rc == ODISE_OK) {
+        t->slots = ttl + 1;
+        const size_t ring_bytes = (size_t)t->slots * topk * (size_t)t->G.nw * sizeof(u64);
+        const bool ok = hipMalloc((void**)&t->state, sizeof(InstTrackState)) == hipSuccess && hipMalloc((void**)&t->ring, ring_bytes) == hipSuccess &&
+                        hipMalloc((void**)&t->inter, inst_track_inter_bytes(t)) == hipSuccess &&
+                        hipMalloc((void**)&t->area, (size_t)2 * topk * sizeof(int)) == hipSuccess;
+        if (!ok) rc = track_no_memory("inst_track_create", sizeof(InstTrackState) + ring_bytes + inst_track_inter_bytes(t) + (size_t)2 * topk * sizeof(int));
     }
-    int rc = ODISE_OK;
-    if (hipMemcpy(t->pool, pool_rgb, (size_t)n_pool * 3, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("inst_track_create: copying the colour pool failed");
-        rc = ODISE_ERR_HIP;
-    }
-    if (rc == ODISE_OK) rc = inst_track_clear(ctx, t);
-    if (rc != ODISE_OK) {
-        (void)hipGetLastError();
-        inst_track_free(t);
-        return rc;
-    }
-    *out = t;
-    return ODISE_OK;
+    return track_created(rc, ctx, t, out, inst_track_clear, inst_track_free);
 }
 
 extern "C" int odise_hip_inst_track_reset(odise_hip_ctx* ctx, odise_inst_track* track) {
-    ODISE_REQUIRE(ctx, "inst_track_reset: null context");
-    ODISE_REQUIRE(track, "inst_track_reset: null tracker");
-    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    return inst_track_clear(ctx, track);
+    return track_reset("inst_track_reset", ctx, track, inst_track_clear);
 }
 
 extern "C" int odise_hip_inst_track_destroy(odise_hip_ctx* ctx, odise_inst_track* track) {
-    ODISE_REQUIRE(ctx, "inst_track_destroy: null context");
-    ODISE_REQUIRE(track, "inst_track_destroy: null tracker");
-    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // frames in flight read its memory
-    inst_track_free(track);
-    return ODISE_OK;
+    return track_destroy("inst_track_destroy", ctx, track, inst_track_free);
 }
 
 extern "C" int odise_hip_inst_track_frame(odise_hip_ctx* ctx, const odise_inst_track_desc* d) {
@@ -275,18 +246,9 @@ extern "C" int odise_hip_inst_track_frame(odise_hip_ctx* ctx, const odise_inst_t
     hipLaunchKernelGGL(inst_track_inter_kernel, sp.grid, dim3(256), 0, ctx->stream, (const u64*)t->ring, (const InstTrackState*)t->state, table,
                        (const int*)t->area, (const int*)cls, topk, t->slots, new_slot, G.nw, sp.per, t->inter);
     ODISE_CHECK_HIP(hipGetLastError());
-    TrackMatchIo io;
-    io.pool = t->pool; io.n_pool = t->n_pool; io.ttl = t->ttl;
-    io.colors = d->colors; io.edge_colors = d->edge_colors;
-    io.live_out = d->live; io.live_cap = d->live_cap; io.n_live_out = (int*)d->n_live;
-    io.iou_out = d->iou; io.iou_cap = d->iou_cap;
     hipLaunchKernelGGL(inst_track_match_kernel, dim3(1), dim3(kTrackMatchThreads), 0, ctx->stream, t->inter, table, (const int*)t->area, (const int*)cls,
-                       t->state, topk, t->frame, io);
-    const hipError_t launched = hipGetLastError();
-    if (launched != hipSuccess) {   // the intersections are counted and nothing will clear them
-        (void)hipMemsetAsync(t->inter, 0, inst_track_inter_bytes(t), ctx->stream);
-        ODISE_CHECK_HIP(launched);
-    }
+                       t->state, topk, t->frame, track_match_io(t->pool, d));
+    ODISE_TRY(track_match_launched(ctx, t->inter, inst_track_inter_bytes(t)));   // the intersections are counted
     t->frame += 1;
     return ODISE_OK;
 }

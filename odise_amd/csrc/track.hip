@@ -37,12 +37,12 @@ struct TrackState {   // device
 }  // namespace odise
 
 struct odise_track {
-    int H = 0, W = 0, ttl = 0, n_pool = 0;
+    int H = 0, W = 0;
     int64_t map_stride = 0;                  // bytes between ring maps (npix rounded up to 16)
     odise::TrackState* state = nullptr;
     uint8_t* maps = nullptr;                 // [kTrackRing][map_stride]
     int* matrix = nullptr;                   // [kTrackMatrixCells], zero between calls
-    uint8_t* pool = nullptr;                 // [n_pool][3]
+    odise::TrackPool pool;
 };
 
 namespace odise {
@@ -227,7 +227,7 @@ static void track_free(odise_track* t) {
     if (t->state) (void)hipFree(t->state);
     if (t->maps) (void)hipFree(t->maps);
     if (t->matrix) (void)hipFree(t->matrix);
-    if (t->pool) (void)hipFree(t->pool);
+    track_pool_free(&t->pool);
     delete t;
 }
 
@@ -244,11 +244,8 @@ static int track_check_args(const odise_track_desc* d) {
     ODISE_TRY(vis_check_size("track_frame", d->H, d->W));
     ODISE_REQUIRE(d->H == d->track->H && d->W == d->track->W, "track_frame: a %dx%d frame for a tracker of %dx%d", d->H, d->W, d->track->H,
                   d->track->W);
-    ODISE_REQUIRE(d->live_cap >= 0 && d->iou_cap >= 0, "track_frame: negative cap (live_cap %d, iou_cap %d)", d->live_cap, d->iou_cap);
-    ODISE_REQUIRE(!d->live || d->n_live, "track_frame: live without n_live");
-    ODISE_REQUIRE(((uintptr_t)d->pred_ids & 3) == 0 && ((uintptr_t)d->pred_segments & 3) == 0 && ((uintptr_t)d->live & 3) == 0 &&
-                      ((uintptr_t)d->n_live & 3) == 0 && ((uintptr_t)d->iou & 7) == 0,
-                  "track_frame: int32 buffers must be 4-byte aligned, iou 8-byte aligned");
+    ODISE_TRY(track_check_dumps("track_frame", d));
+    ODISE_REQUIRE((((uintptr_t)d->pred_ids | (uintptr_t)d->pred_segments) & 3) == 0, "track_frame: pred_ids / pred_segments must be 4-byte aligned");
     return ODISE_OK;
 }
 
@@ -260,53 +257,23 @@ extern "C" int odise_hip_track_create(odise_hip_ctx* ctx, int H, int W, int ttl,
     ODISE_REQUIRE(ctx, "track_create: null context");
     ODISE_REQUIRE(out && pool_rgb, "track_create: null pointer");
     ODISE_TRY(vis_check_size("track_create", H, W));
-    ODISE_REQUIRE(ttl >= 1 && ttl <= kTrackRing, "track_create: ttl %d outside 1..%d", ttl, kTrackRing);
-    ODISE_REQUIRE(n_pool >= 1 && n_pool <= (1 << 20), "track_create: n_pool %d outside 1..2^20", n_pool);
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
     odise_track* t = new odise_track();
-    t->H = H; t->W = W; t->ttl = ttl; t->n_pool = n_pool;
+    t->H = H; t->W = W;
     t->map_stride = round_up((int64_t)H * W, 16);
-    const size_t bytes = sizeof(TrackState) + (size_t)kTrackRing * t->map_stride + (size_t)kTrackMatrixCells * sizeof(int) + (size_t)n_pool * 3;
-    const bool ok = hipMalloc((void**)&t->state, sizeof(TrackState)) == hipSuccess &&
-                    hipMalloc((void**)&t->maps, (size_t)kTrackRing * t->map_stride) == hipSuccess &&
-                    hipMalloc((void**)&t->matrix, (size_t)kTrackMatrixCells * sizeof(int)) == hipSuccess &&
-                    hipMalloc((void**)&t->pool, (size_t)n_pool * 3) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        track_free(t);
-        set_error("track_create: could not allocate %zu bytes", bytes);
-        return ODISE_ERR_NOMEM;
+    int rc = track_pool_create("track_create", ttl, pool_rgb, n_pool, &t->pool);
+    if (rc == ODISE_OK) {
+        const bool ok = hipMalloc((void**)&t->state, sizeof(TrackState)) == hipSuccess &&
+                        hipMalloc((void**)&t->maps, (size_t)kTrackRing * t->map_stride) == hipSuccess &&
+                        hipMalloc((void**)&t->matrix, (size_t)kTrackMatrixCells * sizeof(int)) == hipSuccess;
+        if (!ok) rc = track_no_memory("track_create", sizeof(TrackState) + (size_t)kTrackRing * t->map_stride + (size_t)kTrackMatrixCells * sizeof(int));
     }
-    int rc = ODISE_OK;
-    if (hipMemcpy(t->pool, pool_rgb, (size_t)n_pool * 3, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("track_create: copying the colour pool failed");
-        rc = ODISE_ERR_HIP;
-    }
-    if (rc == ODISE_OK) rc = track_clear(ctx, t);
-    if (rc != ODISE_OK) {
-        (void)hipGetLastError();
-        track_free(t);
-        return rc;
-    }
-    *out = t;
-    return ODISE_OK;
+    return track_created(rc, ctx, t, out, track_clear, track_free);
 }
 
-extern "C" int odise_hip_track_reset(odise_hip_ctx* ctx, odise_track* track) {
-    ODISE_REQUIRE(ctx, "track_reset: null context");
-    ODISE_REQUIRE(track, "track_reset: null tracker");
-    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    return track_clear(ctx, track);
-}
+extern "C" int odise_hip_track_reset(odise_hip_ctx* ctx, odise_track* track) { return track_reset("track_reset", ctx, track, track_clear); }
 
-extern "C" int odise_hip_track_destroy(odise_hip_ctx* ctx, odise_track* track) {
-    ODISE_REQUIRE(ctx, "track_destroy: null context");
-    ODISE_REQUIRE(track, "track_destroy: null tracker");
-    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
-    ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // frames in flight read its memory
-    track_free(track);
-    return ODISE_OK;
-}
+extern "C" int odise_hip_track_destroy(odise_hip_ctx* ctx, odise_track* track) { return track_destroy("track_destroy", ctx, track, track_free); }
 
 extern "C" int odise_hip_track_frame(odise_hip_ctx* ctx, const odise_track_desc* d) {
     ODISE_REQUIRE(ctx, "track_frame: null context");
@@ -320,12 +287,9 @@ extern "C" int odise_hip_track_frame(odise_hip_ctx* ctx, const odise_track_desc*
     hipLaunchKernelGGL(track_pixel_kernel, dim3(blocks), dim3(256), lds_hist_bytes(lds_cells), ctx->stream, (const int*)d->pred_ids,
                        (const int*)d->pred_segments, (const TrackState*)t->state, t->maps, t->map_stride, npix, vec, lds_cells, t->matrix);
     ODISE_CHECK_HIP(hipGetLastError());
+    // the kernel keeps its loose __restrict__ parameters: with the struct by value a frame measured 1.3 us longer (profiles/tracker_host_refactor.json)
+    const TrackMatchIo io = track_match_io(t->pool, d);
     hipLaunchKernelGGL(track_match_kernel, dim3(1), dim3(kTrackMatchThreads), 0, ctx->stream, t->matrix, (const int*)d->pred_segments, t->state,
-                       (const uint8_t*)t->pool, t->n_pool, t->ttl, d->colors, d->live, d->live_cap, (int*)d->n_live, d->iou, d->iou_cap);
-    const hipError_t launched = hipGetLastError();
-    if (launched != hipSuccess) {   // the pixel pass has counted and nothing will clear its counts
-        (void)hipMemsetAsync(t->matrix, 0, (size_t)kTrackMatrixCells * sizeof(int), ctx->stream);
-        ODISE_CHECK_HIP(launched);
-    }
-    return ODISE_OK;
+                       io.pool, io.n_pool, io.ttl, io.colors, io.live_out, io.live_cap, io.n_live_out, io.iou_out, io.iou_cap);
+    return track_match_launched(ctx, t->matrix, (size_t)kTrackMatrixCells * sizeof(int));   // the pixel pass has counted
 }

@@ -1,7 +1,8 @@
 // track_match.h — what the colour trackers share (track.hip: panoptic things, a byte map per retained frame; inst_track.hip: instance
 // masks, packed words per retained frame; box_track.hip: instance boxes, four floats per live row): the limits of the live list and the one-block match / colour / compact step of detectron2's
 // VideoVisualizer._assign_colors (the rule: include/odise_hip.h above odise_hip_track_frame; host restatement: odise_amd/video.py).
-// Where the IoU comes from is the caller's business: it hands in a functor.
+// Where the IoU comes from is the caller's business: it hands in a functor.  Behind the device code, the host half of the three files:
+// the colour pool, the end of create / reset / destroy, the dump checks, the TrackMatchIo of a descriptor, the tail of a frame.
 #pragma once
 #include "common.h"
 #include "rgb.h"
@@ -130,6 +131,113 @@ __device__ __forceinline__ TrackMatched track_match_block(int n, const int* tab,
     }
     if (tid == 0 && io.n_live_out) io.n_live_out[0] = res.total;
     return res;
+}
+
+// ---- the host half: what odise_hip_track_* / odise_hip_inst_track_* / odise_hip_box_track_* do alike.  `who` is the entry point's
+// name, the front of every refusal.  A tracker keeps its own state struct, buffers, size checks, `clear` and `free`. ----
+
+struct TrackPool {               // a tracker's share of TrackMatchIo: its colour pool on the device, and its ttl
+    uint8_t* rgb = nullptr;      // [n][3]
+    int n = 0, ttl = 0;
+};
+
+static inline int track_no_memory(const char* who, size_t bytes) {
+    (void)hipGetLastError();
+    set_error("%s: could not allocate %zu bytes", who, bytes);
+    return ODISE_ERR_NOMEM;
+}
+
+static inline void track_pool_free(TrackPool* p) {
+    if (p->rgb) (void)hipFree(p->rgb);
+    p->rgb = nullptr;
+}
+
+// The limits of ttl and n_pool, then the pool: allocated and filled from pool_rgb (HOST [n_pool][3]) by a synchronous copy.  A pool
+// that was refused holds nothing.
+static inline int track_pool_create(const char* who, int ttl, const uint8_t* pool_rgb, int n_pool, TrackPool* p) {
+    ODISE_REQUIRE(ttl >= 1 && ttl <= kTrackRing, "%s: ttl %d outside 1..%d", who, ttl, kTrackRing);
+    ODISE_REQUIRE(n_pool >= 1 && n_pool <= (1 << 20), "%s: n_pool %d outside 1..2^20", who, n_pool);
+    if (hipMalloc((void**)&p->rgb, (size_t)n_pool * 3) != hipSuccess) {
+        p->rgb = nullptr;
+        return track_no_memory(who, (size_t)n_pool * 3);
+    }
+    if (hipMemcpy(p->rgb, pool_rgb, (size_t)n_pool * 3, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        track_pool_free(p);
+        set_error("%s: copying the colour pool failed", who);
+        return ODISE_ERR_HIP;
+    }
+    p->n = n_pool;
+    p->ttl = ttl;
+    return ODISE_OK;
+}
+
+// The end of every *_create: rc = what allocating gave; a tracker that cannot be cleared is freed, one that can is handed out.
+template <class T>
+static int track_created(int rc, odise_hip_ctx* ctx, T* t, T** out, int (*clear)(odise_hip_ctx*, T*), void (*free_)(T*)) {
+    if (rc == ODISE_OK) rc = clear(ctx, t);
+    if (rc != ODISE_OK) {
+        (void)hipGetLastError();
+        free_(t);
+        return rc;
+    }
+    *out = t;
+    return ODISE_OK;
+}
+
+template <class T>
+static int track_reset(const char* who, odise_hip_ctx* ctx, T* t, int (*clear)(odise_hip_ctx*, T*)) {
+    ODISE_REQUIRE(ctx, "%s: null context", who);
+    ODISE_REQUIRE(t, "%s: null tracker", who);
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    return clear(ctx, t);
+}
+
+template <class T>
+static int track_destroy(const char* who, odise_hip_ctx* ctx, T* t, void (*free_)(T*)) {
+    ODISE_REQUIRE(ctx, "%s: null context", who);
+    ODISE_REQUIRE(t, "%s: null tracker", who);
+    ODISE_CHECK_HIP(hipSetDevice(ctx->device));
+    ODISE_CHECK_HIP(hipStreamSynchronize(ctx->stream));   // frames in flight read its memory
+    free_(t);
+    return ODISE_OK;
+}
+
+// The dump arguments of a frame descriptor (odise_track_desc, odise_inst_track_desc and odise_box_track_desc name them alike)
+template <class Desc>
+static int track_check_dumps(const char* who, const Desc* d) {
+    ODISE_REQUIRE(d->live_cap >= 0 && d->iou_cap >= 0, "%s: negative cap (live_cap %d, iou_cap %d)", who, d->live_cap, d->iou_cap);
+    ODISE_REQUIRE(!d->live || d->n_live, "%s: live without n_live", who);
+    ODISE_REQUIRE((((uintptr_t)d->live | (uintptr_t)d->n_live) & 3) == 0 && ((uintptr_t)d->iou & 7) == 0,
+                  "%s: live / n_live must be 4-byte aligned, iou 8-byte aligned", who);
+    return ODISE_OK;
+}
+
+// edge_colors of a descriptor that has the member; odise_track_desc has none
+template <class Desc>
+static auto track_edge_colors(const Desc* d, int) -> decltype(d->edge_colors) { return d->edge_colors; }
+template <class Desc>
+static uint8_t* track_edge_colors(const Desc*, long) { return nullptr; }
+
+template <class Desc>
+static TrackMatchIo track_match_io(const TrackPool& p, const Desc* d) {
+    TrackMatchIo io;
+    io.pool = p.rgb; io.n_pool = p.n; io.ttl = p.ttl;
+    io.colors = d->colors; io.edge_colors = track_edge_colors(d, 0);
+    io.live_out = d->live; io.live_cap = d->live_cap; io.n_live_out = (int*)d->n_live;
+    io.iou_out = d->iou; io.iou_cap = d->iou_cap;
+    return io;
+}
+
+// After the match launch, the last of a frame.  When it failed to launch, nothing will clear what the launches before it counted
+// (`counts`, zero between calls): that is done here.
+static inline int track_match_launched(odise_hip_ctx* ctx, void* counts, size_t bytes) {
+    const hipError_t launched = hipGetLastError();
+    if (launched != hipSuccess) {
+        if (bytes) (void)hipMemsetAsync(counts, 0, bytes, ctx->stream);
+        ODISE_CHECK_HIP(launched);
+    }
+    return ODISE_OK;
 }
 
 }  // namespace odise

@@ -2,7 +2,8 @@
 arithmetic of COCOPanopticEvaluator.evaluate, which stays on the host.
 
 `image_stats` is panopticapi's `pq_compute_single_core` for one picture, written the way it is written there - `np.unique` over
-`gt * 2**24 + pred`, dictionaries and Python loops - with the cases in which that code raises turned into flags:
+`gt * 2**24 + pred`, dictionaries and Python loops - with the cases in which that code raises turned into flags.  The rule stands once, in
+`_image_stats`; `image_stats` and `image_boundary_stats` both call it, the second with its boundary counts:
 
     pred area of a segment   its pixels in the predicted map
     inter[g, p]              pixels with ground-truth id g and predicted id p; VOID is id 0 on both sides
@@ -109,13 +110,10 @@ def gt_table(gt_segments) -> np.ndarray:
     return np.asarray(gt_segments, np.int64).reshape(-1, 4).astype(np.int32)
 
 
-def image_stats(pan_gt, gt_segments, pan_pred, pred_segments, C: int, trace: dict | None = None, into: PQStats | None = None):
-    """One picture.  pan_gt / pan_pred: integer id maps of one shape; gt_segments rows (id, category_id, iscrowd, area); pred_segments rows
-    (id, isthing, category_id); categories in 0..C-1 on both sides.  -> (PQStats, flags).  Raises nothing: a picture with a flag adds
-    nothing.  `into`: the statistics of the pictures so far, added to pair by pair (and returned) - the way the evaluator's one PQStat
-    runs through a stream of pictures, which is not the same floating-point sum as adding per-picture totals.  `trace` (optional dict)
-    receives what happened on the way: candidates rejected at iou <= 0.5, false positives skipped through VOID alone and through a crowd
-    region."""
+def _image_stats(pan_gt, gt_segments, pan_pred, pred_segments, C: int, into, trace, boundary=None):
+    """The one body of the per-picture rule (the module docstring), behind `image_stats` and `image_boundary_stats`.  `boundary`: None, or
+    a function of the two id lists of the tables that returns b_iou(g, p); it is called once a picture has no flag, a candidate then
+    counts with min(iou, b_iou(g, p)), and `trace` also receives `demoted` and `lowered`."""
     stats = into if into is not None else PQStats(C)
     assert len(stats) == C
     gt_rows = [tuple(int(v) for v in r) for r in np.asarray(gt_segments, np.int64).reshape(-1, 4)]
@@ -145,119 +143,7 @@ def image_stats(pan_gt, gt_segments, pan_pred, pred_segments, C: int, trace: dic
 
     keys, cnt = np.unique(pan_gt * OFFSET + pan_pred, return_counts=True)
     inter = {(int(k) // OFFSET, int(k) % OFFSET): int(c) for k, c in zip(keys, cnt)}
-
-    gt_matched, pred_matched = set(), set()
-    rejected = 0
-    for (g, p), n in inter.items():                      # np.unique sorts: ascending (g, p)
-        if g not in gt_row_of or p not in pred_row_of:
-            continue
-        gi, pi = gt_row_of[g], pred_row_of[p]
-        _, g_cat, g_crowd, g_area = gt_rows[gi]
-        if g_crowd == 1 or g_cat != pred_rows[pi][2]:
-            continue
-        union = area_pred[p] + g_area - n - inter.get((VOID, p), 0)
-        if union <= 0:
-            continue
-        iou = n / union
-        if iou > 0.5:
-            stats.tp[g_cat] += 1
-            stats.iou[g_cat] += iou
-            gt_matched.add(gi)
-            pred_matched.add(pi)
-        else:
-            rejected += 1
-
-    crowd_of = {}
-    for gi, (g, g_cat, g_crowd, _) in enumerate(gt_rows):
-        if gi in gt_matched:
-            continue
-        if g_crowd == 1:
-            crowd_of[g_cat] = gi
-            continue
-        stats.fn[g_cat] += 1
-
-    skipped_void = skipped_crowd = 0
-    for pi, (p, _, p_cat) in enumerate(pred_rows):
-        if pi in pred_matched:
-            continue
-        void = inter.get((VOID, p), 0)
-        ign = void
-        if p_cat in crowd_of:
-            gi = crowd_of[p_cat]
-            if gt_row_of.get(gt_rows[gi][0]) == gi:
-                ign += inter.get((gt_rows[gi][0], p), 0)
-        if ign / area_pred[p] > 0.5:
-            if void / area_pred[p] > 0.5:
-                skipped_void += 1
-            else:
-                skipped_crowd += 1
-            continue
-        stats.fp[p_cat] += 1
-    if trace is not None:
-        trace.update(rejected=rejected, skipped_void=skipped_void, skipped_crowd=skipped_crowd)
-    return stats, flags
-
-
-def segment_boundaries(pan, table, radius=None) -> np.ndarray:
-    """uint8 [H, W]: 1 where a pixel lies on the boundary B(s) of its own segment, for the segments whose ids `table` lists; pixels of id 0
-    and of ids absent from the table are 0.  Literal: one binary mask per id through instance_eval.mask_boundary (the segments are
-    disjoint, so their boundaries are too).  radius None (or <= 0): sem_boundary.boundary_radius(H, W)."""
-    from .instance_eval import mask_boundary
-    pan = np.asarray(pan).astype(np.int64)
-    assert pan.ndim == 2, pan.shape
-    out = np.zeros(pan.shape, np.uint8)
-    for i in dict.fromkeys(int(v) for v in np.asarray(table, np.int64).reshape(-1)):
-        if i != VOID:
-            out |= mask_boundary((pan == i)[None], radius)[0]
-    return out
-
-
-def image_boundary_stats(pan_gt, gt_segments, pan_pred, pred_segments, C: int, radius=None, into: PQStats | None = None,
-                         trace: dict | None = None):
-    """`image_stats` with min(iou, boundary iou) in place of iou (the rule: the module docstring).  pan_gt / pan_pred must be [H, W] maps.
-    -> (PQStats, flags); `into` as there.  `trace` receives, beside the three counts of `image_stats` (rejected: candidates with
-    iou_b <= 0.5), `demoted`, the pairs with iou > 0.5 >= iou_b, and `lowered`, the pairs matched with b_iou < iou."""
-    stats = into if into is not None else PQStats(C)
-    assert len(stats) == C
-    gt_rows = [tuple(int(v) for v in r) for r in np.asarray(gt_segments, np.int64).reshape(-1, 4)]
-    pred_rows = [tuple(int(v) for v in r) for r in np.asarray(pred_segments, np.int64).reshape(-1, 3)]
-    map_gt, map_pred = np.asarray(pan_gt).astype(np.int64), np.asarray(pan_pred).astype(np.int64)
-    assert map_gt.ndim == 2 and map_gt.shape == map_pred.shape, (map_gt.shape, map_pred.shape)
-    pan_gt, pan_pred = map_gt.reshape(-1), map_pred.reshape(-1)
-    gt_row_of, pred_row_of = {}, {}
-    for i, r in enumerate(gt_rows):
-        if r[0] != VOID:
-            gt_row_of.setdefault(r[0], i)
-    for i, r in enumerate(pred_rows):
-        if r[0] != VOID:
-            pred_row_of.setdefault(r[0], i)
-
-    labels, cnt = np.unique(pan_pred, return_counts=True)
-    area_pred = {int(l): int(c) for l, c in zip(labels, cnt)}
-    flags = 0
-    if any(l != VOID and l not in pred_row_of for l in area_pred):
-        flags |= FLAG_MISSING_ID
-    if any(pred_row_of.get(r[0]) != i or r[0] not in area_pred for i, r in enumerate(pred_rows)):
-        flags |= FLAG_EMPTY_ROW
-    if any(not 0 <= r[2] < C for r in pred_rows):
-        flags |= FLAG_BAD_CATEGORY
-    if flags:
-        return stats, flags
-
-    keys, cnt = np.unique(pan_gt * OFFSET + pan_pred, return_counts=True)
-    inter = {(int(k) // OFFSET, int(k) % OFFSET): int(c) for k, c in zip(keys, cnt)}
-    # the boundaries: pixels of B(g), of B(p), of both
-    on_gt = segment_boundaries(map_gt, list(gt_row_of), radius).reshape(-1) != 0
-    on_pred = segment_boundaries(map_pred, list(pred_row_of), radius).reshape(-1) != 0
-    labels, cnt = np.unique(pan_gt[on_gt], return_counts=True)
-    b_area_gt = {int(l): int(c) for l, c in zip(labels, cnt)}
-    labels, cnt = np.unique(pan_pred[on_pred], return_counts=True)
-    b_area_pred = {int(l): int(c) for l, c in zip(labels, cnt)}
-    labels, cnt = np.unique(pan_pred[on_pred & (pan_gt == VOID)], return_counts=True)
-    b_void = {int(l): int(c) for l, c in zip(labels, cnt)}
-    both = on_gt & on_pred
-    keys, cnt = np.unique(pan_gt[both] * OFFSET + pan_pred[both], return_counts=True)
-    b_inter = {(int(k) // OFFSET, int(k) % OFFSET): int(c) for k, c in zip(keys, cnt)}
+    b_iou_of = boundary(list(gt_row_of), list(pred_row_of)) if boundary is not None else None
 
     gt_matched, pred_matched = set(), set()
     rejected = demoted = lowered = 0
@@ -272,9 +158,7 @@ def image_boundary_stats(pan_gt, gt_segments, pan_pred, pred_segments, C: int, r
         if union <= 0:
             continue
         iou = n / union
-        n_b = b_inter.get((g, p), 0)
-        union_b = b_area_pred.get(p, 0) + b_area_gt.get(g, 0) - n_b - b_void.get(p, 0)
-        b_iou = n_b / union_b if union_b > 0 else 0.0
+        b_iou = b_iou_of(g, p) if b_iou_of is not None else iou
         iou_b = min(iou, b_iou)
         if iou_b > 0.5:
             stats.tp[g_cat] += 1
@@ -313,8 +197,65 @@ def image_boundary_stats(pan_gt, gt_segments, pan_pred, pred_segments, C: int, r
             continue
         stats.fp[p_cat] += 1
     if trace is not None:
-        trace.update(rejected=rejected, skipped_void=skipped_void, skipped_crowd=skipped_crowd, demoted=int(demoted), lowered=int(lowered))
+        trace.update(rejected=rejected, skipped_void=skipped_void, skipped_crowd=skipped_crowd)
+        if boundary is not None:
+            trace.update(demoted=int(demoted), lowered=int(lowered))
     return stats, flags
+
+
+def image_stats(pan_gt, gt_segments, pan_pred, pred_segments, C: int, trace: dict | None = None, into: PQStats | None = None):
+    """One picture.  pan_gt / pan_pred: integer id maps of one shape; gt_segments rows (id, category_id, iscrowd, area); pred_segments rows
+    (id, isthing, category_id); categories in 0..C-1 on both sides.  -> (PQStats, flags).  Raises nothing: a picture with a flag adds
+    nothing.  `into`: the statistics of the pictures so far, added to pair by pair (and returned) - the way the evaluator's one PQStat
+    runs through a stream of pictures, which is not the same floating-point sum as adding per-picture totals.  `trace` (optional dict)
+    receives what happened on the way: candidates rejected at iou <= 0.5, false positives skipped through VOID alone and through a crowd
+    region."""
+    return _image_stats(pan_gt, gt_segments, pan_pred, pred_segments, C, into, trace)
+
+
+def segment_boundaries(pan, table, radius=None) -> np.ndarray:
+    """uint8 [H, W]: 1 where a pixel lies on the boundary B(s) of its own segment, for the segments whose ids `table` lists; pixels of id 0
+    and of ids absent from the table are 0.  Literal: one binary mask per id through instance_eval.mask_boundary (the segments are
+    disjoint, so their boundaries are too).  radius None (or <= 0): sem_boundary.boundary_radius(H, W)."""
+    from .instance_eval import mask_boundary
+    pan = np.asarray(pan).astype(np.int64)
+    assert pan.ndim == 2, pan.shape
+    out = np.zeros(pan.shape, np.uint8)
+    for i in dict.fromkeys(int(v) for v in np.asarray(table, np.int64).reshape(-1)):
+        if i != VOID:
+            out |= mask_boundary((pan == i)[None], radius)[0]
+    return out
+
+
+def image_boundary_stats(pan_gt, gt_segments, pan_pred, pred_segments, C: int, radius=None, into: PQStats | None = None,
+                         trace: dict | None = None):
+    """`image_stats` with min(iou, boundary iou) in place of iou (the rule: the module docstring).  pan_gt / pan_pred must be [H, W] maps.
+    -> (PQStats, flags); `into` as there.  `trace` receives, beside the three counts of `image_stats` (rejected: candidates with
+    iou_b <= 0.5), `demoted`, the pairs with iou > 0.5 >= iou_b, and `lowered`, the pairs matched with b_iou < iou."""
+    map_gt, map_pred = np.asarray(pan_gt).astype(np.int64), np.asarray(pan_pred).astype(np.int64)
+    assert map_gt.ndim == 2 and map_gt.shape == map_pred.shape, (map_gt.shape, map_pred.shape)
+
+    def boundary(gt_ids, pred_ids):
+        """The boundary counts of the picture: pixels of B(g), of B(p), of B(p) over VOID, of both -> b_iou(g, p)."""
+        pan_gt, pan_pred = map_gt.reshape(-1), map_pred.reshape(-1)
+        on_gt = segment_boundaries(map_gt, gt_ids, radius).reshape(-1) != 0
+        on_pred = segment_boundaries(map_pred, pred_ids, radius).reshape(-1) != 0
+        labels, cnt = np.unique(pan_gt[on_gt], return_counts=True)
+        b_area_gt = {int(l): int(c) for l, c in zip(labels, cnt)}
+        labels, cnt = np.unique(pan_pred[on_pred], return_counts=True)
+        b_area_pred = {int(l): int(c) for l, c in zip(labels, cnt)}
+        labels, cnt = np.unique(pan_pred[on_pred & (pan_gt == VOID)], return_counts=True)
+        b_void = {int(l): int(c) for l, c in zip(labels, cnt)}
+        both = on_gt & on_pred
+        keys, cnt = np.unique(pan_gt[both] * OFFSET + pan_pred[both], return_counts=True)
+        b_inter = {(int(k) // OFFSET, int(k) % OFFSET): int(c) for k, c in zip(keys, cnt)}
+
+        def b_iou(g, p):
+            n_b = b_inter.get((g, p), 0)
+            union_b = b_area_pred.get(p, 0) + b_area_gt.get(g, 0) - n_b - b_void.get(p, 0)
+            return n_b / union_b if union_b > 0 else 0.0
+        return b_iou
+    return _image_stats(map_gt, gt_segments, map_pred, pred_segments, C, into, trace, boundary)
 
 
 def pq_average(stats: PQStats, isthing: Sequence[bool], which: str = "all") -> dict:

@@ -113,6 +113,59 @@ def _boundary_task(boundary):
     return t
 
 
+def _labels_or_scores(pred: DeviceArray, K: Optional[int]):
+    """pred = labels int32 [H,W] (needs K) or sem_seg float32 [K,H,W] -> (labels, sem, K, H, W), one of the first two None."""
+    if pred.dtype == np.float32:
+        assert len(pred.shape) == 3 and (K is None or int(K) == pred.shape[0]), (pred.shape, K)
+        K, H, W = pred.shape
+        return None, pred, int(K), H, W
+    assert pred.dtype == np.int32 and len(pred.shape) == 2 and K is not None, (pred.dtype, pred.shape, K)
+    H, W = pred.shape
+    return pred, None, int(K), H, W
+
+
+def _fill_track_dumps(d, live, n_live, iou, live_cap, iou_cap) -> None:
+    """The optional dumps that TrackDesc, InstTrackDesc and BoxTrackDesc share: live [cap] records of video.TRACK_ROW_DTYPE with n_live
+    int32 [1], iou float64 [cap, MAX_SEGMENTS]; live_cap / iou_cap: fewer rows than the arrays hold."""
+    from ._lib import MAX_SEGMENTS
+    from .video import TRACK_ROW_DTYPE
+    if live is not None:
+        assert live.dtype == TRACK_ROW_DTYPE and (n_live is None or n_live.dtype == np.int32)
+        d.live, d.live_cap = live.ptr, live.shape[0] if live_cap is None else int(live_cap)
+        assert d.live_cap <= live.shape[0]
+    if n_live is not None:
+        d.n_live = n_live.ptr
+    if iou is not None:
+        assert iou.dtype == np.float64 and len(iou.shape) == 2 and iou.shape[1] == MAX_SEGMENTS, (iou.dtype, iou.shape)
+        d.iou, d.iou_cap = iou.ptr, iou.shape[0] if iou_cap is None else int(iou_cap)
+        assert d.iou_cap <= iou.shape[0]
+
+
+def _inst_eval_desc(what: str, *, out_hw, table_row, scores_row, topk, gt: dict, num_categories, image, rows, n_rows, flags, masks, b, pad_hw,
+                    img_hw, iou_thresholds):
+    """-> (InstEvalDesc, the host threshold array it points to) of the arguments that `instance_eval` and `instance_eval_bbox` share."""
+    from ._lib import InstEvalDesc
+    from .instance_eval import IOU_THRS
+    thr = np.ascontiguousarray(IOU_THRS if iou_thresholds is None else iou_thresholds, np.float64)
+    assert thr.shape == (10,), thr.shape
+    d = InstEvalDesc()
+    _fill_inst_source(d, what, out_hw, topk, table_row, scores_row, masks, b, pad_hw, img_hw)
+    d.gt_runs, d.gt_offsets, d.gt_rows, d.n_gt = gt["runs"].ptr, gt["offsets"].ptr, gt["rows"].ptr, int(gt["n_gt"])
+    d.num_categories, d.image, d.iou_thresholds = int(num_categories), int(image), thr.ctypes.data
+    d.rows, d.n_rows, d.flags = _ptr(rows), _ptr(n_rows), _ptr(flags)
+    return d, thr
+
+
+def _inst_poly_gt(gt: dict):
+    """byref(InstPolyGt) of a ground truth that carries polygons (`instance_gt_to_device`), else None."""
+    from ._lib import InstPolyGt
+    if "gt_polys" not in gt:
+        return None
+    p = InstPolyGt()
+    p.xy, p.poly_offsets, p.gt_polys, p.n_poly = gt["xy"].ptr, gt["poly_offsets"].ptr, gt["gt_polys"].ptr, int(gt["n_poly"])
+    return C.byref(p)
+
+
 class Context:
     def __init__(self, device: int = 0):
         self.lib = _lib.load()
@@ -503,21 +556,13 @@ class Context:
         offsets-and-area int64 [2 max_classes + 1]) device arrays to use instead of fresh ones (a retry still allocates its own).
         pq_stats [K] records (panoptic_quality.STAT_DTYPE; needs a gt): the first launch is `odise_hip_semantic_eval_pq` and also adds the
         picture's semantic PQ statistics (`semantic_pq`) from the same label map; a retry never counts."""
-        if pred.dtype == np.float32:
-            assert len(pred.shape) == 3 and (K is None or int(K) == pred.shape[0]), (pred.shape, K)
-            K, H, W = pred.shape
-        else:
-            assert pred.dtype == np.int32 and len(pred.shape) == 2 and K is not None, (pred.dtype, pred.shape, K)
-            H, W = pred.shape
-        K = int(K)
+        _labels, _sem, K, H, W = _labels_or_scores(pred, K)
         assert gt is None or (gt.dtype == np.int32 and tuple(gt.shape) == (H, W)), "gt must be int32 [H,W]"
         if gt is not None and conf is None and b_conf is None and pq_stats is None:
             conf = self.zeros((K + 1, K + 1), np.int64)
         for m in (conf, b_conf):
             assert m is None or (m.dtype == np.int64 and int(np.prod(m.shape)) == (K + 1) * (K + 1)), "conf / b_conf must be int64 [(K+1),(K+1)]"
-        if flags is None:
-            flags = self.zeros((1,), np.int32)
-        assert flags.dtype == np.int32
+        flags = self._flags_buffer(flags)
         if pq_stats is not None:
             from .panoptic_quality import STAT_DTYPE
             assert gt is not None and pq_stats.dtype == STAT_DTYPE and pq_stats.shape == (K,), "pq_stats needs a gt and [K] records"
@@ -541,22 +586,9 @@ class Context:
         [K,H,W] (first-maximum arg-max); gt int32 [H,W] with the ignore label already mapped to K (anything outside [0,K] counts as K)
         -> (stats, flags): `stats` [K] records (panoptic_quality.STAT_DTYPE) added to, `flags` int32 [1] OR-ed into (1 = a label
         outside [0,K): that picture adds nothing); fresh zeroed ones when none are given."""
-        from .panoptic_quality import STAT_DTYPE
-        if pred.dtype == np.float32:
-            assert len(pred.shape) == 3 and (K is None or int(K) == pred.shape[0]), (pred.shape, K)
-            K, H, W = pred.shape
-            labels, sem = None, pred
-        else:
-            assert pred.dtype == np.int32 and len(pred.shape) == 2 and K is not None, (pred.dtype, pred.shape, K)
-            H, W = pred.shape
-            labels, sem = pred, None
-        K = int(K)
+        labels, sem, K, H, W = _labels_or_scores(pred, K)
         assert gt.dtype == np.int32 and tuple(gt.shape) == (H, W), "gt must be int32 [H,W]"
-        if stats is None:
-            stats = self.zeros((K,), STAT_DTYPE)
-        if flags is None:
-            flags = self.zeros((1,), np.int32)
-        assert stats.dtype == STAT_DTYPE and stats.shape == (K,) and flags.dtype == np.int32
+        stats, flags = self._stats_buffer(K, stats), self._flags_buffer(flags)
         check(self.lib.odise_hip_semantic_pq(self.h, _p(labels), _p(sem), _p(gt), K, H, W, _p(stats), _p(flags)), "semantic_pq")
         return stats, flags
 
@@ -578,10 +610,24 @@ class Context:
         check(self.lib.odise_hip_panoptic_quality(self.h, C.byref(d)), "panoptic_quality")
         return stats, flags
 
+    def _stats_buffer(self, n: int, stats: Optional[DeviceArray]) -> DeviceArray:
+        """`stats` [n] records of panoptic_quality.STAT_DTYPE; a fresh zeroed one when None."""
+        from .panoptic_quality import STAT_DTYPE
+        if stats is None:
+            stats = self.zeros((int(n),), STAT_DTYPE)
+        assert stats.dtype == STAT_DTYPE and stats.shape == (int(n),)
+        return stats
+
+    def _flags_buffer(self, flags: Optional[DeviceArray]) -> DeviceArray:
+        """`flags` int32 [1]; a fresh zeroed one when None."""
+        if flags is None:
+            flags = self.zeros((1,), np.int32)
+        assert flags.dtype == np.int32
+        return flags
+
     def _pq_desc(self, pred_ids, pred_segments, gt, gt_segments, num_categories, stats, flags):
         """-> (PqDesc, the host table it points to, stats, flags) of the arguments of `panoptic_quality`."""
         from ._lib import PqDesc
-        from .panoptic_quality import STAT_DTYPE
         if gt.dtype == np.uint8:
             assert len(gt.shape) == 3 and gt.shape[2] == 3, gt.shape
             layout = 0
@@ -592,11 +638,7 @@ class Context:
         assert pred_ids.dtype == np.int32 and int(np.prod(pred_ids.shape)) == H * W, (pred_ids.dtype, pred_ids.shape, (H, W))
         assert pred_segments.dtype == np.int32
         table = np.ascontiguousarray(np.asarray(gt_segments, np.int64).reshape(-1, 4), np.int32)
-        if stats is None:
-            stats = self.zeros((int(num_categories),), STAT_DTYPE)
-        if flags is None:
-            flags = self.zeros((1,), np.int32)
-        assert stats.dtype == STAT_DTYPE and stats.shape == (int(num_categories),) and flags.dtype == np.int32
+        stats, flags = self._stats_buffer(num_categories, stats), self._flags_buffer(flags)
         d = PqDesc()
         d.H, d.W, d.pred_ids, d.pred_segments, d.gt, d.gt_layout = H, W, pred_ids.ptr, pred_segments.ptr, gt.ptr, layout
         d.gt_segments, d.n_gt, d.num_categories = table.ctypes.data, table.shape[0], int(num_categories)
@@ -619,11 +661,8 @@ class Context:
         what `panoptic_quality` adds, `b_stats` [num_categories] records the matching on min(mask IoU, boundary IoU); radius <= 0: the
         formula of `boundary_radius`.  Fresh zeroed accumulators when none are given."""
         from ._lib import PqBoundaryTask
-        from .panoptic_quality import STAT_DTYPE
         d, _table, stats, flags = self._pq_desc(pred_ids, pred_segments, gt, gt_segments, num_categories, stats, flags)
-        if b_stats is None:
-            b_stats = self.zeros((int(num_categories),), STAT_DTYPE)
-        assert b_stats.dtype == STAT_DTYPE and b_stats.shape == (int(num_categories),)
+        b_stats = self._stats_buffer(num_categories, b_stats)
         b = PqBoundaryTask()
         b.stats, b.radius = b_stats.ptr, int(radius)
         check(self.lib.odise_hip_panoptic_quality_boundary(self.h, C.byref(d), C.byref(b)), "panoptic_quality_boundary")
@@ -731,23 +770,24 @@ class Context:
         record), colors uint8 [MAX_SEGMENTS,3] in/out (the rows of the frame's instances are rewritten).  Optional dumps: live [cap]
         records of video.TRACK_ROW_DTYPE with n_live int32 [1], iou float64 [cap, MAX_SEGMENTS]."""
         from ._lib import MAX_SEGMENTS, TrackDesc
-        from .video import TRACK_ROW_DTYPE
         H, W = pred_ids.shape
         assert pred_ids.dtype == np.int32 and pred_segments.dtype == np.int32
         assert colors.dtype == np.uint8 and colors.nbytes >= 3 * MAX_SEGMENTS, (colors.dtype, colors.shape)
         d = TrackDesc()
         d.track, d.H, d.W, d.pred_ids, d.pred_segments, d.colors = tracker.handle, H, W, pred_ids.ptr, pred_segments.ptr, colors.ptr
-        if live is not None:
-            assert live.dtype == TRACK_ROW_DTYPE and (n_live is None or n_live.dtype == np.int32)
-            d.live, d.live_cap = live.ptr, live.shape[0] if live_cap is None else int(live_cap)
-            assert d.live_cap <= live.shape[0]
-        if n_live is not None:
-            d.n_live = n_live.ptr
-        if iou is not None:
-            assert iou.dtype == np.float64 and len(iou.shape) == 2 and iou.shape[1] == MAX_SEGMENTS, (iou.dtype, iou.shape)
-            d.iou, d.iou_cap = iou.ptr, iou.shape[0] if iou_cap is None else int(iou_cap)
-            assert d.iou_cap <= iou.shape[0]
+        _fill_track_dumps(d, live, n_live, iou, live_cap, iou_cap)
         check(self.lib.odise_hip_track_frame(self.h, C.byref(d)), "track_frame")
+        return colors
+
+    def _fill_track_colors(self, d, topk: int, colors: Optional[DeviceArray], edge_colors: Optional[DeviceArray]) -> DeviceArray:
+        """colors uint8 [topk,3] by table index (zeros when None) and the optional edge_colors of InstTrackDesc / BoxTrackDesc -> colors."""
+        if colors is None:
+            colors = self.zeros((topk, 3), np.uint8)
+        assert colors.dtype == np.uint8 and colors.nbytes >= 3 * topk, (colors.dtype, colors.shape)
+        d.colors = colors.ptr
+        if edge_colors is not None:
+            assert edge_colors.dtype == np.uint8 and edge_colors.nbytes >= 3 * topk, (edge_colors.dtype, edge_colors.shape)
+            d.edge_colors = edge_colors.ptr
         return colors
 
     # ---- colours of overlapping instance masks across frames (odise_hip_inst_track_*; host restatement: video.InstanceColorTracker) -----
@@ -765,29 +805,12 @@ class Context:
         index (allocated as zeros when None; the rows of the frame's instances are rewritten), edge_colors the same for the outline
         colours.  Optional dumps as in `track_frame`: live [cap] records of video.TRACK_ROW_DTYPE with n_live int32 [1], iou float64
         [cap, MAX_SEGMENTS]."""
-        from ._lib import MAX_SEGMENTS, InstTrackDesc
-        from .video import TRACK_ROW_DTYPE
-        topk = tracker.topk
+        from ._lib import InstTrackDesc
         d = InstTrackDesc()
         d.track, d.min_score = tracker.handle, float(min_score)
-        _fill_inst_source(d, "inst_track_frame", tracker.hw, topk, table_row, scores_row, masks, b, pad_hw, img_hw)
-        if colors is None:
-            colors = self.zeros((topk, 3), np.uint8)
-        assert colors.dtype == np.uint8 and colors.nbytes >= 3 * topk, (colors.dtype, colors.shape)
-        d.colors = colors.ptr
-        if edge_colors is not None:
-            assert edge_colors.dtype == np.uint8 and edge_colors.nbytes >= 3 * topk, (edge_colors.dtype, edge_colors.shape)
-            d.edge_colors = edge_colors.ptr
-        if live is not None:
-            assert live.dtype == TRACK_ROW_DTYPE and (n_live is None or n_live.dtype == np.int32)
-            d.live, d.live_cap = live.ptr, live.shape[0] if live_cap is None else int(live_cap)
-            assert d.live_cap <= live.shape[0]
-        if n_live is not None:
-            d.n_live = n_live.ptr
-        if iou is not None:
-            assert iou.dtype == np.float64 and len(iou.shape) == 2 and iou.shape[1] == MAX_SEGMENTS, (iou.dtype, iou.shape)
-            d.iou, d.iou_cap = iou.ptr, iou.shape[0] if iou_cap is None else int(iou_cap)
-            assert d.iou_cap <= iou.shape[0]
+        _fill_inst_source(d, "inst_track_frame", tracker.hw, tracker.topk, table_row, scores_row, masks, b, pad_hw, img_hw)
+        colors = self._fill_track_colors(d, tracker.topk, colors, edge_colors)
+        _fill_track_dumps(d, live, n_live, iou, live_cap, iou_cap)
         check(self.lib.odise_hip_inst_track_frame(self.h, C.byref(d)), "inst_track_frame")
         return colors
 
@@ -804,29 +827,13 @@ class Context:
         """One frame, enqueued (one launch): boxes float32 [topk,4] XYXY on the device (as `instance_boxes` returns them), the selection
         table_row [1 + 2 topk] / scores_row [topk] (both optional: every box counts, every class is 0, no score test).  colors /
         edge_colors and the dumps as in `inst_track_frame`."""
-        from ._lib import MAX_SEGMENTS, BoxTrackDesc
-        from .video import TRACK_ROW_DTYPE
+        from ._lib import BoxTrackDesc
         topk = tracker.topk
         assert boxes.dtype == np.float32 and boxes.nbytes >= 16 * topk, (boxes.dtype, boxes.shape)
         d = BoxTrackDesc()
         d.track, d.boxes, d.inst_table, d.inst_scores, d.topk, d.min_score = tracker.handle, boxes.ptr, _ptr(table_row), _ptr(scores_row), topk, float(min_score)
-        if colors is None:
-            colors = self.zeros((topk, 3), np.uint8)
-        assert colors.dtype == np.uint8 and colors.nbytes >= 3 * topk, (colors.dtype, colors.shape)
-        d.colors = colors.ptr
-        if edge_colors is not None:
-            assert edge_colors.dtype == np.uint8 and edge_colors.nbytes >= 3 * topk, (edge_colors.dtype, edge_colors.shape)
-            d.edge_colors = edge_colors.ptr
-        if live is not None:
-            assert live.dtype == TRACK_ROW_DTYPE and (n_live is None or n_live.dtype == np.int32)
-            d.live, d.live_cap = live.ptr, live.shape[0] if live_cap is None else int(live_cap)
-            assert d.live_cap <= live.shape[0]
-        if n_live is not None:
-            d.n_live = n_live.ptr
-        if iou is not None:
-            assert iou.dtype == np.float64 and len(iou.shape) == 2 and iou.shape[1] == MAX_SEGMENTS, (iou.dtype, iou.shape)
-            d.iou, d.iou_cap = iou.ptr, iou.shape[0] if iou_cap is None else int(iou_cap)
-            assert d.iou_cap <= iou.shape[0]
+        colors = self._fill_track_colors(d, topk, colors, edge_colors)
+        _fill_track_dumps(d, live, n_live, iou, live_cap, iou_cap)
         check(self.lib.odise_hip_box_track_frame(self.h, C.byref(d)), "box_track_frame")
         return colors
 
@@ -877,19 +884,11 @@ class Context:
         """labels int32 [H,W] (needs K) or sem_seg float32 [K,H,W] -> the panoptic record int32 [H*W + 1 + 3*MAX_SEGMENTS] of the semantic
         result (ids = category + 1, rows (id, 0, category) by descending pixel count), enqueued."""
         from ._lib import record_len
-        a = labels_or_sem_seg
-        if a.dtype == np.float32:
-            assert len(a.shape) == 3 and (K is None or int(K) == a.shape[0]), (a.shape, K)
-            K, H, W = a.shape
-            labels, sem = None, a
-        else:
-            assert a.dtype == np.int32 and len(a.shape) == 2 and K is not None, (a.dtype, a.shape, K)
-            H, W = a.shape
-            labels, sem = a, None
+        labels, sem, K, H, W = _labels_or_scores(labels_or_sem_seg, K)
         if out is None:
             out = self.empty((record_len(H, W),), np.int32)
         assert out.dtype == np.int32 and int(np.prod(out.shape)) >= record_len(H, W)
-        check(self.lib.odise_hip_semantic_record(self.h, _p(labels), _p(sem), int(K), H, W, _p(out)), "semantic_record")
+        check(self.lib.odise_hip_semantic_record(self.h, _p(labels), _p(sem), K, H, W, _p(out)), "semantic_record")
         return out
 
     # ---- COCO RLE of instance masks (segm evaluation; include/odise_hip.h odise_hip_rle_encode / odise_hip_instance_rle) ----------------
@@ -947,7 +946,6 @@ class Context:
             raise RuntimeError(f"polygon_rle: malformed polygon(s) (flags {f})")
         return rles, area
 
-
     # ---- segm evaluation of instance masks (include/odise_hip.h odise_hip_mask_iou / odise_hip_instance_eval; host restatement:
     # odise_amd/instance_eval.py) ------------------------------------------------------------------------------------------------------
     def instance_gt_to_device(self, gt_table, runs, offsets, xy=None, poly_offsets=None, gt_polys=None, boxes=None) -> dict:
@@ -985,6 +983,20 @@ class Context:
             gt["boxes"] = buf.view((n_gt, 4), np.float64, at[at_boxes])
         return gt
 
+    def _gt_counts_to_device(self, gt_counts) -> dict:
+        """A list of uncompressed count arrays as an `instance_gt_to_device` dict (uploaded, which waits); such a dict as it is."""
+        if isinstance(gt_counts, dict):
+            return gt_counts
+        offs = np.concatenate(([0], np.cumsum([len(c) for c in gt_counts]))).astype(np.int64)
+        runs = np.concatenate([np.asarray(c, np.uint32) for c in gt_counts]) if len(gt_counts) else np.zeros(0, np.uint32)
+        return self.instance_gt_to_device(np.zeros((len(offs) - 1, 3), np.int32), runs, offs)
+
+    def _mask_iou_inputs(self, gt_counts, iscrowd, flags):
+        """-> (gt dict, n_gt, iscrowd on the device or None, flags: a fresh zeroed int32 [1] when None) of `mask_iou` / `mask_boundary_iou`."""
+        gt = self._gt_counts_to_device(gt_counts)
+        crowd = None if iscrowd is None else (iscrowd if isinstance(iscrowd, DeviceArray) else self.to_device(np.asarray(iscrowd, np.uint8)))
+        return gt, gt["n_gt"], crowd, flags if flags is not None else self.zeros((1,), np.int32)
+
     def mask_iou(self, masks: DeviceArray, gt_counts, iscrowd=None, flags: Optional[DeviceArray] = None, with_counts: bool = False):
         """pycocotools' mask.iou of dense device masks [n, h, w] (float32 / uint8 / bool) against run-length masks: gt_counts = a list of
         uncompressed count arrays (uploaded here, which waits) or an `instance_gt_to_device` dict -> (iou float64 [n, n_gt] on the device,
@@ -992,14 +1004,7 @@ class Context:
         freed on return by the library's synchronising free."""
         n, h, w = masks.shape
         dt = _mask_dtype(masks, "mask_iou")
-        if not isinstance(gt_counts, dict):
-            offs = np.concatenate(([0], np.cumsum([len(c) for c in gt_counts]))).astype(np.int64)
-            runs = np.concatenate([np.asarray(c, np.uint32) for c in gt_counts]) if len(gt_counts) else np.zeros(0, np.uint32)
-            gt_counts = self.instance_gt_to_device(np.zeros((len(offs) - 1, 3), np.int32), runs, offs)
-        n_gt = gt_counts["n_gt"]
-        crowd = None if iscrowd is None else (iscrowd if isinstance(iscrowd, DeviceArray) else self.to_device(np.asarray(iscrowd, np.uint8)))
-        if flags is None:
-            flags = self.zeros((1,), np.int32)
+        gt_counts, n_gt, crowd, flags = self._mask_iou_inputs(gt_counts, iscrowd, flags)
         iou = self.empty((n, n_gt), np.float64)
         extra = (self.empty((n, n_gt), np.int32), self.empty((n,), np.int64), self.empty((n_gt,), np.int64)) if with_counts else (None, None, None)
         check(self.lib.odise_hip_mask_iou(self.h, _p(masks), dt, n, h, w, _p(gt_counts["runs"]), _p(gt_counts["offsets"]), n_gt, _p(crowd), _p(iou),
@@ -1014,24 +1019,15 @@ class Context:
         (int32 [1]) are device arrays or pointers.  A gt that carries polygons goes through odise_hip_instance_eval_poly.
         boundary = (rows, n_rows) or (rows, n_rows, radius): the Boundary AP task from the same pack and decode
         (odise_hip_instance_eval_boundary; radius 0 / absent = the formula); `rows` / `n_rows` may both be None then."""
-        from ._lib import InstEvalDesc, InstPolyGt
-        from .instance_eval import IOU_THRS
-        thr = np.ascontiguousarray(IOU_THRS if iou_thresholds is None else iou_thresholds, np.float64)
-        assert thr.shape == (10,), thr.shape
-        d = InstEvalDesc()
-        _fill_inst_source(d, "instance_eval", out_hw, topk, table_row, scores_row, masks, b, pad_hw, img_hw)
-        d.gt_runs, d.gt_offsets, d.gt_rows, d.n_gt = gt["runs"].ptr, gt["offsets"].ptr, gt["rows"].ptr, int(gt["n_gt"])
-        d.num_categories, d.image, d.iou_thresholds = int(num_categories), int(image), thr.ctypes.data
-        d.rows, d.n_rows, d.flags = _ptr(rows), _ptr(n_rows), _ptr(flags)
-        p = None
-        if "gt_polys" in gt:
-            p = InstPolyGt()
-            p.xy, p.poly_offsets, p.gt_polys, p.n_poly = gt["xy"].ptr, gt["poly_offsets"].ptr, gt["gt_polys"].ptr, int(gt["n_poly"])
+        d, _thr = _inst_eval_desc("instance_eval", out_hw=out_hw, table_row=table_row, scores_row=scores_row, topk=topk, gt=gt, num_categories=num_categories,
+                                  image=image, rows=rows, n_rows=n_rows, flags=flags, masks=masks, b=b, pad_hw=pad_hw, img_hw=img_hw,
+                                  iou_thresholds=iou_thresholds)
+        p = _inst_poly_gt(gt)
         if boundary is not None:
-            check(self.lib.odise_hip_instance_eval_boundary(self.h, C.byref(d), C.byref(p) if p is not None else None, None,
-                                                            C.byref(_boundary_task(boundary))), "instance_eval_boundary")
+            check(self.lib.odise_hip_instance_eval_boundary(self.h, C.byref(d), p, None, C.byref(_boundary_task(boundary))),
+                  "instance_eval_boundary")
         elif p is not None:
-            check(self.lib.odise_hip_instance_eval_poly(self.h, C.byref(d), C.byref(p)), "instance_eval_poly")
+            check(self.lib.odise_hip_instance_eval_poly(self.h, C.byref(d), p), "instance_eval_poly")
         else:
             check(self.lib.odise_hip_instance_eval(self.h, C.byref(d)), "instance_eval")
 
@@ -1073,27 +1069,19 @@ class Context:
         "boxes" (`instance_gt_to_device(..., boxes=instance_eval.gt_boxes(annotations))`); bbox_rows / bbox_n_rows take the bbox
         task's rows; boxes (optional, float32 [topk, 4]) the detections' XYXY boxes; boundary as in `instance_eval`: the third task
         of the same call (odise_hip_instance_eval_boundary)."""
-        from ._lib import InstBboxTask, InstEvalDesc, InstPolyGt
-        from .instance_eval import IOU_THRS
-        thr = np.ascontiguousarray(IOU_THRS if iou_thresholds is None else iou_thresholds, np.float64)
-        assert thr.shape == (10,), thr.shape
+        from ._lib import InstBboxTask
         assert "boxes" in gt, "instance_eval_bbox: the ground truth carries no boxes"
-        d = InstEvalDesc()
-        _fill_inst_source(d, "instance_eval_bbox", out_hw, topk, table_row, scores_row, masks, b, pad_hw, img_hw)
-        d.gt_runs, d.gt_offsets, d.gt_rows, d.n_gt = gt["runs"].ptr, gt["offsets"].ptr, gt["rows"].ptr, int(gt["n_gt"])
-        d.num_categories, d.image, d.iou_thresholds = int(num_categories), int(image), thr.ctypes.data
-        d.rows, d.n_rows, d.flags = _ptr(rows), _ptr(n_rows), _ptr(flags)
+        d, _thr = _inst_eval_desc("instance_eval_bbox", out_hw=out_hw, table_row=table_row, scores_row=scores_row, topk=topk, gt=gt, num_categories=num_categories,
+                                  image=image, rows=rows, n_rows=n_rows, flags=flags, masks=masks, b=b, pad_hw=pad_hw, img_hw=img_hw,
+                                  iou_thresholds=iou_thresholds)
         t = InstBboxTask()
         t.gt_boxes, t.rows, t.n_rows, t.boxes = gt["boxes"].ptr, _ptr(bbox_rows), _ptr(bbox_n_rows), _ptr(boxes)
-        p = None
-        if "gt_polys" in gt:
-            p = InstPolyGt()
-            p.xy, p.poly_offsets, p.gt_polys, p.n_poly = gt["xy"].ptr, gt["poly_offsets"].ptr, gt["gt_polys"].ptr, int(gt["n_poly"])
+        p = _inst_poly_gt(gt)
         if boundary is not None:
-            check(self.lib.odise_hip_instance_eval_boundary(self.h, C.byref(d), C.byref(p) if p is not None else None, C.byref(t),
-                                                            C.byref(_boundary_task(boundary))), "instance_eval_boundary")
+            check(self.lib.odise_hip_instance_eval_boundary(self.h, C.byref(d), p, C.byref(t), C.byref(_boundary_task(boundary))),
+                  "instance_eval_boundary")
             return
-        check(self.lib.odise_hip_instance_eval_bbox(self.h, C.byref(d), C.byref(p) if p is not None else None, C.byref(t)), "instance_eval_bbox")
+        check(self.lib.odise_hip_instance_eval_bbox(self.h, C.byref(d), p, C.byref(t)), "instance_eval_bbox")
 
     def mask_boundary(self, masks: DeviceArray, radius: int = 0, out: Optional[DeviceArray] = None, with_area: bool = False):
         """The boundaries of dense device masks [n, h, w] (float32 / uint8 / bool; odise_hip_mask_boundary: mask & ~erode(mask), the
@@ -1114,14 +1102,7 @@ class Context:
         `mask_iou`."""
         n, h, w = masks.shape
         dt = _mask_dtype(masks, "mask_boundary_iou")
-        if not isinstance(gt_counts, dict):
-            offs = np.concatenate(([0], np.cumsum([len(c) for c in gt_counts]))).astype(np.int64)
-            runs = np.concatenate([np.asarray(c, np.uint32) for c in gt_counts]) if len(gt_counts) else np.zeros(0, np.uint32)
-            gt_counts = self.instance_gt_to_device(np.zeros((len(offs) - 1, 3), np.int32), runs, offs)
-        n_gt = gt_counts["n_gt"]
-        crowd = None if iscrowd is None else (iscrowd if isinstance(iscrowd, DeviceArray) else self.to_device(np.asarray(iscrowd, np.uint8)))
-        if flags is None:
-            flags = self.zeros((1,), np.int32)
+        gt_counts, n_gt, crowd, flags = self._mask_iou_inputs(gt_counts, iscrowd, flags)
         iou, m_iou, b_iou = (self.empty((n, n_gt), np.float64) for _ in range(3))
         check(self.lib.odise_hip_mask_boundary_iou(self.h, _p(masks), dt, n, h, w, _p(gt_counts["runs"]), _p(gt_counts["offsets"]), n_gt, _p(crowd),
                                                    int(radius), _p(iou), _p(m_iou), _p(b_iou), None, None, None, _p(flags)), "mask_boundary_iou")
@@ -1177,7 +1158,6 @@ class Context:
             raise InstanceAccumulateError(f, precision, recall)
         return precision, recall
 
-
     def jpeg_decode(self, data: bytes, apply_orientation: bool = True, out: Optional[DeviceArray] = None) -> DeviceArray:
         """read_image(file, "RGB") for a baseline JPEG: host Huffman decoding, IDCT / upsampling / colour conversion / EXIF transpose on
         the device -> uint8 [H,W,3], bit-identical to Pillow.  Baseline, extended-sequential and progressive files; raises `UnsupportedInput` for arithmetic-coded / CMYK / RGB-coded ones."""
@@ -1193,101 +1173,75 @@ class Context:
         return out.view((h.value, w.value, 3)) if out.shape != (h.value, w.value, 3) else out
 
 
-class Tracker:
+class _Handle:
+    """An object of the library behind a handle.  A subclass sets `ctx` and calls `_create`; its class attributes `_reset` and `_destroy`
+    name the library's functions (without the odise_hip_ prefix).  `close()` (or collection) releases it."""
+    _reset = _destroy = ""
+    handle = None
+
+    def _create(self, name: str, *args) -> None:
+        h = C.c_void_p()
+        check(getattr(self.ctx.lib, "odise_hip_" + name)(self.ctx.h, *args, C.byref(h)), name)
+        self.handle = h.value
+
+    def reset(self) -> None:
+        check(getattr(self.ctx.lib, "odise_hip_" + self._reset)(self.ctx.h, C.c_void_p(self.handle)), self._reset)
+
+    def close(self) -> None:
+        if self.handle and self.ctx.h:
+            getattr(self.ctx.lib, "odise_hip_" + self._destroy)(self.ctx.h, C.c_void_p(self.handle))
+        self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _track_pool(pool) -> np.ndarray:
+    """The colour pool of a tracker, uint8 [P,3] on the host: video.default_pool() when None."""
+    from .video import default_pool
+    return default_pool() if pool is None else np.ascontiguousarray(np.asarray(pool, np.uint8).reshape(-1, 3))
+
+
+class Tracker(_Handle):
     """odise_track (include/odise_hip.h): the library's tracker object for frames of one size; `close()` (or collection) releases it."""
+    _reset, _destroy = "track_reset", "track_destroy"
 
     def __init__(self, ctx: Context, hw, ttl: int = 8, pool=None):
-        from .video import default_pool
-        pool = default_pool() if pool is None else np.ascontiguousarray(np.asarray(pool, np.uint8).reshape(-1, 3))
-        self.ctx, self.hw, self.ttl, self.pool = ctx, (int(hw[0]), int(hw[1])), int(ttl), pool
-        h = C.c_void_p()
-        check(ctx.lib.odise_hip_track_create(ctx.h, self.hw[0], self.hw[1], self.ttl, pool.ctypes.data_as(C.c_void_p), len(pool), C.byref(h)),
-              "track_create")
-        self.handle = h.value
-
-    def reset(self) -> None:
-        check(self.ctx.lib.odise_hip_track_reset(self.ctx.h, C.c_void_p(self.handle)), "track_reset")
-
-    def close(self) -> None:
-        if self.handle and self.ctx.h:
-            self.ctx.lib.odise_hip_track_destroy(self.ctx.h, C.c_void_p(self.handle))
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.ctx, self.hw, self.ttl, self.pool = ctx, (int(hw[0]), int(hw[1])), int(ttl), _track_pool(pool)
+        self._create("track_create", self.hw[0], self.hw[1], self.ttl, self.pool.ctypes.data_as(C.c_void_p), len(self.pool))
 
 
-class InstTracker:
+class InstTracker(_Handle):
     """odise_inst_track (include/odise_hip.h): the library's tracker object for selections of `topk` instance masks of one size;
     `close()` (or collection) releases it."""
+    _reset, _destroy = "inst_track_reset", "inst_track_destroy"
 
     def __init__(self, ctx: Context, hw, topk: int, ttl: int = 8, pool=None):
-        from .video import default_pool
-        pool = default_pool() if pool is None else np.ascontiguousarray(np.asarray(pool, np.uint8).reshape(-1, 3))
-        self.ctx, self.hw, self.topk, self.ttl, self.pool = ctx, (int(hw[0]), int(hw[1])), int(topk), int(ttl), pool
-        h = C.c_void_p()
-        check(ctx.lib.odise_hip_inst_track_create(ctx.h, self.hw[0], self.hw[1], self.topk, self.ttl, pool.ctypes.data_as(C.c_void_p), len(pool),
-                                                  C.byref(h)), "inst_track_create")
-        self.handle = h.value
-
-    def reset(self) -> None:
-        check(self.ctx.lib.odise_hip_inst_track_reset(self.ctx.h, C.c_void_p(self.handle)), "inst_track_reset")
-
-    def close(self) -> None:
-        if self.handle and self.ctx.h:
-            self.ctx.lib.odise_hip_inst_track_destroy(self.ctx.h, C.c_void_p(self.handle))
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.ctx, self.hw, self.topk, self.ttl, self.pool = ctx, (int(hw[0]), int(hw[1])), int(topk), int(ttl), _track_pool(pool)
+        self._create("inst_track_create", self.hw[0], self.hw[1], self.topk, self.ttl, self.pool.ctypes.data_as(C.c_void_p), len(self.pool))
 
 
-class BoxTracker:
+class BoxTracker(_Handle):
     """odise_box_track (include/odise_hip.h): the library's tracker object for selections of `topk` instance boxes; `close()` (or
     collection) releases it."""
+    _reset, _destroy = "box_track_reset", "box_track_destroy"
 
     def __init__(self, ctx: Context, topk: int, ttl: int = 8, pool=None):
-        from .video import default_pool
-        pool = default_pool() if pool is None else np.ascontiguousarray(np.asarray(pool, np.uint8).reshape(-1, 3))
-        self.ctx, self.topk, self.ttl, self.pool = ctx, int(topk), int(ttl), pool
-        h = C.c_void_p()
-        check(ctx.lib.odise_hip_box_track_create(ctx.h, self.topk, self.ttl, pool.ctypes.data_as(C.c_void_p), len(pool), C.byref(h)), "box_track_create")
-        self.handle = h.value
-
-    def reset(self) -> None:
-        check(self.ctx.lib.odise_hip_box_track_reset(self.ctx.h, C.c_void_p(self.handle)), "box_track_reset")
-
-    def close(self) -> None:
-        if self.handle and self.ctx.h:
-            self.ctx.lib.odise_hip_box_track_destroy(self.ctx.h, C.c_void_p(self.handle))
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.ctx, self.topk, self.ttl, self.pool = ctx, int(topk), int(ttl), _track_pool(pool)
+        self._create("box_track_create", self.topk, self.ttl, self.pool.ctypes.data_as(C.c_void_p), len(self.pool))
 
 
-class SemanticTTA:
+class SemanticTTA(_Handle):
     """odise_tta (include/odise_hip.h): the views of one picture laid end to end for one semantic product; `close()` (or collection)
     releases the device buffers (S_cat: out_h * out_w * max_views * Qpad fp16)."""
+    _reset, _destroy = "tta_reset", "tta_destroy"
 
     def __init__(self, ctx: Context, out_hw, K: int, Q: int, max_views: int):
         self.ctx, self.hw, self.K, self.Q, self.max_views = ctx, (int(out_hw[0]), int(out_hw[1])), int(K), int(Q), int(max_views)
-        self.handle = None
-        h = C.c_void_p()
-        check(ctx.lib.odise_hip_tta_create(ctx.h, self.hw[0], self.hw[1], self.K, self.Q, self.max_views, C.byref(h)), "tta_create")
-        self.handle = h.value
-
-    def reset(self) -> None:
-        check(self.ctx.lib.odise_hip_tta_reset(self.ctx.h, C.c_void_p(self.handle)), "tta_reset")
+        self._create("tta_create", self.hw[0], self.hw[1], self.K, self.Q, self.max_views)
 
     def add_view(self, b: int, mask_cls_b, pad_hw, img_hw, hflip: bool = False) -> None:
         """Image b of the context's current mask logits + its log-probabilities (DeviceArray fp32 [Q, K+1], or a device pointer)."""
@@ -1297,17 +1251,6 @@ class SemanticTTA:
     def finish(self, sem_seg: Optional[DeviceArray] = None, sem_argmax: Optional[DeviceArray] = None) -> None:
         """sem_seg fp32 [K,H,W] = mean over the views; sem_argmax int32 [H,W] = first maximum of their sum.  Either or both."""
         check(self.ctx.lib.odise_hip_tta_finish(self.ctx.h, C.c_void_p(self.handle), _p(sem_seg), _p(sem_argmax)), "tta_finish")
-
-    def close(self) -> None:
-        if self.handle and self.ctx.h:
-            self.ctx.lib.odise_hip_tta_destroy(self.ctx.h, C.c_void_p(self.handle))
-        self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class RlePending:

@@ -156,6 +156,32 @@ def test_bad_arguments_are_refused_and_nothing_is_written(ctx):
         ctx.box_track_create(7, ttl=9)
 
 
+def test_the_dump_refusals_carry_the_entry_points_name(ctx):
+    """live_cap -1, iou_cap -1 and live without n_live: the checks the three trackers share (track_match.h) answer as
+    odise_hip_box_track_frame.  Nothing is launched and nothing is written."""
+    topk = 7
+    pool = np.array([[255, 0, 0], [0, 255, 0], [0, 0, 255]], np.uint8)
+    trk = ctx.box_track_create(topk, 8, pool)
+    try:
+        boxes, colors = ctx.zeros((topk, 4), np.float32), ctx.to_device(BC.prefill(topk))
+        live, n_live = ctx.to_device(live_guard(4)), ctx.to_device(np.full(1, -9, np.int32))
+        iou_fill = np.full((4, MAX_SEGMENTS), -7.0, np.float64)
+        iou = ctx.to_device(iou_fill)
+        for kw in (dict(live_cap=-1), dict(iou_cap=-1), dict(n_live=None)):
+            d = BoxTrackDesc()
+            d.track, d.boxes, d.topk, d.colors = trk.handle, boxes.ptr, topk, colors.ptr
+            d.live, d.live_cap, d.n_live, d.iou, d.iou_cap = live.ptr, 4, n_live.ptr, iou.ptr, 4
+            for k, v in kw.items():
+                setattr(d, k, v)
+            assert ctx.lib.odise_hip_box_track_frame(ctx.h, C.byref(d)) == -1, kw
+            assert ctx.lib.odise_hip_last_error().decode().startswith("box_track_frame:"), (kw, ctx.lib.odise_hip_last_error())
+        ctx.sync()
+        assert colors.numpy().tobytes() == BC.prefill(topk).tobytes() and live.numpy().tobytes() == live_guard(4).tobytes()
+        assert int(n_live.numpy()[0]) == -9 and iou.numpy().tobytes() == iou_fill.tobytes()
+    finally:
+        trk.close()
+
+
 # ---- boxes straight from odise_hip_instance_boxes of the narrow model's mask logits ---------------------------------------------------------
 @pytest.fixture(scope="module")
 def clip(ctx):

@@ -192,6 +192,42 @@ def test_into_is_the_loop_and_not_the_sum_of_totals():
     assert again == run
 
 
+def host_results() -> dict:
+    """What `image_stats` and `image_boundary_stats` return for the one-row pictures of pq_cases.hand_cases (three flagged ones and the
+    crowd rows among them), for every generated case above, and as running sums over the stream: the records as hex, flags, `trace`."""
+    def entry(got, trace):
+        return {"records": got[0].to_records().tobytes().hex(), "flags": int(got[1]), "trace": trace}
+    out = {}
+    for name, case in list(hand_cases().items()) + list(CASES.items()):
+        tr, b_tr = {}, {}
+        stats = case.stats(tr)
+        radius = getattr(case, "radius", None)
+        b_stats = PQ.image_boundary_stats(case.pan_gt, case.gt_rows, case.pan_pred, case.pred_rows, case.C, radius, trace=b_tr)
+        out[name] = {"stats": entry(stats, tr), "boundary": entry(b_stats, b_tr)}
+    run, b_run = PQ.PQStats(6), PQ.PQStats(6)
+    for c in stream_cases():
+        c.stats(into=run)
+        c.boundary_stats(into=b_run)
+    out["stream_into"] = {"stats": entry((run, 0), {}), "boundary": entry((b_run, 0), {})}
+    return out
+
+
+def test_both_functions_return_what_they_returned_before_they_shared_a_body():
+    """tests/golden/pq_host_records.json holds `host_results()` of the two separate functions, written by json.dump of it at the commit
+    before they became one body: the records byte for byte, the flags and the trace dicts (keys and values) are the same."""
+    import json
+    import pathlib
+    golden = json.loads((pathlib.Path(__file__).parent / "golden" / "pq_host_records.json").read_text())
+    got = host_results()
+    assert sorted(got) == sorted(golden)
+    assert any(golden[n]["stats"]["flags"] for n in golden) and golden["crowd"]["stats"]["trace"] == {"rejected": 0, "skipped_void": 0, "skipped_crowd": 1}
+    for name in sorted(golden):
+        for which in ("stats", "boundary"):
+            assert got[name][which] == golden[name][which], (name, which)
+        assert sorted(got[name]["boundary"]["trace"]) in ([], sorted(["rejected", "skipped_void", "skipped_crowd", "demoted", "lowered"]))
+        assert sorted(got[name]["stats"]["trace"]) in ([], sorted(["rejected", "skipped_void", "skipped_crowd"]))
+
+
 def test_boundary_results_by_hand():
     st = PQ.PQStats(3)
     st.iou[:], st.tp[:], st.fp[:], st.fn[:] = [1.5, 0.0, 0.6], [2, 0, 1], [1, 0, 0], [1, 2, 1]
