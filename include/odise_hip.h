@@ -737,6 +737,93 @@ typedef struct {
     int32_t* flags;                           /* device [1] */
 } odise_inst_accum_desc;
 int odise_hip_instance_accumulate(odise_hip_ctx* ctx, const odise_inst_accum_desc* d);
+/* Video instance segmentation AP (YouTube-VIS: mask2former_video/data_video/ytvis_eval.py over datasets/ytvis_api/ytvoseval.py), which is
+ * COCOeval with two changes: the IoU of a predicted track and a ground-truth track is taken over the whole sequence, and areas are
+ * per-track means with ranges of their own.  Three calls: reset, one frame (any number of times), the end of a video.  Host restatement:
+ * odise_amd/video_eval.py.  The rule is restated from ytvoseval.py and pinned to hand-worked videos (tests/test_video_eval_cpu.py); parity
+ * with the reference evaluator is UNPINNED: pycocotools is no dependency of this project and no test runs the two side by side.
+ *   sums      over the frames of a video, for predicted track s and ground-truth track s': inter[s][s'] = sum of |d & g|, area_d[s] and
+ *             area_g[s'] = the sums of the pixel counts, frames_d[s] = the frames in which the track had a pixel.  A frame in which a
+ *             track has no mask adds nothing for it.  All exact integers in 64 bits: the same bytes from run to run.
+ *   iou       (computeIoU -> iou_seq) inter / (area_d + area_g - inter), one double division of exact integers; 0 when the denominator
+ *             is 0.  iscrowd does NOT enter the IoU (the reference builds the list and never uses it).
+ *   avg_area  of a predicted track (ytvos.py loadRes): area_d / frames_d, one double division; 0 without a frame.  Of a ground-truth
+ *             track: the same mean over the annotation's own `areas`, which the HOST takes (they are the file's floats, not pixel counts).
+ *   ranges    [0, 1e10], [0, 128^2], [128^2, 256^2], [256^2, 1e10], ends included.
+ *   walk      evaluateVid is evaluateImg (odise_hip_instance_eval) with a track where a detection stands: maxDet 100, descending score
+ *             with ties in table order, the crowd bit acting in the walk only, an unmatched track ignored when its avg_area lies outside
+ *             the range.  Accumulate and summarize are COCOeval's: the rows go into odise_hip_instance_accumulate unchanged, topk =
+ *             max_tracks, a video where a picture stands.
+ * The accumulators belong to the caller, so the library keeps no state between the calls: */
+typedef struct {
+    int64_t* inter;      /* device [max_tracks][max_gt] */
+    int64_t* area_d;     /* device [max_tracks]  sum of pixel counts */
+    int64_t* area_g;     /* device [max_gt] */
+    int32_t* frames_d;   /* device [max_tracks]  frames in which the track had a pixel */
+    int max_tracks;      /* 1..100 */
+    int max_gt;          /* 0..1024 */
+} odise_video_eval_state;
+/* Zeroes the four accumulators on the context's stream.  ODISE_ERR_ARG and nothing enqueued: a null pointer (inter and area_g may be
+ * NULL with max_gt = 0), max_tracks outside 1..100, max_gt outside 0..1024, a buffer not aligned to its element. */
+int odise_hip_video_eval_reset(odise_hip_ctx* ctx, const odise_video_eval_state* st);
+/* One frame.  The detections are those of odise_inst_eval_desc (dense masks [topk,h,w], inst_table optional then: NULL = all topk; or
+ * masks == NULL = the selection of image b of the last head forward, sampled from the mask logits); detections past the count of the
+ * table are not read.  det_slot[i] is the track of table index i, gt_slot[j] the ground-truth track of annotation j; a value outside
+ * [0, max_tracks) / [0, max_gt) belongs to no track and is skipped.  The ground truth is this frame's, as in odise_hip_instance_eval_poly:
+ * runs, polygons (p, may be NULL) or both.  The call packs the detections, decodes or rasterises the ground truth into the same words and
+ * adds to the sums above:
+ *   inter[det_slot[i]][gt_slot[j]] += popcount(d_i & g_j)      area_d[s] += |d_i|      frames_d[s] += (|d_i| > 0)      area_g[s'] += |g_j|
+ * The intersection is the tile loop of odise_hip_instance_eval (64 x 32 masks, 32 words, the word axis split over the grid) whose epilogue
+ * adds its partial counts through the two slot tables with 64-bit integer atomics: no [topk][n_gt] matrix is written and read again.
+ * flags (OR-ed): 1, 4 and 8 as in odise_hip_instance_eval_poly, read on the device: a frame that raises one adds nothing.  16 = two
+ * detections below the count share a slot, or two annotations share a gt slot: both are still added (the sums are those of the two masks,
+ * not of their union).
+ * ODISE_ERR_ARG and nothing enqueued: a null required pointer (d, st and its buffers, flags, det_slot; gt_slot, gt_runs and gt_offsets
+ * with n_gt > 0), topk outside 1..100, n_gt outside 0..1024, the limits of the state, h or w < 1, h * w > 2^30, a dtype other than
+ * ODISE_F32 / ODISE_U8, the polygon errors of odise_hip_instance_eval_poly, the geometry errors of odise_hip_instance_rle.  Scratch comes
+ * from the context.  Asynchronous on the context's stream: the host synchronises nowhere and reads no count. */
+typedef struct {
+    int h, w;
+    const void* masks; int dtype;
+    int b, pad_h, pad_w, img_h, img_w;
+    const int32_t* inst_table;
+    const float* inst_scores;       /* unused with dense masks, may be NULL then */
+    int topk;                       /* 1..100 */
+    const int32_t* det_slot;        /* device [topk] */
+    const uint32_t* gt_runs; const int64_t* gt_offsets;   /* as odise_hip_mask_iou */
+    const odise_inst_poly_gt* polys;                      /* HOST, or NULL: no polygon ground truth */
+    int n_gt;                       /* 0..1024: the annotations of this frame */
+    const int32_t* gt_slot;         /* device [n_gt] */
+    const odise_video_eval_state* st;
+    int32_t* flags;                 /* device [1] */
+} odise_video_frame_desc;
+int odise_hip_video_eval_frame(odise_hip_ctx* ctx, const odise_video_frame_desc* d);
+/* The end of a video: evaluateVid on the sums.  Track s (s < n_tracks) has score track_scores[s] and contiguous category
+ * track_category[s]; ground-truth track s' (s' < n_gt) is gt_rows[s'] = category, iscrowd, bits 0..3 = avg_area outside range a (the
+ * host computes these from the annotation, as for odise_hip_instance_eval).  rows / n_rows: odise_inst_eval_row [max_tracks] in descending
+ * score and their count, rows past it zeroed; a row's `area` is the track's avg_area truncated and clamped to int32, its `image` is
+ * `video`, its bits are 10 a + t as everywhere.  iou (double [n_tracks][n_gt]) and avg_area (double [n_tracks]) are optional dumps.
+ * flags (OR-ed): 2 = a track category outside [0, num_categories), 4 = a ground-truth category outside it / iscrowd not 0|1; a video
+ * that raises one writes n_rows = 0 and zeroed rows.  The sums are left as they are: reset starts the next video.
+ * ODISE_ERR_ARG and nothing enqueued: a null required pointer (d, st and its buffers, iou_thresholds, flags; track_scores and
+ * track_category with n_tracks > 0; gt_rows with n_gt > 0), n_tracks outside 0..max_tracks, n_gt outside 0..max_gt, the limits of the
+ * state, num_categories < 1, only one of rows / n_rows, neither rows nor a dump.  Asynchronous on the context's stream. */
+typedef struct {
+    const odise_video_eval_state* st;
+    int n_tracks;                   /* 0..st->max_tracks */
+    const float* track_scores;      /* device [n_tracks] */
+    const int32_t* track_category;  /* device [n_tracks] */
+    const int32_t* gt_rows;         /* device [n_gt][3] */
+    int n_gt;                       /* 0..st->max_gt */
+    int num_categories; int video;
+    const double* iou_thresholds;   /* HOST [10] */
+    odise_inst_eval_row* rows;      /* device [max_tracks] */
+    int32_t* n_rows;                /* device [1] */
+    int32_t* flags;                 /* device [1] */
+    double* iou;                    /* device [n_tracks][n_gt], optional */
+    double* avg_area;               /* device [n_tracks], optional */
+} odise_video_finish_desc;
+int odise_hip_video_eval_finish(odise_hip_ctx* ctx, const odise_video_finish_desc* d);
 
 /* ---- drawing a panoptic result (demo/demo.py:173-199 VisualizationDemo.run_on_image -> detectron2 Visualizer.draw_panoptic_seg) ----
  * The per-pixel work of that call on the panoptic record as it lies in HBM: the pieces of a segment, where its label goes, and the

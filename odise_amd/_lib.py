@@ -149,6 +149,26 @@ class InstAccumDesc(C.Structure):
                 ("npig", c_void_p), ("rec_thrs", c_void_p), ("n_rec", c_int), ("precision", c_void_p), ("recall", c_void_p), ("flags", c_void_p)]
 
 
+class VideoEvalState(C.Structure):
+    """odise_video_eval_state (include/odise_hip.h)."""
+    _fields_ = [("inter", c_void_p), ("area_d", c_void_p), ("area_g", c_void_p), ("frames_d", c_void_p), ("max_tracks", c_int), ("max_gt", c_int)]
+
+
+class VideoFrameDesc(C.Structure):
+    """odise_video_frame_desc (include/odise_hip.h)."""
+    _fields_ = [("h", c_int), ("w", c_int), ("masks", c_void_p), ("dtype", c_int), ("b", c_int), ("pad_h", c_int), ("pad_w", c_int),
+                ("img_h", c_int), ("img_w", c_int), ("inst_table", c_void_p), ("inst_scores", c_void_p), ("topk", c_int), ("det_slot", c_void_p),
+                ("gt_runs", c_void_p), ("gt_offsets", c_void_p), ("polys", c_void_p), ("n_gt", c_int), ("gt_slot", c_void_p), ("st", c_void_p),
+                ("flags", c_void_p)]
+
+
+class VideoFinishDesc(C.Structure):
+    """odise_video_finish_desc (include/odise_hip.h)."""
+    _fields_ = [("st", c_void_p), ("n_tracks", c_int), ("track_scores", c_void_p), ("track_category", c_void_p), ("gt_rows", c_void_p),
+                ("n_gt", c_int), ("num_categories", c_int), ("video", c_int), ("iou_thresholds", c_void_p), ("rows", c_void_p), ("n_rows", c_void_p),
+                ("flags", c_void_p), ("iou", c_void_p), ("avg_area", c_void_p)]
+
+
 class AnchorDesc(C.Structure):
     """odise_anchor_desc (include/odise_hip.h)."""
     _fields_ = [("H", c_int), ("W", c_int), ("pred_ids", c_void_p), ("pred_segments", c_void_p), ("small_area", c_int), ("large_area", c_int),

@@ -44,6 +44,11 @@ struct InstGeom {
 int inst_geom(odise_hip_ctx* ctx, const char* what, const InstSource& s, InstGeom* ig);
 // words [topk][G.nw] of the source: the dense pack, or the logits pack, which leaves the masks past the count of the table unwritten
 int inst_pack(odise_hip_ctx* ctx, const InstSource& s, const InstGeom& ig, const RleGrid& G, u64* words);
+// words_g [n_gt][G.nw] of a picture's ground truth (inst_eval.hip): every mask is zeroed and decoded from its run lengths; with p, one
+// that has polygons is rasterised instead (poly.hip; toggle: [n_gt][G.nw] words of scratch).  flag (device int [1]) collects 1 (runs
+// that do not sum to h * w), 4 (runs AND polygons on one ground truth) and 8 (a bad polygon).  n_gt >= 1.
+int inst_gt_words(odise_hip_ctx* ctx, const uint32_t* gt_runs, const int64_t* gt_offsets, int n_gt, const RleGrid& G, u64* words_g, u64* toggle,
+                  int* flag, const odise_inst_poly_gt* p);
 
 // ---- device: count, candidates, area -------------------------------------------------------------------------------------------------
 // the instances of a selection: table[0] clamped to 0..topk; no table = all topk

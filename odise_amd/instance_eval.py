@@ -275,13 +275,7 @@ def image_rows(masks, scores, classes, gt_counts, gt_table, image: int = 0, iou_
             flags |= FLAG_BAD_GT
     elif any(int(np.asarray(c, np.int64).sum()) != h * w for c in gt_counts):
         flags |= FLAG_BAD_RUNS
-    if num_categories is not None:
-        if n and (classes[:n].min() < 0 or classes[:n].max() >= num_categories):
-            flags |= FLAG_BAD_CLASS
-        if n_gt and (table[:, 0].min() < 0 or table[:, 0].max() >= num_categories):
-            flags |= FLAG_BAD_GT
-    if n_gt and not np.isin(table[:, 1], (0, 1)).all():
-        flags |= FLAG_BAD_GT
+    flags |= _table_flags(n, classes, table, num_categories)
     if flags:
         return np.zeros(0, ROW_DTYPE), flags
     if bbox:
@@ -291,6 +285,27 @@ def image_rows(masks, scores, classes, gt_counts, gt_table, image: int = 0, iou_
         ious, areas = boundary_iou(d, gt_counts, table[:, 1], radius)[0], d.reshape(n, h * w).sum(1)
     else:
         ious, areas = mask_iou(d, gt_counts, table[:, 1]), d.reshape(n, h * w).sum(1)
+    return _walk(n, scores, classes, table, ious, areas, None, image, iou_thrs), 0
+
+
+def _table_flags(n: int, classes, table, num_categories) -> int:
+    """Flags 2 and 4 of the classes of n detections and of a ground-truth table (num_categories None: the ranges are not checked)."""
+    flags, n_gt = 0, len(table)
+    if num_categories is not None:
+        if n and (classes[:n].min() < 0 or classes[:n].max() >= num_categories):
+            flags |= FLAG_BAD_CLASS
+        if n_gt and (table[:, 0].min() < 0 or table[:, 0].max() >= num_categories):
+            flags |= FLAG_BAD_GT
+    if n_gt and not np.isin(table[:, 1], (0, 1)).all():
+        flags |= FLAG_BAD_GT
+    return flags
+
+
+def _walk(n: int, scores, classes, table, ious, areas, outside, image: int, iou_thrs):
+    """The walk of `image_rows` over an IoU matrix from outside -> rows ROW_DTYPE [n] in descending score.  ious float64 [n, n_gt];
+    areas [n]: what a row shows; outside: bool [n, 4], an unmatched detection lies outside range a - None = `area_outside` of the row's
+    area.  The seam video_eval.video_rows enters by: a track stands where a detection stands."""
+    n_gt = len(table)
     order = np.argsort(-scores[:n], kind="mergesort")
     rows = np.zeros(n, ROW_DTYPE)
     rows["score"], rows["category"], rows["image"] = scores[order], classes[order], image
@@ -325,10 +340,10 @@ def image_rows(masks, scores, classes, gt_counts, gt_table, image: int = 0, iou_
                         rows["matched"][pos[i]] |= bit
                         ig = gt_ig[m]
                     else:
-                        ig = area_outside(int(rows["area"][pos[i]]), a)
+                        ig = area_outside(int(rows["area"][pos[i]]), a) if outside is None else bool(outside[i][a])
                     if ig:
                         rows["ignored"][pos[i]] |= bit
-    return rows, 0
+    return rows
 
 
 # ---- accumulate / summarize ---------------------------------------------------------------------------------------------------------------

@@ -954,9 +954,12 @@ class Context:
         `gt_rows(..., polygons=True)` the same upload carries poly_offsets int64 | xy float64 in front of the table and gt_polys int32
         behind it, and the dict gains {"n_poly", "xy", "poly_offsets", "gt_polys"}.  With `boxes` (instance_eval.gt_boxes: float64
         [n_gt, 4] XYWH) the same upload carries them in front of the table and the dict gains {"boxes"}.  The upload waits for the stream."""
-        table = np.ascontiguousarray(np.asarray(gt_table, np.int32).reshape(-1, 3))
         runs, offsets = np.ascontiguousarray(runs, np.uint32), np.ascontiguousarray(offsets, np.int64)
-        n_gt = table.shape[0]
+        if gt_table is None:                                             # masks alone (the frames of the video evaluator): "rows" is empty
+            table, n_gt = np.zeros((0, 3), np.int32), offsets.size - 1
+        else:
+            table = np.ascontiguousarray(np.asarray(gt_table, np.int32).reshape(-1, 3))
+            n_gt = table.shape[0]
         assert offsets.shape == (n_gt + 1,) and int(offsets[-1]) == runs.size, (offsets.shape, n_gt, runs.size)
         parts = [offsets]
         if gt_polys is not None:
@@ -974,7 +977,7 @@ class Context:
         parts += [table.reshape(-1)] + ([gt_polys] if gt_polys is not None else []) + [runs]
         buf = self.to_device(np.concatenate([p.view(np.uint8) for p in parts]))
         at = np.concatenate(([0], np.cumsum([p.nbytes for p in parts]))).tolist()
-        gt = {"n_gt": n_gt, "offsets": buf.view((n_gt + 1,), np.int64), "rows": buf.view((n_gt, 3), np.int32, at[-3 if gt_polys is None else -4]),
+        gt = {"n_gt": n_gt, "offsets": buf.view((n_gt + 1,), np.int64), "rows": buf.view((table.shape[0], 3), np.int32, at[-3 if gt_polys is None else -4]),
               "runs": buf.view((runs.size,), np.uint32, at[-2])}
         if gt_polys is not None:
             gt.update(n_poly=n_poly, poly_offsets=buf.view((n_poly + 1,), np.int64, at[1]), xy=buf.view((xy.size,), np.float64, at[2]),
@@ -1158,6 +1161,47 @@ class Context:
             raise InstanceAccumulateError(f, precision, recall)
         return precision, recall
 
+    # ---- video instance segmentation AP (include/odise_hip.h odise_hip_video_eval_*; host restatement: odise_amd/video_eval.py) --------
+    def video_eval_state(self, max_tracks: int = 100, max_gt: int = 1024) -> "VideoEvalState":
+        """The caller-owned accumulators of one video (odise_video_eval_state), not yet zeroed: `video_eval_reset` starts a video."""
+        return VideoEvalState(self, max_tracks, max_gt)
+
+    def video_eval_reset(self, state: "VideoEvalState") -> None:
+        check(self.lib.odise_hip_video_eval_reset(self.h, C.byref(state.struct)), "video_eval_reset")
+
+    def video_eval_frame(self, state: "VideoEvalState", out_hw, topk: int, det_slot, gt: Optional[dict], gt_slot, flags, table_row=None,
+                         scores_row=None, masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0), img_hw=(0, 0)) -> None:
+        """Enqueue one frame (odise_hip_video_eval_frame): the detections as in `instance_eval` (dense `masks` [topk, h, w], table_row
+        optional then; or the selection table_row / scores_row of image b of the last head forward), det_slot int32 [topk] = the track of
+        every table index; gt = `instance_gt_to_device` of the frame's annotations (None: none) and gt_slot int32 [n_gt] their tracks;
+        slots outside the state's range are skipped.  flags int32 [1]; all device arrays or pointers."""
+        from ._lib import VideoFrameDesc
+        d = VideoFrameDesc()
+        _fill_inst_source(d, "video_eval_frame", out_hw, topk, table_row, scores_row, masks, b, pad_hw, img_hw)
+        d.det_slot, d.st, d.flags = _ptr(det_slot), C.addressof(state.struct), _ptr(flags)
+        p = None
+        if gt is not None and gt["n_gt"]:
+            d.gt_runs, d.gt_offsets, d.n_gt, d.gt_slot = gt["runs"].ptr, gt["offsets"].ptr, int(gt["n_gt"]), _ptr(gt_slot)
+            p = _inst_poly_gt(gt)
+            if p is not None:
+                d.polys = C.addressof(p._obj)
+        check(self.lib.odise_hip_video_eval_frame(self.h, C.byref(d)), "video_eval_frame")
+
+    def video_eval_finish(self, state: "VideoEvalState", n_tracks: int, track_scores, track_category, gt_rows, n_gt: int, num_categories: int,
+                          video: int, rows, n_rows, flags, iou=None, avg_area=None, iou_thresholds=None) -> None:
+        """Enqueue the end of a video (odise_hip_video_eval_finish): track_scores float32 / track_category int32 [n_tracks], gt_rows int32
+        [n_gt, 3] (video_eval.gt_track_rows), rows (instance_eval.ROW_DTYPE [max_tracks]) / n_rows / flags (int32 [1]) and the optional
+        dumps iou float64 [n_tracks, n_gt] / avg_area float64 [n_tracks]: device arrays or pointers."""
+        from ._lib import VideoFinishDesc
+        from .instance_eval import IOU_THRS
+        thr = np.ascontiguousarray(IOU_THRS if iou_thresholds is None else iou_thresholds, np.float64)
+        assert thr.shape == (10,), thr.shape
+        d = VideoFinishDesc()
+        d.st, d.n_tracks, d.track_scores, d.track_category = C.addressof(state.struct), int(n_tracks), _ptr(track_scores), _ptr(track_category)
+        d.gt_rows, d.n_gt, d.num_categories, d.video, d.iou_thresholds = _ptr(gt_rows), int(n_gt), int(num_categories), int(video), thr.ctypes.data
+        d.rows, d.n_rows, d.flags, d.iou, d.avg_area = _ptr(rows), _ptr(n_rows), _ptr(flags), _ptr(iou), _ptr(avg_area)
+        check(self.lib.odise_hip_video_eval_finish(self.h, C.byref(d)), "video_eval_finish")
+
     def jpeg_decode(self, data: bytes, apply_orientation: bool = True, out: Optional[DeviceArray] = None) -> DeviceArray:
         """read_image(file, "RGB") for a baseline JPEG: host Huffman decoding, IDCT / upsampling / colour conversion / EXIF transpose on
         the device -> uint8 [H,W,3], bit-identical to Pillow.  Baseline, extended-sequential and progressive files; raises `UnsupportedInput` for arithmetic-coded / CMYK / RGB-coded ones."""
@@ -1171,6 +1215,37 @@ class Context:
         check(self.lib.odise_hip_jpeg_decode(self.h, buf, C.c_int64(len(data)), _p(out), C.c_int64(out.nbytes), int(bool(apply_orientation)),
                                              C.byref(h), C.byref(w)), "jpeg_decode")
         return out.view((h.value, w.value, 3)) if out.shape != (h.value, w.value, 3) else out
+
+
+class VideoEvalState:
+    """odise_video_eval_state: the sums of one video in ONE device buffer - inter int64 [max_tracks, max_gt] | area_d int64 [max_tracks] |
+    area_g int64 [max_gt] | frames_d int32 [max_tracks] - with `.struct` for the calls.  `numpy()` reads all four back at once."""
+
+    def __init__(self, ctx: "Context", max_tracks: int, max_gt: int):
+        from ._lib import VideoEvalState as _State
+        self.ctx, self.max_tracks, self.max_gt = ctx, int(max_tracks), int(max_gt)
+        T, G = self.max_tracks, self.max_gt
+        self.buf = ctx.empty((8 * (T * G + T + G) + 4 * T,), np.uint8)
+        self.inter = self.buf.view((T, G), np.int64)
+        self.area_d = self.buf.view((T,), np.int64, 8 * T * G)
+        self.area_g = self.buf.view((G,), np.int64, 8 * (T * G + T))
+        self.frames_d = self.buf.view((T,), np.int32, 8 * (T * G + T + G))
+        self.struct = _State()
+        self.struct.inter, self.struct.area_d, self.struct.area_g, self.struct.frames_d = self.inter.ptr, self.area_d.ptr, self.area_g.ptr, self.frames_d.ptr
+        self.struct.max_tracks, self.struct.max_gt = T, G
+
+    def numpy(self):
+        """-> (inter, area_d, area_g, frames_d) on the host (one read, which waits)."""
+        T, G = self.max_tracks, self.max_gt
+        raw = self.buf.numpy()
+        i64 = raw[:8 * (T * G + T + G)].view(np.int64)
+        return i64[:T * G].reshape(T, G), i64[T * G:T * G + T], i64[T * G + T:], raw[8 * (T * G + T + G):].view(np.int32)
+
+    def copy_from(self, inter, area_d, area_g, frames_d) -> None:
+        """Upload all four (tests preload them)."""
+        parts = [np.ascontiguousarray(inter, np.int64).reshape(-1), np.ascontiguousarray(area_d, np.int64), np.ascontiguousarray(area_g, np.int64),
+                 np.ascontiguousarray(frames_d, np.int32)]
+        self.buf.copy_from(np.concatenate([p.view(np.uint8) for p in parts]))
 
 
 class _Handle:
