@@ -737,6 +737,50 @@ typedef struct {
     int32_t* flags;                           /* device [1] */
 } odise_inst_accum_desc;
 int odise_hip_instance_accumulate(odise_hip_ctx* ctx, const odise_inst_accum_desc* d);
+/* LVIS AP for iouType "segm" (lvis-api LVISEval / LVISResults as detectron2's LVISEvaluator drives them): the walk of
+ * odise_hip_instance_eval with LVIS' federated rules, at up to 300 detections of a picture over ALL categories.  Host restatement, which
+ * is the specification: odise_amd/lvis_eval.py.  The rule is restated from lvis-api and pinned to hand-worked pictures
+ * (tests/test_lvis_eval_cpu.py); parity with the lvis package is UNPINNED: it is no dependency of this project and no test runs the two
+ * side by side.  "bbox" and "boundary" for LVIS are not part of this.
+ *   cut          the caller's table holds the picture's detections cut at 300 by score (d->topk 1..300; lvis_eval.limit_dets).
+ *   federation   pos = the categories with a ground truth in the picture (taken from d->gt_rows on the device); lv->neg_bits = those known
+ *                to be absent, lv->not_exhaustive_bits = those annotated incompletely: device uint32 [ceil(K / 32)] each, bit k % 32 of
+ *                word k / 32 = category k; bits at K and above are not looked at.  A detection whose category is in neither pos nor neg is
+ *                DROPPED: it gives no row and is counted nowhere.
+ *   walk         odise_hip_instance_eval's, with no crowd: LVIS has none, and iscrowd != 0 raises flag 4.  A ground truth with the
+ *                annotation's `ignore` set comes as outside bits 0b1111: it is matched like any other, once, and hands its ignore bit on.
+ *   unmatched    a detection without a match is ignored in range a when its area lies outside a OR its category is not exhaustive.
+ * d->rows: the kept detections in descending score (ties in table order), row k = rank k among the KEPT; *d->n_rows = their count; rows
+ * past it up to topk are zeroed.  Flags 1 / 2 / 4 / 8 as for odise_hip_instance_eval_poly; a picture that raises one writes n_rows = 0
+ * and zeroed rows.  p: polygon ground truth, NULL = run lengths only.
+ * With detections taken from the mask logits (d->masks NULL) the table holds (query, class) pairs, and every distinct query is sampled,
+ * counted and intersected ONCE, however many classes it stands with; the rows are those of the same call on the dense masks of the pairs.
+ * ODISE_ERR_ARG and nothing written: a null pointer (lv and both bitsets included), topk outside 1..300, n_gt outside 0..1024,
+ * num_categories outside 1..65535, the geometry errors of odise_hip_instance_rle.  Scratch comes from the context.  Asynchronous on the
+ * context's stream; no host synchronisation. */
+typedef struct {
+    const uint32_t* neg_bits;             /* device [ceil(K / 32)] */
+    const uint32_t* not_exhaustive_bits;  /* device [ceil(K / 32)] */
+} odise_lvis_task;
+int odise_hip_lvis_eval(odise_hip_ctx* ctx, const odise_inst_eval_desc* d, const odise_inst_poly_gt* p, const odise_lvis_task* lv);
+/* LVISEval.accumulate on the rows of odise_hip_lvis_eval: odise_hip_instance_accumulate (blocks, slots, order, flags, limits, scratch) with
+ * topk 1..300 and ONE cut, the 300 per picture that the rows already respect, so there is no maxDets axis: precision [10][R][K][4],
+ * recall [10][K][4].  Byte for byte what odise_amd/lvis_eval.py accumulate returns for the same rows. */
+typedef struct {
+    int n_blocks;
+    const odise_inst_eval_row* const* rows;   /* HOST [n_blocks] of device pointers */
+    const int32_t* const* counts;             /* HOST [n_blocks] of device pointers */
+    const int32_t* slots;                     /* HOST [n_blocks] */
+    int topk;                                 /* rows per slot, 1..300 */
+    int num_categories;                       /* K */
+    const int64_t* npig;                      /* device [K][4] */
+    const double* rec_thrs;                   /* device [n_rec], ascending */
+    int n_rec;                                /* R */
+    double* precision;                        /* device [10][R][K][4] */
+    double* recall;                           /* device [10][K][4] */
+    int32_t* flags;                           /* device [1] */
+} odise_lvis_accum_desc;
+int odise_hip_lvis_accumulate(odise_hip_ctx* ctx, const odise_lvis_accum_desc* d);
 /* Video instance segmentation AP (YouTube-VIS: mask2former_video/data_video/ytvis_eval.py over datasets/ytvis_api/ytvoseval.py), which is
  * COCOeval with two changes: the IoU of a predicted track and a ground-truth track is taken over the whole sequence, and areas are
  * per-track means with ranges of their own.  Three calls: reset, one frame (any number of times), the end of a video.  Host restatement:

@@ -149,6 +149,16 @@ class InstAccumDesc(C.Structure):
                 ("npig", c_void_p), ("rec_thrs", c_void_p), ("n_rec", c_int), ("precision", c_void_p), ("recall", c_void_p), ("flags", c_void_p)]
 
 
+class LvisTask(C.Structure):
+    """odise_lvis_task (include/odise_hip.h)."""
+    _fields_ = [("neg_bits", c_void_p), ("not_exhaustive_bits", c_void_p)]
+
+
+class LvisAccumDesc(C.Structure):
+    """odise_lvis_accum_desc (include/odise_hip.h): the members of odise_inst_accum_desc."""
+    _fields_ = list(InstAccumDesc._fields_)
+
+
 class VideoEvalState(C.Structure):
     """odise_video_eval_state (include/odise_hip.h)."""
     _fields_ = [("inter", c_void_p), ("area_d", c_void_p), ("area_g", c_void_p), ("frames_d", c_void_p), ("max_tracks", c_int), ("max_gt", c_int)]

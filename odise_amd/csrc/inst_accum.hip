@@ -21,6 +21,10 @@
 //               positive writes precision[t, r, k, a, m] for every r with c[r] == e; cells with c[r] beyond the total are 0.  Rows past a
 //               maxDet cut carry the counts of the row before them, so they never raise the maximum.
 //
+// odise_hip_lvis_accumulate (LVISEval.accumulate; host restatement odise_amd/lvis_eval.py accumulate) is the same five steps with up to 300
+// rows per slot (five rows per lane in step 2) and ONE cut, which the rows of odise_hip_lvis_eval already respect: every row is selected
+// (bit 40), there is no rank, and the outputs have no maxDets axis.
+//
 // Counts are integers and the maximum is exact: the same bytes from run to run.  No fast-math, no contraction: the divisions are IEEE.
 #include <algorithm>
 
@@ -30,7 +34,7 @@
 
 namespace odise {
 
-constexpr int kAccumMaxTopk = 100, kAccumMaxRec = 101, kAccumMaxK = 65535;
+constexpr int kAccumMaxTopk = 100, kLvisAccumMaxTopk = 300, kAccumMaxRec = 101, kAccumMaxK = 65535;
 constexpr int64_t kAccumMaxRows = 1 << 24;
 constexpr int kAccumT = 10, kAccumA = 4, kAccumM = 3;
 constexpr int kAccumChunkBlocks = 32;      // blocks of rows described by value in one launch of the slot kernel
@@ -69,21 +73,23 @@ __device__ __forceinline__ uint32_t score_key(float s) {
     return ~u;
 }
 
+// kPer: the rows of a slot that a lane takes (64 kPer >= topk); kOneCut: no maxDets cuts, every row is selected (bit 40)
+template <int kPer, bool kOneCut>
 __global__ void __launch_bounds__(256) accum_rows_kernel(const uint32_t* __restrict__ order, const odise_inst_eval_row* const* __restrict__ slot_rows,
                                                         const int* __restrict__ slot_n, int n_slots, int topk, int K,
                                                         sort_key* __restrict__ keys, uint32_t* __restrict__ vals, u64* __restrict__ tpw,
                                                         u64* __restrict__ fpw, int* __restrict__ status, int* __restrict__ flags) {
-    __shared__ int cats[4][128];
+    __shared__ int cats[4][64 * kPer];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int r = blockIdx.x * 4 + wave;                       // position of the slot in image order
     const bool live = r < n_slots;
     const int slot = live ? (int)order[r] : 0;
     const odise_inst_eval_row* rows = live ? slot_rows[slot] : nullptr;
     const int n = live ? slot_n[slot] : 0;
-    odise_inst_eval_row row[2];
+    odise_inst_eval_row row[kPer];
     int f = 0;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < kPer; ++h) {
         const int i = lane + 64 * h;
         int cat = K;
         if (i < n) {
@@ -97,7 +103,7 @@ __global__ void __launch_bounds__(256) accum_rows_kernel(const uint32_t* __restr
     __syncthreads();
     if (!live) return;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < kPer; ++h) {
         const int i = lane + 64 * h;
         if (i >= topk) continue;
         const int64_t o = (int64_t)r * topk + i;
@@ -105,9 +111,12 @@ __global__ void __launch_bounds__(256) accum_rows_kernel(const uint32_t* __restr
         u64 tw = 0ull, fw = 0ull;
         sort_key key = ((sort_key)(uint32_t)K << 32) | 0xFFFFFFFFull;
         if (cat < K) {                                         // an existing row without a flag
-            int rank = 0;
-            for (int j = 0; j < n; ++j) rank += (j < i && cats[wave][j] == cat) ? 1 : 0;
-            const u64 sel = (rank < 1 ? 1ull : 0ull) | (rank < 10 ? 2ull : 0ull) | (rank < 100 ? 4ull : 0ull);
+            u64 sel = 1ull;
+            if constexpr (!kOneCut) {
+                int rank = 0;
+                for (int j = 0; j < n; ++j) rank += (j < i && cats[wave][j] == cat) ? 1 : 0;
+                sel = (rank < 1 ? 1ull : 0ull) | (rank < 10 ? 2ull : 0ull) | (rank < 100 ? 4ull : 0ull);
+            }
             tw = (row[h].matched & ~row[h].ignored & kCellMask) | (sel << 40);
             fw = ~row[h].matched & ~row[h].ignored & kCellMask;
             key = ((sort_key)(uint32_t)cat << 32) | score_key(row[h].score);
@@ -144,6 +153,8 @@ __device__ __forceinline__ int first_of_category(const sort_key* keys, int n, ui
     return lo;
 }
 
+// kM: the maxDets cuts, the last axis of both outputs (3: bits 40..42 of a row's first word; 1: bit 40, which every row carries)
+template <int kM>
 __global__ void __launch_bounds__(64 * kAccumT) accum_cells_kernel(const sort_key* __restrict__ keys, const u64* __restrict__ tps,
                                                                   const u64* __restrict__ fps, int n_rows, int K, int R,
                                                                   const long long* __restrict__ npig, const double* __restrict__ rec_thrs,
@@ -152,11 +163,11 @@ __global__ void __launch_bounds__(64 * kAccumT) accum_cells_kernel(const sort_ke
     __shared__ int c[kAccumMaxRec];      // the true positives that reach recall threshold r, at least 1
     __shared__ int seg[2];
     const int tid = threadIdx.x, lane = tid & 63, t = tid >> 6;
-    const int k = blockIdx.x, a = blockIdx.y / kAccumM, m = blockIdx.y - a * kAccumM;
+    const int k = blockIdx.x, a = blockIdx.y / kM, m = blockIdx.y - a * kM;
     const long long np = npig[(int64_t)k * kAccumA + a];
-    const int64_t pstride = (int64_t)K * (kAccumA * kAccumM);                                   // between r and r + 1
-    double* prec = precision + (int64_t)t * R * pstride + (int64_t)k * (kAccumA * kAccumM) + a * kAccumM + m;
-    double* rec = recall + ((int64_t)t * K + k) * (kAccumA * kAccumM) + a * kAccumM + m;
+    const int64_t pstride = (int64_t)K * (kAccumA * kM);                                        // between r and r + 1
+    double* prec = precision + (int64_t)t * R * pstride + (int64_t)k * (kAccumA * kM) + a * kM + m;
+    double* rec = recall + ((int64_t)t * K + k) * (kAccumA * kM) + a * kM + m;
     if (status[0] != 0 || np <= 0) {     // no non-ignored ground truth in (k, a), or the call raised a flag
         for (int r = lane; r < R; r += 64) prec[r * pstride] = -1.0;
         if (lane == 0) rec[0] = -1.0;
@@ -236,21 +247,24 @@ using namespace odise;
 
 extern "C" int odise_hip_sizeof_inst_accum_desc(void) { return (int)sizeof(odise_inst_accum_desc); }
 
-extern "C" int odise_hip_instance_accumulate(odise_hip_ctx* ctx, const odise_inst_accum_desc* d) {
-    ODISE_REQUIRE(ctx && d, "instance_accumulate: null argument");
-    ODISE_REQUIRE(d->npig && d->rec_thrs && d->precision && d->recall && d->flags, "instance_accumulate: null pointer");
-    ODISE_REQUIRE(d->topk >= 1 && d->topk <= kAccumMaxTopk, "instance_accumulate: topk %d (1..%d)", d->topk, kAccumMaxTopk);
-    ODISE_REQUIRE(d->num_categories >= 1 && d->num_categories <= kAccumMaxK, "instance_accumulate: num_categories %d (1..%d)", d->num_categories,
+// COCOeval.accumulate (odise_inst_accum_desc: maxDets 1 / 10 / 100, topk <= 100) or LVISEval.accumulate (odise_lvis_accum_desc: one cut,
+// topk <= 300) of a descriptor; the two have the same members
+template <class Desc, int kMaxTopk, int kM>
+static int accum_run(odise_hip_ctx* ctx, const Desc* d, const char* what) {
+    ODISE_REQUIRE(ctx && d, "%s: null argument", what);
+    ODISE_REQUIRE(d->npig && d->rec_thrs && d->precision && d->recall && d->flags, "%s: null pointer", what);
+    ODISE_REQUIRE(d->topk >= 1 && d->topk <= kMaxTopk, "%s: topk %d (1..%d)", what, d->topk, kMaxTopk);
+    ODISE_REQUIRE(d->num_categories >= 1 && d->num_categories <= kAccumMaxK, "%s: num_categories %d (1..%d)", what, d->num_categories,
                   kAccumMaxK);
-    ODISE_REQUIRE(d->n_rec >= 1 && d->n_rec <= kAccumMaxRec, "instance_accumulate: %d recall thresholds (1..%d)", d->n_rec, kAccumMaxRec);
-    ODISE_REQUIRE(d->n_blocks >= 0 && (d->n_blocks == 0 || (d->rows && d->counts && d->slots)), "instance_accumulate: %d blocks, null block table",
+    ODISE_REQUIRE(d->n_rec >= 1 && d->n_rec <= kAccumMaxRec, "%s: %d recall thresholds (1..%d)", what, d->n_rec, kAccumMaxRec);
+    ODISE_REQUIRE(d->n_blocks >= 0 && (d->n_blocks == 0 || (d->rows && d->counts && d->slots)), "%s: %d blocks, null block table", what,
                   d->n_blocks);
     int64_t n_slots = 0;
     for (int b = 0; b < d->n_blocks; ++b) {
-        ODISE_REQUIRE(d->slots[b] >= 0 && (d->slots[b] == 0 || (d->rows[b] && d->counts[b])), "instance_accumulate: block %d: %d slots, null pointer", b,
+        ODISE_REQUIRE(d->slots[b] >= 0 && (d->slots[b] == 0 || (d->rows[b] && d->counts[b])), "%s: block %d: %d slots, null pointer", what, b,
                       d->slots[b]);
         n_slots += d->slots[b];
-        ODISE_REQUIRE(n_slots * d->topk <= kAccumMaxRows, "instance_accumulate: more than %lld rows", (long long)kAccumMaxRows);
+        ODISE_REQUIRE(n_slots * d->topk <= kAccumMaxRows, "%s: more than %lld rows", what, (long long)kAccumMaxRows);
     }
     ODISE_CHECK_HIP(hipSetDevice(ctx->device));
     const int K = d->num_categories, R = d->n_rec, topk = d->topk, S = (int)n_slots;
@@ -301,7 +315,8 @@ extern "C" int odise_hip_instance_accumulate(odise_hip_ctx* ctx, const odise_ins
             }
         }
         ODISE_TRY(radix_sort_pairs(ctx->stream, ss, S, 32, &side));
-        hipLaunchKernelGGL(accum_rows_kernel, dim3((unsigned)ceil_div(S, 4)), dim3(256), 0, ctx->stream, (const uint32_t*)ss.vals[side],
+        hipLaunchKernelGGL((accum_rows_kernel<(kMaxTopk + 63) / 64, kM == 1>), dim3((unsigned)ceil_div(S, 4)), dim3(256), 0, ctx->stream,
+                           (const uint32_t*)ss.vals[side],
                            (const odise_inst_eval_row* const*)slot_rows, (const int*)slot_n, S, topk, K, rs.keys[0], rs.vals[0], tpw, fpw, status,
                            (int*)d->flags);
         ODISE_CHECK_HIP(hipGetLastError());
@@ -312,8 +327,16 @@ extern "C" int odise_hip_instance_accumulate(odise_hip_ctx* ctx, const odise_ins
                            (const u64*)tpw, (const u64*)fpw, N, tps, fps);
         ODISE_CHECK_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(accum_cells_kernel, dim3((unsigned)K, kAccumA * kAccumM), dim3(64 * kAccumT), 0, ctx->stream, (const sort_key*)rs.keys[side],
+    hipLaunchKernelGGL(accum_cells_kernel<kM>, dim3((unsigned)K, kAccumA * kM), dim3(64 * kAccumT), 0, ctx->stream, (const sort_key*)rs.keys[side],
                        (const u64*)tps, (const u64*)fps, N, K, R, (const long long*)d->npig, d->rec_thrs, (const int*)status, d->precision, d->recall);
     ODISE_CHECK_HIP(hipGetLastError());
     return ODISE_OK;
+}
+
+extern "C" int odise_hip_instance_accumulate(odise_hip_ctx* ctx, const odise_inst_accum_desc* d) {
+    return accum_run<odise_inst_accum_desc, kAccumMaxTopk, kAccumM>(ctx, d, "instance_accumulate");
+}
+
+extern "C" int odise_hip_lvis_accumulate(odise_hip_ctx* ctx, const odise_lvis_accum_desc* d) {
+    return accum_run<odise_lvis_accum_desc, kLvisAccumMaxTopk, 1>(ctx, d, "lvis_accumulate");
 }

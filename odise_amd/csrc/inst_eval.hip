@@ -175,27 +175,15 @@ __global__ void __launch_bounds__(256) inst_biou_kernel(const int* __restrict__ 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------------------
-struct InstScratch {
-    u64 *words_d, *words_g;
-    long long* area;   // [n + n_gt]
-    int* inter;        // [n][n_gt], then one int: the status of the call
-    size_t inter_bytes;
-    u64* toggle;       // with polygon ground truth: the toggle planes of poly.hip, [n_gt] masks
-    float* boxes;      // the bbox task without an output for them: [n][4]
-    // the boundary task: the boundaries of all n + n_gt masks (detections first, like the words they come from), the temporary of
-    // inst_boundary_words, their areas [n + n_gt] and intersections [n][n_gt]
-    u64 *bwords, *btmp;
-    long long* barea;
-    int* binter;
-};
-static int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, InstScratch* s, bool polygons = false, bool boxes = false,
-                        bool boundary = false) {
+int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, InstScratch* s, bool polygons, bool boxes, bool boundary,
+                 size_t extra_bytes) {
     const size_t wb = (size_t)round_up((int64_t)(n + n_gt) * G.nw * 8, 256), ab = (size_t)round_up((int64_t)(n + n_gt) * 8, 256);
     s->inter_bytes = ((size_t)n * n_gt + 1) * sizeof(int);
     const size_t ib = (size_t)round_up((int64_t)s->inter_bytes, 256);
     const size_t bb = boxes ? (size_t)round_up((int64_t)n * 16, 256) : 0;
     const size_t tb = polygons ? (size_t)round_up((int64_t)n_gt * G.nw * 8, 256) : 0;
-    ODISE_TRY(scratch_reserve(ctx->rle, wb + ab + ib + bb + tb + (boundary ? 2 * wb + ab + ib : 0), 8, drain_streams(ctx->stream), "rle"));
+    const size_t db = boundary ? 2 * wb + ab + ib : 0;
+    ODISE_TRY(scratch_reserve(ctx->rle, wb + ab + ib + bb + tb + db + extra_bytes, 8, drain_streams(ctx->stream), "rle"));
     char* p = (char*)ctx->rle.ptr;
     s->words_d = (u64*)p;
     s->words_g = s->words_d + (int64_t)n * G.nw;
@@ -208,6 +196,7 @@ static int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, I
     s->btmp = (u64*)(q + wb);
     s->barea = (long long*)(q + 2 * wb);
     s->binter = (int*)(q + 2 * wb + ab);
+    s->extra = q + db;
     return ODISE_OK;
 }
 
@@ -232,9 +221,9 @@ int inst_gt_words(odise_hip_ctx* ctx, const uint32_t* gt_runs, const int64_t* gt
     return ODISE_OK;
 }
 
-// stages 2 and 3 behind the packed detections: ground-truth words, inter, area; flag 1 (and 4, 8 of polygon ground truth) goes to `flag`
-static int inst_overlaps(odise_hip_ctx* ctx, const InstScratch& s, const RleGrid& G, int n, const uint32_t* gt_runs, const int64_t* gt_offsets, int n_gt,
-                         int* flag, const odise_inst_poly_gt* p = nullptr) {
+// stages 2 and 3 behind the packed detections (declared in inst_words.h)
+int inst_overlaps(odise_hip_ctx* ctx, const InstScratch& s, const RleGrid& G, int n, const uint32_t* gt_runs, const int64_t* gt_offsets, int n_gt,
+                  int* flag, const odise_inst_poly_gt* p) {
     if (n_gt) ODISE_TRY(inst_gt_words(ctx, gt_runs, gt_offsets, n_gt, G, s.words_g, s.toggle, flag, p));
     return inst_counts(ctx, s.words_d, G, n, n_gt, s.inter, s.area);
 }

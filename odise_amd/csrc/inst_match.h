@@ -2,7 +2,8 @@
 // odise_hip_instance_eval(_poly, _bbox, _boundary) (inst_eval.hip: a picture) and odise_hip_video_eval_finish (video_eval.hip: a video,
 // whose "detections" are tracks).  The walk takes its IoU, its areas and its area ranges from a functor; the functors of the picture
 // tasks stand here beside it, the one of the video task in video_eval.hip.
-//   device  rle_iou, InstMatchArgs, SegmIou / BoxIou / BoundaryIou, inst_match_kernel
+//   device  rle_iou, InstMatchArgs, SegmIou / BoxIou / BoundaryIou, NoFederation, inst_match_walk (the walk; its detection arrays have a
+//           compile-time capacity), inst_match_kernel (the walk at 100 detections without federated rules; LVIS' kernel: lvis_eval.hip)
 #pragma once
 #include "inst_words.h"
 
@@ -80,16 +81,24 @@ struct BoundaryIou {   // Boundary AP's IoU: min(rleIou of the masks, rleIou of 
     }
 };
 
+// The federated rules of a dataset whose pictures are annotated for some categories only (LVIS, lvis_eval.hip), as the walk asks for them:
+// kOn: there are such rules, and then no crowds (iscrowd != 0 raises flag 4); keep(cls, cnt): a detection of category cls, which has cnt
+// ground truths in the picture, takes part at all - one that does not produces no row.  Without rules every detection takes part.
+struct NoFederation {
+    static constexpr bool kOn = false;
+    __device__ bool keep(int, int) const { return true; }
+};
+
 // One block.  Detections in descending score (ties keep table order), ground truths of a category in annotation order.  The 40 (area
 // range, threshold) cells of a detection are the lanes 10 a + t of ONE wave, which walks the ground truths of the detection's category
-// once (inst_eval.hip, step 5).
-template <class Iou>
-__global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A, Iou iou_of) {
+// once (inst_eval.hip, step 5).  kCap: the detections the LDS arrays hold, A.topk <= kCap.
+template <class Iou, int kCap, class Fed>
+__device__ __forceinline__ void inst_match_walk(const InstMatchArgs& A, const Iou& iou_of, const Fed& fed) {
     __shared__ int g_cat[kInstMaxGt], g_flag[kInstMaxGt], g_area[kInstMaxGt], g_sorted[kInstMaxGt];   // g_flag: iscrowd | outside bits << 1
     __shared__ u64 g_matched[kInstMaxGt];                                                             // bit = cell
-    __shared__ int d_cls[kInstMaxTopk], d_area[kInstMaxTopk], d_order[kInstMaxTopk], d_lo[kInstMaxTopk], d_cnt[kInstMaxTopk];
-    __shared__ float d_score[kInstMaxTopk];
-    __shared__ int bad;
+    __shared__ int d_cls[kCap], d_area[kCap], d_order[kCap], d_lo[kCap], d_cnt[kCap];
+    __shared__ float d_score[kCap];
+    __shared__ int bad, n_keep;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int topk = A.topk, n_gt = A.n_gt;
     const int n = A.inst_table ? inst_count(A.inst_table, topk) : min(max(A.n_det, 0), topk);
@@ -98,7 +107,7 @@ __global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A
     int f = 0;
     for (int j = tid; j < n_gt; j += kRleThreads) {
         const int cat = A.gt_rows[3 * j], crowd = A.gt_rows[3 * j + 1];
-        if ((unsigned)cat >= (unsigned)A.num_categories || (unsigned)crowd > 1u) f |= 4;
+        if ((unsigned)cat >= (unsigned)A.num_categories || (unsigned)crowd > (Fed::kOn ? 0u : 1u)) f |= 4;
         g_cat[j] = cat;
         g_flag[j] = (crowd & 1) | ((A.gt_rows[3 * j + 2] & 15) << 1);
         f |= iou_of.gt_check(j);
@@ -126,19 +135,46 @@ __global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A
         }
         return;
     }
-    for (int i = n + tid; i < topk; i += kRleThreads) A.rows[i] = zero;
-    if (tid == 0) A.n_rows[0] = n;
+    int nk = n;   // the detections that take part: rows 0 .. nk - 1
+    if constexpr (!Fed::kOn) {
+        for (int i = n + tid; i < topk; i += kRleThreads) A.rows[i] = zero;
+        if (tid == 0) A.n_rows[0] = n;
+    } else {      // the ground truths of every detection's category first: they decide who takes part (d_cnt < 0: not this one)
+        if (tid == 0) n_keep = 0;
+        __syncthreads();
+        for (int i = tid; i < n; i += kRleThreads) {
+            int lo = 0, cnt = 0;
+            for (int j = 0; j < n_gt; ++j) {
+                lo += g_cat[j] < d_cls[i] ? 1 : 0;
+                cnt += g_cat[j] == d_cls[i] ? 1 : 0;
+            }
+            const bool keep = fed.keep(d_cls[i], cnt);
+            d_lo[i] = lo;
+            d_cnt[i] = keep ? cnt : -1;
+            if (keep) atomicAdd(&n_keep, 1);
+        }
+        __syncthreads();
+        nk = n_keep;
+        for (int i = nk + tid; i < topk; i += kRleThreads) A.rows[i] = zero;
+        if (tid == 0) A.n_rows[0] = nk;
+    }
     // descending score, ties in table order; the ground truths of a detection's category: g_sorted[d_lo .. d_lo + d_cnt), annotation order
     for (int i = tid; i < n; i += kRleThreads) {
-        int r = 0, lo = 0, cnt = 0;
-        for (int j = 0; j < n; ++j) r += (d_score[j] > d_score[i] || (d_score[j] == d_score[i] && j < i)) ? 1 : 0;
-        d_order[r] = i;
-        for (int j = 0; j < n_gt; ++j) {
-            lo += g_cat[j] < d_cls[i] ? 1 : 0;
-            cnt += g_cat[j] == d_cls[i] ? 1 : 0;
+        if constexpr (!Fed::kOn) {
+            int r = 0, lo = 0, cnt = 0;
+            for (int j = 0; j < n; ++j) r += (d_score[j] > d_score[i] || (d_score[j] == d_score[i] && j < i)) ? 1 : 0;
+            d_order[r] = i;
+            for (int j = 0; j < n_gt; ++j) {
+                lo += g_cat[j] < d_cls[i] ? 1 : 0;
+                cnt += g_cat[j] == d_cls[i] ? 1 : 0;
+            }
+            d_lo[i] = lo;
+            d_cnt[i] = cnt;
+        } else if (d_cnt[i] >= 0) {   // the rank among those that take part
+            int r = 0;
+            for (int j = 0; j < n; ++j) r += (d_cnt[j] >= 0 && (d_score[j] > d_score[i] || (d_score[j] == d_score[i] && j < i))) ? 1 : 0;
+            d_order[r] = i;
         }
-        d_lo[i] = lo;
-        d_cnt[i] = cnt;
     }
     for (int j = tid; j < n_gt; j += kRleThreads) {
         int r = 0;
@@ -150,7 +186,7 @@ __global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A
     const bool cell = lane < kInstCells;
     const int a = cell ? lane / 10 : 0, t = cell ? lane - 10 * a : 0;
     const double thr = fmin(A.thr[t], 1.0 - 1e-10);
-    for (int k = 0; k < n; ++k) {
+    for (int k = 0; k < nk; ++k) {
         const int d = d_order[k];
         if ((d_cls[d] & (kRleThreads / 64 - 1)) != wave) continue;   // a category belongs to one wave: its ground truths are touched by no other
         const int ad = d_area[d], lo = d_lo[d], cnt = d_cnt[d];
@@ -189,6 +225,11 @@ __global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A
             A.rows[k] = row;
         }
     }
+}
+
+template <class Iou>
+__global__ void __launch_bounds__(kRleThreads) inst_match_kernel(InstMatchArgs A, Iou iou_of) {
+    inst_match_walk<Iou, kInstMaxTopk>(A, iou_of, NoFederation{});
 }
 
 }  // namespace odise

@@ -34,7 +34,8 @@ static inline InstSource inst_source(const Desc& d) {   // odise_inst_eval_desc,
 }
 // What can be refused without the model (the errors carry `what`).  need_table: the caller reads inst_table and inst_scores with dense
 // masks too; max_pixels: the caller's bound on h * w.
-int inst_source_check(const char* what, const InstSource& s, bool need_table, int64_t max_pixels);
+// max_topk: the caller's bound on topk (odise_hip_lvis_eval looks at 300 detections, lvis_eval.hip).
+int inst_source_check(const char* what, const InstSource& s, bool need_table, int64_t max_pixels, int max_topk = kInstMaxTopk);
 // The sampling geometry and the mask logits of a source without dense masks (unused with them): image b of the last head forward, its
 // geometry checked (the errors carry `what`).  Enqueues nothing and touches no scratch, so a caller runs it before it reserves any.
 struct InstGeom {
@@ -49,6 +50,28 @@ int inst_pack(odise_hip_ctx* ctx, const InstSource& s, const InstGeom& ig, const
 // that do not sum to h * w), 4 (runs AND polygons on one ground truth) and 8 (a bad polygon).  n_gt >= 1.
 int inst_gt_words(odise_hip_ctx* ctx, const uint32_t* gt_runs, const int64_t* gt_offsets, int n_gt, const RleGrid& G, u64* words_g, u64* toggle,
                   int* flag, const odise_inst_poly_gt* p);
+
+// The scratch of one picture's evaluation (inst_eval.hip; lvis_eval.hip takes the same) and stages 2 and 3 behind the packed detections.
+struct InstScratch {
+    u64 *words_d, *words_g;
+    long long* area;   // [n + n_gt]
+    int* inter;        // [n][n_gt], then one int: the status of the call
+    size_t inter_bytes;
+    u64* toggle;       // with polygon ground truth: the toggle planes of poly.hip, [n_gt] masks
+    float* boxes;      // the bbox task without an output for them: [n][4]
+    // the boundary task: the boundaries of all n + n_gt masks (detections first, like the words they come from), the temporary of
+    // inst_boundary_words, their areas [n + n_gt] and intersections [n][n_gt]
+    u64 *bwords, *btmp;
+    long long* barea;
+    int* binter;
+    char* extra;       // extra_bytes of the caller's own, 256-byte aligned
+};
+int inst_scratch(odise_hip_ctx* ctx, int n, int n_gt, const RleGrid& G, InstScratch* s, bool polygons = false, bool boxes = false,
+                 bool boundary = false, size_t extra_bytes = 0);
+// ground-truth words, inter [n][n_gt] (zeroed by the caller) and area [n + n_gt] of s.words_d; flag 1 (and 4, 8 of polygon ground truth)
+// goes to `flag`
+int inst_overlaps(odise_hip_ctx* ctx, const InstScratch& s, const RleGrid& G, int n, const uint32_t* gt_runs, const int64_t* gt_offsets, int n_gt,
+                  int* flag, const odise_inst_poly_gt* p = nullptr);
 
 // ---- device: count, candidates, area -------------------------------------------------------------------------------------------------
 // the instances of a selection: table[0] clamped to 0..topk; no table = all topk

@@ -294,9 +294,9 @@ static int rle_pack_logits(odise_hip_ctx* ctx, const f16* logits, const int* ins
     return ODISE_OK;
 }
 
-int inst_source_check(const char* what, const InstSource& s, bool need_table, int64_t max_pixels) {
+int inst_source_check(const char* what, const InstSource& s, bool need_table, int64_t max_pixels, int max_topk) {
     ODISE_REQUIRE((s.inst_table && s.inst_scores) || (s.masks && !need_table), "%s: null inst_table / inst_scores (optional only with dense masks)", what);
-    ODISE_REQUIRE(s.topk >= 1 && s.topk <= kInstMaxTopk, "%s: topk %d (1..%d)", what, s.topk, kInstMaxTopk);
+    ODISE_REQUIRE(s.topk >= 1 && s.topk <= max_topk, "%s: topk %d (1..%d)", what, s.topk, max_topk);
     ODISE_REQUIRE(s.h >= 1 && s.w >= 1 && (int64_t)s.h * s.w <= max_pixels, "%s: mask size %dx%d out of range", what, s.h, s.w);
     ODISE_REQUIRE(!s.masks || s.dtype == ODISE_F32 || s.dtype == ODISE_U8, "%s: dtype %d (ODISE_F32 or ODISE_U8)", what, s.dtype);
     ODISE_REQUIRE((((uintptr_t)s.inst_table | (uintptr_t)s.inst_scores) & 3) == 0, "%s: inst_table / inst_scores must be 4-byte aligned", what);

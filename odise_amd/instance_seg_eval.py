@@ -31,6 +31,19 @@ class HipInstanceSegEvaluator:
     CHUNK = 64          # pictures per block of the row buffer: it grows by whole blocks, rows already written stay where they are
 
     TASKS = ("bbox", "segm", "boundary")                                       # detectron2's order of the result groups, then Boundary AP
+    MAX_TOPK = IE.MAX_DETECTIONS
+
+    # what `evaluate` does behind the gather; HipLvisEvaluator (lvis_seg_eval.py) stands on the same plumbing with its own four
+    def _accumulate_device(self, blocks, npig):
+        return self.ctx.instance_accumulate(blocks, npig, self.K, self.topk)
+
+    def _accumulate_host(self, rows, npig):
+        return IE.accumulate(rows, npig, self.K)
+
+    def _results(self) -> dict:
+        return IE.results(self.precision, self.recall, self.class_names)
+
+    _flag_names = staticmethod(IE.flag_names)
 
     def __init__(self, ctx: Context, thing_dataset_id_to_contiguous_id: Dict[int, int], class_names: Sequence[str], topk: int = 100,
                  tasks: Sequence[str] = ("segm",), boundary_radius: int = 0):
@@ -45,7 +58,7 @@ class HipInstanceSegEvaluator:
         self.class_names = list(class_names)
         self.K, self.topk, self.boundary_radius = len(self.class_names), int(topk), int(boundary_radius)
         assert all(0 <= v < self.K for v in self.to_contiguous.values()), "contiguous ids must lie in [0, len(class_names))"
-        assert 1 <= self.topk <= IE.MAX_DETECTIONS, self.topk
+        assert 1 <= self.topk <= self.MAX_TOPK, self.topk
         self.flags = ctx.zeros((1,), np.int32)
         self.reset()
 
@@ -147,7 +160,7 @@ class HipInstanceSegEvaluator:
                 flags |= int(p[1])                                           # every rank raises when any rank saw a flag
             npig = D.sum_confusion(torch.from_numpy(npig.copy())).numpy()
         if flags:
-            raise RuntimeError("instance evaluation: malformed input(s): " + "; ".join(IE.flag_names(flags)))
+            raise RuntimeError("instance evaluation: malformed input(s): " + "; ".join(self._flag_names(flags)))
         self.task_precision, self.task_recall, out = {}, {}, {}
         for t in self.tasks:
             blocks = None
@@ -159,13 +172,13 @@ class HipInstanceSegEvaluator:
                 blocks = self._task_chunks[t]                                # as they lie
             if blocks is not None:
                 try:
-                    self.precision, self.recall = self.ctx.instance_accumulate(blocks, npig, self.K, self.topk)
+                    self.precision, self.recall = self._accumulate_device(blocks, npig)
                 except InstanceAccumulateError as e:
                     if e.flags != IE.ACCUM_FLAG_NAN_SCORE:
                         raise
                     blocks = None                                            # a NaN score: the device sort has no place for it, numpy's has
             if blocks is None:
-                self.precision, self.recall = IE.accumulate(gathered[t] if many else self.rows(t), npig, self.K)
+                self.precision, self.recall = self._accumulate_host(gathered[t] if many else self.rows(t), npig)
             self.task_precision[t], self.task_recall[t] = self.precision, self.recall
-            out[t] = IE.results(self.precision, self.recall, self.class_names)
+            out[t] = self._results()
         return out["segm"] if self.tasks == ("segm",) else out

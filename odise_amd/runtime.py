@@ -948,12 +948,14 @@ class Context:
 
     # ---- segm evaluation of instance masks (include/odise_hip.h odise_hip_mask_iou / odise_hip_instance_eval; host restatement:
     # odise_amd/instance_eval.py) ------------------------------------------------------------------------------------------------------
-    def instance_gt_to_device(self, gt_table, runs, offsets, xy=None, poly_offsets=None, gt_polys=None, boxes=None) -> dict:
+    def instance_gt_to_device(self, gt_table, runs, offsets, xy=None, poly_offsets=None, gt_polys=None, boxes=None, lvis_bits=None) -> dict:
         """The ground truth of one picture (instance_eval.gt_rows) as ONE packed upload: offsets int64 [n_gt + 1] | table int32 [n_gt, 3] |
         runs uint32 -> {"n_gt", "offsets", "rows", "runs"} (views of one device buffer).  With the polygon part of
         `gt_rows(..., polygons=True)` the same upload carries poly_offsets int64 | xy float64 in front of the table and gt_polys int32
         behind it, and the dict gains {"n_poly", "xy", "poly_offsets", "gt_polys"}.  With `boxes` (instance_eval.gt_boxes: float64
-        [n_gt, 4] XYWH) the same upload carries them in front of the table and the dict gains {"boxes"}.  The upload waits for the stream."""
+        [n_gt, 4] XYWH) the same upload carries them in front of the table and the dict gains {"boxes"}.  With `lvis_bits` = (neg,
+        not_exhaustive), two uint32 [ceil(K / 32)] bitsets (lvis_eval.category_bits), it carries those too and the dict gains
+        {"neg_bits", "not_exhaustive_bits"}.  The upload waits for the stream."""
         runs, offsets = np.ascontiguousarray(runs, np.uint32), np.ascontiguousarray(offsets, np.int64)
         if gt_table is None:                                             # masks alone (the frames of the video evaluator): "rows" is empty
             table, n_gt = np.zeros((0, 3), np.int32), offsets.size - 1
@@ -974,6 +976,11 @@ class Context:
             assert boxes.size == 4 * n_gt, (boxes.size, n_gt)
             at_boxes = len(parts)
             parts.append(boxes)
+        if lvis_bits is not None:
+            neg_bits, nex_bits = (np.ascontiguousarray(x, np.uint32).reshape(-1) for x in lvis_bits)
+            assert neg_bits.size == nex_bits.size and neg_bits.size >= 1, (neg_bits.size, nex_bits.size)
+            at_bits = len(parts)
+            parts += [neg_bits, nex_bits]
         parts += [table.reshape(-1)] + ([gt_polys] if gt_polys is not None else []) + [runs]
         buf = self.to_device(np.concatenate([p.view(np.uint8) for p in parts]))
         at = np.concatenate(([0], np.cumsum([p.nbytes for p in parts]))).tolist()
@@ -984,6 +991,9 @@ class Context:
                       gt_polys=buf.view((n_gt + 1,), np.int32, at[-3]))
         if boxes is not None:
             gt["boxes"] = buf.view((n_gt, 4), np.float64, at[at_boxes])
+        if lvis_bits is not None:
+            gt["neg_bits"] = buf.view((neg_bits.size,), np.uint32, at[at_bits])
+            gt["not_exhaustive_bits"] = buf.view((nex_bits.size,), np.uint32, at[at_bits + 1])
         return gt
 
     def _gt_counts_to_device(self, gt_counts) -> dict:
@@ -1111,16 +1121,37 @@ class Context:
                                                    int(radius), _p(iou), _p(m_iou), _p(b_iou), None, None, None, _p(flags)), "mask_boundary_iou")
         return iou, m_iou, b_iou, flags
 
-    def instance_accumulate(self, blocks, npig, num_categories: int, topk: int, rec_thrs=None):
+    def lvis_eval(self, out_hw, table_row, scores_row, topk: int, gt: dict, num_categories: int, image: int, rows, n_rows, flags,
+                  masks: Optional[DeviceArray] = None, b: int = 0, pad_hw=(0, 0), img_hw=(0, 0), iou_thresholds=None) -> None:
+        """Enqueue LVISEval.evaluate_img of one picture (odise_hip_lvis_eval; host restatement: lvis_eval.image_rows).  Arguments as in
+        `instance_eval` with topk up to 300; gt = `instance_gt_to_device(..., lvis_bits=(neg, not_exhaustive))`.  With detections from
+        the mask logits the table holds (query, class) pairs and every distinct query is packed once."""
+        from ._lib import LvisTask
+        assert "neg_bits" in gt, "lvis_eval: the ground truth carries no category bitsets"
+        assert gt["neg_bits"].shape[0] == (int(num_categories) + 31) // 32, (gt["neg_bits"].shape, num_categories)
+        d, _thr = _inst_eval_desc("lvis_eval", out_hw=out_hw, table_row=table_row, scores_row=scores_row, topk=topk, gt=gt, num_categories=num_categories,
+                                  image=image, rows=rows, n_rows=n_rows, flags=flags, masks=masks, b=b, pad_hw=pad_hw, img_hw=img_hw,
+                                  iou_thresholds=iou_thresholds)
+        t = LvisTask()
+        t.neg_bits, t.not_exhaustive_bits = gt["neg_bits"].ptr, gt["not_exhaustive_bits"].ptr
+        check(self.lib.odise_hip_lvis_eval(self.h, C.byref(d), _inst_poly_gt(gt), C.byref(t)), "lvis_eval")
+
+    def lvis_accumulate(self, blocks, npig, num_categories: int, topk: int, rec_thrs=None):
+        """LVISEval.accumulate on the device (odise_hip_lvis_accumulate; host restatement: lvis_eval.accumulate, which this equals byte
+        for byte): `instance_accumulate` with topk up to 300 and no maxDets axis -> (precision float64 [10, R, K, 4], recall float64
+        [10, K, 4])."""
+        return self.instance_accumulate(blocks, npig, num_categories, topk, rec_thrs, lvis=True)
+
+    def instance_accumulate(self, blocks, npig, num_categories: int, topk: int, rec_thrs=None, lvis: bool = False):
         """COCOeval.accumulate on the device (odise_hip_instance_accumulate; host restatement: instance_eval.accumulate, which this
         equals byte for byte).  blocks: a sequence of (rows, counts) - `rows` a DeviceArray of instance_eval.ROW_DTYPE [slots * topk],
         `counts` a DeviceArray int32 [slots], as the evaluator keeps them - or of host arrays of those shapes, which are uploaded; no two
         slots may share an `image` number.  npig int64 [K, 4] (host or device); rec_thrs: instance_eval.REC_THRS unless given.
         -> (precision float64 [10, R, K, 4, 3], recall float64 [10, K, 4, 3]) after ONE read-back, which is the only wait.  A flag raises
         `InstanceAccumulateError` (its .flags, .precision and .recall hold what the device wrote: -1 everywhere)."""
-        from ._lib import InstAccumDesc
+        from ._lib import InstAccumDesc, LvisAccumDesc
         from . import instance_eval as IE
-        K, topk = int(num_categories), int(topk)
+        K, topk, M = int(num_categories), int(topk), 1 if lvis else 3
         thr = np.ascontiguousarray(IE.REC_THRS if rec_thrs is None else rec_thrs, np.float64).reshape(-1)
         R = thr.size
         dev = []
@@ -1145,17 +1176,20 @@ class Context:
             npig_d, thr_d = up.view((K, 4), np.int64), up.view((R,), np.float64, K * 32)
         else:
             npig_d, thr_d = npig, self.to_device(thr)
-        n_p, n_r = 10 * R * K * 12, 10 * K * 12
+        n_p, n_r = 10 * R * K * 4 * M, 10 * K * 4 * M
         out = self.empty((n_p + n_r + 1,), np.float64)              # precision | recall | flags: one read-back
         flags = out.view((1,), np.int32, (n_p + n_r) * 8)
         check(self.lib.odise_hip_memset(self.h, flags.ptr, 0, 8), "memset")
-        d = InstAccumDesc()
+        d = LvisAccumDesc() if lvis else InstAccumDesc()
         d.n_blocks, d.rows, d.counts, d.slots = nb, C.addressof(row_ptrs), C.addressof(count_ptrs), C.addressof(slots)
         d.topk, d.num_categories, d.npig, d.rec_thrs, d.n_rec = topk, K, npig_d.ptr, thr_d.ptr, R
         d.precision, d.recall, d.flags = out.ptr, out.ptr + n_p * 8, flags.ptr
-        check(self.lib.odise_hip_instance_accumulate(self.h, C.byref(d)), "instance_accumulate")
+        if lvis:
+            check(self.lib.odise_hip_lvis_accumulate(self.h, C.byref(d)), "lvis_accumulate")
+        else:
+            check(self.lib.odise_hip_instance_accumulate(self.h, C.byref(d)), "instance_accumulate")
         host = out.numpy()
-        precision, recall = host[:n_p].reshape(10, R, K, 4, 3), host[n_p:n_p + n_r].reshape(10, K, 4, 3)
+        precision, recall = host[:n_p].reshape((10, R, K, 4) + (() if lvis else (3,))), host[n_p:n_p + n_r].reshape((10, K, 4) + (() if lvis else (3,)))
         f = int(host[n_p + n_r:].view(np.int32)[0])
         if f:
             raise InstanceAccumulateError(f, precision, recall)
